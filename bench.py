@@ -4,19 +4,24 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W --full     (also every side measurement and baseline below)
+    python bench.py ... --dump-outputs DIR                   (also DIR/q.npy, DIR/qdot.npy: the timed launch's final state)
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it measures runs with --full only.
 
 Workload (BASELINE.json configs[1]): 32-link serial revolute chain (scenesRedMax.m:52-79 pattern), BDF1, fp64, 1024
 independent rollouts.  A "step" is one BDF1 step of a rank's batch; `value` = rollout-steps per second summed over all
 ranks, inputs resident in HBM before the timed region, the K steps of a rank are ONE kernel launch, and the only
 collective is the final all-gather of (q, qdot) (redmax_amd/sharding.py; RCCL when every rank has its own GPU).
 
-`value` / `scaling`: weak scaling - 1024 rollouts PER GPU (the batch axis shards, per-GPU work fixed).  The same run also
-measures the strong-scaling reading of BASELINE.json's north_star (1024 rollouts IN TOTAL, 1024/N per GPU) and reports it
+`value` / `scaling`: weak scaling - 1024 rollouts PER GPU (the batch axis shards, per-GPU work fixed).  With --full the same run
+also measures the strong-scaling reading of BASELINE.json's north_star (1024 rollouts IN TOTAL, 1024/N per GPU) and reports it
 as `strong_scaling`; at N = 1 the two coincide.
 
-Objects on the JSON line besides the driver's contract:
+Objects on the JSON line besides the driver's contract (priced from the timed launch itself, no run of their own):
   roofline                 executed fp64 work of the dominant kernel against the fp64 peak (frac <= 1), its issue-bound
                            ceiling, the SURVEY §8(d) "algorithmic" figure for reference, HBM traffic per launch
+and with --full (each one runs launches or host code of its own):
   repeat                   the K-step launch repeated from the same state: median / min / max kernel time
   value_plain_iterate      the same launch with the Newton iterate in plain doubles (rmx_opts.compensated = 0), 100 steps
   value_at_survey_init     the same launch from SURVEY 8(d)'s wide initial-state ranges, 100 steps
@@ -134,6 +139,26 @@ def _free_port():
     return p
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+BURN_STEPS = 100          # steps per untimed burn-in / rehearsal launch at most (the timed launch runs all --steps)
+REPEAT_BUDGET_S = 30.0    # --full: no further repeated launch once the repeats have taken this long (a long --steps repeats less)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array with the rollouts on its first axis} -> out_dir/<name>.npy in float64.  Beyond DUMP_LIMIT_BYTES in
+    all, every array keeps the same fixed seeded sample of rollouts, and their indices go to sample_rows.npy."""
+    arrays = {k: np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for k, v in arrays.items()}
+    rows = min(a.shape[0] for a in arrays.values())
+    per_row = sum(a.nbytes for a in arrays.values()) / max(rows, 1) + 8
+    if rows * per_row > DUMP_LIMIT_BYTES - 65536:                   # (the margin: the .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(rows, int((DUMP_LIMIT_BYTES - 65536) // per_row), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -148,8 +173,9 @@ def parse_args(argv=None):
     ap.add_argument("--links", type=int, default=32)
     ap.add_argument("--tol", type=float, default=1e-9, help="Newton |g| tolerance: the reference's hard-coded 1e-9 (driverRedMaxBDF1.m:95)")
     ap.add_argument("--plain-iterate", action="store_true", help="rmx_opts.compensated = 0 for the headline line (plain doubles)")
-    ap.add_argument("--repeats", type=int, default=5, help="extra timed launches of the same K steps from the same state")
-    ap.add_argument("--burn-in", type=float, default=60.0, help="milliseconds of untimed launches of the same K steps, each from the initial state, BEFORE "
+    ap.add_argument("--repeats", type=int, default=5, help="with --full: extra timed launches of the same K steps from the same state "
+                                                           "(fewer once they have taken %g s)" % REPEAT_BUDGET_S)
+    ap.add_argument("--burn-in", type=float, default=60.0, help="milliseconds of untimed launches of the same kernel (min(K, %d) steps each), each from the initial state, BEFORE " % BURN_STEPS + 
                                                                 "the W warm-up steps (brings the GPU out of its idle clock state); 0: none")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference-tol", "--no-side-legs", dest="no_reference_tol", action="store_true",
@@ -160,6 +186,13 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-traj", type=int, default=0, help="rollouts in the CPU sample (default: one per host thread, <= 256)")
     ap.add_argument("--cpu-steps", type=int, default=40)
     ap.add_argument("--json-out", default="", help="also write the JSON line to this file (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline launch: the repeated launches, the side measurements (plain iterate, SURVEY "
+                         "init ranges, max valid init, tol 1e-8, the straggler policy of ground), strong scaling (N > 1), the CPU baselines "
+                         "with the Newton-count agreement, the adjoint's host-array call.  Off: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed launch computed (rank 0's view: the gathered final q, qdot; adjoint: P, dPdp) to DIR/<name>.npy, "
+                         "float64, at most 64 MB in all (a fixed seeded sample of rollouts beyond that)")
     args = ap.parse_args(argv)
     if args.steps <= 0:
         args.steps = 20 if args.workload == "adjoint" else 100
@@ -338,24 +371,27 @@ def measure(ctx, make_stepper, scene, gen, shard, h, tol, integ, K, W, repeats, 
     st.set_state(q0, qd0)
     ctx.gather(st, shard)              # warm the collective too (before the warm-up steps: nothing but the barrier + device
     burned, burn_ms = 0, 0.0           # sync the contract asks for lies between the warm-up steps and the timed launch)
+    KB, WB = min(K, BURN_STEPS), min(W, BURN_STEPS)
     while burn_ms < burn_in and burned < 200:
         # burn-in: untimed launches of the very kernel that will be timed, each from the initial state, until the GPU has been busy
         # for `burn_in` milliseconds: an idle MI355X runs its first ~20 ms of work about 5 % below its sustained clock (s_memtime
         # ticks per rollout stay the same, the launch takes longer: tools/first_launch_probe.py).  The state is put back afterwards.
+        # (at most BURN_STEPS steps per launch: the kernel does not depend on the step count, and a long --steps must not pay twice)
         st.set_state(q0, qd0)
-        st.launch(K)
+        st.launch(KB)
         burn_ms += st.wait()
         burned += 1
     if burned:
         # ... and ONE untimed rehearsal of the timed sequence itself (counter reset, the synchronous W warm-up steps, device sync,
         # barrier, the K-step launch, wait, gather, barrier): the first launch behind the process's first synchronous step call pays
-        # 13 - 30 us of one-time host / runtime set-up (tools: profiles/r6n_timed_region_probe.txt), 2 - 4 % of a 0.8 ms launch
+        # 13 - 30 us of one-time host / runtime set-up (tools: profiles/r6n_timed_region_probe.txt), 2 - 4 % of a 0.8 ms launch.
+        # That set-up is per call, not per step: the rehearsal runs at most BURN_STEPS warm-up and launch steps
         st.set_state(q0, qd0)
         st.stats_reset()
-        st.warmup(W)
+        st.warmup(WB)
         st.sync_device()
         ctx.barrier()
-        st.launch(K)
+        st.launch(KB)
         st.wait()
         ctx.gather(st, shard)
         ctx.barrier()
@@ -381,6 +417,7 @@ def measure(ctx, make_stepper, scene, gen, shard, h, tol, integ, K, W, repeats, 
         "local_iters": s["newton_iters"].copy(),
         "burned": burned,
         "step_kernel": st.step_kernel() if hasattr(st, "step_kernel") else None,
+        "outputs": {"q": gathered[0], "qdot": gathered[1]} if gathered is not None else {"q": qf, "qdot": qdf},   # (--dump-outputs)
     }
     if hasattr(st, "rollout_ticks"):      # how the launch time is spread over this rank's rollouts (all run concurrently, one wavefront each)
         tk = st.rollout_ticks().astype(np.float64)
@@ -397,6 +434,8 @@ def measure(ctx, make_stepper, scene, gen, shard, h, tol, integ, K, W, repeats, 
         st.warmup(W)
         qw, qdw = st.get_state()
     for _ in range(max(repeats, 0)):
+        if sum(rep_w) > REPEAT_BUDGET_S:  # (rep_w holds maxima over the ranks: every rank stops at the same launch)
+            break
         st.set_state(qw, qdw)
         ctx.barrier()
         t0 = time.perf_counter()
@@ -567,14 +606,17 @@ def rank_main(args, make_stepper=None, backend=None):
     weak = sharding.plan(rank, world, B, "weak")
     comp = 0 if args.plain_iterate else 1
     burn = args.burn_in if on_gpu else 0.0         # a clock ramp is a GPU matter: the CPU stand-ins of the tests skip it
-    m = measure(ctx, make_stepper, scene, gen, weak, h, args.tol, integ, K, W, args.repeats, comp, burn)
+    # a plain run times the headline launch and nothing else; every other launch, leg and baseline below runs with --full only
+    m = measure(ctx, make_stepper, scene, gen, weak, h, args.tol, integ, K, W, args.repeats if args.full else 0, comp, burn)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"])
     plain = strong = wide = soft = cutleg = maxv = None
     KR = args.ref_steps
-    if wl == "ground" and on_gpu and not args.no_reference_tol:
+    if wl == "ground" and on_gpu and args.full and not args.no_reference_tol:
         # the opt-in straggler policy (rmx_opts.ls_fail_limit, NOT reference behaviour): same launch, Newton loop of a step cut at its
         # second failed line search.  A side figure; `value` is the reference's loop.
         cutleg = measure(ctx, make_stepper, scene, gen, weak, h, args.tol, integ, K, W, 0, comp, burn, 2)
-    if wl == "chain" and not args.no_reference_tol:
+    if wl == "chain" and args.full and not args.no_reference_tol:
         # side measurements, always over the reference's own rollout length: the lattice of doubles binds (and the wide initial
         # states fail) late in a rollout, a short --steps window would hide it
         if comp:
@@ -587,7 +629,7 @@ def rank_main(args, make_stepper=None, backend=None):
                        weak, h, args.tol, integ, KR, W, 0, comp, burn)
         if args.tol != 1e-8:
             soft = measure(ctx, make_stepper, scene, gen, weak, h, 1e-8, integ, K, W, 0, comp, burn)
-    if world > 1 and not args.no_strong:
+    if world > 1 and args.full and not args.no_strong:
         strong = measure(ctx, make_stepper, scene, gen, sharding.plan(rank, world, B, "strong"), h, args.tol, integ, K, W, args.repeats, comp, burn)
 
     if rank == 0:
@@ -610,7 +652,7 @@ def rank_main(args, make_stepper=None, backend=None):
                        "parallelism": "batch-sharded x%d (redmax_amd.sharding), one %s all-gather of the final (q,qdot)%s" % (
                            world, "RCCL" if backend == "nccl" else backend,
                            "; ranks share a device, so the gather runs on gloo with host tensors" if (on_gpu and shared) else ""),
-                       "steps_per_launch": K, "untimed_burn_in": {"ms": burn, "launches": m.get("burned", 0), "rehearsal": "one untimed run of the whole timed sequence (W warm-up steps, sync, K-step launch, wait, gather) before the real one" if m.get("burned", 0) else None}, "not_converged_trajectories": m["bad"], "trajectories_with_pivoted_fallback": m["pivoted"],
+                       "steps_per_launch": K, "untimed_burn_in": {"ms": burn, "launches": m.get("burned", 0), "rehearsal": "one untimed run of the whole timed sequence (warm-up steps, sync, launch, wait, gather; at most %d steps each) before the real one" % BURN_STEPS if m.get("burned", 0) else None}, "not_converged_trajectories": m["bad"], "trajectories_with_pivoted_fallback": m["pivoted"],
                        "all_finite": m["finite"], "gathered_rows": m["gathered_rows"]},
             "roofline": roofline(m["kernel_ms"], m["iters"] / world, m["halvings"] / world, B * K, K, W, B, n, wl, args.tol, m["local_iters"],
                                  step_kernel=m.get("step_kernel")) if on_gpu else None,
@@ -698,7 +740,7 @@ def rank_main(args, make_stepper=None, backend=None):
                 "note": "BASELINE.json north_star reading: %d rollouts in TOTAL over the %d ranks.  One rollout is one wavefront and a "
                         "Newton step is a sequential chain, so below 1024 rollouts per GPU the kernel time does not shrink with the "
                         "batch (SIMDs idle): expect a flat curve (SURVEY.md §8(e))" % (strong["rollouts"], world)}
-        if on_gpu and world == 1 and not args.no_cpu_baseline and wl == "chain":
+        if on_gpu and world == 1 and args.full and not args.no_cpu_baseline and wl == "chain":
             out.update(cpu_baselines(scene, args, h))
             # the numbers that decide SURVEY.md 8(d)'s Newton-count statement, at the top level of the line (round-5 review)
             nca = out.get("newton_count_agreement") or {}
@@ -876,18 +918,22 @@ def adjoint_main(args, ctx):
     _, _, timed = run(stats=False)
     elapsed = ctx.max(timed["elapsed"])
     P, dPdp = P_t.cpu().numpy(), dP_t.cpu().numpy()
+    if ctx.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"P": P, "dPdp": dPdp})
     ms = [timed["ms"]]
     info = run()[2]                     # the same job once more, with its counters
     ms.append(info["ms"])
-    for _ in range(max(args.repeats - 1, 0)):
-        ms.append(run()[2]["ms"])
-    run_host()
-    ctx.barrier()
-    t0 = time.perf_counter()
-    Ph, dPh, _ = run_host()
-    ctx.barrier()
-    elapsed_host = ctx.max(time.perf_counter() - t0)
-    same_as_host = bool(np.array_equal(Ph, P) and np.array_equal(dPh, dPdp))
+    elapsed_host = None
+    if args.full:
+        for _ in range(max(args.repeats - 1, 0)):
+            ms.append(run()[2]["ms"])
+        run_host()
+        ctx.barrier()
+        t0 = time.perf_counter()
+        Ph, dPh, _ = run_host()
+        ctx.barrier()
+        elapsed_host = ctx.max(time.perf_counter() - t0)
+        same_as_host = bool(np.array_equal(Ph, P) and np.array_equal(dPh, dPdp))
     sim.close()
     if ctx.rank == 0:
         kernel_ms = float(np.median(ms))
@@ -909,11 +955,12 @@ def adjoint_main(args, ctx):
                           "timed_region": "rmx_adjoint_bdf1_device (forward + backward kernel) from the initial state: state, p, P, dPdp "
                                           "resident in HBM when the region starts (rmx_set_state_device ahead of it); the per-rollout counters "
                                           "reported here are those of the identical untimed repeat that follows"},
-               "value_host_arrays": {"value": round(ctx.world * B * K / elapsed_host, 1), "unit": "rollout-steps/s",
-                                     "ms_per_step": round(1e3 * elapsed_host / K, 5), "same_bits_as_the_device_call": same_as_host,
-                                     "note": "the same job through rmx_set_state + rmx_adjoint_bdf1: q, qdot, p in and P, dPdp out as "
-                                             "host arrays (PCIe-inclusive; what an optimiser on the host binds)"},
                }
+        if elapsed_host is not None:
+            out["value_host_arrays"] = {"value": round(ctx.world * B * K / elapsed_host, 1), "unit": "rollout-steps/s",
+                                        "ms_per_step": round(1e3 * elapsed_host / K, 5), "same_bits_as_the_device_call": same_as_host,
+                                        "note": "the same job through rmx_set_state + rmx_adjoint_bdf1: q, qdot, p in and P, dPdp out as "
+                                                "host arrays (PCIe-inclusive; what an optimiser on the host binds)"}
         # one Newton iteration of the line-search-free newton() (driverRedMaxAdjointBDF1.m:105-146) = one (g, H) evaluation + one solve;
         # per step on top: M, D assembled once (~2 x (66 n + 12 n(n+1)/2) flops), and in the backward sweep one transposed solve and
         # the M / D products (solve + 6 n^2)

@@ -21,7 +21,7 @@ def _run(*args):
 
 def test_default_workload_line():
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
-    d = _run("--steps", "20", "--warmup", "5", "--cpu-steps", "4", "--cpu-traj", "16")
+    d = _run("--steps", "20", "--warmup", "5", "--cpu-steps", "4", "--cpu-traj", "16", "--full")
     assert d["metric"] == base["metric"] and d["unit"] == "rollout-steps/s"
     assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 20, 5)
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["dtype"] == "f64" and d["data"] == "synthetic"
@@ -69,12 +69,37 @@ def test_two_ranks_on_one_gpu_self_launch():
     """`python bench.py --gpus 2` bare (no torchrun): bench.py re-executes itself under torch.distributed.run.  On a 1-GPU box
     both ranks share device 0, where RCCL refuses duplicate GPUs, so the gather goes through gloo with host tensors - the rank
     code, shard plans, barriers and both scaling modes are the ones an 8-GPU RCCL run uses."""
-    d = _run("--gpus", "2", "--steps", "10", "--warmup", "2", "--batch", "256", "--repeats", "1", "--no-side-legs")
+    d = _run("--gpus", "2", "--steps", "10", "--warmup", "2", "--batch", "256", "--repeats", "1", "--no-side-legs", "--full")
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 512 and d["config"]["gathered_rows"] == 512
     assert d["scaling"] == "weak" and d["value"] > 0 and d["config"]["all_finite"]
     s = d["strong_scaling"]
     assert s["global_batch"] == 256 and s["batch_per_gpu"] == 128 and s["value"] > 0
     assert d["value_strong"] == s["value"] and len(d["kernel_ms_per_rank"]["weak"]) == 2 and min(d["kernel_ms_per_rank"]["strong"]) > 0
+
+
+def test_plain_line_and_dump_outputs(tmp_path):
+    """A plain run times the headline launch alone (the side objects need --full); --dump-outputs writes that launch's final state,
+    which is the library's own result for the bench's inputs after the W warm-up and the K timed steps."""
+    import bench
+    import numpy as np
+    d = _run("--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    assert (d["steps"], d["warmup"]) == (5, 2) and abs(d["value"] - 1024 * 5 / (d["ms_per_step"] * 5e-3)) <= 1e-3 * d["value"]
+    assert d["config"]["all_finite"] and d["roofline"]["kernel_ms"] > 0
+    for k in ("repeat", "value_plain_iterate", "value_at_survey_init", "value_at_max_valid_init", "value_at_tol_1e-8", "cpu_baseline",
+              "cpu_baseline_tensor_free", "newton_count_agreement"):
+        assert k not in d, k
+    q, qd = np.load(tmp_path / "q.npy"), np.load(tmp_path / "qdot.npy")
+    assert q.shape == qd.shape == (1024, 32) and q.dtype == qd.dtype == np.float64
+    scene, h, integ, gen = bench.build_workload("chain", 32)
+    st = bench.GpuStepper(scene, 1024, 0, integ)
+    st.set_opts(h, 1e-9)
+    st.set_state(*gen(0, 1024))
+    st.warmup(2)
+    st.launch(5)
+    st.wait()
+    qr, qdr = st.get_state()
+    st.close()
+    assert np.array_equal(q, qr) and np.array_equal(qd, qdr)
 
 
 @pytest.mark.parametrize("wl", ["tree64", "ground"])

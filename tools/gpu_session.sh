@@ -13,12 +13,12 @@ if has tests; then
   tail -5 $OUT/pytest_gpu.log
 fi
 if has bench; then
-  timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-  timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_k20.json 2>> $OUT/bench.err
+  timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout 600 python bench.py --steps 20 --warmup 5 --full > $OUT/bench_k20.json 2>> $OUT/bench.err
   head -c 600 $OUT/bench.json; echo
 fi
 if has bench2; then
-  timeout 900 python bench.py --gpus 2 --no-side-legs > $OUT/bench_gpus2.json 2> $OUT/bench_gpus2.err; echo "bench --gpus 2 rc=$?"
+  timeout 900 python bench.py --gpus 2 --no-side-legs --full > $OUT/bench_gpus2.json 2> $OUT/bench_gpus2.err; echo "bench --gpus 2 rc=$?"
   tail -3 $OUT/bench_gpus2.err
 fi
 BENCH="python $ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-side-legs --repeats 0"
@@ -54,9 +54,9 @@ if has pmc; then
   cd $ROOT
 fi
 if has extra; then
-  timeout 600 python bench.py --workload adjoint > $OUT/bench_adjoint.json 2> $OUT/bench_adjoint.err; echo "adjoint rc=$?"
-  timeout 600 python bench.py --workload tree64 > $OUT/bench_tree64.json 2> $OUT/bench_tree64.err; echo "tree64 rc=$?"
-  timeout 600 python bench.py --workload ground > $OUT/bench_ground.json 2> $OUT/bench_ground.err; echo "ground rc=$?"
+  timeout 600 python bench.py --workload adjoint --full > $OUT/bench_adjoint.json 2> $OUT/bench_adjoint.err; echo "adjoint rc=$?"
+  timeout 600 python bench.py --workload tree64 --full > $OUT/bench_tree64.json 2> $OUT/bench_tree64.err; echo "tree64 rc=$?"
+  timeout 600 python bench.py --workload ground --full > $OUT/bench_ground.json 2> $OUT/bench_ground.err; echo "ground rc=$?"
   timeout 300 python tools/phase_profile.py > $OUT/phase_profile.txt 2>&1
   timeout 300 python tools/quick_bench.py > $OUT/quick_bench.txt 2>&1; cat $OUT/quick_bench.txt
 fi

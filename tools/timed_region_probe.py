@@ -2,7 +2,7 @@
 the K-step launch, wait, torch.cuda.synchronize) six times in one process - the FIRST pass pays 13 - 30 us of one-time set-up, which is why
 bench.py rehearses the sequence once, untimed, before the real one.  GPU box only."""
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 torch.cuda.set_device(0); torch.cuda.synchronize()

@@ -1,5 +1,5 @@
 import sys, os, numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from redmax_amd import BatchSim, sceneTree, syntheticStates
 sc = sceneTree(64); sc.init()
 for B in (512, 256):
