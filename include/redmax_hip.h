@@ -178,6 +178,33 @@ typedef struct rmx_ground_contact {
 } rmx_ground_contact;
 int rmx_model_set_ground_contact(rmx_model* m, const rmx_ground_contact* gc);
 
+/* Body-to-body forces of the reference, acting between points of two (or, for a cable, several) bodies:
+ *   RMX_PF_POINTPOINT    ForcePointPoint(body1, x1, body2, x2)    f = ks dx + kd dv, V = ks |dx|^2 / 2      (ForcePointPoint.m:50-133)
+ *   RMX_PF_SPRINGDAMPER  ForceSpringDamper(body1, x1, body2, x2)  fs = k (l - L)/L + d ldot/L, V = k/2 ((l - L)/L)^2 L
+ *                                                                  (ForceSpringGeneric.m:37-176, ForceSpringDamper.m:37-71)
+ *   RMX_PF_CABLE         ForceCable() + addBodyPoint(body, x)     the same law on the TOTAL length of a polyline through npts points,
+ *                                                                  zero while slack (ForceSpringMultiPointGeneric.m:28-190, ForceCable.m:37-82)
+ * body[k] is the index of the point's body in the caller's joint listing (a multi-DOF joint's body: its last node), -1 the world;
+ * x[k] the point in the body's frame.  L is the rest length of kinds 1, 2 and must be > 0 (the host computes it from the initial
+ * configuration as Force.init does unless setRetLength gave one); kind 0 ignores it.  setStiffness / setDamping: stiffness, damping.
+ * The forces enter rmx_eval (g and H), rmx_step_bdf1 / rmx_step_bdf2 / rmx_step_history (and their _async forms) and the potential
+ * energy of rmx_energy and of the per-step record.  A spring between bodies on different branches makes H dense: such a model always
+ * takes the dense elimination order under the growth guard (RMX_ST_PIVOTED may be set).
+ * Limits: at most RMX_PF_MAX_FORCES forces, 2 .. RMX_PF_MAX_POINTS points per force, RMX_PF_MAX_TOTAL points in all; models of at
+ * most 64 nodes after lowering.  Refused with RMX_E_INVALID: beyond those limits; together with ForceGroundCuboid or JointSpherical /
+ * JointFree3D in one model; and, for a model that has point forces, rmx_step_euler, rmx_adjoint_*, rmx_eval_mfd and
+ * rmx_compute_values.  rmx_group_create has no slot for them.  nforces = 0 removes the forces.  Call before stepping. */
+enum { RMX_PF_POINTPOINT = 0, RMX_PF_SPRINGDAMPER = 1, RMX_PF_CABLE = 2 };
+enum { RMX_PF_MAX_FORCES = 32, RMX_PF_MAX_POINTS = 8, RMX_PF_MAX_TOTAL = 128 };
+typedef struct rmx_point_force {
+    int kind;                /* RMX_PF_*                                              */
+    int npts;                /* 2 (kinds 0, 1) or 2 .. RMX_PF_MAX_POINTS (cable)     */
+    const int* body;         /* [npts] listing index of each point's body, -1 = world */
+    const double* x;         /* [npts][3] the points in their bodies' frames          */
+    double stiffness, damping, L;
+} rmx_point_force;
+int rmx_model_set_point_forces(rmx_model* m, const rmx_point_force* f, int nforces);
+
 /* JointSpherical / JointFree3D (JointSpherical.m:4-17, 28-34, 63-102): every such joint is in one of 12 Euler charts, numbered as
  * the reference's CHART_* constants (1 XYX, 2 XZX, 3 YZY, 4 YXY, 5 ZXZ, 6 ZYZ, 7 XYZ, 8 XZY, 9 YZX, 10 YXZ, 11 ZXY, 12 ZYX) and
  * constructed in CHART_XYZ.  rmx_step_bdf1/bdf2 run reparam_ after every step per trajectory (status bit RMX_ST_CHART when a

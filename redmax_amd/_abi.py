@@ -20,7 +20,7 @@ _ip = C.POINTER(C.c_int)
 SYMBOLS = (
     "rmx_last_error", "rmx_version", "rmx_device_count", "rmx_opts_default",
     "rmx_model_create", "rmx_model_destroy", "rmx_model_nr", "rmx_model_nm", "rmx_model_idxR",
-    "rmx_model_set_ground_contact", "rmx_model_nsph", "rmx_get_charts", "rmx_set_charts",
+    "rmx_model_set_ground_contact", "rmx_model_set_point_forces", "rmx_model_nsph", "rmx_get_charts", "rmx_set_charts",
     "rmx_batch_create", "rmx_batch_destroy", "rmx_batch_size",
     "rmx_set_state", "rmx_get_state", "rmx_set_state_device", "rmx_get_state_device",
     "rmx_eval", "rmx_eval_mfd", "rmx_compute_values", "rmx_step_bdf1", "rmx_step_bdf2", "rmx_step_history", "rmx_step_euler", "rmx_adjoint_bdf1", "rmx_adjoint_bdf2", "rmx_adjoint_bdf1_device", "rmx_adjoint_bdf2_device", "rmx_energy",
@@ -66,6 +66,11 @@ class GroundContact(C.Structure):
                 ("kd_body", _dp)]
 
 
+class PointForce(C.Structure):
+    _fields_ = [("kind", C.c_int), ("npts", C.c_int), ("body", _ip), ("x", _dp), ("stiffness", C.c_double), ("damping", C.c_double),
+                ("L", C.c_double)]
+
+
 class History(C.Structure):
     _fields_ = [("T", _dp), ("V", _dp), ("q", _dp), ("qdot", _dp), ("charts", _ip)]
 
@@ -98,6 +103,7 @@ def lib():
     L.rmx_model_nm.argtypes = [vp]
     L.rmx_model_idxR.argtypes = [vp, _ip]
     L.rmx_model_set_ground_contact.argtypes = [vp, C.POINTER(GroundContact)]
+    L.rmx_model_set_point_forces.argtypes = [vp, C.POINTER(PointForce), C.c_int]
     L.rmx_model_nsph.argtypes = [vp]
     L.rmx_get_charts.argtypes = [vp, _ip]
     L.rmx_set_charts.argtypes = [vp, _ip]
@@ -194,6 +200,26 @@ def make_ground_contact(d, keep):
             keep["g" + k] = np.ascontiguousarray(gb[k], dtype=np.float64)
             setattr(gc, k + "_body", dptr(keep["g" + k]))
     return gc
+
+
+def make_point_forces(d, keep):
+    """desc()["point_forces"] (ForcePointPoint / ForceSpringDamper / ForceCable of a Scene) -> (array of PointForce, count), or
+    (None, 0) when the scene has none."""
+    pfs = d.get("point_forces")
+    if not pfs:
+        return None, 0
+    arr = (PointForce * len(pfs))()
+    keep["pf"] = []
+    for a, f in zip(arr, pfs):
+        body = np.ascontiguousarray(f["body"], dtype=np.int32)
+        x = np.ascontiguousarray(f["x"], dtype=np.float64).reshape(-1, 3)
+        if len(body) != len(x):
+            raise ValueError("point force: body and x must have one entry per point")
+        keep["pf"].append((body, x))
+        a.kind, a.npts = int(f["kind"]), len(body)
+        a.body, a.x = iptr(body), dptr(x)
+        a.stiffness, a.damping, a.L = float(f["stiffness"]), float(f["damping"]), float(f.get("L", 0.0))
+    return arr, len(pfs)
 
 
 def make_desc(d):

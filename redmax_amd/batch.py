@@ -27,6 +27,14 @@ class BatchSim:
         gc = _abi.make_ground_contact(d, self._keep)      # scene.forces: ForceGroundCuboid
         if gc is not None:
             _abi.check(self._L.rmx_model_set_ground_contact(self._model, C.byref(gc)), "rmx_model_set_ground_contact")
+        pf, npf = _abi.make_point_forces(d, self._keep)   # scene.forces: ForcePointPoint / ForceSpringDamper / ForceCable
+        if npf:
+            rc = self._L.rmx_model_set_point_forces(self._model, pf, npf)
+            if rc != 0:
+                msg = self._L.rmx_last_error()
+                self._L.rmx_model_destroy(self._model)
+                self._model = None
+                raise _abi.RedMaxHipError("rmx_model_set_point_forces failed (%d): %s" % (rc, msg.decode() if msg else "?"))
         self.nsph = self._L.rmx_model_nsph(self._model)
         self.B = int(batch)
         self.device = int(device)
@@ -339,6 +347,9 @@ class GroupSim:
     def __init__(self, scene_or_desc, batch, devices=(0,)):
         d = scene_or_desc.desc() if hasattr(scene_or_desc, "desc") else scene_or_desc
         self._L = _abi.lib()
+        if d.get("point_forces"):
+            raise _abi.RedMaxHipError("GroupSim: rmx_group_create has no slot for point forces (ForcePointPoint / ForceSpringDamper / "
+                                      "ForceCable); use BatchSim")
         self._desc, self._keep = _abi.make_desc(d)
         gc = _abi.make_ground_contact(d, self._keep)
         dev = np.ascontiguousarray(list(devices), dtype=np.int32)

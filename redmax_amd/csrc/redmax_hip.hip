@@ -570,6 +570,7 @@ extern "C" void rmx_model_destroy(rmx_model* m) {
     if (m->dcon) (void)hipFree(m->dcon);
     if (m->dsph) (void)hipFree(m->dsph);
     if (m->dgconst) (void)hipFree(m->dgconst);
+    if (m->dpf) (void)hipFree(m->dpf);
     delete m;
 }
 
@@ -578,6 +579,11 @@ extern "C" void rmx_model_destroy(rmx_model* m) {
 extern "C" int rmx_model_set_ground_contact(rmx_model* m, const rmx_ground_contact* gc) {
     if (!m || !gc || !gc->flags || !gc->sides) return fail(RMX_E_INVALID, "null argument");
     if (!(gc->kn >= 0) || !(gc->kt >= 0) || !(gc->mu >= 0) || !(gc->kd >= 0)) return fail(RMX_E_INVALID, "contact constants must be >= 0");
+    if (m->dpf) {
+        bool any_flag = false;
+        for (int L = 0; L < m->nlist; ++L) any_flag = any_flag || gc->flags[L];
+        if (any_flag) return fail(RMX_E_INVALID, "rmx_model_set_ground_contact: the model has point forces (rmx_model_set_point_forces); ForceGroundCuboid together with them is not supported");
+    }
     HIPCHK(hipSetDevice(m->device));
     const int MAXN = m->dm.stride;        // node stride of the table: rmx::MAXN, or BIG_MAXN for the one-workgroup kernels (rmx_big.hip)
     std::vector<double> con((size_t)NCON * MAXN, 0.0);
@@ -620,6 +626,68 @@ extern "C" int rmx_model_set_ground_contact(rmx_model* m, const rmx_ground_conta
     if (m->dcon) (void)hipFree(m->dcon);
     m->dcon = fresh;
     m->dm.con = (const double*)fresh;
+    return RMX_OK;
+}
+
+// scene.forces{end+1} = ForcePointPoint / ForceSpringDamper / ForceCable (scenesRedMax.m:286-288, 332-337, 365-370): the force table of
+// the kernels around rmx_pf.h.  Bodies arrive by listing index and go through node_of_listing like the contact flags.
+extern "C" int rmx_model_set_point_forces(rmx_model* m, const rmx_point_force* f, int nforces) {
+    if (!m || nforces < 0 || (nforces > 0 && !f)) return fail(RMX_E_INVALID, "null argument");
+    if (nforces > 0) {
+        if (m->big) return fail(RMX_E_INVALID, "rmx_model_set_point_forces: point forces run on the one-wavefront kernels only (models of at most " + std::to_string(rmx::MAXN) + " nodes); this one has " + std::to_string(m->n));
+        if (m->dm.con) return fail(RMX_E_INVALID, "rmx_model_set_point_forces: the model has ForceGroundCuboid (rmx_model_set_ground_contact); point forces together with it are not supported");
+        if (m->dm.nsph) return fail(RMX_E_INVALID, "rmx_model_set_point_forces: point forces together with JointSpherical / JointFree3D are not supported");
+        if (nforces > PF_MAX_FORCES) return fail(RMX_E_INVALID, "rmx_model_set_point_forces: " + std::to_string(nforces) + " forces; the limit is RMX_PF_MAX_FORCES = " + std::to_string(PF_MAX_FORCES));
+    }
+    std::vector<PfTable> tab(1);
+    PfTable& T = tab[0];
+    memset(&T, 0, sizeof(T));
+    T.nf = nforces;
+    int np = 0;
+    for (int i = 0; i < nforces; ++i) {
+        const rmx_point_force& fi = f[i];
+        const std::string who = "rmx_model_set_point_forces: force " + std::to_string(i) + ": ";
+        if (fi.kind != RMX_PF_POINTPOINT && fi.kind != RMX_PF_SPRINGDAMPER && fi.kind != RMX_PF_CABLE) return fail(RMX_E_INVALID, who + "unknown kind (RMX_PF_*)");
+        if (!fi.body || !fi.x) return fail(RMX_E_INVALID, who + "null body / x");
+        if (fi.kind != RMX_PF_CABLE && fi.npts != 2) return fail(RMX_E_INVALID, who + "a point-point force or a spring-damper has exactly 2 points");
+        if (fi.npts < 2 || fi.npts > PF_MAX_POINTS) return fail(RMX_E_INVALID, who + std::to_string(fi.npts) + " points; a force has 2 .. RMX_PF_MAX_POINTS = " + std::to_string(PF_MAX_POINTS));
+        if (np + fi.npts > PF_MAX_TOTAL) return fail(RMX_E_INVALID, who + "more than RMX_PF_MAX_TOTAL = " + std::to_string(PF_MAX_TOTAL) + " points in all forces of the model");
+        if (!std::isfinite(fi.stiffness) || !std::isfinite(fi.damping)) return fail(RMX_E_INVALID, who + "stiffness and damping must be finite");
+        if (fi.kind != RMX_PF_POINTPOINT && !(fi.L > 0 && std::isfinite(fi.L))) return fail(RMX_E_INVALID, who + "the rest length L must be > 0 (the host computes it from the initial configuration: Force.init)");
+        T.first[i] = np;
+        T.kind[i] = fi.kind;
+        T.ks[i] = fi.stiffness;
+        T.kd[i] = fi.damping;
+        T.L[i] = fi.kind == RMX_PF_POINTPOINT ? 1.0 : fi.L;
+        for (int k = 0; k < fi.npts; ++k, ++np) {
+            const int L = fi.body[k];
+            if (L < -1 || L >= m->nlist) return fail(RMX_E_INVALID, who + "body index out of range (listing index, -1 = the world)");
+            T.node[np] = L < 0 ? -1 : m->node_of_listing[L];
+            for (int c = 0; c < 3; ++c) {
+                if (!std::isfinite(fi.x[3 * k + c])) return fail(RMX_E_INVALID, who + "x must be finite");
+                T.xl[np][c] = fi.x[3 * k + c];
+            }
+        }
+    }
+    for (int i = nforces; i <= PF_MAX_FORCES; ++i) T.first[i] = np;
+    HIPCHK(hipSetDevice(m->device));
+    // as rmx_model_set_ground_contact: upload first, drain this model's batches, then swap
+    void* fresh = nullptr;
+    if (nforces > 0) {
+        HIPCHK(hipMalloc(&fresh, sizeof(PfTable)));
+        const hipError_t e = hipMemcpy(fresh, &T, sizeof(PfTable), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(fresh); return fail(RMX_E_HIP, std::string("hipMemcpy(point forces): ") + hipGetErrorString(e)); }
+    }
+    for (rmx_batch* bb : m->batches) {
+        const hipError_t es = hipStreamSynchronize(bb->stream);
+        if (es != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            return fail(RMX_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+        }
+        bb->async_pending = false;
+    }
+    if (m->dpf) (void)hipFree(m->dpf);
+    m->dpf = fresh;
     return RMX_OK;
 }
 extern "C" int rmx_model_nr(const rmx_model* m) { return m ? m->nr : RMX_E_INVALID; }
@@ -781,7 +849,8 @@ extern "C" int rmx_eval(rmx_batch* b, const double* q, const double* qA, const d
         (void)hipMemsetAsync(dH, 0, nv * m->nr * sizeof(double), b->stream);
     }
     if (m->big) launch_big_eval(m, b, H != nullptr, eta, dg, dH);
-    else DISPATCH_NP(m->NP, launch_eval, m, b, H != nullptr, eta, dg, dH);
+    else if (m->dpf) { DISPATCH_NP(m->NP, launch_eval_pf, m, b, H != nullptr, eta, dg, dH); }      // body-to-body forces: the kernels around rmx_pf.h
+    else { DISPATCH_NP(m->NP, launch_eval, m, b, H != nullptr, eta, dg, dH); }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(g, dg, nv * sizeof(double), hipMemcpyDeviceToHost, b->stream);
     if (e == hipSuccess && H) e = hipMemcpyAsync(H, dH, nv * m->nr * sizeof(double), hipMemcpyDeviceToHost, b->stream);
@@ -795,6 +864,7 @@ extern "C" int rmx_eval(rmx_batch* b, const double* q, const double* qA, const d
 extern "C" int rmx_eval_mfd(rmx_batch* b, const double* q, const double* qdot, double* M, double* f, double* D) {
     if (!b || !q || !qdot || !M || !f || !D) return fail(RMX_E_INVALID, "null argument");
     rmx_model* m = b->m;
+    if (m->dpf) return fail(RMX_E_INVALID, "rmx_eval_mfd: models with point forces (rmx_model_set_point_forces) run rmx_eval / rmx_step_bdf1/bdf2 / rmx_energy only");
     if (m->big) return rmx_compute_values(b, q, qdot, nullptr, M, f, D, nullptr, nullptr, nullptr);   // no M / D kernel of their own: from H
     HIPCHK(hipSetDevice(m->device));
     if (int rc = pending_error_check(b, "rmx_eval_mfd")) return rc;
@@ -825,6 +895,7 @@ extern "C" int rmx_compute_values(rmx_batch* b, const double* q, const double* q
     if (!b || !q || !qdot) return fail(RMX_E_INVALID, "null argument");
     if (dMv && !v) return fail(RMX_E_INVALID, "rmx_compute_values: dMv needs v");
     rmx_model* m = b->m;
+    if (m->dpf) return fail(RMX_E_INVALID, "rmx_compute_values: models with point forces (rmx_model_set_point_forces) run rmx_eval / rmx_step_bdf1/bdf2 / rmx_energy only");
     const size_t nr = (size_t)m->nr, nv = (size_t)b->B * nr, nn = nv * nr;
     if (nv == 0) return RMX_OK;
     std::vector<double> qA(nv), qB(nv), g(nv), H1(nn), Mt, Dt, ft;
@@ -996,11 +1067,12 @@ static int launch_step(rmx_batch* b, const rmx_opts* opts, int nsteps, int integ
     // the per-rollout tick counters: the kernels of a call ADD their share (a contact-capable call is up to three launches); the
     // headline kernel (one launch, rmx_kernels.hip RMX_PART 7 - the condition is launch_step_np_32's) stores its count instead, and the
     // fill dispatch ahead of a 0.8 ms launch is saved
-    const bool stores_ticks = !m->big && m->NP == 32 && !m->dm.con && m->dm.nsph == 0 && m->dm.is_chain && m->dm.n == 32 && integ == INTEG_BDF1 && a.pairc;
+    const bool stores_ticks = !m->big && !m->dpf && m->NP == 32 && !m->dm.con && m->dm.nsph == 0 && m->dm.is_chain && m->dm.n == 32 && integ == INTEG_BDF1 && a.pairc;
     if (!stores_ticks) HIPCHK(hipMemsetAsync(b->ticks, 0, sizeof(unsigned long long) * b->B, b->stream));
     HIPCHK(hipEventRecord(b->ev0, b->stream));
     if (m->big) launch_big_step(m, b, integ, o, a);
-    else DISPATCH_NP(m->NP, launch_step_np, m, b, integ, o, a);
+    else if (m->dpf) { DISPATCH_NP(m->NP, launch_step_pf, m, b, integ, o, a); }      // body-to-body forces: the kernels around rmx_pf.h
+    else { DISPATCH_NP(m->NP, launch_step_np, m, b, integ, o, a); }
     // BDF2 keeps (q, qdot) of step k-1 in qp/qdp.  BDF1 steps do not maintain them (and, with JointSpherical, may leave q in
     // another Euler chart than qp), so a BDF1 call invalidates the multistep history: the next rmx_step_bdf2 restarts with
     // SDIRK2, as a fresh driverRedMaxBDF2 run from that state would (driverRedMaxBDF2.m:64-88).
@@ -1184,6 +1256,7 @@ extern "C" int rmx_step_euler(rmx_batch* b, double h, int nsteps, double* hT, do
     if (b->m->dm.con) return fail(RMX_E_INVALID, "rmx_step_euler: matlab-simple has no ForceGroundCuboid; use rmx_step_bdf1/bdf2");
     if (b->m->dm.nsph) return fail(RMX_E_INVALID, "rmx_step_euler: matlab-simple has no JointSpherical; use rmx_step_bdf1/bdf2");
     if (b->m->big) return fail(RMX_E_INVALID, "rmx_step_euler: trees of more than 64 nodes run rmx_step_bdf1/bdf2 only");
+    if (b->m->dpf) return fail(RMX_E_INVALID, "rmx_step_euler: models with point forces (rmx_model_set_point_forces) run rmx_step_bdf1/bdf2 only");
     if (nsteps < 0 || !(h > 0)) return fail(RMX_E_INVALID, "bad nsteps / h");
     if ((hT == nullptr) != (hV == nullptr)) return fail(RMX_E_INVALID, "hist_T and hist_V must be given together");
     rmx_model* m = b->m;
@@ -1228,6 +1301,7 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
     if (m->dm.con) return fail(RMX_E_INVALID, "rmx_adjoint: ground contact is outside the adjoint path (SURVEY.md 8(f))");
     if (m->dm.nsph) return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
     if (m->big) return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
+    if (m->dpf) return fail(RMX_E_INVALID, "rmx_adjoint: point forces (rmx_model_set_point_forces) are outside the adjoint path");
     if (task->body < 0 || task->body >= m->nlist) return fail(RMX_E_INVALID, "task body out of range");
     if (task->step < 1 || task->step > nsteps) return fail(RMX_E_INVALID, "task step must be in [1, nsteps]");
     HIPCHK(hipSetDevice(m->device));
@@ -1435,7 +1509,8 @@ extern "C" int rmx_energy(rmx_batch* b, double* T, double* V) {
     hipError_t e = hipMalloc((void**)&dV, sizeof(double) * b->B);
     if (e != hipSuccess) { (void)hipFree(dT); return fail(RMX_E_NOMEM, "hipMalloc(energy)"); }
     if (m->big) launch_big_energy(m, b, dT, dV);
-    else DISPATCH_NP(m->NP, launch_energy, m, b, dT, dV);
+    else if (m->dpf) { DISPATCH_NP(m->NP, launch_energy_pf, m, b, dT, dV); }
+    else { DISPATCH_NP(m->NP, launch_energy, m, b, dT, dV); }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(T, dT, sizeof(double) * b->B, hipMemcpyDeviceToHost, b->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(V, dV, sizeof(double) * b->B, hipMemcpyDeviceToHost, b->stream);

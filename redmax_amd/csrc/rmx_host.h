@@ -9,6 +9,7 @@
 
 #include "redmax_hip_profile.h"   /* redmax_hip.h + the measurement hooks */
 #include "rmx_device.h"
+#include "rmx_pf.h"
 
 using namespace rmx;
 
@@ -77,6 +78,7 @@ struct rmx_model {
     int w2_max_batch = 0;           // 33..64-node trees / the full 32-link chain: batches of up to this many rollouts take two wavefronts each (0: never; RMX_W2_MAX)
     int adj_help_max_batch = 0;     // trees of <= 16 nodes: adjoint batches of up to this many rollouts take a second wavefront each for M, D (rmx_kernels.hip RMX_PART 8; 0: never)
     int w2_min_batch = 0;           // the full 32-link chain: ... and of at least this many (RMX_W2C_MIN; smaller batches keep the one-wave kernel every test pins)
+    void* dpf = nullptr;            // body-to-body forces (rmx_model_set_point_forces): the PfTable of rmx_pf.h on the device, or null
     bool big = false;               // more than 64 nodes: the one-workgroup-per-tree kernels of rmx_big.hip
     bool pair32 = false;            // serial chain of <= 32 nodes with ForceGroundCuboid, no Euler-chart joints: the kernels around newton_pair
     std::vector<struct rmx_batch*> batches;   // live batches of this model (rmx_model_set_ground_contact drains their streams only)
@@ -139,7 +141,10 @@ struct rmx_batch {
     void RMX_CAT(launch_eval_ct_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
     void RMX_CAT(launch_step_ct_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_energy_ct_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
-    void RMX_CAT(launch_step_fullchain_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
+    void RMX_CAT(launch_step_fullchain_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
+    void RMX_CAT(launch_eval_pf_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
+    void RMX_CAT(launch_step_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
+    void RMX_CAT(launch_energy_pf_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV);
 // 64-lane plain step kernels reading the per-node constants from global memory (rmx_kernels.hip RMX_PART 3) and the staging kernel
 void launch_step_gconst_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
 void launch_step_fulln_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);

@@ -136,7 +136,7 @@ def _main(argv=None):
     listed scenes (default: every scene this build covers), printing the reference's '### PASS ###' line per scene."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m redmax_amd.driver", description=_main.__doc__)
-    ap.add_argument("scenes", nargs="*", type=int, default=[0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 14])
+    ap.add_argument("scenes", nargs="*", type=int, default=list(range(15)))
     ap.add_argument("--bdf2", action="store_true", help="driverRedMaxBDF2 instead of driverRedMaxBDF1")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)

@@ -13,8 +13,8 @@ Only what the path needs is mirrored: Body/BodyCuboid (Body.m, BodyCuboid.m),
 Joint + JointRevolute/JointPrismatic/JointFixed (Joint.m, JointRevolute.m,
 JointPrismatic.m, JointFixed.m), the multi-DOF joints whose motion is a product of one-parameter motions
 (JointPlanar.m, JointTranslational.m, JointUniversal.m, JointFree2D.m; rmx_model_create lowers them to chains of
-1-DOF nodes with massless links), ForceGroundCuboid and Scene (Scene.m init/reset/saveHistory/plotEnergies).
-Drawing, FD self-tests, JointSpherical/JointFree3D and the other force types are out of scope.
+1-DOF nodes with massless links), ForceGroundCuboid, the body-to-body forces ForcePointPoint / ForceSpringDamper / ForceCable
+and Scene (Scene.m init/reset/saveHistory/plotEnergies).  Drawing and the FD self-tests are out of scope.
 """
 from __future__ import annotations
 
@@ -271,6 +271,105 @@ class ForceGroundCuboid:
         return (self.kn, self.kt, self.mu, self.kd) + tuple(self.E.reshape(-1))
 
 
+PF_POINTPOINT, PF_SPRINGDAMPER, PF_CABLE = 0, 1, 2      # rmx_point_force.kind (include/redmax_hip.h)
+
+
+class _PointForce:
+    """What the three body-to-body forces share: a polyline of (body, local point) pairs - a body of None is the world - a
+    stiffness, a damping and (kinds 1, 2) a rest length that ``Scene.init`` takes from the initial configuration unless
+    ``setRetLength`` gave one (ForceSpringDamper.m:37-60, ForceCable.m:37-64)."""
+    kind = None
+
+    def __init__(self):
+        self.bodies = []
+        self.xls = []
+        self.stiffness = 1.0
+        self.damping = 1.0
+        self.L = 0.0
+
+    def _name(self):
+        return "-".join(b.name if b is not None else "NULL" for b in self.bodies)
+
+    def setStiffness(self, stiffness):
+        self.stiffness = float(stiffness)
+
+    def setDamping(self, damping):
+        self.damping = float(damping)
+
+    def _add(self, body, xl):
+        if isinstance(body, (list, tuple)) and len(body) == 0:      # MATLAB's [] for the world
+            body = None
+        self.bodies.append(body)
+        self.xls.append(np.array(xl, dtype=np.float64).reshape(3))
+
+
+class ForcePointPoint(_PointForce):
+    """Linear zero-rest-length spring + damper between two points, f = ks dx + kd dv, V = ks |dx|^2 / 2
+    (matlab-diff/+redmax/ForcePointPoint.m:15-34, 50-133)."""
+    kind = PF_POINTPOINT
+
+    def __init__(self, body1, x_1, body2, x_2):
+        super().__init__()
+        self.damping = 0.0                   # ForcePointPoint.m:32-33
+        self._add(body1, x_1)
+        self._add(body2, x_2)
+        self.name = self._name()
+
+
+class ForceSpringDamper(_PointForce):
+    """Strain spring between two points, fs = k (l - L)/L + d ldot/L, V = k/2 ((l - L)/L)^2 L
+    (ForceSpringGeneric.m:37-176, ForceSpringDamper.m:12-71)."""
+    kind = PF_SPRINGDAMPER
+
+    def __init__(self, body1, x_1, body2, x_2):
+        super().__init__()
+        self._add(body1, x_1)
+        self._add(body2, x_2)
+        self.name = self._name()
+
+    def setRetLength(self, L):
+        self.L = float(L)
+
+
+class ForceCable(_PointForce):
+    """One scalar tension from the total length of a polyline through 2..P points, zero while slack
+    (ForceSpringMultiPointGeneric.m:28-190, ForceCable.m:12-82)."""
+    kind = PF_CABLE
+
+    def __init__(self):
+        super().__init__()
+        self.name = "cable"
+
+    def addBodyPoint(self, body, xl):
+        self._add(body, xl)
+        self.name = self._name()
+
+    def setRetLength(self, L):
+        self.L = float(L)
+
+
+def _joint_motion(j):
+    """Q(q) of a joint (the *.update_ methods of the reference) - only for the rest lengths ``Scene.init`` computes."""
+    Q = np.eye(4)
+    q = j.q
+    if j.jtype == JOINT_REVOLUTE:
+        Q[:3, :3] = se3.aaToMat(j.axis, q[0])
+    elif j.jtype == JOINT_PRISMATIC:
+        Q[:3, 3] = j.axis * q[0]
+    elif j.jtype == JOINT_PLANAR:
+        Q[:3, 3] = j.plane @ q[:2]
+    elif j.jtype == JOINT_TRANSLATIONAL:
+        Q[:3, 3] = q[:3]
+    elif j.jtype == JOINT_UNIVERSAL:
+        Q[:3, :3] = se3.aaToMat([1, 0, 0], q[0]) @ se3.aaToMat([0, 1, 0], q[1])
+    elif j.jtype == JOINT_FREE2D:
+        Q[:3, :3] = se3.aaToMat([0, 0, 1], q[2])
+        Q[:2, 3] = q[:2]
+    elif j.jtype != JOINT_FIXED:
+        raise NotImplementedError("point forces together with JointSpherical / JointFree3D are not supported")
+    return Q
+
+
 class Scene:
     """Scene container (matlab-diff/+redmax/Scene.m).
 
@@ -313,8 +412,14 @@ class Scene:
         if any(j.body is not b for j, b in zip(joints, self.bodies)):
             raise ValueError("bodies must be listed in the same order as their joints")
         for f in self.forces:
+            if isinstance(f, _PointForce):
+                if len(f.bodies) < 2:
+                    raise ValueError("%s needs at least two points" % type(f).__name__)
+                if any(b is not None and all(b is not c for c in self.bodies) for b in f.bodies):
+                    raise ValueError("%s: every body must be a body of this scene (or None for the world)" % type(f).__name__)
+                continue
             if not isinstance(f, ForceGroundCuboid):
-                raise NotImplementedError("only ForceNull and ForceGroundCuboid are in scope (SURVEY.md §2 row 10)")
+                raise NotImplementedError("force type %s is not in scope (SURVEY.md §2 row 10)" % type(f).__name__)
             if not isinstance(f.cuboid, BodyCuboid) or f.cuboid not in self.bodies:
                 raise ValueError("ForceGroundCuboid needs a BodyCuboid of this scene")
         nr = 0
@@ -333,11 +438,40 @@ class Scene:
         for b in self.bodies:
             b.computeInertia()
         self.qInit, self.qdotInit = self.getQ()
+        self._init_point_forces()
         self.nsteps = int(math.ceil(self.tEnd / self.h))
         self._desc = None
         self.t = 0.0
         self.k = 0
         self.history = []
+
+    def pointForces(self):
+        return [f for f in self.forces if isinstance(f, _PointForce)]
+
+    def bodyTransforms(self):
+        """E_wi of every body at the joints' current q (Joint.update :401-408, Body.update :70-72), in listing order."""
+        E = {}
+        out = []
+        for j in self.joints:
+            Ewp = np.eye(4) if j.parent is None else E[id(j.parent)] @ se3.inv(j.parent.body.E0_ji)
+            Ewj = Ewp @ (j.E0_pj if j.E0_pj is not None else np.eye(4)) @ _joint_motion(j)
+            E[id(j)] = Ewj @ j.body.E0_ji
+            out.append(E[id(j)])
+        return out
+
+    def _init_point_forces(self):
+        """Force.init (ForceSpringDamper.m:37-60, ForceCable.m:37-64): the rest length is the initial length of the polyline."""
+        pfs = self.pointForces()
+        if not pfs:
+            return
+        Ew = {id(b): E for b, E in zip(self.bodies, self.bodyTransforms())}
+        for f in pfs:
+            if f.kind == PF_POINTPOINT or f.L > 0:
+                continue
+            xw = [x if b is None else Ew[id(b)][:3, :3] @ x + Ew[id(b)][:3, 3] for b, x in zip(f.bodies, f.xls)]
+            f.L = float(sum(np.linalg.norm(xw[k + 1] - xw[k]) for k in range(len(xw) - 1)))
+            if not f.L > 0:
+                raise ValueError("%s %s: the initial length is zero; give a rest length with setRetLength" % (type(f).__name__, f.name))
 
     # -- gather / scatter in the reference's reduced ordering (Joint.getQ / setQ) --
     def getQ(self):
@@ -392,16 +526,24 @@ class Scene:
             "qdotR": self.getQ()[1],
             "qRestR": np.concatenate([np.zeros(0)] + [getattr(j, "qRestAll", np.array(j.q[:j.ndof], dtype=np.float64)) for j in reversed(joints)]),
         }
-        if self.forces:
+        pfs = self.pointForces()
+        if pfs:
+            # body-to-body forces (rmx_model_set_point_forces): bodies by listing index, -1 = the world
+            bidx = {id(b): i for i, b in enumerate(self.bodies)}
+            d["point_forces"] = [{"kind": f.kind, "body": np.array([-1 if b is None else bidx[id(b)] for b in f.bodies], dtype=np.int32),
+                                  "x": np.ascontiguousarray(np.stack(f.xls), dtype=np.float64), "stiffness": f.stiffness,
+                                  "damping": f.damping, "L": f.L} for f in pfs]
+        ground = [f for f in self.forces if isinstance(f, ForceGroundCuboid)]
+        if ground:
             # The reference keeps its force objects in a list (Force.m:26-56, Scene.m:87-89): a body may carry several
             # ForceGroundCuboid (a floor and a wall).  The C ABI takes ONE per listing entry (rmx_ground_contact: flags[n], E_body[n] ...),
             # so the second, third ... force of a body is listed as a fixed, massless child of that body's joint with the body's own
             # transform and sides: the same corners moving with the same twist, hence the same wrench, K and D blocks pulled through the
             # same Jacobian rows - as the multi-DOF joints are chains with massless links.  No DOF is added: q, qdot, idxR are unchanged.
             first = {}
-            for f in self.forces:
+            for f in ground:
                 first.setdefault(id(f.cuboid), f)
-            extra = [f for f in self.forces if first[id(f.cuboid)] is not f]
+            extra = [f for f in ground if first[id(f.cuboid)] is not f]
             body_joint = {id(j.body): i for i, j in enumerate(joints)}
             lit = None
             if extra:
@@ -418,7 +560,7 @@ class Scene:
                 d["qLimL"] = np.concatenate([d["qLimL"], np.full(len(extra), -np.inf)])
                 d["qLimU"] = np.concatenate([d["qLimU"], np.full(len(extra), np.inf)])
                 d["njoints"] = n + len(extra)
-            f0 = self.forces[0]
+            f0 = ground[0]
             flag = [1 if id(j.body) in first else 0 for j in joints]
             sides = [getattr(j.body, "sides", np.zeros(3)) for j in joints]
             fb = [first.get(id(j.body), f0) for j in joints]
@@ -431,7 +573,7 @@ class Scene:
                 return {"E": np.stack([np.asarray(f.E, dtype=np.float64) for f in fs]),
                         "kn": np.array([f.kn for f in fs], dtype=np.float64), "kt": np.array([f.kt for f in fs], dtype=np.float64),
                         "mu": np.array([f.mu for f in fs], dtype=np.float64), "kd": np.array([f.kd for f in fs], dtype=np.float64)}
-            same = all(np.array_equal(f.E, f0.E) and (f.kn, f.kt, f.mu, f.kd) == (f0.kn, f0.kt, f0.mu, f0.kd) for f in self.forces)
+            same = all(np.array_equal(f.E, f0.E) and (f.kn, f.kt, f.mu, f.kd) == (f0.kn, f0.kt, f0.mu, f0.kd) for f in ground)
             if not same:
                 d["ground_body"] = per_entry(fb + extra)
             if lit is not None:

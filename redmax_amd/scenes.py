@@ -13,7 +13,7 @@ import math
 import numpy as np
 
 from . import se3
-from .redmax import (BodyCuboid, ForceGroundCuboid, JointFixed, JointFree2D, JointFree3D, JointPlanar, JointPrismatic,
+from .redmax import (BodyCuboid, ForceCable, ForceGroundCuboid, ForcePointPoint, ForceSpringDamper, JointFixed, JointFree2D, JointFree3D, JointPlanar, JointPrismatic,
                      JointRevolute, JointSpherical, JointTranslational, JointUniversal, Scene)
 
 BDF1 = 1
@@ -232,6 +232,79 @@ def scenesRedMax(sceneID):
         f.setDamping(3e1)
         f.setFriction(0.5)
         scene.forces = [f]
+    elif sceneID == 10:
+        # scenesRedMax.m:261-289 'Loop': two branches closed by a stiff ForcePointPoint.  The reference lists joint 3 (the second
+        # child of joint 1) between joints 2 and 4; Scene.init wants the listing depth-first, so it is listed 1, 2, 4, 5, 3 here.
+        # That renumbers the DOFs (reduced indices run from the last listed joint to the first) and changes no energy.
+        scene.name = "Loop"
+        scene.Hexpected[BDF1 - 1] = 1.2376477982839792e03     # :264
+        scene.Hexpected[BDF2 - 1] = 4.1146190850293169e03     # :265
+        dims = ([20, 1, 1], [1, 1, 10], [1, 1, 10], [20, 1, 1], [1, 1, 10])
+        b = [BodyCuboid(density, dd) for dd in dims]
+        j1 = JointFixed(None, b[0])
+        j2 = JointRevolute(j1, b[1], [0, 1, 0])
+        j4 = JointRevolute(j2, b[3], [0, 1, 0])
+        j5 = JointRevolute(j4, b[4], [0, 1, 0])
+        j3 = JointRevolute(j1, b[2], [0, 1, 0])
+        for bb, pp in zip(b, ([0, 0, 0], [0, 0, -5], [0, 0, -5], [10, 0, 0], [0, 0, -5])):
+            bb.setBodyTransform(_T(pp))
+        for jj, pp in zip((j1, j2, j3, j4, j5), ([0, 0, 0], [-10, 0, 0], [10, 0, 0], [0, 0, -10], [10, 0, 0])):
+            jj.setJointTransform(_T(pp))
+        j5.qdot[0] = 5.0                                      # :289
+        scene.bodies = [b[0], b[1], b[3], b[4], b[2]]
+        scene.joints = [j1, j2, j4, j5, j3]
+        f = ForcePointPoint(b[2], [0, 0, -5], b[3], [10, 0, 0])   # :286-288
+        f.setStiffness(1e7)
+        f.setDamping(0)
+        scene.forces = [f]
+    elif sceneID == 12:
+        # scenesRedMax.m:312-337 'Spring-damper': a world-anchored spring and one between the two links
+        scene.name = "Spring-damper"
+        scene.Hexpected[BDF1 - 1] = -2.2145412057327565e04    # :314
+        scene.Hexpected[BDF2 - 1] = -8.9887693524038732e03    # :315
+        b = [BodyCuboid(density, [10, 1, 1]) for _ in range(2)]
+        j1 = JointRevolute(None, b[0], [0, 1, 0])
+        j1.setJointTransform(np.eye(4))
+        j2 = JointRevolute(j1, b[1], [0, 1, 0])
+        j2.setJointTransform(_T([10, 0, 0]))
+        for bb in b:
+            bb.setBodyTransform(_T([5, 0, 0]))
+        scene.bodies, scene.joints = b, [j1, j2]
+        f1 = ForceSpringDamper(None, [-5, 0, -5], b[1], [0, 0, -2])
+        f2 = ForceSpringDamper(b[0], [0, 0, 2], b[1], [0, 0, 2])
+        for f in (f1, f2):
+            f.setStiffness(1e6)
+            f.setDamping(1e3)
+        scene.forces = [f1, f2]
+    elif sceneID == 13:
+        # scenesRedMax.m:338-370 'Cables': a cable from a sprung slider through two points of a double pendulum
+        scene.name = "Cables"
+        scene.Hexpected[BDF1 - 1] = -3.1874892332895153e04    # :340
+        scene.Hexpected[BDF2 - 1] = -2.7872894793863266e04    # :341
+        b = [BodyCuboid(density, [0.1, 0.1, 0.1]), BodyCuboid(density, [10, 1, 1]), BodyCuboid(density, [10, 1, 1]),
+             BodyCuboid(density, [1, 1, 1])]
+        j1 = JointFixed(None, b[0])
+        j2 = JointRevolute(j1, b[1], [0, 1, 0])
+        j2.setJointTransform(np.eye(4))
+        b[1].setBodyTransform(_T([5, 0, 0]))
+        j2.q[0] = math.pi / 2
+        j3 = JointRevolute(j2, b[2], [0, 1, 0])
+        j3.setJointTransform(_T([10, 0, 0]))
+        b[2].setBodyTransform(_T([5, 0, 0]))
+        j3.q[0] = -math.pi / 2
+        j4 = JointPrismatic(j1, b[3], [1, 0, 0])
+        j4.setJointTransform(_T([10, 0, 0]))
+        b[3].setBodyTransform(np.eye(4))
+        j4.setStiffness(1e4)
+        j4.setDamping(1e3)
+        scene.bodies, scene.joints = b, [j1, j2, j3, j4]
+        f = ForceCable()
+        f.setStiffness(1e6)
+        f.setDamping(1e3)
+        f.addBodyPoint(b[3], [0, 0, 0])
+        f.addBodyPoint(b[1], [-4, 0, 1])
+        f.addBodyPoint(b[2], [-4, 0, 1])
+        scene.forces = [f]
     elif sceneID == 100:
         return sceneAdjointChain(2)                            # scenesRedMax.m:402-436 ('Adjoint BDF1')
     elif sceneID == 101:
@@ -244,6 +317,7 @@ def scenesRedMax(sceneID):
 IN_SCOPE_SCENES = (0, 1, 2, 3, 14)          # 0/1-DOF joints only
 COMPOSITE_SCENES = (4, 5, 6, 8)             # JointPlanar / Translational / Free2D / Universal (lowered to 1-DOF chains)
 SPHERICAL_SCENES = (7, 9)                   # JointSpherical / JointFree3D (Euler charts with switching)
+POINT_FORCE_SCENES = (10, 12, 13)           # ForcePointPoint / ForceSpringDamper / ForceCable (body-to-body forces)
 
 
 def sceneAdjointChain(n=2, bdf2=False):
@@ -284,6 +358,29 @@ def sceneChain(n=32, axis=(0, 1, 0), q0=0.0):
         scene.joints[-1].setJointTransform(np.eye(4) if i == 0 else _T([10, 0, 0]))
         scene.bodies[-1].setBodyTransform(_T([5, 0, 0]))
         scene.joints[-1].q[0] = q0
+    return scene
+
+
+def sceneChainSprings(n=32):
+    """The n-link chain of sceneChain with the three body-to-body forces on it: a world-anchored ForceSpringDamper on the tip,
+    a ForcePointPoint between two links a quarter of the chain apart and a three-point ForceCable (a synthetic load case for
+    the point-force kernels; n >= 8)."""
+    scene = sceneChain(n)
+    scene.name = "%d-link chain with springs and a cable" % n
+    b = scene.bodies
+    f1 = ForceSpringDamper(None, [10.0 * n, 0, -5.0], b[n - 1], [5, 0, 0])
+    f1.setStiffness(1e4)
+    f1.setDamping(1e2)
+    f2 = ForcePointPoint(b[n // 2], [0, 0, -0.5], b[n // 2 + n // 4], [0, 0, -0.5])
+    f2.setStiffness(1e2)
+    f2.setDamping(1e1)
+    f3 = ForceCable()
+    f3.setStiffness(1e5)
+    f3.setDamping(1e2)
+    f3.addBodyPoint(b[0], [0, 0, 1])
+    f3.addBodyPoint(b[n // 4], [0, 0, 1])
+    f3.addBodyPoint(b[n // 2 - 1], [2, 0, 1])
+    scene.forces = [f1, f2, f3]
     return scene
 
 

@@ -21,6 +21,10 @@ ROWS = (  # (name fragment, what it runs)
     ("k_step_bdf1<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF1"),
     ("k_step_bdf2<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF2"),
     ("k_big_step", "trees of 65..256 nodes (one workgroup per rollout)"),
+    ("k_step_pf<32, 1>", "body-to-body forces (rmx_pf.h), <= 32 nodes, BDF1"),
+    ("k_step_pf<32, 2>", "body-to-body forces, <= 32 nodes, BDF2"),
+    ("k_step_pf<64, 1>", "body-to-body forces, 33..64 nodes, BDF1"),
+    ("k_step_pf<64, 2>", "body-to-body forces, 33..64 nodes, BDF2"),
 )
 
 
