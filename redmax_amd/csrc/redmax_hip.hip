@@ -122,6 +122,21 @@ void m3v(const double A[9], const double x[3], double y[3]) {
 
 // Scene.init() for a listing of fixed / revolute / prismatic joints.  idx_explicit (or NULL): reduced index of every listed
 // joint, given when the listing is the lowered form of a scene with multi-DOF joints (rmx_model_create below).
+// The environment variables a model reads, once, when it is created (tests set them before they create it; the per-call switches
+// are rmx_select.h's StepKnobs).
+struct ModelEnv {
+    int lds_limit;        // RMX_BIG_LDS_LIMIT: development aid (0: H of large trees stays in HBM); default: the device's limit
+    bool tree_solve;      // RMX_TREE_SOLVE=0: the dense guarded solve for every tree (tests)
+    int gconst_min;       // RMX_GCONST_MIN: 33..64-node trees, batches from this size on read the constants from global memory
+    int w2_max, w2c_min;  // RMX_W2_MAX, RMX_W2C_MIN: the batch sizes that take two wavefronts per rollout (w2c_min: the full 32-link chain)
+};
+static ModelEnv model_env(const int n_simd, const int lds_limit) {
+    using rmx_select::env_int;
+    return ModelEnv{env_int("RMX_BIG_LDS_LIMIT", lds_limit), env_int("RMX_TREE_SOLVE", 1) != 0,
+                    env_int("RMX_GCONST_MIN", n_simd > 0 ? n_simd / 2 + 1 : 513), env_int("RMX_W2_MAX", n_simd > 0 ? n_simd / 2 : 512),
+                    env_int("RMX_W2C_MIN", 128)};
+}
+
 static int model_create_flat(const rmx_model_desc* d, const int* idx_explicit, const std::vector<int>* sph_first, int device,
                              rmx_model** out) {
     if (!d || !out) return fail(RMX_E_INVALID, "null argument");
@@ -350,8 +365,9 @@ static int model_create_flat(const rmx_model_desc* d, const int* idx_explicit, c
             const bool shader_rate = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && prop.clockRate > 0;
             m->coop_ticks = shader_rate ? 2000ull * (unsigned long long)prop.clockRate : 200000000ull;
         }
-        if (const char* lim = getenv("RMX_BIG_LDS_LIMIT")) m->lds_limit = atoi(lim);     // development aid (0: H of large trees stays in HBM)
     }
+    const ModelEnv env = model_env(m->n_simd, m->lds_limit);
+    m->lds_limit = env.lds_limit;
     if (hipSetDevice(device) != hipSuccess) { delete m; return fail(RMX_E_HIP, "hipSetDevice failed"); }
     // the tree as the multifrontal solve of 33..64-node branching trees walks it (DevModel::tree, tree_solve64 in rmx_device.h)
     std::vector<int> tree((size_t)TREE_ROWS * NS, -1);
@@ -381,8 +397,7 @@ static int model_create_flat(const rmx_model_desc* d, const int* idx_explicit, c
             }
         }
         if (!ok || tree_dmax < 1) tree_dmax = 0;
-        const char* ts = getenv("RMX_TREE_SOLVE");             // 0: the dense guarded solve for every tree (tests)
-        if (ts && atoi(ts) == 0) tree_dmax = 0;
+        if (!env.tree_solve) tree_dmax = 0;
     }
     const size_t nd = K.size() + sb.size() + I4.size() + prm.size();
     const size_t ni = type.size() + idx.size() + endd.size() + anc.size() + tree.size();
@@ -437,19 +452,15 @@ static int model_create_flat(const rmx_model_desc* d, const int* idx_explicit, c
             return fail(RMX_E_HIP, msg);
         }
         m->dm.gconst = (const double*)m->dgconst;
-        const char* thr = getenv("RMX_GCONST_MIN");
-        m->gconst_min_batch = thr ? atoi(thr) : (m->n_simd > 0 ? m->n_simd / 2 + 1 : 513);
-        // ... and batches of at most one rollout per two SIMDs the two-wave kernels (rmx_kernels.hip RMX_PART 5)
-        const char* w2 = getenv("RMX_W2_MAX");
-        m->w2_max_batch = w2 ? atoi(w2) : (m->n_simd > 0 ? m->n_simd / 2 : 512);
     }
-    if (m->NP == 32 && nsph == 0 && m->dm.is_chain && m->dm.n == 32) {
-        // the full 32-link chain (BASELINE.json configs[1]) in shards of 128 .. one rollout per two SIMDs: the two-wave kernel of
-        // rmx_kernels.hip RMX_PART 6 (RMX_W2_MAX / RMX_W2C_MIN move the bounds)
-        const char* w2 = getenv("RMX_W2_MAX");
-        const char* w2m = getenv("RMX_W2C_MIN");
-        m->w2_max_batch = w2 ? atoi(w2) : (m->n_simd > 0 ? m->n_simd / 2 : 512);
-        m->w2_min_batch = w2m ? atoi(w2m) : 128;
+    // the batch sizes at which rmx_select.h changes kernels (one rollout per two SIMDs = one two-wave workgroup per CU pair of SIMDs)
+    if (m->NP == 64 && nsph == 0) {      // RMX_PART 3 from gconst_min_batch rollouts on, RMX_PART 5 up to w2_max_batch
+        m->gconst_min_batch = env.gconst_min;
+        m->w2_max_batch = env.w2_max;
+    }
+    if (m->NP == 32 && nsph == 0 && m->dm.is_chain && m->dm.n == 32) {      // the full 32-link chain (BASELINE.json configs[1]): RMX_PART 6
+        m->w2_max_batch = env.w2_max;
+        m->w2_min_batch = env.w2c_min;
     }
     if (m->NP == 16 && !big) m->adj_help_max_batch = m->n_simd > 0 ? m->n_simd / 2 : 512;      // (one rollout per two SIMDs)
     *out = m;
@@ -977,6 +988,20 @@ extern "C" int rmx_compute_values(rmx_batch* b, const double* q, const double* q
     return RMX_OK;
 }
 
+using rmx_select::AdjKernel;
+using rmx_select::StepKernel;
+// what rmx_select.h's choice of kernel depends on, from the model and its device
+static rmx_select::StepTraits step_traits(const rmx_model* m) {
+    rmx_select::StepTraits t;
+    t.NP = m->NP; t.n = m->dm.n; t.big = m->big;
+    t.point_forces = m->dpf != nullptr; t.contact = m->dm.con != nullptr; t.spherical = m->dm.nsph > 0;
+    t.is_chain = m->dm.is_chain; t.gconst = m->dm.gconst != nullptr;
+    t.n_simd = m->n_simd; t.coop_g = COOP_G;
+    t.w2_max_batch = m->w2_max_batch; t.w2_min_batch = m->w2_min_batch;
+    t.gconst_min_batch = m->gconst_min_batch; t.adj_help_max_batch = m->adj_help_max_batch;
+    return t;
+}
+
 static int make_opts(const rmx_batch* b, const rmx_opts* o, DevOpts& d) {
     rmx_opts def;
     rmx_opts_default(&def);
@@ -998,7 +1023,7 @@ static int make_opts(const rmx_batch* b, const rmx_opts* o, DevOpts& d) {
 
 static int launch_step(rmx_batch* b, const rmx_opts* opts, int nsteps, int integ, bool with_stats, double* dT, double* dV,
                        double* dQ = nullptr, double* dQd = nullptr, int* dC = nullptr) {
-    rmx_model* m = b->m;
+    const rmx_model* m = b->m;
     DevOpts o;
     int rc = make_opts(b, opts, o);
     if (rc) return rc;
@@ -1014,17 +1039,15 @@ static int launch_step(rmx_batch* b, const rmx_opts* opts, int nsteps, int integ
     a.ticks = b->ticks;
     rc = pending_error_check(b, "rmx_step");
     if (rc) return rc;
+    const rmx_select::StepKnobs knobs = rmx_select::knobs_from_env();
+    const rmx_select::StepPlan plan = rmx_select::select_step(step_traits(m), b->B, integ, dT != nullptr, knobs);
+    b->last_kernel = plan.label;
     // Park and relaunch (rmx_device.h CoopCtx): serial chains of <= 32 nodes with ForceGroundCuboid.  A rollout whose Newton solve keeps
     // running out its line searches is parked by the launch with the contact terms and finished by groups of COOP_G wavefronts that
     // evaluate the reference's trial points side by side - same decisions, same results, the launch no longer waits for one wavefront
     // walking through 20 trials 320 times.  RMX_PARK_HALVINGS=0 switches it off (one wavefront per rollout throughout).
-    o.parkHalv = 0;
-    m->pair32 = !m->big && m->NP == 32 && m->dm.con && m->dm.is_chain && m->dm.nsph == 0;
-    if (m->pair32 && m->n_simd >= COOP_G && b->B >= 1) {
-        const char* e = getenv("RMX_PARK_HALVINGS");       // (read at every call: tests and tools switch it inside one process)
-        o.parkHalv = e ? atoi(e) : 24;
-    }
-    if (o.parkHalv > 0) {
+    o.parkHalv = plan.park_halvings;
+    if (plan.parks) {
         // buffers for the most groups a launch of this batch can ever hold (it alone on the device); each under its own check, so that a
         // failed allocation leaves nothing half set up for the next call
         const int cap = std::min(b->B, m->n_simd / COOP_G);
@@ -1045,34 +1068,42 @@ static int launch_step(rmx_batch* b, const rmx_opts* opts, int nsteps, int integ
         a.xch = b->xch;
         a.xrec = b->xrec;
         a.ngroups = b->ngroups;
-        const char* cm = getenv("RMX_COOP_MAP");
-        a.coop_map = cm ? atoi(cm) : 0;
+        a.coop_map = knobs.coop_map;
     }
-    {
-        const char* ra = getenv("RMX_W2_RUNAHEAD");
-        a.w2_noahead = (ra && atoi(ra) == 0) ? 1 : 0;
-        const char* pc = getenv("RMX_PAIRC");        // (read at every call, like the others: tests switch it inside one process)
-        a.pairc = (pc && atoi(pc) == 0) ? 0 : 1;
-    }
-    if (m->pair32) {
-        // RMX_GROUND_FUSED: 1 (default) ONE launch for the whole call - the rollouts (free flight, then the steps with the contact terms)
-        // and, behind them in dispatch order, the cooperative groups that pick the parked rollouts up as they appear: no launch
-        // boundary holds a rollout back (rmx_kernels.hip k_ground32); 2 the groups in a second launch; 0 three launches (lean, contact
-        // terms, groups); 3 measurement aid (the groups as a second launch of k_ground32)
-        const char* f = getenv("RMX_GROUND_FUSED");
-        a.fused = f ? atoi(f) : 1;
-        if (a.fused == 1 && o.parkHalv <= 0) a.fused = 2;
-        if (a.fused && !b->gargs) HIPCHK(hipMalloc(&b->gargs, RMX_GARGS_BYTES));
-    }
+    a.w2_noahead = knobs.w2_runahead ? 0 : 1;
+    a.pairc = knobs.pairc ? 1 : 0;
+    // RMX_GROUND_FUSED: 1 (default) ONE launch for the whole call - the rollouts (free flight, then the steps with the contact terms)
+    // and, behind them in dispatch order, the cooperative groups that pick the parked rollouts up as they appear: no launch
+    // boundary holds a rollout back (rmx_kernels.hip k_ground32); 2 the groups in a second launch; 0 three launches (lean, contact
+    // terms, groups); 3 measurement aid (the groups as a second launch of k_ground32)
+    a.fused = plan.fused;
+    if (plan.kernel == StepKernel::Ground32 && !b->gargs) HIPCHK(hipMalloc(&b->gargs, RMX_GARGS_BYTES));
     // the per-rollout tick counters: the kernels of a call ADD their share (a contact-capable call is up to three launches); the
-    // headline kernel (one launch, rmx_kernels.hip RMX_PART 7 - the condition is launch_step_np_32's) stores its count instead, and the
-    // fill dispatch ahead of a 0.8 ms launch is saved
-    const bool stores_ticks = !m->big && !m->dpf && m->NP == 32 && !m->dm.con && m->dm.nsph == 0 && m->dm.is_chain && m->dm.n == 32 && integ == INTEG_BDF1 && a.pairc;
-    if (!stores_ticks) HIPCHK(hipMemsetAsync(b->ticks, 0, sizeof(unsigned long long) * b->B, b->stream));
+    // headline kernel (one launch, rmx_kernels.hip RMX_PART 7) stores its count instead, and the fill dispatch ahead of a 0.8 ms
+    // launch is saved
+    if (!plan.stores_ticks) HIPCHK(hipMemsetAsync(b->ticks, 0, sizeof(unsigned long long) * b->B, b->stream));
     HIPCHK(hipEventRecord(b->ev0, b->stream));
-    if (m->big) launch_big_step(m, b, integ, o, a);
-    else if (m->dpf) { DISPATCH_NP(m->NP, launch_step_pf, m, b, integ, o, a); }      // body-to-body forces: the kernels around rmx_pf.h
-    else { DISPATCH_NP(m->NP, launch_step_np, m, b, integ, o, a); }
+    switch (plan.kernel) {
+        case StepKernel::Big: launch_big_step(m, b, integ, o, a); break;
+        case StepKernel::PointForces: DISPATCH_NP(m->NP, launch_step_pf, m, b, integ, o, a); break;
+        case StepKernel::Ct: DISPATCH_NP(m->NP, launch_step_ct, m, b, integ, o, a, plan.contact_pass); break;
+        case StepKernel::Ground32: launch_step_ground_32(m, b, integ, o, a); break;
+        case StepKernel::StepPair32:      // free flight in the lean launch, the rest of the steps around newton_pair
+            launch_step_ct_32(m, b, integ, o, a, false);
+            launch_step_pair_32(m, b, integ, o, a);
+            break;
+        case StepKernel::W2_64: launch_step_w2_64(m, b, integ, o, a, plan.fullchain, plan.fulln, plan.energy); break;
+        case StepKernel::PairChain32: launch_step_pairchain_32(m, b, o, a, plan.energy); break;
+        case StepKernel::W2Chain32: launch_step_w2c_32(m, b, o, a); break;
+        case StepKernel::FullChain:
+            if (m->NP == 16) launch_step_fullchain_16(m, b, integ, o, a);
+            else if (m->NP == 32) launch_step_fullchain_32(m, b, integ, o, a);
+            else launch_step_fullchain_64(m, b, integ, o, a);
+            break;
+        case StepKernel::Gconst64: launch_step_gconst_64(m, b, integ, o, a, plan.fulln); break;
+        case StepKernel::FullN64: launch_step_fulln_64(m, b, integ, o, a); break;
+        case StepKernel::Plain: DISPATCH_NP(m->NP, launch_step_plain, m, b, integ, o, a); break;
+    }
     // BDF2 keeps (q, qdot) of step k-1 in qp/qdp.  BDF1 steps do not maintain them (and, with JointSpherical, may leave q in
     // another Euler chart than qp), so a BDF1 call invalidates the multistep history: the next rmx_step_bdf2 restarts with
     // SDIRK2, as a fresh driverRedMaxBDF2 run from that state would (driverRedMaxBDF2.m:64-88).
@@ -1359,8 +1390,13 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
         if (on_device) {          // the caller's device arrays directly: nothing staged, nothing copied back
             a.p = p; a.P = P; a.dPdp = dPdp;
         }
+        const rmx_select::AdjPlan plan = rmx_select::select_adjoint(step_traits(m), b->B, rmx_select::knobs_from_env());
         e = hipEventRecord(b->ev0, b->stream);
-            DISPATCH_NP(m->NP, launch_adjoint, m, b, integ, o, a);
+        switch (plan.kernel) {
+            case AdjKernel::Help16: launch_adjoint_help_16(m, b, integ, o, a, plan.fullchain); break;
+            case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, integ, o, a); break;
+            case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, integ, o, a); break;
+        }
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
         // after a BDF2 rollout (q, qdot) of step k-1 are in place: rmx_step_bdf2 may continue it; a BDF1 rollout invalidates them
@@ -1484,7 +1520,9 @@ extern "C" int rmx_profile_phases(rmx_batch* b, int reps, double h, double* cycl
     if (int rc = pending_error_check(b, "rmx_profile_phases")) return rc;
     unsigned long long* d = nullptr;
     HIPCHK(hipMalloc((void**)&d, sizeof(unsigned long long) * 16 * b->B));
-    DISPATCH_NP(m->NP, launch_phase, m, b, reps, h, d);
+    // the full 32-link chain: the stages of the kernel that runs it (RMX_PART 7); everything else: the generic device functions
+    if (rmx_select::full_chain32_plain(step_traits(m))) launch_phase_pairchain_32(m, b, reps, h, d);
+    else { DISPATCH_NP(m->NP, launch_phase, m, b, reps, h, d); }
     std::vector<unsigned long long> hbuf(16 * (size_t)b->B);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(hbuf.data(), d, sizeof(unsigned long long) * hbuf.size(), hipMemcpyDeviceToHost, b->stream);

@@ -1,6 +1,9 @@
 // rmx_host.h -- what the host translation unit (redmax_hip.hip: the C ABI) and the kernel translation units
 // (rmx_kernels.hip, compiled once per padded tree size RMX_NP in {4,8,16,32,64} so the builds run in parallel) share:
 // launch argument blocks, the model / batch objects and the per-size launcher entry points.
+// Which step / adjoint kernel a call runs is decided in rmx_select.h (select_step / select_adjoint) and nowhere else: the host unit
+// executes the plan through the step and adjoint launchers below, each of which launches one kernel family and takes the choice of
+// instantiation as an argument.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +13,7 @@
 #include "redmax_hip_profile.h"   /* redmax_hip.h + the measurement hooks */
 #include "rmx_device.h"
 #include "rmx_pf.h"
+#include "rmx_select.h"
 
 using namespace rmx;
 
@@ -80,7 +84,6 @@ struct rmx_model {
     int w2_min_batch = 0;           // the full 32-link chain: ... and of at least this many (RMX_W2C_MIN; smaller batches keep the one-wave kernel every test pins)
     void* dpf = nullptr;            // body-to-body forces (rmx_model_set_point_forces): the PfTable of rmx_pf.h on the device, or null
     bool big = false;               // more than 64 nodes: the one-workgroup-per-tree kernels of rmx_big.hip
-    bool pair32 = false;            // serial chain of <= 32 nodes with ForceGroundCuboid, no Euler-chart joints: the kernels around newton_pair
     std::vector<struct rmx_batch*> batches;   // live batches of this model (rmx_model_set_ground_contact drains their streams only)
 };
 
@@ -107,7 +110,7 @@ struct rmx_batch {
     void* adjws = nullptr;          // rmx_adjoint_*: H, M, D of every step and rollout, dP/dq, P, dP/dp - one allocation that is kept
     size_t adjws_bytes = 0;         // between calls and only ever grows (hipMalloc + hipFree of 3 x 20 MB cost more than the kernels)
     double last_ms = 0.0;
-    mutable const char* last_kernel = "";   // label of the step kernel the last step call launched (rmx_last_step_kernel; set by the launchers)
+    const char* last_kernel = "";   // label of the step kernel the last step call launched (rmx_last_step_kernel; StepPlan::label)
     bool async_pending = false;     // an rmx_step_*_async launch nobody has waited for yet (see pending_error_check)
     // per-step record of the last step call (Scene.saveHistory): device buffers, kept until the next step call so that an
     // asynchronous launch can be read back after rmx_sync (rmx_history_read)
@@ -131,7 +134,7 @@ struct rmx_batch {
 #define RMX_CAT(a, b) RMX_CAT_(a, b)
 #define RMX_DECLARE_LAUNCHERS(NPV) \
     void RMX_CAT(launch_eval_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
-    void RMX_CAT(launch_step_np_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
+    void RMX_CAT(launch_step_plain_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_euler_, NPV)(const rmx_model* m, const rmx_batch* b, double h, const StepArgs& a); \
     void RMX_CAT(launch_energy_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_adjoint_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
@@ -139,25 +142,32 @@ struct rmx_batch {
     void RMX_CAT(launch_mfd_, NPV)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD); \
     void RMX_CAT(launch_mfd_ct_, NPV)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD); \
     void RMX_CAT(launch_eval_ct_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
-    void RMX_CAT(launch_step_ct_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
+    void RMX_CAT(launch_step_ct_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool contact_pass); \
     void RMX_CAT(launch_energy_ct_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_step_fullchain_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_eval_pf_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
     void RMX_CAT(launch_step_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_energy_pf_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV);
-// 64-lane plain step kernels reading the per-node constants from global memory (rmx_kernels.hip RMX_PART 3) and the staging kernel
-void launch_step_gconst_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
-void launch_step_fulln_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
-void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
-void launch_step_w2c_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a);
-// rmx_kernels.hip RMX_PART 7: the full 32-link chain, BDF1, two points per evaluation (rmx_pair32.h)
-void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a);
-void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a);
-void launch_phase_pairchain_32(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d);
-// rmx_kernels.hip RMX_PART 4 (32 lanes): serial chains with ground contact - the launch with the contact terms around newton_pair
-// (rmx_ct32.h) and the cooperative launch that finishes the rollouts it parked
-void launch_step_pair_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fused);
+// The one-size step launchers (StepKernel of rmx_select.h; the bools are StepPlan's instantiation flags)
+// RMX_PART 3: 64-lane plain step kernels reading the per-node constants from global memory, and the staging kernel (part 0)
+void launch_step_gconst_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fulln);
 void launch_stage_consts_64(const rmx_model* m, double* dst, hipStream_t stream);
+// RMX_PART 2: a tree that fills all 64 node slots
+void launch_step_fulln_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
+// RMX_PART 5 / 6: two wavefronts per rollout - 33..64-node trees, the full 32-link chain under BDF1
+void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fullchain, bool fulln, bool energy);
+void launch_step_w2c_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a);
+// RMX_PART 7: the full 32-link chain, BDF1, two points per evaluation (rmx_pair32.h)
+void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a, bool energy);
+void launch_phase_pairchain_32(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d);
+// RMX_PART 4 (32 lanes): serial chains with ground contact, the kernels around newton_pair (rmx_ct32.h).  ground: the whole call in
+// k_ground32 (StepArgs::fused 1, 2, 3); pair: the steps with the contact terms behind the lean launch of launch_step_ct_32 (fused 0).
+// Both end with the cooperative launch that finishes the rollouts they parked, where the call parks (StepArgs::park).
+void launch_step_ground_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
+void launch_step_pair_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
+// the adjoint pair for trees of <= 16 nodes: RMX_PART 8 (a second wavefront per rollout for M, D), and part 0's full 16-link chain
+void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain);
+void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a);
 // rmx_big.hip: trees of 65..BIG_MAXN nodes, one workgroup per rollout
 size_t big_ws_doubles(const rmx_model* m);
 void launch_big_step(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);

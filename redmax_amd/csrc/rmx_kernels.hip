@@ -1304,6 +1304,8 @@ __global__ void __launch_bounds__(64) k_phase_time(const DevModel M, const int r
 
 // ============================================================================ launchers (declared in rmx_host.h)
 //
+// The step and adjoint launchers decide nothing: rmx_select.h picks the kernel family and the instantiation, the host unit calls the
+// launcher of that family with the plan's flags.  An instantiation stays in the part it is launched from (the parts differ in flags).
 // RMX_PART 0: the plain kernels (every scene without ForceGroundCuboid / JointSpherical) plus Euler, adjoint, phase timing.
 // RMX_PART 1: the extended (CT) instantiations of eval / step / energy.
 // RMX_PART 2: the FULLCHAIN instantiations of the plain step kernels.  One object per part and size, so the builds run in parallel.
@@ -1315,8 +1317,6 @@ __global__ void __launch_bounds__(64) k_phase_time(const DevModel M, const int r
 // More than 64 KiB of dynamic LDS (trees of 33..64 nodes: 34 KiB of per-node constants + H row-major for the block-column solve)
 // is an opt-in per kernel and device; it costs microseconds, so it is set at every launch rather than cached (a process may
 // drive several devices from several threads).
-#define RMX_STR_(x) #x
-#define RMX_STR(x) RMX_STR_(x)
 #define RMX_LAUNCH(kernel, grid, block, bytes, stream, ...)                                                                         \
     do {                                                                                                                            \
         if ((bytes) > 64 * 1024)                                                                                                    \
@@ -1329,11 +1329,10 @@ __global__ void __launch_bounds__(64) k_phase_time(const DevModel M, const int r
 #error "RMX_PART 3 is compiled with -DRMX_GLOBAL_CONSTS"
 #endif
 
-void RMX_CAT(launch_step_gconst_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+void RMX_CAT(launch_step_gconst_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fulln) {
     const dim3 grid(b->B), block(64);
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_bdf1<64,gconst>" : "k_step_bdf2<64,gconst>";
     const size_t bytes = sizeof(double) * (size_t)acc_doubles(m->n, RMX_NP);
-    if (m->dm.n == RMX_NP) {          // every node slot in use: the n == NP instantiation
+    if (fulln) {          // every node slot in use: the n == NP instantiation
         if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_FULLN + 1>), grid, block, bytes, b->stream, m->dm, o, a);
         else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_FULLN + 1>), grid, block, bytes, b->stream, m->dm, o, a);
         return;
@@ -1677,40 +1676,41 @@ __global__ void __launch_bounds__(256) k_park_audit(const StepArgs a, const int 
         a.qd[(size_t)traj * nr + i] = nan;
     }
 }
-static void launch_step_pair_32_impl(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fused);
-void launch_step_pair_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fused) {
-    launch_step_pair_32_impl(m, b, integ, o, a, fused);
-    if (a.park && o.parkHalv > 0) k_park_audit<<<dim3((b->B + 255) / 256), dim3(256), 0, b->stream>>>(a, m->nr);
+// (a.park is set exactly where the call parks: StepPlan::parks)
+static void park_audit(const rmx_model* m, const rmx_batch* b, const StepArgs& a) {
+    if (a.park) k_park_audit<<<dim3((b->B + 255) / 256), dim3(256), 0, b->stream>>>(a, m->nr);
 }
-static void launch_step_pair_32_impl(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fused) {
-    b->last_kernel = fused ? "k_ground32" : "k_step_pair";
-    if (fused) {
-        // a.fused 1: rollouts and cooperative groups in one launch; 2: the rollouts (free flight + contact terms) in one launch, the groups in a second
-        const int inline_groups = a.fused == 1 ? a.ngroups : 0;
-        GroundArgs ga;
-        ga.M = m->dm; ga.o = o; ga.a = a; ga.integ = integ;
-        ga.a.ngroups = inline_groups;
-        ga.coop_only = 0;
-        static_assert(2 * sizeof(GroundArgs) <= RMX_GARGS_BYTES, "rmx_batch::gargs");
-        // (pageable source: staged before the call returns; a failed copy must not be followed by a launch that reads the block - the
-        // sticky error surfaces in the caller's hipGetLastError)
-        if (hipMemcpyAsync(b->gargs, &ga, sizeof ga, hipMemcpyHostToDevice, b->stream) != hipSuccess) return;
-        RMX_LAUNCH(k_ground32, dim3(b->B + inline_groups * COOP_G), dim3(64), m->smem_bytes, b->stream, (const GroundArgs*)b->gargs);
-        if (a.fused == 3 && a.park && o.parkHalv > 0) {      // measurement aid: the groups as a second launch of the SAME kernel (its out-of-line role)
-            ga.a.ngroups = a.ngroups;
-            ga.coop_only = 1;
-            GroundArgs* g2 = (GroundArgs*)b->gargs + 1;
-            if (hipMemcpyAsync(g2, &ga, sizeof ga, hipMemcpyHostToDevice, b->stream) != hipSuccess) return;
-            RMX_LAUNCH(k_ground32, dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, (const GroundArgs*)g2);
-            return;
-        }
-        if (a.fused != 1 && a.park && o.parkHalv > 0)
-            RMX_LAUNCH((k_step_pair<true>), dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
+// a.fused 1: rollouts and cooperative groups in one launch; 2: the rollouts (free flight + contact terms) in one launch, the groups in a second
+static void ground32_launches(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+    const int inline_groups = a.fused == 1 ? a.ngroups : 0;
+    GroundArgs ga;
+    ga.M = m->dm; ga.o = o; ga.a = a; ga.integ = integ;
+    ga.a.ngroups = inline_groups;
+    ga.coop_only = 0;
+    static_assert(2 * sizeof(GroundArgs) <= RMX_GARGS_BYTES, "rmx_batch::gargs");
+    // (pageable source: staged before the call returns; a failed copy must not be followed by a launch that reads the block - the
+    // sticky error surfaces in the caller's hipGetLastError)
+    if (hipMemcpyAsync(b->gargs, &ga, sizeof ga, hipMemcpyHostToDevice, b->stream) != hipSuccess) return;
+    RMX_LAUNCH(k_ground32, dim3(b->B + inline_groups * COOP_G), dim3(64), m->smem_bytes, b->stream, (const GroundArgs*)b->gargs);
+    if (a.fused == 3 && a.park) {      // measurement aid: the groups as a second launch of the SAME kernel (its out-of-line role)
+        ga.a.ngroups = a.ngroups;
+        ga.coop_only = 1;
+        GroundArgs* g2 = (GroundArgs*)b->gargs + 1;
+        if (hipMemcpyAsync(g2, &ga, sizeof ga, hipMemcpyHostToDevice, b->stream) != hipSuccess) return;
+        RMX_LAUNCH(k_ground32, dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, (const GroundArgs*)g2);
         return;
     }
+    if (a.fused != 1 && a.park) RMX_LAUNCH((k_step_pair<true>), dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
+}
+void launch_step_ground_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+    ground32_launches(m, b, integ, o, a);
+    park_audit(m, b, a);
+}
+void launch_step_pair_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
     RMX_LAUNCH((k_step_pair<false>), dim3(b->B), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
     // group g = workgroups COOP_G g .. COOP_G g + COOP_G - 1, all of them resident at once
-    if (a.park && o.parkHalv > 0) RMX_LAUNCH((k_step_pair<true>), dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
+    if (a.park) RMX_LAUNCH((k_step_pair<true>), dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
+    park_audit(m, b, a);
 }
 
 #elif RMX_PART == 5      // 64-node trees, two wavefronts per rollout (RMX_W2): batches of up to one rollout per two SIMDs
@@ -1718,18 +1718,17 @@ static void launch_step_pair_32_impl(const rmx_model* m, const rmx_batch* b, int
 #error "RMX_PART 5 is compiled for RMX_NP = 64 with -DRMX_W2=1 and a wave-local RMX_SYNC()"
 #endif
 
-void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fullchain, bool fulln, bool energy) {
     const dim3 grid(b->B), block(128);
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_bdf1<64,w2>" : "k_step_bdf2<64,w2>";
     const size_t smem_bytes = m->smem_bytes + ((sizeof(double) * W2_HELP_DOUBLES + 15) & ~(size_t)15);      // + the helper wave's own area
-    if (m->dm.is_chain && m->dm.n == RMX_NP) {      // a serial chain that fills every node slot: FULLCHAIN (no tree paths in the front)
+    if (fullchain) {      // a serial chain that fills every node slot: FULLCHAIN (no tree paths in the front)
         if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, true, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
         else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, true, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
         return;
     }
-    if (m->dm.n == RMX_NP) {          // every node slot in use: the n == NP instantiation
+    if (fulln) {          // every node slot in use: the n == NP instantiation
         // (BDF1 without an energy record - the benchmark's launch -: the instantiation that does not carry the last evaluation's energies)
-        if (integ == INTEG_BDF1 && !a.histT) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_W2_NOE>), grid, block, smem_bytes, b->stream, m->dm, o, a);
+        if (!energy) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_W2_NOE>), grid, block, smem_bytes, b->stream, m->dm, o, a);
         else if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
         else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
         return;
@@ -1745,7 +1744,6 @@ void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const 
 
 void launch_step_w2c_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a) {
     const dim3 grid(b->B), block(128);
-    b->last_kernel = "k_step_bdf1<32,fullchain,w2>";
     const size_t smem_bytes = m->smem_bytes + ((sizeof(double) * W2C_HELP_DOUBLES + 15) & ~(size_t)15);      // + the helper wave's own area
     RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, true, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
 }
@@ -1855,11 +1853,10 @@ void launch_phase_pairchain_32(const rmx_model* m, const rmx_batch* b, int reps,
     RMX_LAUNCH(k_phase_time_pair32, grid, block, m->smem_bytes, b->stream, m->dm, reps, b->q, b->qd, h, d);
 }
 
-void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a) {
+void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a, bool energy) {
     const dim3 grid(b->B), block(64);
-    b->last_kernel = "k_step_bdf1_pair32";
     // (a call that records T, V per step takes the instantiation that carries the energies of the last evaluation)
-    if (a.histT) RMX_LAUNCH(k_step_bdf1_pair32<true>, grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+    if (energy) RMX_LAUNCH(k_step_bdf1_pair32<true>, grid, block, m->smem_bytes, b->stream, m->dm, o, a);
     else RMX_LAUNCH(k_step_bdf1_pair32<false>, grid, block, m->smem_bytes, b->stream, m->dm, o, a);
 }
 
@@ -1868,13 +1865,13 @@ void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevO
 #error "RMX_PART 8 is compiled for RMX_NP = 16 with a wave-local RMX_SYNC()"
 #endif
 
-void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain) {
     const dim3 grid(b->B);
     const size_t smem_bytes = m->smem_bytes + sizeof(double) * adj_hand_doubles(RMX_NP);
-    if (integ == INTEG_BDF1 && m->dm.is_chain && m->dm.n == RMX_NP) {      // (configs[3]: the full 16-link chain)
+    if (integ == INTEG_BDF1 && fullchain) {      // (configs[3]: the full 16-link chain)
         RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, true, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
         k_adjoint_bwd<RMX_NP, 1, true><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    } else if (m->dm.is_chain && m->dm.n == RMX_NP) {
+    } else if (fullchain) {
         RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, true, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
         k_adjoint_bwd<RMX_NP, 2, true><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
     } else if (integ == INTEG_BDF1) {
@@ -2034,7 +2031,6 @@ void RMX_CAT(launch_eval_pf_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bo
 void RMX_CAT(launch_step_pf_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
     const dim3 grid(b->B), block(64);
     const PfTable* pf = (const PfTable*)m->dpf;
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_pf<" RMX_STR(RMX_NP) ",bdf1>" : "k_step_pf<" RMX_STR(RMX_NP) ",bdf2>";
     if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_pf<RMX_NP, INTEG_BDF1>), grid, block, m->smem_bytes, b->stream, m->dm, o, a, pf);
     else RMX_LAUNCH((k_step_pf<RMX_NP, INTEG_BDF2>), grid, block, m->smem_bytes, b->stream, m->dm, o, a, pf);
 }
@@ -2047,7 +2043,6 @@ void RMX_CAT(launch_energy_pf_, RMX_NP)(const rmx_model* m, const rmx_batch* b, 
 
 void RMX_CAT(launch_step_fullchain_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
     const dim3 grid(b->B), block(64);
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_bdf1<" RMX_STR(RMX_NP) ",fullchain>" : "k_step_bdf2<" RMX_STR(RMX_NP) ",fullchain>";
     if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
     else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
 }
@@ -2055,7 +2050,6 @@ void RMX_CAT(launch_step_fullchain_, RMX_NP)(const rmx_model* m, const rmx_batch
 // a tree that fills all 64 node slots (n == NP at compile time; LDS-resident constants)
 void launch_step_fulln_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
     const dim3 grid(b->B), block(64);
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_bdf1<64,fulln>" : "k_step_bdf2<64,fulln>";
     if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_FULLN>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
     else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_FULLN>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
 }
@@ -2072,22 +2066,14 @@ void RMX_CAT(launch_mfd_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, dou
     const dim3 grid(b->B), block(64);
     RMX_LAUNCH((k_eval_mfd<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, dM, df, dD, b->chart);
 }
-void RMX_CAT(launch_step_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+// contact_pass false: the lean launch alone (scenes without ForceGroundCuboid; serial chains of <= 32 nodes, whose steps with the
+// contact terms RMX_PART 4's launch_step_pair_32 takes)
+void RMX_CAT(launch_step_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool contact_pass) {
     const dim3 grid(b->B), block(64);
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_bdf1<" RMX_STR(RMX_NP) ",ct>" : "k_step_bdf2<" RMX_STR(RMX_NP) ",ct>";      // (lean launch + launch with the contact terms)
-#if RMX_NP == 32
-    // serial chains with ForceGroundCuboid (no Euler-chart joints): free flight, contact and the cooperative groups in ONE launch
-    if (m->pair32 && m->dm.con && a.fused) return launch_step_pair_32(m, b, integ, o, a, true);
-#endif
     // every trajectory as far as it stays clear of the ground (all the way in scenes without ForceGroundCuboid) ...
     if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, true, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
     else RMX_LAUNCH((k_step_bdf2<RMX_NP, true, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    if (!m->dm.con) return;
-#if RMX_NP == 32
-    // serial chains (no Euler-chart joints): the kernels around newton_pair (RMX_PART 4, rmx_ct32.h) take the rest of the steps with the
-    // contact terms, and what they park (a Newton solve that keeps running out its line searches) in cooperative groups
-    if (m->pair32) return launch_step_pair_32(m, b, integ, o, a, false);
-#endif
+    if (!contact_pass) return;
     // ... and the rest of its steps with the contact terms
     if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
     else RMX_LAUNCH((k_step_bdf2<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
@@ -2107,34 +2093,8 @@ void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool 
     else RMX_LAUNCH((k_eval<RMX_NP, false, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, nullptr);
 }
 
-void RMX_CAT(launch_step_np_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+void RMX_CAT(launch_step_plain_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
     const dim3 grid(b->B), block(64);
-    b->last_kernel = integ == INTEG_BDF1 ? "k_step_bdf1<" RMX_STR(RMX_NP) ">" : "k_step_bdf2<" RMX_STR(RMX_NP) ">";      // (the launchers taken below overwrite it)
-    if (m->dm.con != nullptr || m->dm.nsph > 0) return RMX_CAT(launch_step_ct_, RMX_NP)(m, b, integ, o, a);
-#if RMX_NP == 64
-    // 33..64 nodes in a batch of at most one rollout per two SIMDs: a second wavefront per rollout for the Hessian and the solve
-    if (m->w2_max_batch > 0 && b->B <= m->w2_max_batch) return launch_step_w2_64(m, b, integ, o, a);
-#endif
-#if RMX_NP == 32
-    // the full 32-link chain under BDF1 (BASELINE.json configs[1]): two points per evaluation, the second one the next step's first
-    // (rmx_pair32.h; bit-identical to the one-point kernels below, which RMX_PAIRC=0 keeps reachable)
-    if (m->dm.is_chain && m->dm.n == RMX_NP && integ == INTEG_BDF1 && a.pairc) return launch_step_pairchain_32(m, b, o, a);
-    // the full 32-link chain in a shard of one rollout per two SIMDs or fewer (the 1024-rollout batch on two or more GPUs): a second
-    // wavefront per rollout evaluates the point that may end a step's solve while the first evaluates the next step's first point
-    if (m->dm.is_chain && m->dm.n == RMX_NP && integ == INTEG_BDF1 && m->w2_max_batch > 0 && b->B >= m->w2_min_batch && b->B <= m->w2_max_batch)
-        return launch_step_w2c_32(m, b, o, a);
-#endif
-#if RMX_NP >= 16 && !defined(RMX_NO_FULLCHAIN)      // (the macro: development aid, tools/build_variant.py)
-    if (m->dm.is_chain && m->dm.n == RMX_NP) return RMX_CAT(launch_step_fullchain_, RMX_NP)(m, b, integ, o, a);
-#endif
-#if RMX_NP == 64
-    // More than two rollouts per CU: the kernels that read the per-node constants from global memory (33.8 KB of LDS per wavefront
-    // instead of 68.6 KB: four wavefronts per CU instead of two).  Up to two per CU the LDS-resident constants are faster (-7 %).
-    if (m->dm.gconst && m->gconst_min_batch > 0 && b->B >= m->gconst_min_batch) return launch_step_gconst_64(m, b, integ, o, a);
-#if !defined(RMX_NO_FULLCHAIN)
-    if (m->dm.n == RMX_NP) return launch_step_fulln_64(m, b, integ, o, a);
-#endif
-#endif
     if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
     else RMX_LAUNCH((k_step_bdf2<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
 }
@@ -2152,25 +2112,6 @@ void RMX_CAT(launch_energy_, RMX_NP)(const rmx_model* m, const rmx_batch* b, dou
 
 void RMX_CAT(launch_adjoint_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
     const dim3 grid(b->B), block(64);
-#if RMX_NP == 16
-    // up to one rollout per two SIMDs: a second wavefront per rollout forms and stores M, D (RMX_PART 8; RMX_ADJ_HELP=0: tests)
-    {
-        const char* ah = getenv("RMX_ADJ_HELP");      // (read at every call: tests switch it inside one process)
-        if (!(ah && atoi(ah) == 0) && m->adj_help_max_batch > 0 && b->B <= m->adj_help_max_batch) return launch_adjoint_help_16(m, b, integ, o, a);
-    }
-#endif
-#if RMX_NP == 16
-    if (integ == INTEG_BDF1 && m->dm.is_chain && m->dm.n == RMX_NP) {      // the full 16-link chain: the instantiation RMX_PART 8 runs with its helper wave
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-        return;
-    }
-    if (m->dm.is_chain && m->dm.n == RMX_NP) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-        return;
-    }
-#endif
     if (integ == INTEG_BDF1) {
         RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
         k_adjoint_bwd<RMX_NP, 1><<<grid, block, 0, b->stream>>>(m->dm, o, a);
@@ -2179,8 +2120,22 @@ void RMX_CAT(launch_adjoint_, RMX_NP)(const rmx_model* m, const rmx_batch* b, in
         k_adjoint_bwd<RMX_NP, 2><<<grid, block, 0, b->stream>>>(m->dm, o, a);
     }
 }
+#if RMX_NP == 16
+// the full 16-link chain: the instantiation RMX_PART 8 runs with its helper wave
+void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) {
+        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        k_adjoint_bwd<RMX_NP, 1, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    } else {
+        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        k_adjoint_bwd<RMX_NP, 2, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    }
+}
+#endif
 
 void RMX_CAT(launch_mfd_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD) {
+    // (con alone, not con || nsph as eval / step / energy: k_eval_mfd sets the Euler charts up itself in BOTH instantiations, CT adds only the contact terms)
     if (m->dm.con) return RMX_CAT(launch_mfd_ct_, RMX_NP)(m, b, dM, df, dD);
     const dim3 grid(b->B), block(64);
     RMX_LAUNCH((k_eval_mfd<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, dM, df, dD, b->chart);
@@ -2194,10 +2149,6 @@ void launch_stage_consts_64(const rmx_model* m, double* dst, hipStream_t stream)
 
 void RMX_CAT(launch_phase_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d) {
     const dim3 grid(b->B), block(64);
-#if RMX_NP == 32
-    // the full 32-link chain: the stages of the kernel that runs it (RMX_PART 7); everything else: the generic device functions below
-    if (m->dm.is_chain && m->dm.n == RMX_NP && !m->dm.con && !m->dm.nsph) return launch_phase_pairchain_32(m, b, reps, h, d);
-#endif
     RMX_LAUNCH((k_phase_time<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, reps, b->q, b->qd, h, d);
 }
 

@@ -1,0 +1,163 @@
+// rmx_select.h -- which kernel family a step / adjoint call runs: the ONE place that decides it.
+// Host only and free of HIP types (tests/test_step_plan.py compiles it with plain g++): select_step() maps what the model, the
+// device, the call and the environment say onto a StepPlan; launch_step (redmax_hip.hip) executes the plan through leaf launchers
+// (rmx_kernels.hip, rmx_big.hip) that decide nothing themselves.  The table is DESIGN.md "Which kernel runs"; first match wins.
+#pragma once
+#include <cstdlib>
+
+namespace rmx_select {
+
+enum { BDF1 = 1, BDF2 = 2 };      // (INTEG_BDF1 / INTEG_BDF2 of rmx_host.h)
+
+// What the choice depends on, from the model and its device (fixed once the model's forces are set).
+struct StepTraits {
+    int NP = 0, n = 0;                  // padded size (4 .. 64; anything for big) and nodes in use
+    bool big = false;                   // more than 64 nodes
+    bool point_forces = false, contact = false, spherical = false;      // rmx_pf.h table, ForceGroundCuboid, nsph > 0
+    bool is_chain = false, gconst = false;                               // serial chain; constants staged in global memory
+    int n_simd = 0;                     // SIMDs of the device
+    int coop_g = 0;                     // wavefronts of a cooperative group (COOP_G of rmx_device.h, a build constant)
+    int w2_max_batch = 0, w2_min_batch = 0, gconst_min_batch = 0, adj_help_max_batch = 0;      // read at model creation
+};
+
+// The per-call switches.  Tests and tools change them inside one process, so they are read at every call.
+struct StepKnobs {
+    int park_halvings = 24;             // RMX_PARK_HALVINGS (0: one wavefront per rollout throughout)
+    int coop_map = 0;                   // RMX_COOP_MAP (measurement aid)
+    bool w2_runahead = true;            // RMX_W2_RUNAHEAD
+    bool pairc = true;                  // RMX_PAIRC (0: the one-point kernels for the full 32-link chain)
+    int ground_fused = 1;               // RMX_GROUND_FUSED: 1 one launch, 2 the groups in a second, 0 three launches, 3 measurement aid
+    bool adj_help = true;               // RMX_ADJ_HELP
+};
+inline int env_int(const char* name, const int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+inline StepKnobs knobs_from_env() {
+    StepKnobs k;
+    k.park_halvings = env_int("RMX_PARK_HALVINGS", 24);
+    k.coop_map = env_int("RMX_COOP_MAP", 0);
+    k.w2_runahead = env_int("RMX_W2_RUNAHEAD", 1) != 0;
+    k.pairc = env_int("RMX_PAIRC", 1) != 0;
+    k.ground_fused = env_int("RMX_GROUND_FUSED", 1);
+    k.adj_help = env_int("RMX_ADJ_HELP", 1) != 0;
+    return k;
+}
+
+#ifdef RMX_NO_FULLCHAIN      // development aid (tools/build_variant.py --host): without the n == NP specialisations of rows 8 and 10
+constexpr bool USE_FULL_SPECIALISATIONS = false;
+#else
+constexpr bool USE_FULL_SPECIALISATIONS = true;
+#endif
+
+// One enumerator per launch recipe (the row of the table in the comment).
+enum class StepKernel {
+    Big,             //  1 rmx_big.hip
+    PointForces,     //  2 part 9
+    Ct,              //  3 part 1: the lean launch, then (contact) the launch with the contact terms
+    Ground32,        //  4 part 4: k_ground32 (fused modes 1, 2, 3)
+    StepPair32,      //  4 part 1's lean launch, then part 4: k_step_pair (fused mode 0)
+    W2_64,           //  5 part 5
+    PairChain32,     //  6 part 7
+    W2Chain32,       //  7 part 6
+    FullChain,       //  8 part 2
+    Gconst64,        //  9 part 3
+    FullN64,         // 10 part 2
+    Plain,           // 11 part 0
+};
+
+struct StepPlan {
+    StepKernel kernel = StepKernel::Plain;
+    const char* label = "";             // what rmx_last_step_kernel reports
+    bool stores_ticks = false;          // the kernel STORES its tick count (every other one adds: the caller zeroes the counters first)
+    bool parks = false;                 // rollouts may be parked for cooperative groups: the caller sets their buffers up
+    int park_halvings = 0;              // DevOpts::parkHalv
+    int fused = 0;                      // StepArgs::fused, the effective RMX_GROUND_FUSED
+    bool contact_pass = false;          // Ct: the launch with the contact terms follows the lean one
+    bool fullchain = false, fulln = false;      // W2_64, Gconst64: the serial-chain / n == NP instantiation
+    bool energy = true;                 // false: the instantiation that does not carry the last evaluation's energies (W2_64 fulln, PairChain32)
+    int block = 64;                     // threads per workgroup (128: a helper wavefront, which brings its own LDS area)
+};
+
+// The full 32-link plain chain: what the two-point kernel (and its phase-timing twin) is built for.
+inline bool full_chain32_plain(const StepTraits& t) {
+    return !t.big && t.NP == 32 && t.is_chain && t.n == 32 && !t.contact && !t.spherical;
+}
+
+// "<PRE><NP><S1>" under BDF1, "<PRE2><NP><S2>" under BDF2, as literals
+#define RMX_SEL_LABEL(NPV, P1, S1, P2, S2) \
+    case NPV: return bdf1 ? P1 #NPV S1 : P2 #NPV S2;
+#define RMX_SEL_LABELS(P1, S1, P2, S2)                                                                                              \
+    switch (NP) {                                                                                                                   \
+        RMX_SEL_LABEL(4, P1, S1, P2, S2) RMX_SEL_LABEL(8, P1, S1, P2, S2) RMX_SEL_LABEL(16, P1, S1, P2, S2)                          \
+        RMX_SEL_LABEL(32, P1, S1, P2, S2) default : return bdf1 ? P1 "64" S1 : P2 "64" S2;                                           \
+    }
+inline const char* label_plain(const int NP, const bool bdf1) { RMX_SEL_LABELS("k_step_bdf1<", ">", "k_step_bdf2<", ">") }
+inline const char* label_ct(const int NP, const bool bdf1) { RMX_SEL_LABELS("k_step_bdf1<", ",ct>", "k_step_bdf2<", ",ct>") }
+inline const char* label_fullchain(const int NP, const bool bdf1) { RMX_SEL_LABELS("k_step_bdf1<", ",fullchain>", "k_step_bdf2<", ",fullchain>") }
+inline const char* label_pf(const int NP, const bool bdf1) { RMX_SEL_LABELS("k_step_pf<", ",bdf1>", "k_step_pf<", ",bdf2>") }
+#undef RMX_SEL_LABELS
+#undef RMX_SEL_LABEL
+
+inline StepPlan select_step(const StepTraits& t, const int B, const int integ, const bool records_energy, const StepKnobs& k) {
+    StepPlan p;
+    const bool bdf1 = integ == BDF1;
+    const bool full = t.n == t.NP, fullchain = t.is_chain && full;
+    const bool w2_fits = t.w2_max_batch > 0 && B <= t.w2_max_batch;
+    auto is = [&](const StepKernel kern, const char* label) { p.kernel = kern; p.label = label; return p; };
+    if (t.big) return is(StepKernel::Big, "k_big_step");                                                              // 1
+    if (t.point_forces) return is(StepKernel::PointForces, label_pf(t.NP, bdf1));                                    // 2
+    if (t.NP == 32 && t.contact && t.is_chain && !t.spherical) {                                                     // 4
+        p.park_halvings = (t.n_simd >= t.coop_g && B >= 1) ? k.park_halvings : 0;      // (a group needs a SIMD per member)
+        p.parks = p.park_halvings > 0;
+        p.fused = (k.ground_fused == 1 && !p.parks) ? 2 : k.ground_fused;      // (one launch for rollouts AND groups needs groups)
+        return p.fused ? is(StepKernel::Ground32, "k_ground32") : is(StepKernel::StepPair32, "k_step_pair");
+    }
+    if (t.contact || t.spherical) {                                                                                  // 3
+        p.contact_pass = t.contact;
+        return is(StepKernel::Ct, label_ct(t.NP, bdf1));
+    }
+    if (t.NP == 64 && w2_fits) {                                                                                     // 5
+        p.fullchain = fullchain;
+        p.fulln = full && !fullchain;
+        p.energy = !(p.fulln && bdf1) || records_energy;
+        p.block = 128;
+        return is(StepKernel::W2_64, bdf1 ? "k_step_bdf1<64,w2>" : "k_step_bdf2<64,w2>");
+    }
+    if (full_chain32_plain(t) && bdf1 && k.pairc) {                                                                  // 6
+        p.stores_ticks = true;
+        p.energy = records_energy;
+        return is(StepKernel::PairChain32, "k_step_bdf1_pair32");
+    }
+    if (full_chain32_plain(t) && bdf1 && w2_fits && B >= t.w2_min_batch) {                                           // 7
+        p.block = 128;
+        return is(StepKernel::W2Chain32, "k_step_bdf1<32,fullchain,w2>");
+    }
+    if (USE_FULL_SPECIALISATIONS && t.NP >= 16 && fullchain) return is(StepKernel::FullChain, label_fullchain(t.NP, bdf1));      // 8
+    if (t.NP == 64 && t.gconst && t.gconst_min_batch > 0 && B >= t.gconst_min_batch) {                               // 9
+        p.fulln = full;
+        return is(StepKernel::Gconst64, bdf1 ? "k_step_bdf1<64,gconst>" : "k_step_bdf2<64,gconst>");
+    }
+    if (USE_FULL_SPECIALISATIONS && t.NP == 64 && full) return is(StepKernel::FullN64, bdf1 ? "k_step_bdf1<64,fulln>" : "k_step_bdf2<64,fulln>");      // 10
+    return is(StepKernel::Plain, label_plain(t.NP, bdf1));                                                          // 11
+}
+
+// The adjoint pair (forward sweep + backward sweep) of trees of <= 64 nodes without contact, Euler charts or point forces.
+enum class AdjKernel {
+    Help16,          // part 8: a second wavefront per rollout forms and stores M, D (batches of up to one rollout per two SIMDs)
+    FullChain16,     // part 0: the full 16-link chain
+    Generic,         // part 0
+};
+struct AdjPlan {
+    AdjKernel kernel = AdjKernel::Generic;
+    bool fullchain = false;             // Help16: the full 16-link chain's instantiation
+};
+inline AdjPlan select_adjoint(const StepTraits& t, const int B, const StepKnobs& k) {
+    AdjPlan p;
+    p.fullchain = t.NP == 16 && t.is_chain && t.n == 16;
+    if (t.NP == 16 && k.adj_help && t.adj_help_max_batch > 0 && B <= t.adj_help_max_batch) p.kernel = AdjKernel::Help16;
+    else if (p.fullchain) p.kernel = AdjKernel::FullChain16;
+    return p;
+}
+
+}      // namespace rmx_select

@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--part", type=int, default=0)
     ap.add_argument("--no-vform", action="store_true")
     ap.add_argument("--no-ilp", action="store_true", help="drop -amdgpu-sched-strategy=max-ilp where the in-tree build uses it (part 1, 64-lane objects)")
+    ap.add_argument("--host", action="store_true", help="also recompile the host unit under the extra flags (rmx_select.h chooses the kernel there: -DRMX_NO_FULLCHAIN)")
     ap.add_argument("--asm", action="store_true", help="also write the device assembly to build/isa/var_<name>.s")
     a = ap.parse_args(argv)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -49,7 +50,11 @@ def main():
                                       stderr=subprocess.DEVNULL))
     if any(p.wait() != 0 for p in procs):
         raise SystemExit("hipcc failed")
-    objs = [os.path.join(ge.OBJ_DIR, "redmax_hip.o"), os.path.join(ge.OBJ_DIR, "rmx_big.o")]
+    host_obj = os.path.join(ge.OBJ_DIR, "redmax_hip.o")
+    if a.host:
+        host_obj = os.path.join(vdir, "%s_host.o" % a.name)
+        subprocess.check_call([hipcc] + flags + extra + ["-c", "-o", host_obj, ge.HIP_HOST_SRC])
+    objs = [host_obj, os.path.join(ge.OBJ_DIR, "rmx_big.o")]
     for n in ge.HIP_NPS:
         for part in (0, 1, 2):
             if part == 2 and n < 16:
@@ -57,6 +62,7 @@ def main():
             objs.append(obj if (n == a.np and part == a.part) else os.path.join(ge.OBJ_DIR, "rmx_kernels_np%d_p%d.o" % (n, part)))
     for n, part in ((64, 3), (32, 4), (64, 5), (32, 6), (32, 7), (16, 8)):      # the one-size parts
         objs.append(obj if (n == a.np and part == a.part) else os.path.join(ge.OBJ_DIR, "rmx_kernels_np%d_p%d.o" % (n, part)))
+    objs += [obj if (n == a.np and a.part == 9) else os.path.join(ge.OBJ_DIR, "rmx_kernels_np%d_p9.o" % n) for n in ge.HIP_NPS]      # (point forces)
     out = os.path.join(ROOT, "redmax_amd", "variants", "libredmax_hip_%s.so" % a.name)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out] + objs)
     print(out)
