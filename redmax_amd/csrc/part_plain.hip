@@ -1,0 +1,65 @@
+// part_plain.hip (part 0 of the former rmx_kernels.hip) -- the plain kernels for ONE padded tree size RMX_NP (every scene without ForceGroundCuboid /
+// JointSpherical) plus Euler, adjoint, phase timing.
+#include "rmx_kernels.h"
+
+void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
+    const dim3 grid(b->B), block(64);
+    if (wantH) RMX_LAUNCH((k_eval<RMX_NP, true, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, nullptr);
+    else RMX_LAUNCH((k_eval<RMX_NP, false, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, nullptr);
+}
+
+void RMX_CAT(launch_step_plain_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+    else RMX_LAUNCH((k_step_bdf2<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+}
+
+void RMX_CAT(launch_euler_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double h, const StepArgs& a) {
+    const dim3 grid(b->B), block(64);
+    RMX_LAUNCH((k_step_euler<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, h, a);
+}
+
+void RMX_CAT(launch_energy_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV) {
+    const dim3 grid(b->B), block(64);
+    RMX_LAUNCH((k_energy<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->q, b->qd, dT, dV, nullptr);
+}
+
+void RMX_CAT(launch_adjoint_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) {
+        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        k_adjoint_bwd<RMX_NP, 1><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    } else {
+        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        k_adjoint_bwd<RMX_NP, 2><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    }
+}
+#if RMX_NP == 16
+// the full 16-link chain: the instantiation part_adjhelp16.hip runs with its helper wave
+void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) {
+        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        k_adjoint_bwd<RMX_NP, 1, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    } else {
+        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        k_adjoint_bwd<RMX_NP, 2, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    }
+}
+#endif
+
+void RMX_CAT(launch_mfd_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD) {
+    const dim3 grid(b->B), block(64);
+    RMX_LAUNCH((k_eval_mfd<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, dM, df, dD, b->chart);
+}
+
+#if RMX_NP == 64
+void launch_stage_consts_64(const rmx_model* m, double* dst, hipStream_t stream) {
+    k_stage_consts<64><<<dim3(1), dim3(64), 0, stream>>>(m->dm, dst);
+}
+#endif
+
+void RMX_CAT(launch_phase_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d) {
+    const dim3 grid(b->B), block(64);
+    RMX_LAUNCH((k_phase_time<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, reps, b->q, b->qd, h, d);
+}

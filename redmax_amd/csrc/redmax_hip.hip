@@ -1,8 +1,8 @@
 // redmax_hip.hip -- the C ABI of include/redmax_hip.h (host side).
 //
 // Scene.init()-equivalent flattening of the scene listing into SoA device constants (matlab-diff/+redmax/Scene.m:59-119),
-// batch state in HBM, streams/events and launch plumbing.  Kernels and their launchers: rmx_kernels.hip (one object per
-// padded tree size, declared in rmx_host.h); device code: rmx_device.h.
+// batch state in HBM, streams/events and launch plumbing.  Kernels and their launchers: the part_*.hip files around
+// rmx_kernels.h (one object per part and padded tree size, declared in rmx_host.h); device code: rmx_device.h.
 // There is no CPU fallback: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -454,11 +454,11 @@ static int model_create_flat(const rmx_model_desc* d, const int* idx_explicit, c
         m->dm.gconst = (const double*)m->dgconst;
     }
     // the batch sizes at which rmx_select.h changes kernels (one rollout per two SIMDs = one two-wave workgroup per CU pair of SIMDs)
-    if (m->NP == 64 && nsph == 0) {      // RMX_PART 3 from gconst_min_batch rollouts on, RMX_PART 5 up to w2_max_batch
+    if (m->NP == 64 && nsph == 0) {      // part_gconst64.hip from gconst_min_batch rollouts on, part_w2_tree64.hip up to w2_max_batch
         m->gconst_min_batch = env.gconst_min;
         m->w2_max_batch = env.w2_max;
     }
-    if (m->NP == 32 && nsph == 0 && m->dm.is_chain && m->dm.n == 32) {      // the full 32-link chain (BASELINE.json configs[1]): RMX_PART 6
+    if (m->NP == 32 && nsph == 0 && m->dm.is_chain && m->dm.n == 32) {      // the full 32-link chain (BASELINE.json configs[1]): part_w2_chain32.hip
         m->w2_max_batch = env.w2_max;
         m->w2_min_batch = env.w2c_min;
     }
@@ -861,6 +861,8 @@ extern "C" int rmx_eval(rmx_batch* b, const double* q, const double* qA, const d
     }
     if (m->big) launch_big_eval(m, b, H != nullptr, eta, dg, dH);
     else if (m->dpf) { DISPATCH_NP(m->NP, launch_eval_pf, m, b, H != nullptr, eta, dg, dH); }      // body-to-body forces: the kernels around rmx_pf.h
+    // scenes with ForceGroundCuboid or JointSpherical run the extended instantiations (CT), everything else the plain ones
+    else if (m->dm.con != nullptr || m->dm.nsph > 0) { DISPATCH_NP(m->NP, launch_eval_ct, m, b, H != nullptr, eta, dg, dH); }
     else { DISPATCH_NP(m->NP, launch_eval, m, b, H != nullptr, eta, dg, dH); }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(g, dg, nv * sizeof(double), hipMemcpyDeviceToHost, b->stream);
@@ -888,7 +890,9 @@ extern "C" int rmx_eval_mfd(rmx_batch* b, const double* q, const double* qdot, d
     if (e == hipSuccess) e = hipMemcpyAsync(b->tmpA, q, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(b->tmpB, qdot, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess) {
-            DISPATCH_NP(m->NP, launch_mfd, m, b, dM, df, dD);
+        // (con alone, not con || nsph as eval / step / energy: k_eval_mfd sets the Euler charts up itself in BOTH instantiations, CT adds only the contact terms)
+        if (m->dm.con) { DISPATCH_NP(m->NP, launch_mfd_ct, m, b, dM, df, dD); }
+        else { DISPATCH_NP(m->NP, launch_mfd, m, b, dM, df, dD); }
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(M, dM, nn * sizeof(double), hipMemcpyDeviceToHost, b->stream);
@@ -1074,12 +1078,12 @@ static int launch_step(rmx_batch* b, const rmx_opts* opts, int nsteps, int integ
     a.pairc = knobs.pairc ? 1 : 0;
     // RMX_GROUND_FUSED: 1 (default) ONE launch for the whole call - the rollouts (free flight, then the steps with the contact terms)
     // and, behind them in dispatch order, the cooperative groups that pick the parked rollouts up as they appear: no launch
-    // boundary holds a rollout back (rmx_kernels.hip k_ground32); 2 the groups in a second launch; 0 three launches (lean, contact
+    // boundary holds a rollout back (part_ground32.hip k_ground32); 2 the groups in a second launch; 0 three launches (lean, contact
     // terms, groups); 3 measurement aid (the groups as a second launch of k_ground32)
     a.fused = plan.fused;
     if (plan.kernel == StepKernel::Ground32 && !b->gargs) HIPCHK(hipMalloc(&b->gargs, RMX_GARGS_BYTES));
     // the per-rollout tick counters: the kernels of a call ADD their share (a contact-capable call is up to three launches); the
-    // headline kernel (one launch, rmx_kernels.hip RMX_PART 7) stores its count instead, and the fill dispatch ahead of a 0.8 ms
+    // headline kernel (one launch, part_pair32.hip) stores its count instead, and the fill dispatch ahead of a 0.8 ms
     // launch is saved
     if (!plan.stores_ticks) HIPCHK(hipMemsetAsync(b->ticks, 0, sizeof(unsigned long long) * b->B, b->stream));
     HIPCHK(hipEventRecord(b->ev0, b->stream));
@@ -1520,7 +1524,7 @@ extern "C" int rmx_profile_phases(rmx_batch* b, int reps, double h, double* cycl
     if (int rc = pending_error_check(b, "rmx_profile_phases")) return rc;
     unsigned long long* d = nullptr;
     HIPCHK(hipMalloc((void**)&d, sizeof(unsigned long long) * 16 * b->B));
-    // the full 32-link chain: the stages of the kernel that runs it (RMX_PART 7); everything else: the generic device functions
+    // the full 32-link chain: the stages of the kernel that runs it (part_pair32.hip); everything else: the generic device functions
     if (rmx_select::full_chain32_plain(step_traits(m))) launch_phase_pairchain_32(m, b, reps, h, d);
     else { DISPATCH_NP(m->NP, launch_phase, m, b, reps, h, d); }
     std::vector<unsigned long long> hbuf(16 * (size_t)b->B);
@@ -1548,6 +1552,7 @@ extern "C" int rmx_energy(rmx_batch* b, double* T, double* V) {
     if (e != hipSuccess) { (void)hipFree(dT); return fail(RMX_E_NOMEM, "hipMalloc(energy)"); }
     if (m->big) launch_big_energy(m, b, dT, dV);
     else if (m->dpf) { DISPATCH_NP(m->NP, launch_energy_pf, m, b, dT, dV); }
+    else if (m->dm.con || m->dm.nsph) { DISPATCH_NP(m->NP, launch_energy_ct, m, b, dT, dV); }
     else { DISPATCH_NP(m->NP, launch_energy, m, b, dT, dV); }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(T, dT, sizeof(double) * b->B, hipMemcpyDeviceToHost, b->stream);

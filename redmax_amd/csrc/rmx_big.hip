@@ -1,6 +1,6 @@
 // rmx_big.hip -- the general kernels for trees of 65..BIG_MAXN (256) nodes: ONE WORKGROUP per trajectory, thread = node.
 //
-// The one-wavefront kernels (rmx_device.h, rmx_kernels.hip) hold a tree in the 64 lanes of a wavefront and stop at 64 nodes, where
+// The one-wavefront kernels (rmx_device.h, rmx_kernels.h) hold a tree in the 64 lanes of a wavefront and stop at 64 nodes, where
 // every multi-DOF joint counts one node per DOF (a JointFree3D body is 6 nodes).  The reference has no size limit.  These kernels
 // remove the limit with the SAME algebra - the world-frame recursive Newton-Euler with analytic derivatives of DESIGN.md section 3,
 // restated node by node in oracle/redmax_tensorfree.c - laid out for a workgroup instead of a wavefront:
@@ -44,26 +44,11 @@
 namespace {
 
 constexpr int BT = BIG_MAXN;          // threads per workgroup = node slots
-#ifndef RMX_BIG_PHASEB_DPP_HL
-#define RMX_BIG_PHASEB_DPP_HL 1         // phase B of the guarded LU on DPP broadcasts also when H is in LDS (0: LDS broadcasts there; build variants)
-#endif
-// How the Newton loop is laid out for the compiler (build variants; ticks per Newton iteration at 72 / 128 / 256 links, profiles/r05p_*):
+// How the Newton loop is laid out for the compiler (ticks per Newton iteration at 72 / 128 / 256 links, profiles/r05p_*):
 // one call site for the evaluation with H and one per solve, everything inlined 255 / 394 / 1 065 k; the same with the PIVOTING solve
 // out of line (it runs only when the guard trips, and inlined its registers are the hot path's to carry) 229 / 361 / 1 066 k; two call
 // sites for the evaluation (guarded path, fallback) 254 / 392 / 1 064 k.  Left to the inliner's own heuristics the layout flipped with
 // every change of code size (a Newton loop left out of line costs 60 - 70 k ticks per iteration).
-#ifndef RMX_BIG_NEWTON_ONE_SITE
-#define RMX_BIG_NEWTON_ONE_SITE 1
-#endif
-#ifndef RMX_BIG_NEWTON_ROT
-#define RMX_BIG_NEWTON_ROT 1             // the rotated Newton loop (0: the reference's order of evaluations; build variants)
-#endif
-#ifndef RMX_BIG_PIVOT_INLINE
-#define RMX_BIG_PIVOT_INLINE 0
-#endif
-#ifndef RMX_BIG_HESS_MFMA
-#define RMX_BIG_HESS_MFMA 1             // the Hessian's two products on the matrix cores (0: the column loop; build variants)
-#endif
 
 // The per-node workspace lives in LDS (the dynamic array `dyn`, rows of per-node data are [component][n]); only H goes to global memory
 // when it does not fit next to it.  Offsets in doubles; region X is reused: E, V (path products / sums) -> the in-place suffix scan -> H.
@@ -635,7 +620,7 @@ __device__ __forceinline__ void big_eval(const DevModel& M, const BigWs& w, cons
     // ~1.7 k ticks per column (in-kernel timers, tools/big_profile.py), a fifth of a Newton iteration at 128 DOFs.
     const int nr = M.nr;
     const int ka = act ? M.idx[tj] : -1;
-    if constexpr (RMX_BIG_HESS_MFMA && HL) {
+    if constexpr (HL) {
     // The two products ARE matrix products - H_upper = S (n x 6) CU (6 x n) above the diagonal, H_lower = RL (n x 12 | 18) CL below - and
     // run on the fp64 matrix cores, tile by tile (v_mfma_f64_16x16x4_f64, the transposed form of the LU's trailing update: a lane's four
     // results are four columns of one row, a store touches 16 consecutive rows).  A wavefront takes the four row blocks of its own 64
@@ -1177,34 +1162,6 @@ __device__ __forceinline__ double big_solve_diag(const DevModel& M, const BigWs&
         PROF_ADD(3);
         if (ncol > 0) {          // a full panel (nb == NB) with rows and columns behind it
             PROF_T0();
-            if constexpr (HL && !RMX_BIG_PHASEB_DPP_HL) {
-            if (below) {
-                if (!inA) {      // row r of L21: the rows of U11 come out of LDS as broadcasts
-                    double bb = lu_b[r];
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) {
-                        const double l = a[j] * lu_xs[kb + j];
-                        gg.see(a[j] * l);
-#pragma unroll
-                        for (int c = j + 1; c < NB; ++c) a[c] = fma(-l, dyn[pb + c * nr + kb + j], a[c]);
-                        bb = fma(-l, lu_b[kb + j], bb);
-                        a[j] = l;
-                    }
-                    lu_b[r] = bb;
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) dyn[pb + j * nr + r] = a[j];
-                }
-                // column c = r of U12: forward substitution with the unit lower triangle L11, a column of it per step
-                const size_t col = (size_t)r * nr + kb;
-#pragma unroll
-                for (int i = 0; i < NB; ++i) {
-#pragma unroll
-                    for (int j = i + 1; j < NB; ++j) u[j] = fma(-dyn[pb + i * nr + kb + j], u[i], u[j]);
-                    HW(col + i, u[i]);
-                    dyn[oU + i * sU + (t - c0)] = -u[i];
-                }
-            }
-            } else {
             // The entries of U11 / L11 are wavefront-uniform, and fetching each one as an LDS broadcast made this phase the LDS pipe's:
             // ~1 000 reads per thread and 32-column panel, ~8 clocks each with four wavefronts on one pipe.  Instead ROW j of U11 (column
             // i of L11) is read ONCE into a register - lane 16 r + c holds entry c, the same in all four 16-lane rows - and every
@@ -1254,7 +1211,6 @@ __device__ __forceinline__ double big_solve_diag(const DevModel& M, const BigWs&
                         dyn[oU + i * sU + (t - c0)] = -u[i];
                     }
                 });
-            }
             }
             __syncthreads();
             PROF_ADD(4);
@@ -1357,13 +1313,8 @@ __device__ __forceinline__ double big_solve_diag(const DevModel& M, const BigWs&
     return dxr;
 }
 
-#if RMX_BIG_PIVOT_INLINE
-#define BIG_PIVOT_INL __forceinline__
-#else
-#define BIG_PIVOT_INL __noinline__
-#endif
 template <bool HL>
-__device__ BIG_PIVOT_INL double big_solve(const DevModel& M, const BigWs& w, const int t, const int ka, const double g) {
+__device__ __noinline__ double big_solve(const DevModel& M, const BigWs& w, const int t, const int ka, const double g) {
     if constexpr (!HL) return big_solve_blocked<false>(M, w, t, ka, g);
     // H in LDS: from ~100 DOFs up the blocked form (16-column panels in place, trailing update on the matrix cores) is ahead - the
     // unblocked update below moves the whole trailing matrix through LDS once per pivot, 1.5 k clocks of LDS bandwidth at 128 DOFs;
@@ -1441,15 +1392,14 @@ template <bool HL, bool CT>
 __device__ __forceinline__ double big_newton_inl(const DevModel& M, const DevOpts& o, const BigWs& w, const NodeConsts& nc, const int t,
                                                  const int ka, double x, const double qA, const double qB, const double eta, BigOut& last,
                                                  int& iters, int& halvings, int& status, double& xlo) {
-#if RMX_BIG_NEWTON_ROT
     // The ROTATED loop (newton_rot of rmx_device.h): the reference evaluates the residual twice at every point it accepts - as the line
     // search's trial, then with H at the top of the next iteration.  Here the evaluation at the top of the loop IS the first trial of the
     // running line search, taken with H: accepted - the usual case - the solve follows at once and a residual-only evaluation (57 of
     // 361 k ticks per iteration at 128 DOFs) is saved.  The evaluation asks back once its residual is complete (the gate of big_eval):
     // a trial that is rejected, or accepted and converged, ends there, before the Hessian's share of the work - nothing is wasted; the
     // halving then goes on with residual-only evaluations and H is evaluated at the point it ends on, as before.  Same points, same tests,
-    // same decisions as the loop below (g of the two instantiations agrees bit for bit, tests/test_gpu_big_trees.py); ONE call site for
-    // the evaluation with H, one for the residual-only one (the layout finding above).
+    // same decisions as the reference's order of evaluations (g of the two instantiations agrees bit for bit, tests/test_gpu_big_trees.py);
+    // ONE call site for the evaluation with H, one for the residual-only one (the layout finding above).
     double lo = 0.0;
     BigOut e, e0;
     int iter = 1, lsfail = 0, pivstreak = 0, pivhold = 0, iterLs = 1;
@@ -1539,101 +1489,6 @@ __device__ __forceinline__ double big_newton_inl(const DevModel& M, const DevOpt
         }
         inLs = true;
     }
-#else
-    double lo = 0.0;
-    BigOut e;
-    int iter = 1, lsfail = 0, pivstreak = 0, pivhold = 0;
-    while (true) {
-#if RMX_BIG_NEWTON_ONE_SITE
-        // One call site each for the evaluation and the two solves (all three are inlined: a call costs these kernels more than it
-        // saves - arguments by reference live in scratch, the callee saves its registers).  Round 0: H, then elimination on the diagonal;
-        // if its guard trips, round 1: H again (the solve destroyed it in place), then partial pivoting.
-        double dx = 0.0;
-#pragma unroll 1
-        for (int round = 0; round < 2; ++round) {
-            { PROF_T0(); big_eval<true, HL, CT>(M, w, nc, t, x, ((x - qA) + lo) / eta, (x - qB) + lo, eta, e); PROF_ADD(0); }
-            PROF_T0();
-            if (round == 0 && o.lu_mode == 0 && pivhold == 0) {          // workgroup-uniform
-                bool lu_ok = false;
-                dx = big_solve_diag<HL>(M, w, t, ka, e.g, lu_ok);
-                PROF_ADD(1);
-                if (lu_ok) {
-                    pivstreak = 0;
-                    break;
-                }
-                status |= 16;                                // growth guard tripped
-                if (++pivstreak >= 2) pivhold = 1;           // a solve that keeps tripping: partial pivoting for the rest of this solve
-            } else {
-                dx = big_solve<HL>(M, w, t, ka, e.g);
-                PROF_ADD(1);
-                break;
-            }
-        }
-        const BigOut e0 = e;
-        last = e;
-        ++iters;
-#else
-        { PROF_T0(); big_eval<true, HL, CT>(M, w, nc, t, x, ((x - qA) + lo) / eta, (x - qB) + lo, eta, e); PROF_ADD(0); }
-        const BigOut e0 = e;
-        last = e;
-        ++iters;
-        double dx;
-        {
-            PROF_T0();
-            bool lu_ok = false;
-            if (o.lu_mode == 0 && pivhold == 0) dx = big_solve_diag<HL>(M, w, t, ka, e.g, lu_ok);
-            if (!lu_ok) {
-                if (o.lu_mode == 0 && pivhold == 0) {        // growth guard tripped: H was destroyed in place - re-assemble, then pivot
-                    status |= 16;
-                    if (++pivstreak >= 2) pivhold = 1;       // a solve that keeps tripping: partial pivoting for the rest of this solve
-                    big_eval<true, HL, CT>(M, w, nc, t, x, ((x - qA) + lo) / eta, (x - qB) + lo, eta, e);
-                }
-                dx = big_solve<HL>(M, w, t, ka, e.g);
-            } else {
-                pivstreak = 0;
-            }
-            PROF_ADD(1);
-        }
-#endif
-        const double dxn2 = block_sum(dx * dx, t);
-        if (!(dxn2 == dxn2)) { status |= 4; break; }
-        if (sqrt(dxn2) > o.dxMax) { status |= 1; break; }
-        double alpha = 1.0;
-        const double g0n2 = block_sum(e.g * e.g, t);
-        const double f0 = 0.5 * g0n2;
-        const double x0 = x, lo0 = lo;
-        int iterLs = 1;
-        double gn2 = g0n2;
-        bool stalled = false;
-        while (true) {
-            two_sum(x0, fma(alpha, dx, lo0), x, lo);
-            lo *= o.comp;
-            if (block_all(x == x0 && lo == lo0, t)) {
-                stalled = true;
-                iterLs = o.iterLsMax;
-                e = e0;
-                break;
-            }
-            { PROF_T0(); big_eval<false, false, CT>(M, w, nc, t, x, ((x - qA) + lo) / eta, (x - qB) + lo, eta, e); PROF_ADD(2); }
-            gn2 = block_sum(e.g * e.g, t);
-            if (0.5 * gn2 < f0) break;
-            if (iterLs >= o.iterLsMax) break;
-            alpha *= 0.5;
-            ++iterLs;
-        }
-        last = e;
-        halvings += iterLs - 1;
-        if (stalled) {
-            if (!(sqrt(g0n2) < o.tol)) status |= 2 | 8;
-            break;
-        }
-        if (sqrt(gn2) < o.tol) break;
-        if (iter >= o.iterMax) { status |= 2; break; }
-        lsfail += (0.5 * gn2 < f0) ? 0 : 1;              // rmx_opts.ls_fail_limit, see newton_impl
-        if (o.lsFailLimit > 0 && lsfail >= o.lsFailLimit) { status |= 2 | ST_LS_CUT; break; }
-        ++iter;
-    }
-#endif
     xlo = lo;
     return x;
 }

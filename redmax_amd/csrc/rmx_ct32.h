@@ -25,7 +25,7 @@
 
 namespace rmx {
 
-// measurement builds (tools/build_variant.py --part 4 -- -DRMX_TICK_PHASE=k): RMX_TICK_PHASE=k makes rmx_step_ticks report the shader-clock ticks of ONE phase of
+// measurement builds (tools/build_variant.py --part part_ground32 -- -DRMX_TICK_PHASE=k): RMX_TICK_PHASE=k makes rmx_step_ticks report the shader-clock ticks of ONE phase of
 // newton_pair instead of the rollout's whole share of the launch: 1 front, 2 Hessian stage, 3 solve, 4 exchange, 5 wait for the winner,
 // 6 publish
 #ifdef RMX_TICK_PHASE
@@ -89,9 +89,7 @@ __device__ __forceinline__ void chain_suffix_sum_pair_lds(double* __restrict__ s
         for (int t = 0; t < 32; ++t) a[t] = blk[t * AS + jc];      // components >= NS: finite junk, never stored
         // every read in flight before the first addition: left alone, the scheduler issues the reads two ahead of the serial chains
         // that consume them, and the lone wavefront pays one LDS round trip per pair of nodes
-#ifndef RMX_PAIR_SCAN_NOSB
         __builtin_amdgcn_sched_barrier(0);
-#endif
         double up = 0.0, dn = 0.0;
 #pragma unroll
         for (int t = 15; t >= 0; --t) {                            // (two independent serial chains)

@@ -25,7 +25,7 @@
 #ifndef RMX_SYNC
 #define RMX_SYNC() __syncthreads()
 #endif
-// RMX_W2 (a translation unit compiled with it, rmx_kernels.hip RMX_PART 5): workgroups of TWO wavefronts per 64-node tree.  Wave 0 is
+// RMX_W2 (a translation unit that defines it, part_w2_tree64.hip): workgroups of TWO wavefronts per 64-node tree.  Wave 0 is
 // the rollout; wave 1 joins it for the Hessian tiles (its column half) and for the block-column elimination (its share of the later
 // column blocks of every phase) and waits at a workgroup barrier otherwise.  RMX_SYNC() is wave-local ordering in that unit (the
 // front, the pivoting fallback and everything else belong to wave 0 alone); RMX_WG_BAR() is the barrier both waves meet at.
@@ -33,9 +33,6 @@
 #define RMX_W2 0
 #endif
 #define RMX_WG_BAR() __syncthreads()
-#ifndef RMX_W2_FULL_HELPER
-#define RMX_W2_FULL_HELPER 0      // 1: the helper wave stays in the solve to its end (back substitution included, result dropped)
-#endif
 #if RMX_W2
 // (the base of the dynamic LDS: RMX_CONSTS of that translation unit must not depend on which scratch an evaluation works on)
 __device__ __forceinline__ double* rmx_smem_base() {
@@ -49,19 +46,17 @@ __device__ __forceinline__ void rmx_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 #endif
-// RMX_SYNC() for a translation unit whose workgroups are ONE wavefront (-DRMX_SYNC()=rmx_lane_sync()): the LDS executes the DS
+// RMX_SYNC() for a translation unit whose workgroups are ONE wavefront (#define RMX_SYNC() rmx_lane_sync() at its head): the LDS executes the DS
 // instructions of a wavefront in issue order, so a read that follows a write in program order sees it whatever lanes are involved -
 // what is needed is that the COMPILER keeps the order (a wavefront-scope fence: no code), not that the wavefront waits for its own
 // writes to be acknowledged (what __syncthreads() / a workgroup-scope fence compile to: s_waitcnt lgkmcnt(0), a full LDS round trip
 // at every hand-over; the waits a read's RESULT needs are the register dependencies the compiler tracks anyway).
 __device__ __forceinline__ void rmx_lane_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#ifndef RMX_LANE_SYNC_NO_WB
     __builtin_amdgcn_wave_barrier();
-#endif
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// RMX_GLOBAL_CONSTS (a translation unit compiled with it, rmx_kernels.hip RMX_PART 3): the per-node constants are NOT staged in LDS
+// RMX_GLOBAL_CONSTS (the translation unit that defines it, part_gconst64.hip): the per-node constants are NOT staged in LDS
 // but read from a table in global memory (DevModel::gconst, same [row][node] layout, L2-resident and shared by the whole batch).
 // A 64-lane tree needs 33.8 KB of scratch (H for the block-column solve) plus 34.8 KB of constants per wavefront: two wavefronts
 // per CU; without the constants four fit, and a batch of more than two rollouts per CU runs in half the time.
@@ -1345,17 +1340,9 @@ __device__ __forceinline__ void wave_sum_dual(double v, double& sa, double& sb) 
 
 // g of two iterates of a serial chain of n <= 32 nodes (see above).  xq, xqd, xv: the coordinates of node lane & 31 at trial point
 // lane >> 5, zeros where the node has no DOF.  Same formulas, in the same order, as eval_front_e2<32, false, false, CT>.
-#ifndef RMX_DUAL_INLINE
-#define RMX_DUAL_INLINE 1          // 0: eval_front_dual as an out-of-line function with scalar arguments only (build variants)
-#endif
-#if RMX_DUAL_INLINE
-#define RMX_DUAL_FN __device__ __forceinline__
-#else
-#define RMX_DUAL_FN __device__ __attribute__((noinline))
-#endif
 struct Grav3 { double x, y, z; };
 template <bool CT>
-RMX_DUAL_FN double eval_front_dual(const double* __restrict__ cK, const Grav3 grav, const int lane, const double xq,
+__device__ __forceinline__ double eval_front_dual(const double* __restrict__ cK, const Grav3 grav, const int lane, const double xq,
                                    const double xqd, const double xv, const double eta, const double tau_add) {
     constexpr int NP = 32;
     constexpr int CS = cstride(NP);
@@ -1919,7 +1906,7 @@ constexpr int W2_HELP_AS = 7;
 constexpr int W2_HELP_ARGS = (MAXN + 1) * W2_HELP_AS + 1;
 constexpr int W2_HELP_RES = W2_HELP_ARGS + 3 * 64 + 2;         // |g|^2, T, V
 constexpr int W2_HELP_DOUBLES = W2_HELP_RES + 4;
-// ... and of a workgroup of chains of <= 32 nodes (rmx_kernels.hip RMX_PART 6), whose helper runs the FULL evaluation (the chain's
+// ... and of a workgroup of chains of <= 32 nodes (part_w2_chain32.hip), whose helper runs the FULL evaluation (the chain's
 // residual-only front sums by a register scan: other last bits) on a full-stride scratch
 constexpr int W2C_HELP_ARGS = (32 + 1) * ACC_STRIDE + 1;
 constexpr int W2C_HELP_RES = W2C_HELP_ARGS + 3 * 64 + 2;
@@ -2745,9 +2732,6 @@ __device__ __forceinline__ bool sph_reparam(const DevModel& M, double* __restric
 // raw multipliers are large for scaling reasons only.  If any step violates the guard (or is NaN) `ok` comes back false and
 // the caller redoes the solve with full partial pivoting (lu_solve_neg) on a re-assembled H: pivoting semantics are kept,
 // its cost is paid only when needed.
-#ifndef RMX_BACKSUB32
-#define RMX_BACKSUB32 1            // 1: back substitution without lane conditions (v_writelane capture); 0: the select form (build variants)
-#endif
 constexpr double LU_GROWTH_MAX = 8.0;
 constexpr int LU_BATCH = 8;
 // The positive-pivot half of the guard: every pivot must be positive, finite and non-zero.  It is tested on the reciprocals, which
@@ -2755,9 +2739,6 @@ constexpr int LU_BATCH = 8;
 // positive finite < +inf, NaN (0x7ff00000 ...) < negative (0x80000000 ...), so the running unsigned maximum of the high words
 // stays below 0x7ff00000 exactly when every reciprocal is positive and finite (a zero or denormal pivot gives inf / NaN).
 // (fmin on the pivots cost two instructions each: the compiler canonicalises the scalar operand of v_min_f64 first.)
-#ifndef RMX_PIVGUARD_INT
-#define RMX_PIVGUARD_INT 1
-#endif
 // The growth half of the guard, l'^2 = l^2 u_kk / d_i <= LU_GROWTH_MAX^2 with l^2 u_kk = a_ik l: the running maximum of the products
 // a_ik l is kept on their HIGH WORDS as signed integers (for non-negative doubles integer order is numeric order; a negative product
 // or -0 - a row that is not being eliminated has l = 0 - compares low and is ignored: negative products need a negative pivot, which
@@ -2767,18 +2748,13 @@ constexpr int LU_BATCH = 8;
 struct GrowGuard {
     int hi = 0;
     __device__ __forceinline__ void see(const double prod) {
-#ifdef RMX_VAR_NO_GROW_GUARD      // measurement aid (tools/build_variant.py): what the growth half of the guard costs
-        (void)prod;
-#else
         const int h = __double2hiint(prod);
         hi = h > hi ? h : hi;
-#endif
     }
     __device__ __forceinline__ void pin() { asm volatile("" : "+v"(hi)); }
     __device__ __forceinline__ bool bad(const double lim) const { return hi > __double2hiint(lim); }      // lim = 64 d_i > 0
 };
 struct PivGuard {
-#if RMX_PIVGUARD_INT
     unsigned hi = 0u;
     __device__ __forceinline__ void see(const double piv, const double rinv) {
         (void)piv;
@@ -2787,15 +2763,6 @@ struct PivGuard {
     }
     __device__ __forceinline__ void pin() { asm volatile("" : "+v"(hi)); }
     __device__ __forceinline__ bool ok() const { return hi < 0x7ff00000u; }
-#else
-    double pmin = 1.0;
-    __device__ __forceinline__ void see(const double piv, const double rinv) {
-        (void)rinv;
-        pmin = fmin(pmin, piv);
-    }
-    __device__ __forceinline__ void pin() { asm volatile("" : "+v"(pmin)); }
-    __device__ __forceinline__ bool ok() const { return pmin > 0.0; }
-#endif
 };
 __device__ __forceinline__ void lu_pin(double (&pv)[LU_BATCH]) {
     asm volatile("" : "+s"(pv[0]), "+s"(pv[1]), "+s"(pv[2]), "+s"(pv[3]), "+s"(pv[4]), "+s"(pv[5]), "+s"(pv[6]), "+s"(pv[7]));
@@ -2893,7 +2860,7 @@ __device__ __forceinline__ double lu_solve_neg_diag(const int lane, double (&Hro
     }
     if constexpr (KTAIL < NP) lu_diag_tail<NP, KTAIL>(Hrow, b, gmax, pg, piv, rinv, rinvs, rinv_own, lv);
     double dx = 0.0;
-    if constexpr (KEEP_ALL && RMX_BACKSUB32 == 1) {
+    if constexpr (KEEP_ALL) {
         // without lane conditions: see lu_solve_neg_diag32 (x_k written into lane k of dx, the update on all lanes)
         int dlo = 0, dhi = 0;
 #pragma unroll
@@ -2908,9 +2875,7 @@ __device__ __forceinline__ double lu_solve_neg_diag(const int lane, double (&Hro
     } else {
 #pragma unroll
         for (int k = NP - 1; k >= 0; --k) {
-            double xk;
-            if constexpr (KEEP_ALL) xk = readlane_d(b, k) * rinvs[k];
-            else xk = readlane_d(b * rinv_own, k);
+            const double xk = readlane_d(b * rinv_own, k);
             if (lv == k) dx = xk;
             if (lv < k) b -= Hrow[k] * xk;
         }
@@ -2929,9 +2894,6 @@ __device__ __forceinline__ double lu_solve_neg_diag(const int lane, double (&Hro
 // return through LDS to row-per-lane (lane = row), which is exactly the state lu_solve_neg_diag has after 16 pivots: the last
 // 16 pivots (lu_diag_tail) and the back substitution are shared.  Same operations on the same values in the same order
 // per matrix entry: the results are bit-identical to lu_solve_neg_diag.
-#ifndef RMX_P1_BFIRST
-#define RMX_P1_BFIRST 1
-#endif
 template <int K>
 __device__ __forceinline__ void lu32_phase1(double (&A)[16], double (&AX)[4], double (&B)[16], double (&BX)[4], double& bA,
                                             double& bB, GrowGuard& gmaxA, GrowGuard& gmaxB, PivGuard& pg, double& piv, double& rinv,
@@ -2948,7 +2910,6 @@ __device__ __forceinline__ void lu32_phase1(double (&A)[16], double (&AX)[4], do
         gmaxA.pin();
         gmaxB.pin();
         pg.pin();
-#if RMX_P1_BFIRST
         // Order inside a step: every update of set B (rows 16..31) reads the pivot row out of a set-A register (lane K, which the
         // step's own set-A update leaves unchanged: its multiplier is 0), so B goes FIRST and A second.  With A first, each B
         // update followed the asm statement that had just written its source register, and the compiler - which cannot see into
@@ -2977,28 +2938,6 @@ __device__ __forceinline__ void lu32_phase1(double (&A)[16], double (&AX)[4], do
 #pragma unroll
         for (int c = 0; c < 4; ++c) fmsub_rowbcast<K>(AX[c], AX[c], lA);
         fmsub_rowbcast<K>(bA, bA, lA);
-#else      // the order of rounds 1-3 (build variants)
-        if constexpr (K + 1 < 16) {
-            fmsub_rowbcast<K>(A[K + 1], A[K + 1], lA);
-            piv = row_bcast<K + 1>(A[K + 1]);
-            rinv = recip(piv);
-        } else {
-            fmsub_rowbcast<K>(BX[0], AX[0], lB);
-            piv = readlane_d(BX[0], 0);
-            rinv = recip(piv);
-        }
-#pragma unroll
-        for (int c = K + 2; c < 16; ++c) fmsub_rowbcast<K>(A[c], A[c], lA);
-#pragma unroll
-        for (int c = K + 1; c < 16; ++c) fmsub_rowbcast<K>(B[c], A[c], lB);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            fmsub_rowbcast<K>(AX[c], AX[c], lA);
-            if (K + 1 < 16 || c > 0) fmsub_rowbcast<K>(BX[c], AX[c], lB);
-        }
-        fmsub_rowbcast<K>(bB, bA, lB);
-        fmsub_rowbcast<K>(bA, bA, lA);
-#endif
         lu32_phase1<K + 1>(A, AX, B, BX, bA, bB, gmaxA, gmaxB, pg, piv, rinv, rinvs, jv);
     }
 }
@@ -3073,7 +3012,6 @@ __device__ __forceinline__ double lu_solve_neg_diag32(const int n, const int lan
     double rinv_own = 0.0;
     lu_diag_tail<NP, 16>(Hrow, b, gmax, pg, piv, rinv, rinvs, rinv_own, lv);
     double dx = 0.0;
-#if RMX_BACKSUB32 == 1
     // x_k = b_k / U_kk is formed in every lane (lane k holds it), read out of lane k into a scalar pair and written into lane k of dx
     // (v_writelane); the update b_i -= U_ik x_k then runs on ALL lanes: a lane i >= k is finished (its b_i was consumed at step i,
     // k descends) and what it computes from its stale b_i is never read.  5-6 issue slots per step and no lane condition, against
@@ -3091,14 +3029,6 @@ __device__ __forceinline__ double lu_solve_neg_diag32(const int n, const int lan
         }
         dx = __hiloint2double(dhi, dlo);
     }
-#else
-#pragma unroll
-    for (int k = NP - 1; k >= 0; --k) {
-        const double xk = readlane_d(b, k) * rinvs[k];
-        if (lv == k) dx = xk;
-        if (lv < k) b -= Hrow[k] * xk;
-    }
-#endif
     ok = !__any(lane < NP && gmax.bad(lim)) && pg.ok();
     RMX_SYNC();                 // sAcc goes back to the front, whose subtree scan relies on a zero row n
     if (lane < ACC_STRIDE) sAcc[n * ACC_STRIDE + lane] = 0.0;
@@ -3216,7 +3146,7 @@ __device__ __forceinline__ void lu64_phase(double* sH, const int lane, double (&
             for (int c = 0; c < CW / 2; ++c) w[c] = v2d{X[s][2 * c], X[s][2 * c + 1]};
         }
     }
-    if constexpr (RMX_W2 && (P < 3 || RMX_W2_FULL_HELPER)) RMX_WG_BAR();      // (phase 3 has no later block: wave 0 alone)
+    if constexpr (RMX_W2 && P < 3) RMX_WG_BAR();      // (phase 3 has no later block: wave 0 alone)
     else RMX_SYNC();                           // the next phase reads what all the DPP rows have written
     // the finished rows of this phase: their part of U, for the back substitution
     if (RMX_W2 ? threadIdx.x < 16 : lane < 16) {
@@ -3265,15 +3195,14 @@ __device__ __forceinline__ double lu_solve_neg_diag64_staged(const int n, const 
     lu64_phase<0>(sH, lane, b, gm, rown, pg, jv);
     lu64_phase<1>(sH, lane, b, gm, rown, pg, jv);
     lu64_phase<2>(sH, lane, b, gm, rown, pg, jv);
-    if constexpr (RMX_W2 && !RMX_W2_FULL_HELPER) {     // the helper wave has applied its share of the last later block: the rest is wave 0's
+    if constexpr (RMX_W2) {     // the helper wave has applied its share of the last later block: the rest is wave 0's
         if (threadIdx.x >= 64) {
             ok = true;
             return 0.0;
         }
     }
     lu64_phase<3>(sH, lane, b, gm, rown, pg, jv);
-    if constexpr (RMX_W2 && RMX_W2_FULL_HELPER) RMX_WG_BAR();
-    else RMX_SYNC();            // (the finished rows of phase 3)
+    RMX_SYNC();                 // (the finished rows of phase 3)
     // back substitution, block column by block column from the right
     double x[4];
 #pragma unroll
@@ -3310,7 +3239,6 @@ __device__ __forceinline__ double lu_solve_neg_diag64_staged(const int n, const 
     ok = !__any(bad) && pg.ok();
     const double dx = r4 == 0 ? x[0] : (r4 == 1 ? x[1] : (r4 == 2 ? x[2] : x[3]));
     if constexpr (RMX_W2) {     // (the caller hands the scratch back to the front: w2_lu_call is one function for every n)
-        if constexpr (RMX_W2_FULL_HELPER) RMX_WG_BAR();           // both waves have read their last of H
         return dx;
     }
     RMX_SYNC();                 // sAcc goes back to the front, whose subtree scan relies on a zero row n
@@ -3547,11 +3475,8 @@ struct W2Lu {
     double dx;
     int ok;
 };
-#ifdef RMX_W2_LU_SHARED      // measurement aid: ONE out-of-line copy of the solve for both waves (416 B of callee-saved registers in scratch: 5 % slower)
-__attribute__((noinline)) __device__ W2Lu w2_lu_call() {
-#else
+// (inlined into both waves' call sites: ONE out-of-line copy of the solve for both waves keeps 416 B of callee-saved registers in scratch, 5 % slower)
 __device__ __forceinline__ W2Lu w2_lu_call() {
-#endif
     extern __shared__ __attribute__((aligned(16))) double smem[];
     bool ok;
     const double dx = lu_solve_neg_diag64_staged(64, (int)(threadIdx.x & 63u), smem, ok);
@@ -3774,9 +3699,6 @@ __device__ __forceinline__ bool coop_exchange(CoopCtx& cx, const int lane, const
     coop_post(cx, lane, bits);
     return coop_gather(cx, lane, word, 0, 0, true);      // (every word: this form is a plain all-to-all exchange)
 }
-#ifndef RMX_DUAL_LS
-#define RMX_DUAL_LS 1              // two line-search points per evaluation (eval_front_dual); 0: one (build variants, measurements)
-#endif
 template <int NP, bool PIVOT_ONLY, bool CT = false, bool LEAN = false, bool COOP = false>
 __device__ __forceinline__ double newton_impl(const DevModel& M, const DevOpts& o, double* sAcc, double* sCol, const int lane,
                                               double x, const double qA, const double qB, const double eta, NodeOut& last,
@@ -3856,7 +3778,7 @@ __device__ __forceinline__ double newton_impl(const DevModel& M, const DevOpts& 
         bool stalled = false;
         // chains of at most 32 nodes in the kernels with the contact terms: from the second trial on the line search evaluates its
         // points two at a time (eval_front_dual) - same points, same order of decisions
-        constexpr bool DUAL_LS = CT && !LEAN && NP == 32 && RMX_DUAL_LS;
+        constexpr bool DUAL_LS = CT && !LEAN && NP == 32;
         while (true) {
             if constexpr (DUAL_LS && COOP) {
                 static_assert(!COOP || (CT && !LEAN && NP == 32), "the cooperative line search belongs to the 32-lane kernels with the contact terms");
@@ -4032,9 +3954,6 @@ __device__ __forceinline__ double newton_impl(const DevModel& M, const DevOpts& 
 // (~180 v_mov / v_accvgpr per Newton iteration of the 32-link chain kernel, 5 % of its issue slots).  Same decisions in the same
 // order, same arithmetic: the results are bit-identical.  Plain kernels only (the contact-capable ones keep newton_impl with its
 // two-point line search and the lean exit).
-#ifndef RMX_NEWTON_ROT
-#define RMX_NEWTON_ROT 1
-#endif
 template <int NP, bool PIVOT_ONLY>
 __device__ __forceinline__ double newton_rot(const DevModel& M, const DevOpts& o, double* sAcc, double* sCol, const int lane,
                                              double x, const double qA, const double qB, const double eta, NodeOut& last,
@@ -4149,7 +4068,7 @@ template <int NP, bool CT, bool LEAN, bool COOP = false>
 __device__ __forceinline__ double newton_policy(const DevModel& M, const DevOpts& o, double* sAcc, double* sCol, const int lane,
                                                 double x, const double qA, const double qB, const double eta, NodeOut& last,
                                                 int& iters, int& halvings, int& status, PivotPolicy& piv, double& xlo, CoopCtx& cx) {
-    constexpr bool ROT = RMX_NEWTON_ROT && !CT && !LEAN;
+    constexpr bool ROT = !CT && !LEAN;
     if (o.lu_mode != 0 || piv.hold > 0) {     // wave-uniform
         if (piv.hold > 0) --piv.hold;
         if constexpr (ROT) return newton_rot<NP, true>(M, o, sAcc, sCol, lane, x, qA, qB, eta, last, iters, halvings, status, piv, xlo);
@@ -4162,7 +4081,7 @@ __device__ __forceinline__ double newton_policy(const DevModel& M, const DevOpts
     return r;
 }
 
-// One implicit solve of a step.  LEAN (the first of the two launches of a contact-capable step, rmx_kernels.hip): the plain
+// One implicit solve of a step.  LEAN (the first of the two launches of a contact-capable step, part_ct.hip): the plain
 // evaluation plus a test that every cuboid of the tree is clear of the ground, under which the contact terms vanish
 // identically.  The first evaluation that fails the test ends the solve: status bit ST_LEFT_LEAN comes back set, nothing else
 // is touched, and the caller parks the trajectory at the start of this step for the launch with the contact terms.

@@ -1,5 +1,6 @@
 // rmx_host.h -- what the host translation unit (redmax_hip.hip: the C ABI) and the kernel translation units
-// (rmx_kernels.hip, compiled once per padded tree size RMX_NP in {4,8,16,32,64} so the builds run in parallel) share:
+// (the part_*.hip files around rmx_kernels.h, one object per part and padded tree size RMX_NP in {4,8,16,32,64} so the builds run in
+// parallel; rmx_big.hip) share:
 // launch argument blocks, the model / batch objects and the per-size launcher entry points.
 // Which step / adjoint kernel a call runs is decided in rmx_select.h (select_step / select_adjoint) and nowhere else: the host unit
 // executes the plan through the step and adjoint launchers below, each of which launches one kernel family and takes the choice of
@@ -44,9 +45,9 @@ struct StepArgs {
     unsigned* xch;    // [ngroups][COOP_WORDS] exchange words of the cooperative groups (zero before the cooperative launch)
     int ngroups;      // cooperative groups in flight: group g finishes parked rollouts g, g + ngroups, ... one after the other
     int coop_map;     // measurement aid (RMX_COOP_MAP): 1 = member-major mapping of the cooperative launch's workgroups onto (group, member)
-    int fused;        // the whole call in one launch (rmx_kernels.hip k_ground32): rollouts and cooperative groups side by side
+    int fused;        // the whole call in one launch (part_ground32.hip k_ground32): rollouts and cooperative groups side by side
     unsigned long long* xrec;   // [ngroups][2 COOP_REC] what the winner of a line search publishes to its group (rmx_ct32.h CoopPub; zero before the launch)
-    int w2_noahead;   // two-wave tree kernels (rmx_kernels.hip w2_steps_bdf1): 1 = no evaluation is run ahead (RMX_W2_RUNAHEAD=0; tests)
+    int w2_noahead;   // two-wave tree kernels (rmx_kernels.h w2_steps_bdf1): 1 = no evaluation is run ahead (RMX_W2_RUNAHEAD=0; tests)
     int pairc;        // the full 32-link chain under BDF1: 1 = the two-point kernel of rmx_pair32.h (default), 0 = the one-point kernel (RMX_PAIRC=0; tests)
 };
 
@@ -80,7 +81,7 @@ struct rmx_model {
     void* dgconst = nullptr;        // 64-lane plain models: the staged per-node constants in global memory (DevModel::gconst)
     int gconst_min_batch = 0;       // batches of at least this many rollouts run the global-constants kernels (0: never)
     int w2_max_batch = 0;           // 33..64-node trees / the full 32-link chain: batches of up to this many rollouts take two wavefronts each (0: never; RMX_W2_MAX)
-    int adj_help_max_batch = 0;     // trees of <= 16 nodes: adjoint batches of up to this many rollouts take a second wavefront each for M, D (rmx_kernels.hip RMX_PART 8; 0: never)
+    int adj_help_max_batch = 0;     // trees of <= 16 nodes: adjoint batches of up to this many rollouts take a second wavefront each for M, D (part_adjhelp16.hip; 0: never)
     int w2_min_batch = 0;           // the full 32-link chain: ... and of at least this many (RMX_W2C_MIN; smaller batches keep the one-wave kernel every test pins)
     void* dpf = nullptr;            // body-to-body forces (rmx_model_set_point_forces): the PfTable of rmx_pf.h on the device, or null
     bool big = false;               // more than 64 nodes: the one-workgroup-per-tree kernels of rmx_big.hip
@@ -102,7 +103,7 @@ struct rmx_batch {
     int* park = nullptr;            // see StepArgs.park / xch (allocated for models whose steps can park: rmx_model::coop)
     unsigned* xch = nullptr;
     unsigned long long* xrec = nullptr;
-    void* gargs = nullptr;          // RMX_GARGS_BYTES: the arguments of the fused ground launch (rmx_kernels.hip GroundArgs)
+    void* gargs = nullptr;          // RMX_GARGS_BYTES: the arguments of the fused ground launch (part_ground32.hip GroundArgs)
     int ngroups = 0;
     unsigned long long* ticks = nullptr;   // [B] see StepArgs.ticks (rmx_step_ticks)
     double* bigws = nullptr;        // trees of more than 64 nodes: per-rollout workspace of the rmx_big.hip kernels
@@ -129,7 +130,7 @@ struct rmx_batch {
     } hpool;
 };
 
-// launchers defined by rmx_kernels.hip for one RMX_NP each
+// launchers defined by the multi-size parts (part_plain / part_ct / part_fullchain / part_pf .hip) for one RMX_NP each
 #define RMX_CAT_(a, b) a##b
 #define RMX_CAT(a, b) RMX_CAT_(a, b)
 #define RMX_DECLARE_LAUNCHERS(NPV) \
@@ -149,23 +150,23 @@ struct rmx_batch {
     void RMX_CAT(launch_step_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_energy_pf_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV);
 // The one-size step launchers (StepKernel of rmx_select.h; the bools are StepPlan's instantiation flags)
-// RMX_PART 3: 64-lane plain step kernels reading the per-node constants from global memory, and the staging kernel (part 0)
+// part_gconst64.hip: 64-lane plain step kernels reading the per-node constants from global memory, and the staging kernel (part_plain.hip)
 void launch_step_gconst_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fulln);
 void launch_stage_consts_64(const rmx_model* m, double* dst, hipStream_t stream);
-// RMX_PART 2: a tree that fills all 64 node slots
+// part_fullchain.hip: a tree that fills all 64 node slots
 void launch_step_fulln_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
-// RMX_PART 5 / 6: two wavefronts per rollout - 33..64-node trees, the full 32-link chain under BDF1
+// part_w2_tree64.hip / part_w2_chain32.hip: two wavefronts per rollout - 33..64-node trees, the full 32-link chain under BDF1
 void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fullchain, bool fulln, bool energy);
 void launch_step_w2c_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a);
-// RMX_PART 7: the full 32-link chain, BDF1, two points per evaluation (rmx_pair32.h)
+// part_pair32.hip: the full 32-link chain, BDF1, two points per evaluation (rmx_pair32.h)
 void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a, bool energy);
 void launch_phase_pairchain_32(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d);
-// RMX_PART 4 (32 lanes): serial chains with ground contact, the kernels around newton_pair (rmx_ct32.h).  ground: the whole call in
+// part_ground32.hip (32 lanes): serial chains with ground contact, the kernels around newton_pair (rmx_ct32.h).  ground: the whole call in
 // k_ground32 (StepArgs::fused 1, 2, 3); pair: the steps with the contact terms behind the lean launch of launch_step_ct_32 (fused 0).
 // Both end with the cooperative launch that finishes the rollouts they parked, where the call parks (StepArgs::park).
 void launch_step_ground_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
 void launch_step_pair_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
-// the adjoint pair for trees of <= 16 nodes: RMX_PART 8 (a second wavefront per rollout for M, D), and part 0's full 16-link chain
+// the adjoint pair for trees of <= 16 nodes: part_adjhelp16.hip (a second wavefront per rollout for M, D), and part_plain.hip's full 16-link chain
 void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain);
 void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a);
 // rmx_big.hip: trees of 65..BIG_MAXN nodes, one workgroup per rollout

@@ -1,6 +1,8 @@
-// rmx_kernels.hip -- kernel entry points for gfx950 and their launchers, for ONE padded tree size RMX_NP (lanes in use per
-// wavefront: 4, 8, 16, 32 or 64).  __graft_entry__.build() compiles this file once per size, in parallel, and links the
-// objects with redmax_hip.hip (host side / C ABI).  Device code: rmx_device.h.
+// rmx_kernels.h -- what the kernel translation units (the part_*.hip files, one object per part and padded tree size RMX_NP: lanes
+// in use per wavefront, 4, 8, 16, 32 or 64) share: the kernel templates from stage_consts to k_phase_time, and RMX_LAUNCH.  A part
+// file defines the macros that make it what it is (RMX_NP, RMX_W2, RMX_SYNC, RMX_CONSTS, RMX_GLOBAL_CONSTS) AHEAD of this include;
+// the multi-size parts take RMX_NP from the build (__graft_entry__.HIP_UNITS).  Device code: rmx_device.h.
+#pragma once
 #ifndef RMX_NP
 #error "compile with -DRMX_NP=4|8|16|32|64"
 #endif
@@ -88,8 +90,8 @@ __global__ void __launch_bounds__(64) k_stage_consts(const DevModel M, double* _
 // TAG >= TAG_FULLN: a tree (not necessarily a chain) that fills every node slot: n == NP at compile time, so the per-row bounds of partly
 // filled sizes go (the 64-joint tree of BASELINE.json configs[2]).
 constexpr int TAG_FULLN = 4;
-constexpr int TAG_COOP = 8;      // k_step_bdf1/2<32, true, false, false, TAG_COOP>: the cooperative launch (RMX_PART 4)
-constexpr int TAG_W2 = 16;       // k_step_bdf1/2<64, false, false, false, TAG_W2>: two wavefronts per 64-node tree (RMX_PART 5, RMX_W2);
+constexpr int TAG_COOP = 8;      // k_step_bdf1/2<32, true, false, false, TAG_COOP>: the cooperative launch (part_ground32.hip)
+constexpr int TAG_W2 = 16;       // k_step_bdf1/2<64, false, false, false, TAG_W2>: two wavefronts per 64-node tree (part_w2_tree64.hip, RMX_W2);
                                  // TAG_W2 + 1: the same for trees of 33..63 nodes (n at run time)
 constexpr int TAG_W2_NOE = TAG_W2 + 2;      // TAG_W2 for a call that records no energies (the benchmark's launch): the energies of the last
                                              // evaluation are neither copied per Newton iteration nor summed by the helper wave
@@ -155,7 +157,7 @@ __device__ __forceinline__ void w2_helper(const DevModel& M, double* __restrict_
         }
     }
 }
-// RMX_W2, chains of <= 32 nodes (RMX_PART 6): the helper wave only evaluates - the point wave 0 posts, with the FULL front (see W2C_HELP_*)
+// RMX_W2, chains of <= 32 nodes (part_w2_chain32.hip): the helper wave only evaluates - the point wave 0 posts, with the FULL front (see W2C_HELP_*)
 template <int NP>
 __device__ __forceinline__ void w2c_helper(const DevModel& M, double* __restrict__ sAcc, const int lane) {
     if constexpr (NP == 32 && RMX_W2) {
@@ -224,10 +226,7 @@ __device__ __forceinline__ int w2_steps_bdf1(const DevModel& M, const DevOpts& o
         ++done;
     };
     while (true) {
-#ifndef RMX_W2_SPEC
-#define RMX_W2_SPEC 1      // 0: measurement aid, the loop without the run-ahead
-#endif
-                const bool spec = RMX_W2_SPEC && !spec_failed && ls && iter == predict && piv.streak == 0 && s + 1 < a.nsteps && !a.w2_noahead;      // (wave-uniform)
+        const bool spec = !spec_failed && ls && iter == predict && piv.streak == 0 && s + 1 < a.nsteps && !a.w2_noahead;      // (wave-uniform)
         // (the run-ahead swaps the next step's point INTO x, lo, qA, qB: the expressions handed to the front stay newton_rot's)
         const double sx = x, slo = lo, sqA = qA, sqB = qB;
         if (spec) {
@@ -439,7 +438,7 @@ __global__ void __launch_bounds__(tag_w2(TAG) ? 128 : 64) k_step_bdf1(const DevM
 #if RMX_W2
         if constexpr (tag_w2(TAG) && (!FULLCHAIN || NP == 32)) {
             // guarded solves of a tree: the loop that runs ahead into the next step (w2_steps_bdf1); pivoting solves and the 64-lane serial
-            // chains (whose residual-only front sums by another scan) keep newton_node.  NP == 32: the chains of RMX_PART 6, whose helper
+            // chains (whose residual-only front sums by another scan) keep newton_node.  NP == 32: the chains of part_w2_chain32.hip, whose helper
             // runs the full front
             if ((NP == 32 || !M.is_chain) && o.lu_mode == 0 && piv.hold == 0) {
                 s += w2_steps_bdf1<NP, TAG != TAG_W2_NOE>(M, o, a, sAcc, lane, traj, id, off, s, q, qd, iters, halv, status, piv, w2_predict) - 1;
@@ -733,7 +732,7 @@ __global__ void __launch_bounds__(64) k_step_euler(const DevModel M, const doubl
 // (TaskBDF1.m:45-81) / TaskBDF2.calcFinal (TaskBDF2.m:45-107).  Every forward solve is the common residual
 //     qdot = (x - qA)/eta,  v = x - qB,  g = M v - eta^2 f,  H = dg/dx      (evalBDF1, evalSDIRK2a/b, evalBDF2).
 
-// HELP (RMX_PART 8, trees of <= 16 nodes in batches of at most one rollout per two SIMDs - configs[3]'s 512 rollouts): a workgroup of
+// HELP (part_adjhelp16.hip, trees of <= 16 nodes in batches of at most one rollout per two SIMDs - configs[3]'s 512 rollouts): a workgroup of
 // TWO wavefronts per rollout.  M and D of a step do not enter the Newton iteration; forming and storing them is 9.5 % of the launch
 // pair (profiles/r05w_adjoint_md_bound.txt).  Wave 0 - the rollout - leaves the 39 numbers per node that eval_MD reads in a
 // double-buffered hand-over area of the workgroup's LDS at the end of each step and goes on with the next step; wave 1 forms M, D
@@ -969,11 +968,7 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
                 }
             } else if (last_solve) {
                 double Mrow[NP], Drow[NP];
-#ifdef RMX_ADJ_SKIP_MD      // measurement aid: what the forward kernel costs without forming M, D (they are stored as zeros)
-                for (int i = 0; i < NP; ++i) Mrow[i] = Drow[i] = 0.0;
-#else
                 eval_MD<NP>(M, lane, fs, Mrow, Drow);       // fs: the state of the last evaluated iterate
-#endif
                 if (lane < n) {
 #pragma unroll
                     for (int i = 0; i < NP; ++i)
@@ -1071,9 +1066,6 @@ __device__ __forceinline__ void adj_block(double& y, const double* __restrict__ 
     }
 }
 
-#ifndef RMX_ADJ_BWD_PIVOT
-#define RMX_ADJ_BWD_PIVOT 0          // 1: the backward sweep's solves with the pivot search always (build variants)
-#endif
 template <int NP, int INTEG, bool FC = false>
 __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const DevOpts o, const AdjArgs a) {
     const DevModel M = model_view<NP, FC>(Min);
@@ -1115,7 +1107,7 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
             for (int i = 0; i < NP; ++i) Hrow[i] = (i < n && lane < n) ? hv[i] : ((i == lane) ? 1.0 : 0.0);
         }
         double z;
-        if constexpr (NP <= 32 && !RMX_ADJ_BWD_PIVOT) {
+        if constexpr (NP <= 32) {
             // as in the forward sweep: diagonal pivots under the growth guard first (a third of the instructions of the pivot search; H'
             // is as close to symmetric positive definite as H), partial pivoting on a fresh copy of the rows when the guard trips
             const double hdl = Hc[col];
@@ -1304,15 +1296,9 @@ __global__ void __launch_bounds__(64) k_phase_time(const DevModel M, const int r
 
 // ============================================================================ launchers (declared in rmx_host.h)
 //
-// The step and adjoint launchers decide nothing: rmx_select.h picks the kernel family and the instantiation, the host unit calls the
-// launcher of that family with the plan's flags.  An instantiation stays in the part it is launched from (the parts differ in flags).
-// RMX_PART 0: the plain kernels (every scene without ForceGroundCuboid / JointSpherical) plus Euler, adjoint, phase timing.
-// RMX_PART 1: the extended (CT) instantiations of eval / step / energy.
-// RMX_PART 2: the FULLCHAIN instantiations of the plain step kernels.  One object per part and size, so the builds run in parallel.
-// RMX_PART 9: the kernels of models with body-to-body forces (rmx_pf.h), every size.
-#ifndef RMX_PART
-#define RMX_PART 0
-#endif
+// The launchers of the part files decide nothing: rmx_select.h picks the kernel family and the instantiation, the host unit calls the
+// launcher of that family with the plan's flags.  An instantiation stays in the part it is launched from (the parts differ in macros
+// and scheduling flags).  One object per part and size, so the builds run in parallel.
 
 // More than 64 KiB of dynamic LDS (trees of 33..64 nodes: 34 KiB of per-node constants + H row-major for the block-column solve)
 // is an opt-in per kernel and device; it costs microseconds, so it is set at every launch rather than cached (a process may
@@ -1323,833 +1309,3 @@ __global__ void __launch_bounds__(64) k_phase_time(const DevModel M, const int r
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
         kernel<<<grid, block, bytes, stream>>>(__VA_ARGS__);                                                                        \
     } while (0)
-
-#if RMX_PART == 3      // 64-lane plain step kernels with the per-node constants in global memory (RMX_GLOBAL_CONSTS): four wavefronts per CU
-#ifndef RMX_GLOBAL_CONSTS
-#error "RMX_PART 3 is compiled with -DRMX_GLOBAL_CONSTS"
-#endif
-
-void RMX_CAT(launch_step_gconst_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fulln) {
-    const dim3 grid(b->B), block(64);
-    const size_t bytes = sizeof(double) * (size_t)acc_doubles(m->n, RMX_NP);
-    if (fulln) {          // every node slot in use: the n == NP instantiation
-        if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_FULLN + 1>), grid, block, bytes, b->stream, m->dm, o, a);
-        else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_FULLN + 1>), grid, block, bytes, b->stream, m->dm, o, a);
-        return;
-    }
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, 3>), grid, block, bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, 3>), grid, block, bytes, b->stream, m->dm, o, a);
-}
-
-#elif RMX_PART == 4      // serial chains of <= 32 nodes with ForceGroundCuboid: the step kernels around newton_pair (rmx_ct32.h)
-#if RMX_NP != 32
-#error "RMX_PART 4 is compiled for RMX_NP = 32"
-#endif
-#include "rmx_ct32.h"
-
-// simLoop of driverRedMaxBDF1.m:57-91 / driverRedMaxBDF2.m:57-125 (integ, wave-uniform) for one rollout of a chain of <= 32 nodes with
-// ground contact, steps sfirst .. nsteps - 1.  ONE call site of newton_pair for every stage of every integrator: the SDIRK2 start step
-// is two passes of the stage loop, everything else one.
-// Returns the step at which the rollout was handed on (nsteps: it is complete).  One Newton flavour per instantiation:
-// RUN_LEAN: free flight - the lean solve (newton_node<32, true, true>: the plain evaluation plus the test that every cuboid is clear of
-//   the ground, under which the contact terms vanish identically); the rollout is handed on at the start of the first STEP in which an
-//   evaluation fails that test (what the lean launch of launch_step_ct_32 does).
-// RUN_PAIR: newton_pair, one wavefront; a solve whose line searches keep running out their trials hands the rollout on, at the start
-//   of that step, to a cooperative group (DevOpts::parkHalv).
-// RUN_COOP: this wavefront is a member of the group that finishes a parked rollout.
-enum { RUN_LEAN = 0, RUN_PAIR = 1, RUN_COOP = 2 };
-template <int MODE>
-__device__ __forceinline__ int run_rollout(const DevModel& M, const DevOpts& o, const StepArgs& a, const int integ, double* sAcc, double* sCol,
-                                           const int lane, const int traj, const int sfirst, CoopCtx& cx, const CoopPub& pb,
-                                           const unsigned long long tick0) {
-    constexpr int NP = 32;
-    constexpr bool COOP = MODE == RUN_COOP;
-    const bool writer = !COOP || cx.member == 0;     // (members 1.. of a cooperative group compute, member 0 also stores)
-    const double h = o.h;
-    const bool bdf2 = integ == INTEG_BDF2;
-    const int id = (lane < M.n) ? M.idx[lane] : -1;
-    const size_t off = (size_t)traj * M.nr + (id >= 0 ? id : 0);
-    double q = id >= 0 ? a.q[off] : 0.0;
-    double qd = id >= 0 ? a.qd[off] : 0.0;
-    double qp = (bdf2 && id >= 0) ? a.qp[off] : 0.0;       // step k-1 (Joint.q1 / qdot1 in the reference)
-    double qdp = (bdf2 && id >= 0) ? a.qdp[off] : 0.0;
-    const bool started = (*a.started) != 0 || sfirst > 0;    // resumed behind earlier steps of this call: they are its history
-    int iters = 0, halv = 0, status = 0;
-    PivotPolicy piv;
-    if constexpr (COOP) {
-        const int* pp = a.park + 1 + a.B + 3 * traj;
-        piv.hold = pp[0]; piv.len = pp[1]; piv.streak = pp[2];
-    }
-    int stop = a.nsteps;
-    for (int s = sfirst; s < a.nsteps; ++s) {
-        NodeOut last;
-        last.g = last.eT = last.eV = 0.0;
-        double xlo = 0.0;
-        const int it_in = iters, hv_in = halv, st_in = status;
-        const PivotPolicy piv_in = piv;
-        const bool start2 = bdf2 && s == 0 && !started;       // SDIRK2 start step (driverRedMaxBDF2.m:64-88): two solves
-        const double al = (2.0 - sqrt(2.0)) / 2.0;            // (:74)
-        const double q0 = (bdf2 && !start2) ? qp : q, qd0 = (bdf2 && !start2) ? qdp : qd, q1 = q, qd1 = qd;
-        double qa = 0.0, qda = 0.0, xsol = 0.0;
-        bool left = false;
-        for (int stage = 0; stage < (start2 ? 2 : 1) && !left; ++stage) {
-            double xi, qA, qB, eta;
-            if (!bdf2) {                       // BDF1 (evalBDF1 :160-187): eta = h, qA = q0, qB = q0 + h qdot0 = the initial guess (:70)
-                xi = q0 + h * qd0; qA = q0; qB = xi; eta = h;
-            } else if (!start2) {              // BDF2 (evalBDF2 :263-293): eta = 2h/3
-                xi = q1 + h * qd1;
-                qA = (4.0 / 3.0) * q1 - (1.0 / 3.0) * q0;
-                qB = (4.0 / 3.0) * q1 - (1.0 / 3.0) * q0 + (8.0 / 9.0) * h * qd1 - (2.0 / 9.0) * h * qd0;
-                eta = (2.0 / 3.0) * h;
-            } else if (stage == 0) {           // SDIRK2a (evalSDIRK2a :194-225): eta = a h, qA = q0, qB = q0 + a h qdot0
-                xi = q0 + al * h * qd0; qA = q0; qB = q0 + (al * h) * qd0; eta = al * h;
-            } else {                           // SDIRK2b (evalSDIRK2b :228-260)
-                xi = qa + (1.0 - al) * h * qda;
-                qA = q0 + (1.0 - al) * h * qda;
-                qB = q0 + (2.0 * al - 1.0) * h * qd0 + 2.0 * (1.0 - al) * h * qda;
-                eta = al * h;
-            }
-            if constexpr (MODE == RUN_LEAN) {
-                xsol = newton_node<NP, true, true, false>(M, o, sAcc, sCol, lane, xi, qA, qB, eta, last, iters, halv, status, piv, xlo, cx);
-                left = (status & ST_LEFT_LEAN) != 0;   // a cuboid comes near the ground: nothing of this step is kept
-            } else {
-                // the pivot policy of newton_policy (rmx_device.h): a hold after three tripped solves in a row
-                const bool pivot_all = o.lu_mode != 0 || piv.hold > 0;
-                if (piv.hold > 0) --piv.hold;
-                xsol = newton_pair<COOP>(M, o, sAcc, lane, xi, qA, qB, eta, last, iters, halv, status, piv, pivot_all, xlo, cx, pb);
-                if (!pivot_all) pivot_policy_update(piv);
-                left = (MODE == RUN_PAIR && (status & ST_PARK)) || (COOP && (status & ST_COOP_FAULT));
-            }
-            if (start2 && stage == 0 && !left) {
-                qa = xsol;
-                qda = (qa - q0) / (al * h);
-            }
-        }
-        if (left) {
-            if (COOP) break;                   // (ST_COOP_FAULT stays in the status)
-            // nothing of this step is kept: whoever takes the rollout on starts the step again (a solve of the start step that went through included)
-            iters = it_in; halv = hv_in; status = st_in & ~(ST_PARK | ST_LEFT_LEAN); piv = piv_in;
-            stop = s;
-            break;
-        }
-        if (!bdf2) {
-            qd = ((xsol - q0) + xlo) / h;      // (:72), with the low-order part of the iterate the residual was evaluated at
-            q = xsol;
-        } else if (start2) {
-            qd = (xsol - q0 - (1.0 - al) * h * qda) / (al * h);
-            q = xsol;
-            qp = q0;
-            qdp = qd0;
-        } else {
-            qp = q1;
-            qdp = qd1;
-            qd = (3.0 / (2.0 * h)) * (xsol - (4.0 / 3.0) * q1 + (1.0 / 3.0) * q0);
-            q = xsol;
-        }
-        if (a.histT && writer) {               // Scene.saveHistory (Scene.m:134-161)
-            const double T = wave_sum(last.eT), V = wave_sum(last.eV);
-            if (lane == 0) {
-                a.histT[(size_t)s * a.B + traj] = T;
-                a.histV[(size_t)s * a.B + traj] = V;
-            }
-        }
-        if (a.histQ && id >= 0 && writer) {
-            a.histQ[(size_t)s * a.B * M.nr + off] = q;
-            a.histQd[(size_t)s * a.B * M.nr + off] = qd;
-        }
-    }
-    if (id >= 0 && writer) {
-        a.q[off] = q;
-        a.qd[off] = qd;
-        if (bdf2) {
-            a.qp[off] = qp;
-            a.qdp[off] = qdp;
-        }
-    }
-    if constexpr (COOP) {
-        // a parked rollout a group has taken to its end: k_park_audit tells it from one nobody picked up by this
-        if (lane == 0 && writer && !(status & ST_COOP_FAULT)) a.resume[traj] = a.nsteps;
-    }
-    if constexpr (!COOP) {
-        if (lane == 0) {
-            a.resume[traj] = stop;
-            if (MODE == RUN_PAIR && a.park && stop < a.nsteps) {
-                int* pp = a.park + 1 + a.B + 3 * traj;
-                pp[0] = piv.hold; pp[1] = piv.len; pp[2] = piv.streak;
-            }
-        }
-    }
-    if (lane == 0 && a.it && writer) {
-        a.it[traj] += iters;
-        a.ls[traj] += halv;
-        a.status[traj] |= status;
-    }
-#ifdef RMX_TICK_PHASE
-    if (lane == 0 && a.ticks && writer) a.ticks[traj] += cx.phase;
-    cx.phase = 0;
-#else
-    if (lane == 0 && a.ticks && writer) a.ticks[traj] += __builtin_amdgcn_s_memtime() - tick0;      // this rollout's share of the launch (rmx_step_ticks)
-#endif
-    return stop;
-}
-
-// Three launches (RMX_GROUND_FUSED=0, and whenever the cooperative groups are switched off): the lean launch of launch_step_ct_32, then
-// COOP = false for every rollout from its a.resume, then COOP = true: group g finishes the parked rollouts g, g + ngroups, ...
-template <bool COOP>
-__global__ void __launch_bounds__(64) k_step_pair(const DevModel M, const DevOpts o, const StepArgs a, const int integ) {
-    constexpr int NP = 32;
-    unsigned long long tick0 = __builtin_amdgcn_s_memtime();
-    int traj = blockIdx.x;
-    CoopCtx cx;
-    cx.ticks = o.coopTicks;
-    CoopPub pb;
-    int pk = 0, npark = 1, pstride = 1;
-    if constexpr (COOP) {
-#ifdef RMX_COOP_MAP_AID      // measurement builds: RMX_COOP_MAP=1 scatters the members of a group over the launch (member-major mapping)
-        pk = a.coop_map ? blockIdx.x % a.ngroups : blockIdx.x / COOP_G;
-        cx.member = a.coop_map ? blockIdx.x / a.ngroups : blockIdx.x % COOP_G;
-#else
-        pk = blockIdx.x / COOP_G;
-        cx.member = blockIdx.x % COOP_G;
-#endif
-        cx.words = a.xch + (size_t)pk * COOP_WORDS;
-        pb.rec = a.xrec + (size_t)pk * 2 * COOP_REC;
-        npark = a.park[0];
-        pstride = a.ngroups;
-        if (pk >= npark) return;
-        traj = a.park[1 + pk] - 1;
-    }
-    const int s0 = a.resume ? a.resume[traj] : 0;
-    if (!COOP && s0 >= a.nsteps) return;           // the lean launch took this trajectory all the way
-    double *sAcc, *sCol;
-    smem_setup<NP>(M, sAcc, sCol);
-    const int lane = threadIdx.x;
-    con_setup<NP>(M, sCol);
-    for (; pk < npark; pk += pstride) {              // (one pass unless COOP)
-        int sfirst = s0;
-        if constexpr (COOP) {
-            traj = a.park[1 + pk] - 1;
-            sfirst = a.resume[traj];
-            tick0 = __builtin_amdgcn_s_memtime();
-        }
-        const int stop = run_rollout<COOP ? RUN_COOP : RUN_PAIR>(M, o, a, integ, sAcc, sCol, lane, traj, sfirst, cx, pb, tick0);
-        if constexpr (!COOP) {
-            if (lane == 0 && a.park && stop < a.nsteps) a.park[1 + atomicAdd(a.park, 1)] = traj + 1;
-        }
-    }
-}
-
-// ONE launch for the whole call: workgroups 0 .. B - 1 are the rollouts (lean solve, then newton_pair from the step that comes near the
-// ground, until the end or until a solve parks the rollout), workgroups B .. are the members of the cooperative groups - workgroups are
-// dispatched in index order (per XCD), so they take the SIMDs that finished rollouts leave - and pick the parked rollouts up as they
-// appear: group g the g-th, (g + ngroups)-th ... entry of the list.  No launch boundary anywhere: a rollout that leaves free flight
-// early is not held back by the last one to do so, and a parked rollout does not wait for the last unparked one.
-// The list: a.park[1 + e] = rollout + 1 (zero before the launch), published with release semantics after the rollout's state;
-// a.park[1 + 4 B] counts the rollout workgroups that have finished (the groups leave when all have and the list is exhausted).
-// The three roles are OUT-OF-LINE functions: inlined into one kernel their three Newton loops share one register allocation (688 bytes
-// of scratch, 860 spilled SGPRs, every loop slower than in a kernel of its own).  They take the launch's arguments as a pointer
-// into global memory (scalar loads, as kernel arguments are) and name the LDS array themselves: a generic pointer into LDS handed
-// to an out-of-line function loses its address space.
-struct GroundArgs {
-    DevModel M;
-    DevOpts o;
-    StepArgs a;
-    int integ;
-    int coop_only;      // measurement aid (RMX_GROUND_FUSED=3): every workgroup of this launch is a member of a cooperative group
-};
-__device__ __forceinline__ void role_smem(const DevModel& M, double*& sAcc, double*& sCol) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    sAcc = smem;
-    sCol = smem + acc_doubles(M.n, 32);
-}
-// (the arguments are copied into locals once: read through the pointer, every field would be loaded again behind every store and
-// every scheduling pin of the Newton loop - the compiler cannot know that nothing writes them)
-__device__ __attribute__((noinline)) int role_lean(const GroundArgs* __restrict__ g, const int traj) {
-    const DevModel M = g->M;
-    const DevOpts o = g->o;
-    const StepArgs a = g->a;
-    const int integ = g->integ;
-    double *sAcc, *sCol;
-    role_smem(M, sAcc, sCol);
-    CoopCtx cx;
-    cx.ticks = o.coopTicks;
-    CoopPub pb;
-    return run_rollout<RUN_LEAN>(M, o, a, integ, sAcc, sCol, threadIdx.x, traj, 0, cx, pb, __builtin_amdgcn_s_memtime());
-}
-__device__ __attribute__((noinline)) int role_pair(const GroundArgs* __restrict__ g, const int traj, const int sfirst) {
-    const DevModel M = g->M;
-    const DevOpts o = g->o;
-    const StepArgs a = g->a;
-    const int integ = g->integ;
-    double *sAcc, *sCol;
-    role_smem(M, sAcc, sCol);
-    CoopCtx cx;
-    cx.ticks = o.coopTicks;
-    CoopPub pb;
-    return run_rollout<RUN_PAIR>(M, o, a, integ, sAcc, sCol, threadIdx.x, traj, sfirst, cx, pb, __builtin_amdgcn_s_memtime());
-}
-__device__ __forceinline__ void role_coop(const GroundArgs* __restrict__ g, const int grp, const int member) {
-    const DevModel M = g->M;
-    const DevOpts o = g->o;
-    const StepArgs a = g->a;
-    const int integ = g->integ;
-    double *sAcc, *sCol;
-    role_smem(M, sAcc, sCol);
-    const int lane = threadIdx.x;
-    CoopCtx cx;
-    cx.ticks = o.coopTicks;
-    CoopPub pb;
-    cx.member = member;
-    cx.words = a.xch + (size_t)grp * COOP_WORDS;
-    pb.rec = a.xrec + (size_t)grp * 2 * COOP_REC;
-    int* const done = a.park + 1 + 4 * a.B;
-    for (int e = grp; e < a.B; e += a.ngroups) {
-        int v = 0;
-        // (the wait below ends when the rollout workgroups have all finished or parked.  It relies on their being dispatched - nothing
-        // in the programming model promises that workgroups start in index order -, so it is bounded: a group that has seen no entry and
-        // no end for 16 x the group timeout leaves, and k_park_audit marks whatever stays unfinished RMX_ST_COOP_FAULT)
-        const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-        while (true) {
-            // (relaxed polls: an agent-scope ACQUIRE invalidates this XCD's L2 under every wavefront that lives in it, hundreds of
-            // times per microsecond with ~500 idle members polling; the one fence below, after the entry has been seen, is what orders
-            // the reads of the rollout's state)
-            if (lane == 0) v = __hip_atomic_load(a.park + 1 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            v = __builtin_amdgcn_readfirstlane(v);
-            if (v != 0) break;
-            int d = 0, cnt = 0;
-            if (lane == 0) {
-                d = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                cnt = __hip_atomic_load(a.park, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            d = __builtin_amdgcn_readfirstlane(d);
-            cnt = __builtin_amdgcn_readfirstlane(cnt);
-            // every rollout has finished or parked (its list entry is written BEFORE it is counted, both by the same lane with release
-            // semantics), and the count of entries, read after the count of finished rollouts, does not reach this one
-            if (d >= a.B && cnt <= e) return;
-            if (__builtin_amdgcn_s_memtime() - tw0 > 16ull * cx.ticks) return;
-            __builtin_amdgcn_s_sleep(127);
-        }
-        __threadfence();                                 // acquire
-        const int traj = v - 1;
-        const int sfirst = __hip_atomic_load(a.resume + traj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        run_rollout<RUN_COOP>(M, o, a, integ, sAcc, sCol, lane, traj, sfirst, cx, pb, __builtin_amdgcn_s_memtime());
-    }
-}
-__global__ void __launch_bounds__(64) k_ground32(const GroundArgs* __restrict__ g) {
-    constexpr int NP = 32;
-    {
-        double *sAcc, *sCol;
-        smem_setup<NP>(g->M, sAcc, sCol);
-        con_setup<NP>(g->M, sCol);
-    }
-    const int B = g->coop_only ? 0 : g->a.B, nsteps = g->a.nsteps;
-    if ((int)blockIdx.x >= B) {
-        role_coop(g, ((int)blockIdx.x - B) / COOP_G, ((int)blockIdx.x - B) % COOP_G);
-        return;
-    }
-    const int traj = blockIdx.x;
-    int stop = role_lean(g, traj);
-    if (stop < nsteps) stop = role_pair(g, traj, stop);
-    int* const park = g->a.park;
-    if (!park) return;                                   // (no cooperative groups in this call: nothing parks, nobody waits)
-    __threadfence();                                     // release: this rollout's state, counters and pivot policy before its list entry
-    if (threadIdx.x == 0) {
-        if (stop < nsteps) {
-            const int e = atomicAdd(park, 1);
-            __hip_atomic_store(park + 1 + e, traj + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __hip_atomic_fetch_add(park + 1 + 4 * B, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// the steps with the contact terms of a chain of <= 32 nodes: fused (one launch for everything) or behind the lean launch of launch_step_ct_32
-// After the launches of a call that may park rollouts: a rollout that was parked and that no group took to its end (a group that gave
-// up waiting, see role_coop; never observed) must not pass for a result - RMX_ST_COOP_FAULT | RMX_ST_NAN and a NaN state, as for a rollout
-// whose group faulted.
-__global__ void __launch_bounds__(256) k_park_audit(const StepArgs a, const int nr) {
-    const int traj = blockIdx.x * blockDim.x + threadIdx.x;
-    if (traj >= a.B || a.resume[traj] >= a.nsteps) return;
-    if (a.status) a.status[traj] |= ST_COOP_FAULT | 4;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    for (int i = 0; i < nr; ++i) {
-        a.q[(size_t)traj * nr + i] = nan;
-        a.qd[(size_t)traj * nr + i] = nan;
-    }
-}
-// (a.park is set exactly where the call parks: StepPlan::parks)
-static void park_audit(const rmx_model* m, const rmx_batch* b, const StepArgs& a) {
-    if (a.park) k_park_audit<<<dim3((b->B + 255) / 256), dim3(256), 0, b->stream>>>(a, m->nr);
-}
-// a.fused 1: rollouts and cooperative groups in one launch; 2: the rollouts (free flight + contact terms) in one launch, the groups in a second
-static void ground32_launches(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    const int inline_groups = a.fused == 1 ? a.ngroups : 0;
-    GroundArgs ga;
-    ga.M = m->dm; ga.o = o; ga.a = a; ga.integ = integ;
-    ga.a.ngroups = inline_groups;
-    ga.coop_only = 0;
-    static_assert(2 * sizeof(GroundArgs) <= RMX_GARGS_BYTES, "rmx_batch::gargs");
-    // (pageable source: staged before the call returns; a failed copy must not be followed by a launch that reads the block - the
-    // sticky error surfaces in the caller's hipGetLastError)
-    if (hipMemcpyAsync(b->gargs, &ga, sizeof ga, hipMemcpyHostToDevice, b->stream) != hipSuccess) return;
-    RMX_LAUNCH(k_ground32, dim3(b->B + inline_groups * COOP_G), dim3(64), m->smem_bytes, b->stream, (const GroundArgs*)b->gargs);
-    if (a.fused == 3 && a.park) {      // measurement aid: the groups as a second launch of the SAME kernel (its out-of-line role)
-        ga.a.ngroups = a.ngroups;
-        ga.coop_only = 1;
-        GroundArgs* g2 = (GroundArgs*)b->gargs + 1;
-        if (hipMemcpyAsync(g2, &ga, sizeof ga, hipMemcpyHostToDevice, b->stream) != hipSuccess) return;
-        RMX_LAUNCH(k_ground32, dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, (const GroundArgs*)g2);
-        return;
-    }
-    if (a.fused != 1 && a.park) RMX_LAUNCH((k_step_pair<true>), dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
-}
-void launch_step_ground_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    ground32_launches(m, b, integ, o, a);
-    park_audit(m, b, a);
-}
-void launch_step_pair_32(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    RMX_LAUNCH((k_step_pair<false>), dim3(b->B), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
-    // group g = workgroups COOP_G g .. COOP_G g + COOP_G - 1, all of them resident at once
-    if (a.park) RMX_LAUNCH((k_step_pair<true>), dim3(a.ngroups * COOP_G), dim3(64), m->smem_bytes, b->stream, m->dm, o, a, integ);
-    park_audit(m, b, a);
-}
-
-#elif RMX_PART == 5      // 64-node trees, two wavefronts per rollout (RMX_W2): batches of up to one rollout per two SIMDs
-#if RMX_NP != 64 || !RMX_W2
-#error "RMX_PART 5 is compiled for RMX_NP = 64 with -DRMX_W2=1 and a wave-local RMX_SYNC()"
-#endif
-
-void launch_step_w2_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fullchain, bool fulln, bool energy) {
-    const dim3 grid(b->B), block(128);
-    const size_t smem_bytes = m->smem_bytes + ((sizeof(double) * W2_HELP_DOUBLES + 15) & ~(size_t)15);      // + the helper wave's own area
-    if (fullchain) {      // a serial chain that fills every node slot: FULLCHAIN (no tree paths in the front)
-        if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, true, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-        else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, true, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-        return;
-    }
-    if (fulln) {          // every node slot in use: the n == NP instantiation
-        // (BDF1 without an energy record - the benchmark's launch -: the instantiation that does not carry the last evaluation's energies)
-        if (!energy) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_W2_NOE>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-        else if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-        else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-        return;
-    }
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_W2 + 1>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_W2 + 1>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-}
-
-#elif RMX_PART == 6      // full 32-link serial chains, BDF1, two wavefronts per rollout: the second one evaluates the point that may end a solve
-#if RMX_NP != 32 || !RMX_W2
-#error "RMX_PART 6 is compiled for RMX_NP = 32 with -DRMX_W2=1 and a wave-local RMX_SYNC()"
-#endif
-
-void launch_step_w2c_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a) {
-    const dim3 grid(b->B), block(128);
-    const size_t smem_bytes = m->smem_bytes + ((sizeof(double) * W2C_HELP_DOUBLES + 15) & ~(size_t)15);      // + the helper wave's own area
-    RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, true, TAG_W2>), grid, block, smem_bytes, b->stream, m->dm, o, a);
-}
-
-#elif RMX_PART == 7      // the full 32-link serial chain, BDF1: two points per evaluation of the front (rmx_pair32.h)
-#if RMX_NP != 32
-#error "RMX_PART 7 is compiled for RMX_NP = 32"
-#endif
-#include "rmx_pair32.h"
-
-template <bool ENERGY>
-__global__ void __launch_bounds__(64) k_step_bdf1_pair32(const DevModel Min, const DevOpts o, const StepArgs a) {
-    constexpr int NP = 32;
-    const DevModel M = model_view<NP, true>(Min);
-    const unsigned long long tick0 = __builtin_amdgcn_s_memtime();
-    const int traj = blockIdx.x;
-    double *sAcc, *sCol;
-    smem_setup<NP>(M, sAcc, sCol);
-    const int lane = threadIdx.x;
-    const int id = M.idx[lane & 31];             // both half-waves hold the chain: node = lane & 31
-    const size_t off = (size_t)traj * M.nr + (id >= 0 ? id : 0);
-    double q = id >= 0 ? a.q[off] : 0.0;
-    double qd = id >= 0 ? a.qd[off] : 0.0;
-    int iters = 0, halv = 0, status = 0;
-    PivotPolicy piv;
-    pair_rollout_bdf1<ENERGY>(M, o, a, sAcc, lane, traj, id, off, q, qd, iters, halv, status, piv);
-    if (id >= 0 && lane < 32) {
-        a.q[off] = q;
-        a.qd[off] = qd;
-    }
-    if (lane == 0 && a.it) {
-        a.it[traj] += iters;
-        a.ls[traj] += halv;
-        a.status[traj] |= status;
-    }
-    if (lane == 0 && a.ticks) a.ticks[traj] = __builtin_amdgcn_s_memtime() - tick0;      // (stored, not added: launch_step skips the fill for this kernel)
-}
-
-// Profiling hook (rmx_profile_phases) for the full 32-link chain: shader-clock cycles of the stages of one Newton iteration of the
-// kernel above, measured in place with ITS device functions (the pair front with the LDS scan, the matrix-core Hessian stage staged
-// from a half-wave, the guarded column-split solve) at the production occupancy.  out[16 traj + ..]: 0 one front, 1 front + Hessian
-// stage, 2 solve, 3 the loop's own arithmetic (the two points, both norms, the compensated update); 4.. stamps inside the front and the
-// Hessian stage (numbered as eval_front_e2 / eval_hess number them).
-__global__ void __launch_bounds__(64) k_phase_time_pair32(const DevModel Min, const int reps, const double* __restrict__ q,
-                                                          const double* __restrict__ qd, const double h, unsigned long long* __restrict__ out) {
-    constexpr int NP = 32;
-    const DevModel M = model_view<NP, true>(Min);
-    double *sAcc, *sCol;
-    smem_setup<NP>(M, sAcc, sCol);
-    const int lane = threadIdx.x, traj = blockIdx.x;
-    const int id = M.idx[lane & 31];
-    const size_t off = (size_t)traj * M.nr + (id >= 0 ? id : 0);
-    const double q0 = id >= 0 ? q[off] : 0.0, qd0 = id >= 0 ? qd[off] : 0.0;
-    const double* cK = RMX_CONSTS(sAcc, M.n, NP);
-    const double grav[3] = {M.grav[0], M.grav[1], M.grav[2]};
-    double x = fma(h, qd0, q0), lo = 0.0;
-    const double qB = x;
-    unsigned long long tg = 0, tH = 0, tLU = 0, tred = 0;
-    unsigned long long stamps[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    double sink = 0.0;
-    int prim = 0;
-    for (int r = 0; r < reps; ++r) {
-        NodeOut e;
-        FrontState fs;
-        bool ta, tb;
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        const double qdn = ((x - q0) + lo) / h;
-        const double xn = fma(h, qdn, x);
-        const bool isQ = (lane >> 5) != prim;
-        const double xe = isQ ? xn : x;
-        const double xqd = isQ ? ((xn - x) + 0.0) / h : qdn;
-        const double xv = isQ ? ((xn - xn) + 0.0) : ((x - qB) + lo);
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-        eval_front_pair<false, true>(M.n, cK, grav, lane, xe, xqd, xv, h, e, fs, ta, tb, sAcc);
-        sink += e.g;
-        const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-        eval_front_pair<false, true, true>(M.n, cK, grav, lane, xe, xqd, xv, h, e, fs, ta, tb, sAcc, stamps);
-        double Hdummy[NP];
-        (void)eval_hess<NP, true, false, false, true>(M, lane, fs, Hdummy, stamps, sAcc, e.g, prim);
-        const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-        bool lu_ok;
-        double dx = lu_solve_neg_diag32(M.n, lane, sAcc, e.g, lu_ok);
-        sink += lu_ok ? 0.0 : 1.0;
-        const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-        dx = dup_lo(dx);
-        double ga2, gb2;
-        wave_sum_dual(e.g * e.g, ga2, gb2);
-        const double dxn2 = wave_sum_np<NP>(dx * dx);
-        sink += (prim ? gb2 : ga2) + dxn2;
-        double xs, ls;
-        two_sum(x, fma(1e-3, dx, lo), xs, ls);      // keep the iterations data dependent
-        x = xs;
-        lo = ls;
-        prim ^= 1;
-        const unsigned long long t5 = __builtin_amdgcn_s_memtime();
-        tg += t2 - t1; tH += t3 - t2; tLU += t4 - t3; tred += (t1 - t0) + (t5 - t4);
-    }
-    if (lane == 0) {
-        out[16 * traj + 0] = tg; out[16 * traj + 1] = tH; out[16 * traj + 2] = tLU; out[16 * traj + 3] = tred;
-        for (int k = 0; k < 12; ++k) out[16 * traj + 4 + k] = stamps[k];
-    }
-    if (sink == 1.2345e301) out[0] = 0;   // keep the results live
-}
-
-void launch_phase_pairchain_32(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d) {
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH(k_phase_time_pair32, grid, block, m->smem_bytes, b->stream, m->dm, reps, b->q, b->qd, h, d);
-}
-
-void launch_step_pairchain_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const StepArgs& a, bool energy) {
-    const dim3 grid(b->B), block(64);
-    // (a call that records T, V per step takes the instantiation that carries the energies of the last evaluation)
-    if (energy) RMX_LAUNCH(k_step_bdf1_pair32<true>, grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH(k_step_bdf1_pair32<false>, grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-}
-
-#elif RMX_PART == 8      // adjoint forward sweep of trees of <= 16 nodes with a second wavefront per rollout for M, D (k_adjoint_fwd HELP)
-#if RMX_NP != 16
-#error "RMX_PART 8 is compiled for RMX_NP = 16 with a wave-local RMX_SYNC()"
-#endif
-
-void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain) {
-    const dim3 grid(b->B);
-    const size_t smem_bytes = m->smem_bytes + sizeof(double) * adj_hand_doubles(RMX_NP);
-    if (integ == INTEG_BDF1 && fullchain) {      // (configs[3]: the full 16-link chain)
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, true, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1, true><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    } else if (fullchain) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, true, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2, true><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    } else if (integ == INTEG_BDF1) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    } else {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    }
-}
-
-#elif RMX_PART == 9      // models with body-to-body forces (rmx_model_set_point_forces): the kernels around rmx_pf.h, every size
-
-// simLoop of driverRedMaxBDF1.m:57-91 (INTEG 1) / driverRedMaxBDF2.m:57-125 (INTEG 2: SDIRK2 start step, then BDF2) with the point
-// forces: k_step_bdf1 / k_step_bdf2 of the plain kernels around newton_pf, all steps of a rollout in one launch.
-template <int NP, int INTEG>
-__global__ void __launch_bounds__(64) k_step_pf(const DevModel M, const DevOpts o, const StepArgs a, const PfTable* __restrict__ pf) {
-    const unsigned long long tick0 = __builtin_amdgcn_s_memtime();
-    const int traj = blockIdx.x;
-    double *sAcc, *sCol;
-    smem_setup<NP>(M, sAcc, sCol);
-    const PfTable& T = *pf;
-    const int lane = threadIdx.x;
-    const double h = o.h;
-    const int id = (lane < M.n) ? M.idx[lane] : -1;
-    const size_t off = (size_t)traj * M.nr + (id >= 0 ? id : 0);
-    double q = id >= 0 ? a.q[off] : 0.0;
-    double qd = id >= 0 ? a.qd[off] : 0.0;
-    double qp = 0.0, qdp = 0.0;              // step k-1 (BDF2)
-    bool started = true;
-    if constexpr (INTEG == INTEG_BDF2) {
-        qp = id >= 0 ? a.qp[off] : 0.0;
-        qdp = id >= 0 ? a.qdp[off] : 0.0;
-        started = (*a.started) != 0;
-    }
-    int iters = 0, halv = 0, status = 0;
-    PivotPolicy piv;
-    for (int s = 0; s < a.nsteps; ++s) {
-        NodeOut last;
-        double xlo;
-        if constexpr (INTEG == INTEG_BDF1) {
-            const double q0 = q, qd0 = qd;
-            const double xg = q0 + h * qd0;          // initial guess (:70) and q0 + h qdot0 of dqtmp (:169)
-            const double x = newton_pf<NP>(M, T, o, sAcc, lane, xg, q0, xg, h, last, iters, halv, status, piv, xlo);
-            qd = ((x - q0) + xlo) / h;               // (:72), with the low-order part of the iterate the residual was evaluated at
-            q = x;
-        } else if (s == 0 && !started) {
-            const double al = (2.0 - sqrt(2.0)) / 2.0;    // (:74)
-            const double q0 = q, qd0 = qd;
-            // SDIRK2a (evalSDIRK2a :194-225): eta = a h, qA = q0, qB = q0 + a h qdot0
-            const double xa0 = q0 + al * h * qd0;
-            const double qa = newton_pf<NP>(M, T, o, sAcc, lane, xa0, q0, q0 + (al * h) * qd0, al * h, last, iters, halv, status, piv, xlo);
-            const double qda = (qa - q0) / (al * h);
-            // SDIRK2b (evalSDIRK2b :228-260)
-            const double x10 = qa + (1.0 - al) * h * qda;
-            const double qA = q0 + (1.0 - al) * h * qda;
-            const double qB = q0 + (2.0 * al - 1.0) * h * qd0 + 2.0 * (1.0 - al) * h * qda;
-            const double q1 = newton_pf<NP>(M, T, o, sAcc, lane, x10, qA, qB, al * h, last, iters, halv, status, piv, xlo);
-            qd = (q1 - q0 - (1.0 - al) * h * qda) / (al * h);
-            q = q1;
-            qp = q0;
-            qdp = qd0;
-        } else {
-            // BDF2 (evalBDF2 :263-293): eta = 2h/3
-            const double q0 = qp, qd0 = qdp, q1 = q, qd1 = qd;
-            const double x0 = q1 + h * qd1;
-            const double qA = (4.0 / 3.0) * q1 - (1.0 / 3.0) * q0;
-            const double qB = (4.0 / 3.0) * q1 - (1.0 / 3.0) * q0 + (8.0 / 9.0) * h * qd1 - (2.0 / 9.0) * h * qd0;
-            const double q2 = newton_pf<NP>(M, T, o, sAcc, lane, x0, qA, qB, (2.0 / 3.0) * h, last, iters, halv, status, piv, xlo);
-            qp = q1;
-            qdp = qd1;
-            qd = (3.0 / (2.0 * h)) * (q2 - (4.0 / 3.0) * q1 + (1.0 / 3.0) * q0);
-            q = q2;
-        }
-        if (a.histT) {                               // Scene.saveHistory (Scene.m:134-161)
-            const double Tk = wave_sum(last.eT), Vk = wave_sum(last.eV);
-            if (lane == 0) {
-                a.histT[(size_t)s * a.B + traj] = Tk;
-                a.histV[(size_t)s * a.B + traj] = Vk;
-            }
-        }
-        if (a.histQ && id >= 0) {
-            a.histQ[(size_t)s * a.B * M.nr + off] = q;
-            a.histQd[(size_t)s * a.B * M.nr + off] = qd;
-        }
-    }
-    if (id >= 0) {
-        a.q[off] = q;
-        a.qd[off] = qd;
-        if constexpr (INTEG == INTEG_BDF2) {
-            a.qp[off] = qp;
-            a.qdp[off] = qdp;
-        }
-    }
-    if (lane == 0 && a.it) {
-        a.it[traj] += iters;
-        a.ls[traj] += halv;
-        a.status[traj] |= status;
-    }
-    if (lane == 0 && a.ticks) a.ticks[traj] += __builtin_amdgcn_s_memtime() - tick0;      // (rmx_step_ticks)
-}
-
-// Parity hook (k_eval) with the point forces.
-template <int NP, bool WANT_H>
-__global__ void __launch_bounds__(64) k_eval_pf(const DevModel M, const int B, const double* __restrict__ q, const double* __restrict__ qA,
-                                                const double* __restrict__ qB, const double eta, double* __restrict__ g, double* __restrict__ H,
-                                                const PfTable* __restrict__ pf) {
-    double *sAcc, *sCol;
-    smem_setup<NP>(M, sAcc, sCol);
-    const int lane = threadIdx.x, traj = blockIdx.x;
-    const int id = (lane < M.n) ? M.idx[lane] : -1;
-    const size_t off = (size_t)traj * M.nr + (id >= 0 ? id : 0);
-    const double x = id >= 0 ? q[off] : 0.0;
-    const double xa = id >= 0 ? qA[off] : 0.0;
-    const double xb = id >= 0 ? qB[off] : 0.0;
-    NodeOut e;
-    double Hrow[NP];
-    eval_node_pf<NP, WANT_H>(M, *pf, sAcc, lane, x, (x - xa) / eta, x - xb, eta, e, Hrow);
-    if (id >= 0) g[off] = e.g;
-    if (WANT_H) {
-        double* Ht = H + (size_t)traj * M.nr * M.nr;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            if (i < M.n) {
-                const int ci = M.idx[i];
-                if (id >= 0 && ci >= 0) Ht[(size_t)ci * M.nr + id] = Hrow[i];   // column-major H(id, ci)
-            }
-        }
-    }
-}
-
-// Joint / Body / Force.computeEnergy at the stored state.
-template <int NP>
-__global__ void __launch_bounds__(64) k_energy_pf(const DevModel M, const int B, const double* __restrict__ q, const double* __restrict__ qd,
-                                                  double* __restrict__ T, double* __restrict__ V, const PfTable* __restrict__ pf) {
-    double *sAcc, *sCol;
-    smem_setup<NP>(M, sAcc, sCol);
-    const int lane = threadIdx.x, traj = blockIdx.x;
-    const int id = (lane < M.n) ? M.idx[lane] : -1;
-    const size_t off = (size_t)traj * M.nr + (id >= 0 ? id : 0);
-    NodeOut e;
-    double Hrow[NP];
-    eval_node_pf<NP, false>(M, *pf, sAcc, lane, id >= 0 ? q[off] : 0.0, id >= 0 ? qd[off] : 0.0, 0.0, 1.0, e, Hrow);
-    const double t = wave_sum(e.eT), v = wave_sum(e.eV);
-    if (lane == 0) {
-        T[traj] = t;
-        V[traj] = v;
-    }
-}
-
-void RMX_CAT(launch_eval_pf_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
-    const dim3 grid(b->B), block(64);
-    const PfTable* pf = (const PfTable*)m->dpf;
-    if (wantH) RMX_LAUNCH((k_eval_pf<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, pf);
-    else RMX_LAUNCH((k_eval_pf<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, pf);
-}
-void RMX_CAT(launch_step_pf_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    const dim3 grid(b->B), block(64);
-    const PfTable* pf = (const PfTable*)m->dpf;
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_pf<RMX_NP, INTEG_BDF1>), grid, block, m->smem_bytes, b->stream, m->dm, o, a, pf);
-    else RMX_LAUNCH((k_step_pf<RMX_NP, INTEG_BDF2>), grid, block, m->smem_bytes, b->stream, m->dm, o, a, pf);
-}
-void RMX_CAT(launch_energy_pf_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV) {
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_energy_pf<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->q, b->qd, dT, dV, (const PfTable*)m->dpf);
-}
-
-#elif RMX_PART == 2      // the FULLCHAIN instantiations of the plain step kernels (sizes 16, 32, 64), one object per size
-
-void RMX_CAT(launch_step_fullchain_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    const dim3 grid(b->B), block(64);
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-}
-#if RMX_NP == 64
-// a tree that fills all 64 node slots (n == NP at compile time; LDS-resident constants)
-void launch_step_fulln_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    const dim3 grid(b->B), block(64);
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false, false, false, TAG_FULLN>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, false, false, false, TAG_FULLN>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-}
-#endif
-
-#elif RMX_PART == 1
-
-void RMX_CAT(launch_eval_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
-    const dim3 grid(b->B), block(64);
-    if (wantH) RMX_LAUNCH((k_eval<RMX_NP, true, true>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, b->chart);
-    else RMX_LAUNCH((k_eval<RMX_NP, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, b->chart);
-}
-void RMX_CAT(launch_mfd_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD) {
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_eval_mfd<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, dM, df, dD, b->chart);
-}
-// contact_pass false: the lean launch alone (scenes without ForceGroundCuboid; serial chains of <= 32 nodes, whose steps with the
-// contact terms RMX_PART 4's launch_step_pair_32 takes)
-void RMX_CAT(launch_step_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool contact_pass) {
-    const dim3 grid(b->B), block(64);
-    // every trajectory as far as it stays clear of the ground (all the way in scenes without ForceGroundCuboid) ...
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, true, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, true, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    if (!contact_pass) return;
-    // ... and the rest of its steps with the contact terms
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-}
-void RMX_CAT(launch_energy_ct_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV) {
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_energy<RMX_NP, true>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->q, b->qd, dT, dV, b->chart);
-}
-
-#else
-
-void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
-    const dim3 grid(b->B), block(64);
-    // scenes with ForceGroundCuboid or JointSpherical run the extended instantiations (CT), everything else the plain ones
-    if (m->dm.con != nullptr || m->dm.nsph > 0) return RMX_CAT(launch_eval_ct_, RMX_NP)(m, b, wantH, eta, dg, dH);
-    if (wantH) RMX_LAUNCH((k_eval<RMX_NP, true, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, nullptr);
-    else RMX_LAUNCH((k_eval<RMX_NP, false, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, b->tmpC, eta, dg, dH, nullptr);
-}
-
-void RMX_CAT(launch_step_plain_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a) {
-    const dim3 grid(b->B), block(64);
-    if (integ == INTEG_BDF1) RMX_LAUNCH((k_step_bdf1<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else RMX_LAUNCH((k_step_bdf2<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-}
-
-void RMX_CAT(launch_euler_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double h, const StepArgs& a) {
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_step_euler<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, h, a);
-}
-
-void RMX_CAT(launch_energy_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV) {
-    const dim3 grid(b->B), block(64);
-    if (m->dm.con || m->dm.nsph) return RMX_CAT(launch_energy_ct_, RMX_NP)(m, b, dT, dV);
-    RMX_LAUNCH((k_energy<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->q, b->qd, dT, dV, nullptr);
-}
-
-void RMX_CAT(launch_adjoint_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
-    const dim3 grid(b->B), block(64);
-    if (integ == INTEG_BDF1) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-    } else {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-    }
-}
-#if RMX_NP == 16
-// the full 16-link chain: the instantiation RMX_PART 8 runs with its helper wave
-void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
-    const dim3 grid(b->B), block(64);
-    if (integ == INTEG_BDF1) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-    } else {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-    }
-}
-#endif
-
-void RMX_CAT(launch_mfd_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD) {
-    // (con alone, not con || nsph as eval / step / energy: k_eval_mfd sets the Euler charts up itself in BOTH instantiations, CT adds only the contact terms)
-    if (m->dm.con) return RMX_CAT(launch_mfd_ct_, RMX_NP)(m, b, dM, df, dD);
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_eval_mfd<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->tmpA, b->tmpB, dM, df, dD, b->chart);
-}
-
-#if RMX_NP == 64
-void launch_stage_consts_64(const rmx_model* m, double* dst, hipStream_t stream) {
-    k_stage_consts<64><<<dim3(1), dim3(64), 0, stream>>>(m->dm, dst);
-}
-#endif
-
-void RMX_CAT(launch_phase_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d) {
-    const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_phase_time<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, reps, b->q, b->qd, h, d);
-}
-
-#endif

@@ -42,11 +42,8 @@ __device__ __forceinline__ void pair_rollout_bdf1(const DevModel& M, const DevOp
     if (a.nsteps <= 0) return;
     const double* cK = RMX_CONSTS(sAcc, M.n, NP);
     const double grav[3] = {M.grav[0], M.grav[1], M.grav[2]};
-#ifndef RMX_PAIR_REGK
-#define RMX_PAIR_REGK 1            // 0: the per-node constants from the wave's LDS copy at every evaluation (build variants)
-#endif
     double rk[PAIR_NK];            // this lane's per-node constants, in registers for the whole rollout (the kernel holds 270 of 512)
-    if constexpr (RMX_PAIR_REGK) pair_load_consts(cK, lane, rk);
+    pair_load_consts(cK, lane, rk);
     const double h = o.h;
     const bool hiH = lane >= 32;
     FrontState fs;
@@ -108,7 +105,7 @@ __device__ __forceinline__ void pair_rollout_bdf1(const DevModel& M, const DevOp
         const double xqd = isQ ? ((xn - x) + 0.0) / h : qdn;
         const double xv = isQ ? ((xn - xn) + 0.0) : ((x - qB) + lo);
         bool ta, tb;
-        eval_front_pair<false, true, false, RMX_PAIR_REGK != 0>(M.n, cK, grav, lane, xe, xqd, xv, h, e, fs, ta, tb, sAcc, nullptr, rk);
+        eval_front_pair<false, true, false, true>(M.n, cK, grav, lane, xe, xqd, xv, h, e, fs, ta, tb, sAcc, nullptr, rk);
         double ga2, gb2;
         wave_sum_dual(e.g * e.g, ga2, gb2);
         if (redo) prim = 0;

@@ -1,6 +1,6 @@
 // rmx_pf.h -- body-to-body forces (ForcePointPoint.m, ForceSpringDamper.m / ForceSpringGeneric.m, ForceCable.m /
 // ForceSpringMultiPointGeneric.m of the reference) for the one-wavefront kernels: the point stage behind eval_front, the dense
-// update of the Hessian rows behind eval_hess, and the Newton loop around them.  rmx_kernels.hip RMX_PART 9 instantiates the
+// update of the Hessian rows behind eval_hess, and the Newton loop around them.  part_pf.hip instantiates the
 // kernels; nothing here is reached by a model without a force table.
 //
 // Point k of a force sits on node b_k at the local position xl_k: x_k = R xl_k + p, Gw_k = [-[x_k], I], v_k = Gw_k phi_{b_k}.

@@ -1,7 +1,7 @@
 // rmx_select.h -- which kernel family a step / adjoint call runs: the ONE place that decides it.
 // Host only and free of HIP types (tests/test_step_plan.py compiles it with plain g++): select_step() maps what the model, the
 // device, the call and the environment say onto a StepPlan; launch_step (redmax_hip.hip) executes the plan through leaf launchers
-// (rmx_kernels.hip, rmx_big.hip) that decide nothing themselves.  The table is DESIGN.md "Which kernel runs"; first match wins.
+// (the part_*.hip files, rmx_big.hip) that decide nothing themselves.  The table is DESIGN.md "Which kernel runs"; first match wins.
 #pragma once
 #include <cstdlib>
 
@@ -44,26 +44,20 @@ inline StepKnobs knobs_from_env() {
     return k;
 }
 
-#ifdef RMX_NO_FULLCHAIN      // development aid (tools/build_variant.py --host): without the n == NP specialisations of rows 8 and 10
-constexpr bool USE_FULL_SPECIALISATIONS = false;
-#else
-constexpr bool USE_FULL_SPECIALISATIONS = true;
-#endif
-
 // One enumerator per launch recipe (the row of the table in the comment).
 enum class StepKernel {
     Big,             //  1 rmx_big.hip
-    PointForces,     //  2 part 9
-    Ct,              //  3 part 1: the lean launch, then (contact) the launch with the contact terms
-    Ground32,        //  4 part 4: k_ground32 (fused modes 1, 2, 3)
-    StepPair32,      //  4 part 1's lean launch, then part 4: k_step_pair (fused mode 0)
-    W2_64,           //  5 part 5
-    PairChain32,     //  6 part 7
-    W2Chain32,       //  7 part 6
-    FullChain,       //  8 part 2
-    Gconst64,        //  9 part 3
-    FullN64,         // 10 part 2
-    Plain,           // 11 part 0
+    PointForces,     //  2 part_pf
+    Ct,              //  3 part_ct: the lean launch, then (contact) the launch with the contact terms
+    Ground32,        //  4 part_ground32: k_ground32 (fused modes 1, 2, 3)
+    StepPair32,      //  4 part_ct's lean launch, then part_ground32: k_step_pair (fused mode 0)
+    W2_64,           //  5 part_w2_tree64
+    PairChain32,     //  6 part_pair32
+    W2Chain32,       //  7 part_w2_chain32
+    FullChain,       //  8 part_fullchain
+    Gconst64,        //  9 part_gconst64
+    FullN64,         // 10 part_fullchain
+    Plain,           // 11 part_plain
 };
 
 struct StepPlan {
@@ -133,20 +127,20 @@ inline StepPlan select_step(const StepTraits& t, const int B, const int integ, c
         p.block = 128;
         return is(StepKernel::W2Chain32, "k_step_bdf1<32,fullchain,w2>");
     }
-    if (USE_FULL_SPECIALISATIONS && t.NP >= 16 && fullchain) return is(StepKernel::FullChain, label_fullchain(t.NP, bdf1));      // 8
+    if (t.NP >= 16 && fullchain) return is(StepKernel::FullChain, label_fullchain(t.NP, bdf1));      // 8
     if (t.NP == 64 && t.gconst && t.gconst_min_batch > 0 && B >= t.gconst_min_batch) {                               // 9
         p.fulln = full;
         return is(StepKernel::Gconst64, bdf1 ? "k_step_bdf1<64,gconst>" : "k_step_bdf2<64,gconst>");
     }
-    if (USE_FULL_SPECIALISATIONS && t.NP == 64 && full) return is(StepKernel::FullN64, bdf1 ? "k_step_bdf1<64,fulln>" : "k_step_bdf2<64,fulln>");      // 10
+    if (t.NP == 64 && full) return is(StepKernel::FullN64, bdf1 ? "k_step_bdf1<64,fulln>" : "k_step_bdf2<64,fulln>");      // 10
     return is(StepKernel::Plain, label_plain(t.NP, bdf1));                                                          // 11
 }
 
 // The adjoint pair (forward sweep + backward sweep) of trees of <= 64 nodes without contact, Euler charts or point forces.
 enum class AdjKernel {
-    Help16,          // part 8: a second wavefront per rollout forms and stores M, D (batches of up to one rollout per two SIMDs)
-    FullChain16,     // part 0: the full 16-link chain
-    Generic,         // part 0
+    Help16,          // part_adjhelp16: a second wavefront per rollout forms and stores M, D (batches of up to one rollout per two SIMDs)
+    FullChain16,     // part_plain: the full 16-link chain
+    Generic,         // part_plain
 };
 struct AdjPlan {
     AdjKernel kernel = AdjKernel::Generic;

@@ -531,7 +531,7 @@ def test_floor_and_wall_on_every_body(oracle_lib):
 
 def test_one_launch_cooperative_path_at_odd_sizes(monkeypatch):
     """The default launch of a chain with ground contact is ONE kernel in which the rollouts and, dispatched behind them, the cooperative
-    groups run side by side (rmx_kernels.hip k_ground32).  Sizes it must survive: more rollouts than SIMDs (1500 on 1024), a handful (37:
+    groups run side by side (part_ground32.hip k_ground32).  Sizes it must survive: more rollouts than SIMDs (1500 on 1024), a handful (37:
     fewer rollouts than a group has members to spare), and two shards of 600 on ONE device - two such launches competing for the SIMDs.
     Every case against one wavefront per rollout: states bit for bit, no group gave up (status 512)."""
     from redmax_amd import BatchSim, GroupSim, sceneChainGround, syntheticStates

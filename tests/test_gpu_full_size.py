@@ -183,7 +183,7 @@ def test_trees_of_33_to_64_nodes_match_oracle(oracle_lib):
 
 def test_tree64_global_constants_kernels(oracle_lib, monkeypatch):
     """Batches of more than two rollouts per CU run the 64-lane step kernels that read the per-node constants from global memory
-    instead of LDS (four wavefronts per CU instead of two; rmx_kernels.hip RMX_PART 3).  Same arithmetic on the same values: the
+    instead of LDS (four wavefronts per CU instead of two; part_gconst64.hip).  Same arithmetic on the same values: the
     results must equal the LDS-constants kernels' (RMX_GCONST_MIN moves the threshold, read at model creation), BDF1 and BDF2, and
     the oracle's."""
     from redmax_amd import BatchSim
@@ -217,7 +217,7 @@ def test_tree64_global_constants_kernels(oracle_lib, monkeypatch):
 
 @pytest.mark.parametrize("nodes", [64, 41, -64])
 def test_tree64_two_wave_kernels(monkeypatch, nodes):
-    """Batches of at most one rollout per two SIMDs give a 33..64-node tree TWO wavefronts (rmx_kernels.hip RMX_PART 5): the second
+    """Batches of at most one rollout per two SIMDs give a 33..64-node tree TWO wavefronts (part_w2_tree64.hip): the second
     one takes the odd columns of the Hessian tiles and its share of the later column blocks in every phase of the block-column
     elimination.  Every matrix entry sees the same operations on the same values in the same order as in the one-wave kernels:
     bit-identical states, iteration counts and status words (RMX_W2_MAX moves the threshold, read at model creation) - BDF2, pivoting
@@ -283,7 +283,7 @@ def test_tree64_two_wave_kernels(monkeypatch, nodes):
 def test_chain32_two_wave_kernel(monkeypatch):
     """Shards of 128 .. 512 rollouts of the full 32-link chain (the 1024-rollout batch of BASELINE.json configs[1] on two or more GPUs) run
     BDF1 with a second wavefront per rollout that evaluates the point which may end a step's solve while the first one evaluates the
-    next step's first point (rmx_kernels.hip RMX_PART 6, w2_steps_bdf1).  The helper runs the full front, every decision is
+    next step's first point (part_w2_chain32.hip, w2_steps_bdf1).  The helper runs the full front, every decision is
     newton_rot's: states, Newton counts, status words and histories equal the one-wave headline kernel's bit for bit, with the run-ahead
     on and off, on the bench states and on states wild enough for line searches."""
     from redmax_amd import BatchSim, sceneChain, syntheticStates
@@ -319,7 +319,7 @@ def test_chain32_two_wave_kernel(monkeypatch):
 
 
 def test_chain32_pair_kernel(monkeypatch):
-    """The headline kernel (rmx_pair32.h, RMX_PART 7): every evaluation of the front carries the next step's first point beside the
+    """The headline kernel (rmx_pair32.h, part_pair32.hip): every evaluation of the front carries the next step's first point beside the
     line-search trial, in the half-wave a 32-node tree leaves idle; a trial that ends a step's solve hands the next solve its first
     evaluation.  Every decision and every operation per point is the one-point kernel's (RMX_PAIRC=0): states, Newton counts, halvings,
     status words and per-step energies must be equal bit for bit - on the bench states at the reference's tol, on states wild enough for

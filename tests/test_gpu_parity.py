@@ -383,7 +383,7 @@ def test_adjoint_with_device_arrays_equals_the_host_call(integ):
 @pytest.mark.parametrize("n,B,K,integ", [(16, 96, 12, 1), (16, 96, 12, 2), (11, 33, 9, 1), (16, 1, 5, 2)])
 def test_adjoint_helper_wave_equals_one_wave(n, B, K, integ, monkeypatch):
     """Trees of <= 16 nodes in batches of up to one rollout per two SIMDs: a second wavefront per rollout forms and stores M, D of every
-    step from the numbers the rollout's wavefront leaves in LDS (rmx_kernels.hip RMX_PART 8, k_adjoint_fwd HELP) - the same function on
+    step from the numbers the rollout's wavefront leaves in LDS (part_adjhelp16.hip, k_adjoint_fwd HELP) - the same function on
     the same numbers: P, dP/dp, the final state and the counters equal the one-wave kernel's (RMX_ADJ_HELP=0) bit for bit."""
     from redmax_amd import BatchSim
     from redmax_amd.scenes import sceneAdjointChain

@@ -1,4 +1,4 @@
-"""configs[3] (16-DOF chain, 512 rollouts, 20 steps): the adjoint launch pair with a second wavefront per rollout for M, D (RMX_PART 8, the
+"""configs[3] (16-DOF chain, 512 rollouts, 20 steps): the adjoint launch pair with a second wavefront per rollout for M, D (part_adjhelp16.hip, the
 default for batches of up to one rollout per two SIMDs) against one wavefront per rollout (RMX_ADJ_HELP=0): P, dP/dp, counters bit for
 bit, kernel milliseconds; BDF1 and BDF2, a second batch size and a smaller tree.
     python tools/adj_help_check.py"""

@@ -1,4 +1,4 @@
-"""The two-point kernel of the full 32-link chain (rmx_pair32.h, RMX_PART 7: every front carries the next step's first point beside the
+"""The two-point kernel of the full 32-link chain (rmx_pair32.h, part_pair32.hip: every front carries the next step's first point beside the
 trial) against the one-point headline kernel (RMX_PAIRC=0): kernel time per K steps, bit-equality of states / Newton counts / halvings /
 status / per-step energies, on the bench states, on wild states (line searches, diverging rollouts), with lu_mode 1 and with
 compensated = 0.  RMX_PAIRC is read at every step call.  Usage: pairc_check.py [batch ...]"""
