@@ -340,6 +340,26 @@ int rmx_adjoint_bdf1_device(rmx_batch* b, const rmx_opts* opts, int nsteps, cons
 int rmx_adjoint_bdf2_device(rmx_batch* b, const rmx_opts* opts, int nsteps, const rmx_task_pointpos* task, const double* d_p,
                             double* d_P, double* d_dPdp, rmx_stats* stats);
 
+/* One torque per joint and STEP, and the gradient for each of them: what trajectory optimisation and policy training need, where
+ * rmx_adjoint_bdf1 / bdf2 take one constant torque vector per rollout.  The reference's own structure is per step - task.applyStep
+ * runs at every step (driverRedMaxAdjointBDF1.m:74) and TaskBDF1.calcFinal forms one z_k per step (TaskBDF1.m:52-79); its one
+ * shipped task sums them because its parameters are constant.
+ * integrator: 1 = BDF1, 2 = BDF2 (as rmx_step_history).  u: host [batch][nsteps][nr], trajectory-major, reduced DOF order; at step
+ * k = 1 .. nsteps the joint torque is tau + pscale * u[b][k-1][:] (under BDF2 step 1's torque holds for both SDIRK2 solves).
+ *     P[b]            = wpos/2 |x(task->step) - xtarget|^2 + wreg/2 * sum over k, j of u[b][k-1][j]^2
+ *     dPdu[b][k-1][j] = wreg * u[b][k-1][j] + e2 * pscale * z_k[j] ,   e2 = h^2 (BDF1) or (4/9) h^2 (BDF2, every step)
+ * which is the constant-parameter formula before its sum over the steps; rows behind task->step hold wreg * u exactly.  Under
+ * BDF2 the k = 1 row therefore carries the reference's own start-step approximation (dg/dp = -(4/9) h^2 pscale I for the SDIRK2
+ * start step too and dg/dqa dropped, TaskBDF2PointPos.m:97-106, TaskBDF2.m:52-55); the rows of k >= 2 are exact.
+ * P: host [batch]; dPdu: host, shape of u, or NULL: the forward sweep alone (the backward kernel is not launched, P is still
+ * written) - a controlled rollout with the reference's line-search-free newton.  u is neither retained nor modified.  Refusals,
+ * opts, stats and the state the batch is left in (with the BDF2 history in place) as rmx_adjoint_bdf1 / bdf2.
+ * rmx_adjoint_controls_device: the same with DEVICE pointers d_u, d_P, d_dPdu (d_dPdu may be NULL), as rmx_adjoint_bdf1_device. */
+int rmx_adjoint_controls(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_pointpos* task,
+                         const double* u, double* P, double* dPdu, rmx_stats* stats);
+int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_pointpos* task,
+                                const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats);
+
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.
  * hist_T/hist_V as in rmx_step_bdf1. */

@@ -130,5 +130,19 @@ classdef HipSim < handle
 			end
 			[P, dPdp, stats] = redmax_hip_mex('adjoint', this.h, hstep, nsteps, task, p, itype);
 		end
+
+		function [P, dPdu, stats] = adjointControls(this, hstep, nsteps, task, u, itype)
+			% the adjoint with one torque per joint and step (task.applyStep at every step): u, dPdu are nr x nsteps x B;
+			% at step k the joint torque is tau + task.pscale*u(:,k,b).  itype 1 (BDF1, default) / 2 (BDF2).
+			% With one output, P = sim.adjointControls(...), only the forward rollout runs.
+			if nargin < 6
+				itype = 1;
+			end
+			if nargout < 2
+				P = redmax_hip_mex('adjoint_controls', this.h, hstep, nsteps, task, u, itype);
+			else
+				[P, dPdu, stats] = redmax_hip_mex('adjoint_controls', this.h, hstep, nsteps, task, u, itype);
+			end
+		end
 	end
 end

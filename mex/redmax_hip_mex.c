@@ -50,6 +50,9 @@
  *                  driverRedMaxAdjointBDF1.m:39-62 (integrator 1, default) or driverRedMaxAdjointBDF2.m:38-62 (integrator 2);
  *                  task: struct body (1-based listing index), xlocal, xtarget, step, pscale, wreg, wpos; p: nr x B;
  *                  st: B x 2 int32 [newton iterations, status]
+ *   [P,dPdu,st]  = redmax_hip_mex('adjoint_controls', h, hstep, nsteps, task, u [, integrator])  rmx_adjoint_controls: one torque
+ *                  per joint and step.  u, dPdu: nr x nsteps x B (the ABI's [B][nsteps][nr]); task, integrator, st as 'adjoint'.
+ *                  With one output the forward sweep runs alone (P of a controlled rollout, no gradient).
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -439,23 +442,27 @@ static void cmd_values(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
     for (int i = 0; i < 5 && (i == 0 || i < nlhs); ++i) plhs[i] = out[i];
 }
 
-static void cmd_adjoint(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 6) die("usage: [P,dPdp,stats] = redmax_hip_mex('adjoint', h, hstep, nsteps, task, p [, integrator])");
-    const mxArray* t = prhs[4];
+/* the task struct of 'adjoint' / 'adjoint_controls' (TaskBDF1PointPos) */
+static void read_task(const mxArray* t, rmx_task_pointpos* task) {
     if (!mxIsStruct(t)) die("task must be a struct");
-    rmx_task_pointpos task;
-    memset(&task, 0, sizeof task);
-    task.body = (int)scalar_field(t, "body", 1) - 1;   /* MATLAB listing index -> 0-based */
+    memset(task, 0, sizeof *task);
+    task->body = (int)scalar_field(t, "body", 1) - 1;   /* MATLAB listing index -> 0-based */
     const mxArray* xl = field(t, "xlocal", 1);
     const mxArray* xt = field(t, "xtarget", 1);
     if (mxGetNumberOfElements(xl) != 3 || mxGetNumberOfElements(xt) != 3) die("task.xlocal / task.xtarget must have 3 elements");
-    memcpy(task.xlocal, mxGetPr(xl), 3 * sizeof(double));
-    memcpy(task.xtarget, mxGetPr(xt), 3 * sizeof(double));
-    task.step = (int)scalar_field(t, "step", 0);
-    task.pscale = scalar_field(t, "pscale", 1.0);
-    task.wreg = scalar_field(t, "wreg", 0.0);
-    task.wpos = scalar_field(t, "wpos", 1.0);
+    memcpy(task->xlocal, mxGetPr(xl), 3 * sizeof(double));
+    memcpy(task->xtarget, mxGetPr(xt), 3 * sizeof(double));
+    task->step = (int)scalar_field(t, "step", 0);
+    task->pscale = scalar_field(t, "pscale", 1.0);
+    task->wreg = scalar_field(t, "wreg", 0.0);
+    task->wpos = scalar_field(t, "wpos", 1.0);
+}
+
+static void cmd_adjoint(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 6) die("usage: [P,dPdp,stats] = redmax_hip_mex('adjoint', h, hstep, nsteps, task, p [, integrator])");
+    rmx_task_pointpos task;
+    read_task(prhs[4], &task);
     rmx_opts o;
     rmx_opts_default(&o);
     o.h = mxGetScalar(prhs[2]);
@@ -489,6 +496,48 @@ static void cmd_adjoint(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     if (nlhs > 2) plhs[2] = st;
 }
 
+static void cmd_adjoint_controls(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 6) die("usage: [P,dPdu,stats] = redmax_hip_mex('adjoint_controls', h, hstep, nsteps, task, u [, integrator])");
+    rmx_task_pointpos task;
+    read_task(prhs[4], &task);
+    rmx_opts o;
+    rmx_opts_default(&o);
+    o.h = mxGetScalar(prhs[2]);
+    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    const int nsteps = (int)mxGetScalar(prhs[3]);
+    if (nsteps < 1) die("adjoint_controls: nsteps must be at least 1");
+    const int integ = nrhs > 6 ? (int)mxGetScalar(prhs[6]) : 1;
+    if (integ != 1 && integ != 2) die("adjoint_controls: the integrator must be 1 (BDF1) or 2 (BDF2)");
+    const mxArray* ua = prhs[5];
+    const size_t per = (size_t)h->nr * (size_t)nsteps;      /* one rollout's controls: nr x nsteps x B is the ABI's [B][nsteps][nr] */
+    if (!mxIsDouble(ua) || mxIsComplex(ua) || mxGetNumberOfElements(ua) != per * (size_t)h->B)
+        mexErrMsgIdAndTxt("redmax:hip", "u must be a real double nr x nsteps x batch (%d x %d x %d) array", h->nr, nsteps, h->B);
+    const double* u = mxGetPr(ua);
+    mxArray* P = mxCreateDoubleMatrix(1, (size_t)h->B, mxREAL);
+    mxArray* dPdu = NULL;                              /* one output: the forward sweep alone */
+    if (nlhs > 1) {
+        const size_t dims[3] = {(size_t)h->nr, (size_t)nsteps, (size_t)h->B};
+        dPdu = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    }
+    mxArray* st = new_i32((size_t)h->B, 2);
+    int* sp = (int*)mxGetData(st);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'adjoint' */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_stats st_s;
+        st_s.newton_iters = sp + f;
+        st_s.ls_halvings = NULL;
+        st_s.status = sp + h->B + f;
+        if (rmx_adjoint_controls(b, &o, nsteps, integ, &task, u + f * per, mxGetPr(P) + f, dPdu ? mxGetPr(dPdu) + f * per : NULL, &st_s))
+            die_rmx("rmx_adjoint_controls");
+    }
+    plhs[0] = P;
+    if (nlhs > 1) plhs[1] = dPdu;
+    if (nlhs > 2) plhs[2] = st;
+    else mxDestroyArray(st);
+}
+
 /* `clear mex` / MATLAB exit: free what is still alive on the device */
 static void at_exit(void) {
     for (int i = 0; i < MAX_LIVE; ++i)
@@ -511,7 +560,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * may name the handle ('step' / 'step_async' refuse with their own text).  Everything below reads or writes the state, the
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
-                                             "adjoint", NULL};
+                                             "adjoint", "adjoint_controls", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -612,6 +661,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[0] = out;
     } else if (!strcmp(cmd, "adjoint")) {
         cmd_adjoint(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "adjoint_controls")) {
+        cmd_adjoint_controls(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

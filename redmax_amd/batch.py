@@ -207,17 +207,7 @@ class BatchSim:
         """taskObjective (driverRedMaxAdjointBDF1.m:39-62) for every trajectory: forward rollout from the current state
         under torques pscale*p, then the backward sweep.  task: dict(body, xlocal, xtarget, t | step, pscale, wreg, wpos);
         p: [B][nr].  Returns (P[B], dPdp[B][nr], info)."""
-        tk = _abi.TaskPointPos()
-        tk.body = int(task["body"])
-        for i in range(3):
-            tk.xlocal[i] = float(task["xlocal"][i])
-            tk.xtarget[i] = float(task["xtarget"][i])
-        tk.step = int(task["step"]) if "step" in task else int(round(float(task["t"]) / float(h)))
-        tk.pscale, tk.wreg, tk.wpos = float(task["pscale"]), float(task["wreg"]), float(task["wpos"])
-        opts = _abi.Opts()
-        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
-        opts.h = float(h)
-        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        tk, opts = self._task_and_opts(task, h)
         p = self._arr(p)
         P = np.empty(self.B)
         dPdp = np.empty((self.B, self.nr))
@@ -235,17 +225,7 @@ class BatchSim:
     def adjoint_bdf1_device(self, nsteps, h, task, p_ptr, P_ptr, dPdp_ptr, stats=False, _fn="rmx_adjoint_bdf1_device"):
         """adjoint_bdf1 with DEVICE pointers (integers, e.g. torch.Tensor.data_ptr()) for p [B][nr], P [B] and dPdp [B][nr]: nothing
         crosses the host boundary but the optional counters.  Returns info."""
-        tk = _abi.TaskPointPos()
-        tk.body = int(task["body"])
-        for i in range(3):
-            tk.xlocal[i] = float(task["xlocal"][i])
-            tk.xtarget[i] = float(task["xtarget"][i])
-        tk.step = int(task["step"]) if "step" in task else int(round(float(task["t"]) / float(h)))
-        tk.pscale, tk.wreg, tk.wpos = float(task["pscale"]), float(task["wreg"]), float(task["wpos"])
-        opts = _abi.Opts()
-        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
-        opts.h = float(h)
-        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        tk, opts = self._task_and_opts(task, h)
         info = {}
         st = None
         if stats:
@@ -259,6 +239,66 @@ class BatchSim:
 
     def adjoint_bdf2_device(self, nsteps, h, task, p_ptr, P_ptr, dPdp_ptr, stats=False):
         return self.adjoint_bdf1_device(nsteps, h, task, p_ptr, P_ptr, dPdp_ptr, stats=stats, _fn="rmx_adjoint_bdf2_device")
+
+    def _task_and_opts(self, task, h):
+        tk = _abi.TaskPointPos()
+        tk.body = int(task["body"])
+        for i in range(3):
+            tk.xlocal[i] = float(task["xlocal"][i])
+            tk.xtarget[i] = float(task["xtarget"][i])
+        tk.step = int(task["step"]) if "step" in task else int(round(float(task["t"]) / float(h)))
+        tk.pscale, tk.wreg, tk.wpos = float(task["pscale"]), float(task["wreg"]), float(task["wpos"])
+        opts = _abi.Opts()
+        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
+        opts.h = float(h)
+        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        return tk, opts
+
+    def adjoint_controls(self, nsteps, h, task, u, integrator=1, stats=False, gradient=True):
+        """rmx_adjoint_controls: the adjoint with one torque per joint and STEP.  u: [B][nsteps][nr] (a [nsteps][nr] array holds for
+        every trajectory); at step k the joint torque is tau + pscale*u[:, k-1].  integrator: 1 (BDF1) or 2 (BDF2).  task as
+        adjoint_bdf1.  Returns (P[B], dPdu[B][nsteps][nr], info); gradient=False runs the forward rollout alone and returns None for
+        dPdu.  Under BDF2 the k = 1 rows of dPdu carry the reference's start-step approximation (include/redmax_hip.h)."""
+        nsteps = int(nsteps)
+        if u is None:
+            raise ValueError("adjoint_controls: u is None")
+        u = np.asarray(u, dtype=np.float64)
+        if u.shape == (nsteps, self.nr):
+            u = np.broadcast_to(u, (self.B, nsteps, self.nr))
+        if u.shape != (self.B, nsteps, self.nr):
+            raise ValueError("adjoint_controls: u must have shape (%d, %d, %d) or (%d, %d), got %r"
+                             % (self.B, nsteps, self.nr, nsteps, self.nr, u.shape))
+        u = np.ascontiguousarray(u)
+        tk, opts = self._task_and_opts(task, h)
+        P = np.empty(self.B)
+        dPdu = np.empty((self.B, nsteps, self.nr)) if gradient else None
+        info = {}
+        st = None
+        if stats:
+            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
+            info["status"] = np.zeros(self.B, dtype=np.int32)
+            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        _abi.check(self._L.rmx_adjoint_controls(self._batch, C.byref(opts), nsteps, int(integrator), C.byref(tk), _abi.dptr(u),
+                                                _abi.dptr(P), _abi.dptr(dPdu), C.byref(st) if st is not None else None),
+                   "rmx_adjoint_controls")
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return P, dPdu, info
+
+    def adjoint_controls_device(self, nsteps, h, task, u_ptr, P_ptr, dPdu_ptr, integrator=1, stats=False):
+        """adjoint_controls with DEVICE pointers (integers) for u [B][nsteps][nr], P [B] and dPdu [B][nsteps][nr]; dPdu_ptr 0 / None:
+        the forward rollout alone.  Returns info."""
+        tk, opts = self._task_and_opts(task, h)
+        info = {}
+        st = None
+        if stats:
+            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
+            info["status"] = np.zeros(self.B, dtype=np.int32)
+            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        _abi.check(self._L.rmx_adjoint_controls_device(self._batch, C.byref(opts), int(nsteps), int(integrator), C.byref(tk),
+                                                       C.c_void_p(u_ptr), C.c_void_p(P_ptr), C.c_void_p(dPdu_ptr or None),
+                                                       C.byref(st) if st is not None else None), "rmx_adjoint_controls_device")
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return info
 
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent

@@ -7,20 +7,26 @@
 #endif
 #include "rmx_kernels.h"
 
-void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain) {
+// (MODE: the integrator, + ADJ_CTL per-step controls, where a null a.dPdu asks for the forward sweep alone)
+template <int MODE, bool FC>
+static void adjoint_help_pair(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
     const dim3 grid(b->B);
     const size_t smem_bytes = m->smem_bytes + sizeof(double) * adj_hand_doubles(RMX_NP);
-    if (integ == INTEG_BDF1 && fullchain) {      // (configs[3]: the full 16-link chain)
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, true, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1, true><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    } else if (fullchain) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, true, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2, true><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
-    } else if (integ == INTEG_BDF1) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
+    RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, true, FC>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
+    if (!(MODE & ADJ_CTL) || a.dPdu) k_adjoint_bwd<RMX_NP, MODE, FC><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
+}
+template <bool FC>
+static void adjoint_help_pairs(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    if (integ == INTEG_BDF1) {
+        if (a.u) adjoint_help_pair<1 | ADJ_CTL, FC>(m, b, o, a);
+        else adjoint_help_pair<1, FC>(m, b, o, a);
     } else {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, true>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
+        if (a.u) adjoint_help_pair<2 | ADJ_CTL, FC>(m, b, o, a);
+        else adjoint_help_pair<2, FC>(m, b, o, a);
     }
+}
+
+void launch_adjoint_help_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain) {
+    if (fullchain) adjoint_help_pairs<true>(m, b, integ, o, a);      // (configs[3]: the full 16-link chain)
+    else adjoint_help_pairs<false>(m, b, integ, o, a);
 }

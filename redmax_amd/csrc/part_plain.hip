@@ -24,27 +24,31 @@ void RMX_CAT(launch_energy_, RMX_NP)(const rmx_model* m, const rmx_batch* b, dou
     RMX_LAUNCH((k_energy<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->q, b->qd, dT, dV, nullptr);
 }
 
-void RMX_CAT(launch_adjoint_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+// the adjoint pair of one instantiation (MODE: the integrator, + ADJ_CTL per-step controls, where a null a.dPdu asks for the forward sweep alone)
+template <int MODE, bool FC>
+static void adjoint_pair(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
     const dim3 grid(b->B), block(64);
+    RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, false, FC>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+    if (!(MODE & ADJ_CTL) || a.dPdu) k_adjoint_bwd<RMX_NP, MODE, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+}
+template <bool FC>
+static void adjoint_pairs(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
     if (integ == INTEG_BDF1) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+        if (a.u) adjoint_pair<1 | ADJ_CTL, FC>(m, b, o, a);
+        else adjoint_pair<1, FC>(m, b, o, a);
     } else {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+        if (a.u) adjoint_pair<2 | ADJ_CTL, FC>(m, b, o, a);
+        else adjoint_pair<2, FC>(m, b, o, a);
     }
+}
+
+void RMX_CAT(launch_adjoint_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    adjoint_pairs<false>(m, b, integ, o, a);
 }
 #if RMX_NP == 16
 // the full 16-link chain: the instantiation part_adjhelp16.hip runs with its helper wave
 void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
-    const dim3 grid(b->B), block(64);
-    if (integ == INTEG_BDF1) {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 1, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-    } else {
-        RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2, false, true>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-        k_adjoint_bwd<RMX_NP, 2, true><<<grid, block, 0, b->stream>>>(m->dm, o, a);
-    }
+    adjoint_pairs<true>(m, b, integ, o, a);
 }
 #endif
 

@@ -1328,9 +1328,10 @@ extern "C" int rmx_step_euler(rmx_batch* b, double h, int nsteps, double* hT, do
 }
 
 
+// controls (rmx_adjoint_controls): p is u[B][nsteps][nr], dPdp is dPdu of the same shape or null (the forward sweep alone)
 static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rmx_task_pointpos* task, const double* p, double* P,
-                        double* dPdp, rmx_stats* stats, const int integ, const bool on_device = false) {
-    if (!b || !task || !p || !P || !dPdp) return fail(RMX_E_INVALID, "null argument");
+                        double* dPdp, rmx_stats* stats, const int integ, const bool on_device = false, const bool controls = false) {
+    if (!b || !task || !p || !P || (!dPdp && !controls)) return fail(RMX_E_INVALID, "null argument");
     rmx_model* m = b->m;
     if (nsteps < 1) return fail(RMX_E_INVALID, "nsteps < 1");
     if (m->dm.con) return fail(RMX_E_INVALID, "rmx_adjoint: ground contact is outside the adjoint path (SURVEY.md 8(f))");
@@ -1345,7 +1346,7 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
     if (rc) return rc;
     rc = pending_error_check(b, "rmx_adjoint");
     if (rc) return rc;
-    const size_t nn = (size_t)m->n * m->n, nv = (size_t)b->B * m->nr;
+    const size_t nn = (size_t)m->n * m->n, nv = (size_t)b->B * m->nr * (controls ? (size_t)nsteps : 1);
     const size_t hist = (size_t)b->B * nsteps * nn * sizeof(double);
     if (3 * hist > ((size_t)200 << 30)) return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
     AdjArgs a{};
@@ -1354,12 +1355,14 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
     a.pscale = task->pscale; a.wreg = task->wreg; a.wpos = task->wpos;
     a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp; a.p = b->tmpA;
     a.it = stats ? b->it : nullptr; a.status = b->status;
-    void* bufs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t sizes[6] = {hist, hist, hist, (size_t)b->B * m->n * sizeof(double), (size_t)b->B * sizeof(double), nv * sizeof(double)};
+    // (the constant parameters are staged in tmpA; the per-step controls, nsteps times as many, in the workspace behind the gradient)
+    void* bufs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t sizes[7] = {hist, hist, hist, (size_t)b->B * m->n * sizeof(double), (size_t)b->B * sizeof(double),
+                             (on_device && controls) ? 0 : nv * sizeof(double), (controls && !on_device) ? nv * sizeof(double) : 0};
     hipError_t e = hipSuccess;
     {   // one workspace per batch, kept between calls (grow-only): parts at 256-byte boundaries
-        size_t total = 0, offs[6];
-        for (int i = 0; i < 6; ++i) {
+        size_t total = 0, offs[7];
+        for (int i = 0; i < 7; ++i) {
             offs[i] = total;
             total += (sizes[i] + 255) & ~(size_t)255;
         }
@@ -1383,16 +1386,21 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
             }
         }
         if (e == hipSuccess)
-            for (int i = 0; i < 6; ++i) bufs[i] = (char*)b->adjws + offs[i];
+            for (int i = 0; i < 7; ++i) bufs[i] = (char*)b->adjws + offs[i];
     }
     // (dPdq needs no fill: the task step lies in [1, nsteps] - checked above -, so the forward kernel writes every entry the backward
     // kernel reads; one dispatch less ahead of a 0.83 ms launch pair)
-    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(b->tmpA, p, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(controls ? bufs[6] : (void*)b->tmpA, p, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess) {
         a.Hs = (double*)bufs[0]; a.Ms = (double*)bufs[1]; a.Ds = (double*)bufs[2];
         a.dPdq = (double*)bufs[3]; a.P = (double*)bufs[4]; a.dPdp = (double*)bufs[5];
         if (on_device) {          // the caller's device arrays directly: nothing staged, nothing copied back
             a.p = p; a.P = P; a.dPdp = dPdp;
+        }
+        if (controls) {
+            a.u = on_device ? p : (const double*)bufs[6];
+            a.dPdu = dPdp ? a.dPdp : nullptr;
+            a.p = nullptr; a.dPdp = nullptr;
         }
         const rmx_select::AdjPlan plan = rmx_select::select_adjoint(step_traits(m), b->B, rmx_select::knobs_from_env());
         e = hipEventRecord(b->ev0, b->stream);
@@ -1406,7 +1414,7 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
         // after a BDF2 rollout (q, qdot) of step k-1 are in place: rmx_step_bdf2 may continue it; a BDF1 rollout invalidates them
         if (e == hipSuccess) e = set_started(b, integ == INTEG_BDF2 ? 1 : 0);
         if (e == hipSuccess && !on_device) e = hipMemcpyAsync(P, a.P, sizes[4], hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(dPdp, a.dPdp, sizes[5], hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && !on_device && dPdp) e = hipMemcpyAsync(dPdp, bufs[5], sizes[5], hipMemcpyDeviceToHost, b->stream);
         if (e == hipSuccess && stats) {
             if (stats->newton_iters) e = hipMemcpyAsync(stats->newton_iters, b->it, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess && stats->status) e = hipMemcpyAsync(stats->status, b->status, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
@@ -1438,6 +1446,17 @@ extern "C" int rmx_adjoint_bdf1_device(rmx_batch* b, const rmx_opts* opts, int n
 extern "C" int rmx_adjoint_bdf2_device(rmx_batch* b, const rmx_opts* opts, int nsteps, const rmx_task_pointpos* task, const double* d_p,
                                        double* d_P, double* d_dPdp, rmx_stats* stats) {
     return adjoint_impl(b, opts, nsteps, task, d_p, d_P, d_dPdp, stats, INTEG_BDF2, true);
+}
+
+extern "C" int rmx_adjoint_controls(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_pointpos* task,
+                                    const double* u, double* P, double* dPdu, rmx_stats* stats) {
+    if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_adjoint_controls: integrator must be 1 (BDF1) or 2 (BDF2)");
+    return adjoint_impl(b, opts, nsteps, task, u, P, dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, false, true);
+}
+extern "C" int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_pointpos* task,
+                                           const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats) {
+    if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_adjoint_controls: integrator must be 1 (BDF1) or 2 (BDF2)");
+    return adjoint_impl(b, opts, nsteps, task, d_u, d_P, d_dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, true, true);
 }
 
 // simLoop of one batch enqueued on its stream, nothing waited for (include/redmax_hip.h "Asynchronous stepping")

@@ -62,6 +62,9 @@ struct AdjArgs {
     double* P;                // [B]
     double* dPdp;             // [B][nr]
     int *it, *status;
+    // rmx_adjoint_controls (the CTL instantiations; behind the members the constant-parameter kernels read, whose offsets stay)
+    const double* u;          // [B][nsteps][nr] one torque per step, or null: the constant parameters p
+    double* dPdu;             // [B][nsteps][nr] (with u), or null: with u the forward sweep alone
 };
 
 struct rmx_model {

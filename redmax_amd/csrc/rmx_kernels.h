@@ -802,8 +802,17 @@ __device__ __forceinline__ void adj_md_helper(const DevModel& M, const AdjArgs& 
 
 // FC: a serial chain that fills every node slot (is_chain && n == NP, decided by the launcher): the two model facts as compile-time
 // constants (model_view), as in the FULLCHAIN step kernels - no tree paths in the front, no per-row bounds
-template <int NP, int INTEG, bool HELP = false, bool FC = false>
+// CTL (rmx_adjoint_controls): one torque per joint and STEP, a.u[B][nsteps][nr], loaded at the top of every step - applyStep is called
+// once per step (TaskBDF1PointPos.m:58-64) - in place of the constant parameters a.p[B][nr]; the backward kernel then stores one row
+// of a.dPdu per step.  Compile-time, not a test on a.u, and carried as a bit of the integrator argument (MODE = 1 | 2, + ADJ_CTL): the
+// constant-parameter kernels keep their names and their instruction streams, which profiles/roofline_calibration.json is tied to
+// (bench.py load_calibration).
+constexpr int ADJ_CTL = 4;
+template <int NP, int MODE, bool HELP = false, bool FC = false>
 __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel Min, const DevOpts o, const AdjArgs a) {
+    constexpr int INTEG = MODE & 3;
+    constexpr bool CTL = (MODE & ADJ_CTL) != 0;
+    static_assert(INTEG == 1 || INTEG == 2, "BDF1 or BDF2");
     static_assert(!HELP || NP <= 16, "the helper-wave form: trees of one DPP row");
     const DevModel M = model_view<NP, FC>(Min);
     double *sAcc, *sCol;
@@ -822,7 +831,9 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     double q = id >= 0 ? a.q[off] : 0.0;
     double qd = id >= 0 ? a.qd[off] : 0.0;
     double qp = 0.0, qdp = 0.0;             // BDF2: the state of step k-1 (Joint.q1 / qdot1)
-    const double pj = id >= 0 ? a.p[off] : 0.0;
+    const double pj = (id >= 0 && !CTL) ? a.p[off] : 0.0;
+    const double* uj = CTL ? a.u + (size_t)traj * a.nsteps * M.nr + (id >= 0 ? id : 0) : nullptr;
+    double ureg = 0.0;                      // CTL: this lane's sum of u^2 over the steps
     const double h = o.h;
     FrontState fs;
     fs.tau_add = a.pscale * pj;
@@ -833,6 +844,11 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     const size_t nn = (size_t)n * n;
     const double al = (2.0 - sqrt(2.0)) / 2.0;       // SDIRK2 (driverRedMaxAdjointBDF2.m:80)
     for (int s = 1; s <= a.nsteps; ++s) {
+        if constexpr (CTL) {                 // (under BDF2 step 1's torque holds for both SDIRK2 solves)
+            const double us = id >= 0 ? uj[(size_t)(s - 1) * M.nr] : 0.0;
+            fs.tau_add = a.pscale * us;
+            ureg += us * us;
+        }
         double* Hk = a.Hs + ((size_t)traj * a.nsteps + (s - 1)) * nn;
         double* Mk = a.Ms + ((size_t)traj * a.nsteps + (s - 1)) * nn;
         double* Dk = a.Ds + ((size_t)traj * a.nsteps + (s - 1)) * nn;
@@ -1027,7 +1043,7 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
             a.qdp[off] = qdp;
         }
     }
-    const double preg = wave_sum(pj * pj);
+    const double preg = wave_sum(CTL ? ureg : pj * pj);
     if (lane == 0) {
         a.P[traj] = Ptask + a.wreg * 0.5 * preg;      // TaskBDF1.calcFinal :49 / TaskBDF2.calcFinal :49
         if (a.it) {
@@ -1066,8 +1082,10 @@ __device__ __forceinline__ void adj_block(double& y, const double* __restrict__ 
     }
 }
 
-template <int NP, int INTEG, bool FC = false>
+template <int NP, int MODE, bool FC = false>
 __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const DevOpts o, const AdjArgs a) {
+    constexpr int INTEG = MODE & 3;              // (MODE: as k_adjoint_fwd)
+    constexpr bool CTL = (MODE & ADJ_CTL) != 0;
     const DevModel M = model_view<NP, FC>(Min);
     const int lane = threadIdx.x, traj = blockIdx.x, n = M.n;
     const int id = (lane < n) ? M.idx[lane] : -1;
@@ -1122,13 +1140,20 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
         } else {
             z = lu_solve_neg<NP, true>(n, lane, Hrow, -y);
         }
-        zs += z;
+        if constexpr (CTL) {    // the constant-parameter formula below before its sum over the steps, one row per step
+            if (id >= 0) {
+                const size_t offk = ((size_t)traj * a.nsteps + (k - 1)) * M.nr + id;
+                a.dPdu[offk] = a.wreg * a.u[offk] + (INTEG == 1 ? h * h : (4.0 / 9.0) * h * h) * a.pscale * z;
+            }
+        } else {
+            zs += z;
+        }
         z4 = z3;
         z3 = z2;
         z2 = z1;
         z1 = z;
     }
-    if (id >= 0) {   // dPdp = wreg*p' - z'*dgdp, dgdp(kk,:) = -eta^2*pscale*I with eta^2 = h^2 (TaskBDF1PointPos.m:104-105) or (4/9) h^2 for
+    if (id >= 0 && !CTL) {   // dPdp = wreg*p' - z'*dgdp, dgdp(kk,:) = -eta^2*pscale*I with eta^2 = h^2 (TaskBDF1PointPos.m:104-105) or (4/9) h^2 for
         const size_t off = (size_t)traj * M.nr + id;                 // EVERY step (TaskBDF2PointPos.m:97-106)
         const double e2 = INTEG == 1 ? h * h : (4.0 / 9.0) * h * h;
         a.dPdp[off] = a.wreg * a.p[off] + e2 * a.pscale * zs;
