@@ -360,6 +360,42 @@ int rmx_adjoint_controls(rmx_batch* b, const rmx_opts* opts, int nsteps, int int
 int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_pointpos* task,
                                 const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats);
 
+/* rmx_adjoint_controls with a tracking objective: point targets on several bodies at several steps, and optionally a target
+ * table of its own for every rollout - the running costs and goal-conditioned objectives of trajectory optimisation and policy
+ * training, in ONE forward and ONE backward sweep (TaskBDF1.calcFinal reads a dPdq of every step, TaskBDF1.m:52-57; the
+ * reference's one shipped task leaves all but one of them zero).  These two entries and their two structs were added WITHOUT a
+ * change of RMX_VERSION (it stays 111): a host that wants them probes for the symbol.
+ *     P[b]            = sum_i wpos_i/2 |x_i(step_i) - xtarget[b][i]|^2  +  wreg/2 * sum over k, j of u[b][k-1][j]^2
+ *     dPdu[b][k-1][j] = wreg * u[b][k-1][j] + e2 * pscale * z_k[j] ,   e2 = h^2 (BDF1) or (4/9) h^2 (BDF2)
+ * z comes from the same backward recursion with the source y_k = sum over the terms with step_i == k of dPdq_i (zero at steps
+ * without a term); each dPdq_i is formed as rmx_task_pointpos's is: the body frame from the final state of the step, J from the
+ * last evaluated Newton iterate (TaskBDF1PointPos.m:77-93).  Terms of one step add up, in P and in y_k, in the order they have
+ * in `terms`; several terms may share a step, a body, or both.  Rows behind the last measured step hold wreg * u exactly.
+ * u, P, dPdu (NULL: the forward sweep alone, P is still written), integrator, opts, stats, the refusals and the state the batch
+ * is left in: as rmx_adjoint_controls.  Further refusals (RMX_E_INVALID): a null task, terms or target table, nterms < 1, a term
+ * whose body is outside the listing or whose step is outside [1, nsteps] (the message names the term's index).  Neither u nor
+ * the targets are retained or modified.
+ * rmx_adjoint_track_device: DEVICE pointers d_u, d_P, d_dPdu (may be NULL) and d_xtarget, a device array of the shape
+ * task->per_rollout names; task->xtarget is ignored, task->terms stays a host array. */
+typedef struct rmx_track_term {
+    int body;            /* listing index of the body, as rmx_task_pointpos.body          */
+    double xlocal[3];    /* point in body coordinates                                      */
+    int step;            /* 1-based step at which this term is measured, 1 .. nsteps      */
+    double wpos;         /* weight of this term                                            */
+} rmx_track_term;
+typedef struct rmx_task_track {
+    int nterms;                    /* >= 1; several terms may share a step, a body, or both */
+    const rmx_track_term* terms;   /* host, any order */
+    const double* xtarget;         /* host: [nterms][3] (per_rollout 0) or [batch][nterms][3] (per_rollout 1),
+                                      indexed by the term's position in `terms` */
+    int per_rollout;
+    double pscale, wreg;
+} rmx_task_track;
+int rmx_adjoint_track(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_track* task,
+                      const double* u, double* P, double* dPdu, rmx_stats* stats);
+int rmx_adjoint_track_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_track* task,
+                             const double* d_xtarget, const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats);
+
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.
  * hist_T/hist_V as in rmx_step_bdf1. */

@@ -144,5 +144,21 @@ classdef HipSim < handle
 				[P, dPdu, stats] = redmax_hip_mex('adjoint_controls', this.h, hstep, nsteps, task, u, itype);
 			end
 		end
+
+		function [P, dPdu, stats] = adjointTrack(this, hstep, nsteps, task, u, itype)
+			% adjointControls with a tracking objective: task.terms is a struct array with the fields body (1-based),
+			% xlocal, step and wpos - point targets on several bodies at several steps -, task.xtarget is 3 x nterms (one
+			% target table for the batch) or 3 x nterms x B (one per rollout), task.pscale and task.wreg as before.
+			% P(b) = sum_i wpos_i/2 |x_i(step_i) - xtarget(:,i,b)|^2 + wreg/2 sum u(:,:,b).^2 ; u, dPdu: nr x nsteps x B.
+			% With one output only the forward rollout runs.
+			if nargin < 6
+				itype = 1;
+			end
+			if nargout < 2
+				P = redmax_hip_mex('adjoint_track', this.h, hstep, nsteps, task, u, itype);
+			else
+				[P, dPdu, stats] = redmax_hip_mex('adjoint_track', this.h, hstep, nsteps, task, u, itype);
+			end
+		end
 	end
 end

@@ -53,6 +53,10 @@
  *   [P,dPdu,st]  = redmax_hip_mex('adjoint_controls', h, hstep, nsteps, task, u [, integrator])  rmx_adjoint_controls: one torque
  *                  per joint and step.  u, dPdu: nr x nsteps x B (the ABI's [B][nsteps][nr]); task, integrator, st as 'adjoint'.
  *                  With one output the forward sweep runs alone (P of a controlled rollout, no gradient).
+ *   [P,dPdu,st]  = redmax_hip_mex('adjoint_track', h, hstep, nsteps, task, u [, integrator])  rmx_adjoint_track: the same with point
+ *                  targets on several bodies at several steps.  task: struct terms (struct array: body 1-based, xlocal, step, wpos),
+ *                  xtarget (3 x nterms, or 3 x nterms x B: one target table per rollout), pscale, wreg; u, dPdu, st, the one-output
+ *                  form as 'adjoint_controls'.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -538,6 +542,83 @@ static void cmd_adjoint_controls(int nlhs, mxArray* plhs[], int nrhs, const mxAr
     else mxDestroyArray(st);
 }
 
+/* field k of element i of the struct array task.terms */
+static const mxArray* term_field(const mxArray* terms, size_t i, const char* k) {
+    const mxArray* f = mxGetField(terms, i, k);
+    if (!f || mxIsEmpty(f)) mexErrMsgIdAndTxt("redmax:hip", "task.terms(%d).%s is required", (int)i + 1, k);
+    return f;
+}
+
+static void cmd_adjoint_track(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 6) die("usage: [P,dPdu,stats] = redmax_hip_mex('adjoint_track', h, hstep, nsteps, task, u [, integrator])");
+    const mxArray* t = prhs[4];
+    if (!mxIsStruct(t)) die("task must be a struct");
+    const mxArray* ta = field(t, "terms", 1);
+    if (!mxIsStruct(ta)) die("task.terms must be a struct array with the fields body, xlocal, step, wpos");
+    const size_t nterms = mxGetNumberOfElements(ta);
+    rmx_opts o;
+    rmx_opts_default(&o);
+    o.h = mxGetScalar(prhs[2]);
+    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    const int nsteps = (int)mxGetScalar(prhs[3]);
+    if (nsteps < 1) die("adjoint_track: nsteps must be at least 1");
+    const int integ = nrhs > 6 ? (int)mxGetScalar(prhs[6]) : 1;
+    if (integ != 1 && integ != 2) die("adjoint_track: the integrator must be 1 (BDF1) or 2 (BDF2)");
+    const mxArray* ua = prhs[5];
+    const size_t per = (size_t)h->nr * (size_t)nsteps;      /* one rollout's controls: nr x nsteps x B is the ABI's [B][nsteps][nr] */
+    if (!mxIsDouble(ua) || mxIsComplex(ua) || mxGetNumberOfElements(ua) != per * (size_t)h->B)
+        mexErrMsgIdAndTxt("redmax:hip", "u must be a real double nr x nsteps x batch (%d x %d x %d) array", h->nr, nsteps, h->B);
+    const mxArray* xa = field(t, "xtarget", 1);
+    const size_t nxt = mxGetNumberOfElements(xa);           /* 3 x nterms, or 3 x nterms x B: the ABI's [B][nterms][3] */
+    if (!mxIsDouble(xa) || mxIsComplex(xa) || (nxt != 3 * nterms && nxt != 3 * nterms * (size_t)h->B))
+        mexErrMsgIdAndTxt("redmax:hip", "task.xtarget must be a real double 3 x nterms (3 x %d) or 3 x nterms x batch (3 x %d x %d) array",
+                          (int)nterms, (int)nterms, h->B);
+    rmx_track_term* terms = (rmx_track_term*)mxCalloc(nterms, sizeof *terms);
+    /* (if a field check below raises, MATLAB frees it on the way out; mex/stub, where mxCalloc is calloc, lets it go with P, dPdu, st) */
+    for (size_t i = 0; i < nterms; ++i) {
+        terms[i].body = (int)mxGetScalar(term_field(ta, i, "body")) - 1;   /* MATLAB listing index -> 0-based */
+        const mxArray* xl = term_field(ta, i, "xlocal");
+        if (!mxIsDouble(xl) || mxGetNumberOfElements(xl) != 3) mexErrMsgIdAndTxt("redmax:hip", "task.terms(%d).xlocal must have 3 elements", (int)i + 1);
+        memcpy(terms[i].xlocal, mxGetPr(xl), 3 * sizeof(double));
+        terms[i].step = (int)mxGetScalar(term_field(ta, i, "step"));
+        terms[i].wpos = mxGetScalar(term_field(ta, i, "wpos"));
+    }
+    rmx_task_track task;
+    memset(&task, 0, sizeof task);
+    task.nterms = (int)nterms;
+    task.terms = terms;
+    task.per_rollout = nxt != 3 * nterms;             /* (a batch of one: the two shapes are the same table) */
+    task.pscale = scalar_field(t, "pscale", 1.0);
+    task.wreg = scalar_field(t, "wreg", 0.0);
+    mxArray* P = mxCreateDoubleMatrix(1, (size_t)h->B, mxREAL);
+    mxArray* dPdu = NULL;                              /* one output: the forward sweep alone */
+    if (nlhs > 1) {
+        const size_t dims[3] = {(size_t)h->nr, (size_t)nsteps, (size_t)h->B};
+        dPdu = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    }
+    mxArray* st = new_i32((size_t)h->B, 2);
+    int* sp = (int*)mxGetData(st);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'adjoint_controls': u, the per-rollout targets and the outputs advance */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_stats st_s;
+        st_s.newton_iters = sp + f;
+        st_s.ls_halvings = NULL;
+        st_s.status = sp + h->B + f;
+        task.xtarget = mxGetPr(xa) + (task.per_rollout ? f * 3 * nterms : 0);
+        if (rmx_adjoint_track(b, &o, nsteps, integ, &task, mxGetPr(ua) + f * per, mxGetPr(P) + f, dPdu ? mxGetPr(dPdu) + f * per : NULL, &st_s)) {
+            mxFree(terms);
+            die_rmx("rmx_adjoint_track");
+        }
+    }
+    mxFree(terms);
+    plhs[0] = P;
+    if (nlhs > 1) plhs[1] = dPdu;
+    if (nlhs > 2) plhs[2] = st;
+    else mxDestroyArray(st);
+}
+
 /* `clear mex` / MATLAB exit: free what is still alive on the device */
 static void at_exit(void) {
     for (int i = 0; i < MAX_LIVE; ++i)
@@ -560,7 +641,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * may name the handle ('step' / 'step_async' refuse with their own text).  Everything below reads or writes the state, the
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
-                                             "adjoint", "adjoint_controls", NULL};
+                                             "adjoint", "adjoint_controls", "adjoint_track", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -663,6 +744,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_adjoint(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "adjoint_controls")) {
         cmd_adjoint_controls(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "adjoint_track")) {
+        cmd_adjoint_track(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

@@ -1,7 +1,7 @@
 /*
  * mex_stub.c -- host-memory implementation of the mx and mex functions declared in mex/stub/mex.h, plus the harness entry
  * rmxstub_call() through which tests/test_mex_gateway.py runs mexFunction outside MATLAB.  Test infrastructure only.
- * Column-major storage, like MATLAB.  A struct array is 1x1 here (all the gateway needs).
+ * Column-major storage, like MATLAB.  A struct array is 1 x N here (all the gateway needs: task.terms of 'adjoint_track').
  */
 #define _POSIX_C_SOURCE 200809L
 #include <setjmp.h>
@@ -23,7 +23,7 @@ struct mxArray_tag {
     void* data;               /* numeric / char data */
     int nfields;              /* struct */
     char* names[MAXFIELDS];
-    mxArray* values[MAXFIELDS];
+    mxArray** values;         /* [elements][nfields] */
 };
 
 static size_t class_size(mxClassID c) {
@@ -70,20 +70,25 @@ mxArray* mxCreateString(const char* s) {
     return a;
 }
 mxArray* mxCreateStructMatrix(mwSize m, mwSize n, int nfields, const char** names) {
-    if (m != 1 || n != 1 || nfields > MAXFIELDS) return NULL;
+    if (m != 1 || n < 1 || nfields > MAXFIELDS) return NULL;
     mxArray* a = (mxArray*)calloc(1, sizeof *a);
     a->cls = mxSTRUCT_CLASS;
     a->ndim = 2;
-    a->dims[0] = a->dims[1] = 1;
+    a->dims[0] = 1;
+    a->dims[1] = n;
     a->nfields = nfields;
+    a->values = (mxArray**)calloc(n * (size_t)(nfields ? nfields : 1), sizeof *a->values);
     for (int i = 0; i < nfields; ++i) a->names[i] = strdup(names[i]);
     return a;
 }
 void mxDestroyArray(mxArray* a) {
     if (!a) return;
-    for (int i = 0; i < a->nfields; ++i) {
-        free(a->names[i]);
-        mxDestroyArray(a->values[i]);
+    if (a->cls == mxSTRUCT_CLASS) {
+        const size_t n = mxGetNumberOfElements(a);
+        for (size_t e = 0; e < n; ++e)
+            for (int i = 0; i < a->nfields; ++i) mxDestroyArray(a->values[e * (size_t)a->nfields + (size_t)i]);
+        for (int i = 0; i < a->nfields; ++i) free(a->names[i]);
+        free(a->values);
     }
     free(a->data);
     free(a);
@@ -114,16 +119,16 @@ int mxGetString(const mxArray* a, char* buf, mwSize buflen) {
     return 0;
 }
 mxArray* mxGetField(const mxArray* a, mwIndex index, const char* name) {
-    if (a->cls != mxSTRUCT_CLASS || index != 0) return NULL;
+    if (a->cls != mxSTRUCT_CLASS || index >= mxGetNumberOfElements(a)) return NULL;
     for (int i = 0; i < a->nfields; ++i)
-        if (!strcmp(a->names[i], name)) return a->values[i];
+        if (!strcmp(a->names[i], name)) return a->values[index * (size_t)a->nfields + (size_t)i];
     return NULL;
 }
 void mxSetField(mxArray* a, mwIndex index, const char* name, mxArray* v) {
-    if (a->cls != mxSTRUCT_CLASS || index != 0) return;
+    if (a->cls != mxSTRUCT_CLASS || index >= mxGetNumberOfElements(a)) return;
     for (int i = 0; i < a->nfields; ++i)
         if (!strcmp(a->names[i], name)) {
-            a->values[i] = v;
+            a->values[index * (size_t)a->nfields + (size_t)i] = v;
             return;
         }
 }

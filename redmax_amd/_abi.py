@@ -23,7 +23,7 @@ SYMBOLS = (
     "rmx_model_set_ground_contact", "rmx_model_set_point_forces", "rmx_model_nsph", "rmx_get_charts", "rmx_set_charts",
     "rmx_batch_create", "rmx_batch_destroy", "rmx_batch_size",
     "rmx_set_state", "rmx_get_state", "rmx_set_state_device", "rmx_get_state_device",
-    "rmx_eval", "rmx_eval_mfd", "rmx_compute_values", "rmx_step_bdf1", "rmx_step_bdf2", "rmx_step_history", "rmx_step_euler", "rmx_adjoint_bdf1", "rmx_adjoint_bdf2", "rmx_adjoint_bdf1_device", "rmx_adjoint_bdf2_device", "rmx_adjoint_controls", "rmx_adjoint_controls_device", "rmx_energy",
+    "rmx_eval", "rmx_eval_mfd", "rmx_compute_values", "rmx_step_bdf1", "rmx_step_bdf2", "rmx_step_history", "rmx_step_euler", "rmx_adjoint_bdf1", "rmx_adjoint_bdf2", "rmx_adjoint_bdf1_device", "rmx_adjoint_bdf2_device", "rmx_adjoint_controls", "rmx_adjoint_controls_device", "rmx_adjoint_track", "rmx_adjoint_track_device", "rmx_energy",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -58,6 +58,15 @@ class Opts(C.Structure):
 class TaskPointPos(C.Structure):
     _fields_ = [("body", C.c_int), ("xlocal", C.c_double * 3), ("xtarget", C.c_double * 3), ("step", C.c_int),
                 ("pscale", C.c_double), ("wreg", C.c_double), ("wpos", C.c_double)]
+
+
+class TrackTerm(C.Structure):
+    _fields_ = [("body", C.c_int), ("xlocal", C.c_double * 3), ("step", C.c_int), ("wpos", C.c_double)]
+
+
+class TaskTrack(C.Structure):
+    _fields_ = [("nterms", C.c_int), ("terms", C.POINTER(TrackTerm)), ("xtarget", _dp), ("per_rollout", C.c_int),
+                ("pscale", C.c_double), ("wreg", C.c_double)]
 
 
 class GroundContact(C.Structure):
@@ -127,6 +136,8 @@ def lib():
     L.rmx_adjoint_bdf2_device.argtypes = L.rmx_adjoint_bdf1_device.argtypes
     L.rmx_adjoint_controls.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.POINTER(TaskPointPos), _dp, _dp, _dp, C.POINTER(Stats)]
     L.rmx_adjoint_controls_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.POINTER(TaskPointPos), vp, vp, vp, C.POINTER(Stats)]
+    L.rmx_adjoint_track.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.POINTER(TaskTrack), _dp, _dp, _dp, C.POINTER(Stats)]
+    L.rmx_adjoint_track_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.POINTER(TaskTrack), vp, vp, vp, vp, C.POINTER(Stats)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.rmx_energy.argtypes = [vp, _dp, _dp]
     L.rmx_last_step_ms.argtypes = [vp]

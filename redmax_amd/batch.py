@@ -300,6 +300,91 @@ class BatchSim:
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
+    def _track_task(self, task, h, nsteps, device_targets=False):
+        """task dict of adjoint_track -> (TaskTrack, Opts, keepalive).  Shapes are checked here, before any call into the library."""
+        terms = list(task["terms"])
+        nterms = len(terms)
+        arr = (_abi.TrackTerm * max(nterms, 1))()
+        for a, t in zip(arr, terms):
+            xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
+            if xl.shape != (3,):
+                raise ValueError("adjoint_track: a term's xlocal must have shape (3,), got %r" % (xl.shape,))
+            a.body = int(t["body"])
+            a.step = int(t["step"]) if "step" in t else int(round(float(t["t"]) / float(h)))
+            a.wpos = float(t["wpos"])
+            for i in range(3):
+                a.xlocal[i] = float(xl[i])
+        tk = _abi.TaskTrack()
+        tk.nterms, tk.terms = nterms, arr
+        tk.pscale, tk.wreg = float(task["pscale"]), float(task["wreg"])
+        xt = None
+        if device_targets:
+            tk.per_rollout = 1 if task.get("per_rollout") else 0
+        else:
+            if task.get("xtarget") is None:
+                raise ValueError("adjoint_track: xtarget is None")
+            xt = np.ascontiguousarray(task["xtarget"], dtype=np.float64)
+            if xt.shape not in ((nterms, 3), (self.B, nterms, 3)):
+                raise ValueError("adjoint_track: xtarget must have shape (%d, 3) or (%d, %d, 3), got %r" % (nterms, self.B, nterms, xt.shape))
+            tk.per_rollout = 1 if xt.ndim == 3 else 0
+            tk.xtarget = _abi.dptr(xt)
+        opts = _abi.Opts()
+        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
+        opts.h = float(h)
+        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        return tk, opts, (arr, xt)
+
+    def adjoint_track(self, nsteps, h, task, u, integrator=1, stats=False, gradient=True):
+        """rmx_adjoint_track: adjoint_controls with a tracking objective - point targets on several bodies at several steps.
+        task: dict(terms=[dict(body, xlocal, step | t, wpos), ...], xtarget, pscale, wreg); xtarget: (nterms, 3), one target table
+        for the batch, or (B, nterms, 3), one per rollout, indexed by the term's position in `terms`.
+        P[b] = sum_i wpos_i/2 |x_i(step_i) - xtarget[b][i]|^2 + wreg/2 sum u[b]^2.  u, integrator, stats, gradient and the result
+        (P[B], dPdu[B][nsteps][nr] or None, info) as adjoint_controls."""
+        nsteps = int(nsteps)
+        if u is None:
+            raise ValueError("adjoint_track: u is None")
+        u = np.asarray(u, dtype=np.float64)
+        if u.shape == (nsteps, self.nr):
+            u = np.broadcast_to(u, (self.B, nsteps, self.nr))
+        if u.shape != (self.B, nsteps, self.nr):
+            raise ValueError("adjoint_track: u must have shape (%d, %d, %d) or (%d, %d), got %r"
+                             % (self.B, nsteps, self.nr, nsteps, self.nr, u.shape))
+        u = np.ascontiguousarray(u)
+        tk, opts, keep = self._track_task(task, h, nsteps)
+        P = np.empty(self.B)
+        dPdu = np.empty((self.B, nsteps, self.nr)) if gradient else None
+        info = {}
+        st = None
+        if stats:
+            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
+            info["status"] = np.zeros(self.B, dtype=np.int32)
+            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        _abi.check(self._L.rmx_adjoint_track(self._batch, C.byref(opts), nsteps, int(integrator), C.byref(tk), _abi.dptr(u),
+                                             _abi.dptr(P), _abi.dptr(dPdu), C.byref(st) if st is not None else None),
+                   "rmx_adjoint_track")
+        del keep
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return P, dPdu, info
+
+    def adjoint_track_device(self, nsteps, h, task, xtarget_ptr, u_ptr, P_ptr, dPdu_ptr, integrator=1, stats=False):
+        """adjoint_track with DEVICE pointers (integers) for the targets ([nterms][3], or [B][nterms][3] with task["per_rollout"] true;
+        task["xtarget"] is not read), u [B][nsteps][nr], P [B] and dPdu [B][nsteps][nr]; dPdu_ptr 0 / None: the forward rollout alone.
+        Returns info."""
+        tk, opts, keep = self._track_task(task, h, int(nsteps), device_targets=True)
+        info = {}
+        st = None
+        if stats:
+            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
+            info["status"] = np.zeros(self.B, dtype=np.int32)
+            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        _abi.check(self._L.rmx_adjoint_track_device(self._batch, C.byref(opts), int(nsteps), int(integrator), C.byref(tk),
+                                                    C.c_void_p(xtarget_ptr or None), C.c_void_p(u_ptr or None), C.c_void_p(P_ptr or None),
+                                                    C.c_void_p(dPdu_ptr or None), C.byref(st) if st is not None else None),
+                   "rmx_adjoint_track_device")
+        del keep
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return info
+
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent
         variant the library chose."""

@@ -7,21 +7,24 @@
 #endif
 #include "rmx_kernels.h"
 
-// (MODE: the integrator, + ADJ_CTL per-step controls, where a null a.dPdu asks for the forward sweep alone)
+// (MODE: the integrator, + ADJ_CTL per-step controls, where a null a.dPdu asks for the forward sweep alone, + ADJ_TRK the tracking
+// objective, whose kept iterate lies behind the hand-over buffers)
 template <int MODE, bool FC>
 static void adjoint_help_pair(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
     const dim3 grid(b->B);
-    const size_t smem_bytes = m->smem_bytes + sizeof(double) * adj_hand_doubles(RMX_NP);
+    const size_t smem_bytes = m->smem_bytes + sizeof(double) * (adj_hand_doubles(RMX_NP) + ((MODE & ADJ_TRK) ? adj_trk_doubles(RMX_NP) : 0));
     RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, true, FC>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
     if (!(MODE & ADJ_CTL) || a.dPdu) k_adjoint_bwd<RMX_NP, MODE, FC><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
 }
 template <bool FC>
 static void adjoint_help_pairs(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
     if (integ == INTEG_BDF1) {
-        if (a.u) adjoint_help_pair<1 | ADJ_CTL, FC>(m, b, o, a);
+        if (a.trk) adjoint_help_pair<1 | ADJ_CTL | ADJ_TRK, FC>(m, b, o, a);
+        else if (a.u) adjoint_help_pair<1 | ADJ_CTL, FC>(m, b, o, a);
         else adjoint_help_pair<1, FC>(m, b, o, a);
     } else {
-        if (a.u) adjoint_help_pair<2 | ADJ_CTL, FC>(m, b, o, a);
+        if (a.trk) adjoint_help_pair<2 | ADJ_CTL | ADJ_TRK, FC>(m, b, o, a);
+        else if (a.u) adjoint_help_pair<2 | ADJ_CTL, FC>(m, b, o, a);
         else adjoint_help_pair<2, FC>(m, b, o, a);
     }
 }

@@ -24,20 +24,24 @@ void RMX_CAT(launch_energy_, RMX_NP)(const rmx_model* m, const rmx_batch* b, dou
     RMX_LAUNCH((k_energy<RMX_NP, false>), grid, block, m->smem_bytes, b->stream, m->dm, b->B, b->q, b->qd, dT, dV, nullptr);
 }
 
-// the adjoint pair of one instantiation (MODE: the integrator, + ADJ_CTL per-step controls, where a null a.dPdu asks for the forward sweep alone)
+// the adjoint pair of one instantiation (MODE: the integrator, + ADJ_CTL per-step controls, where a null a.dPdu asks for the forward sweep alone,
+// + ADJ_TRK the tracking objective, whose forward kernel keeps an iterate in an LDS area of its own behind the constants)
 template <int MODE, bool FC>
 static void adjoint_pair(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
     const dim3 grid(b->B), block(64);
-    RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, false, FC>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+    const size_t smem_bytes = m->smem_bytes + ((MODE & ADJ_TRK) ? sizeof(double) * adj_trk_doubles(RMX_NP) : 0);
+    RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, false, FC>), grid, block, smem_bytes, b->stream, m->dm, o, a);
     if (!(MODE & ADJ_CTL) || a.dPdu) k_adjoint_bwd<RMX_NP, MODE, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
 }
 template <bool FC>
 static void adjoint_pairs(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
     if (integ == INTEG_BDF1) {
-        if (a.u) adjoint_pair<1 | ADJ_CTL, FC>(m, b, o, a);
+        if (a.trk) adjoint_pair<1 | ADJ_CTL | ADJ_TRK, FC>(m, b, o, a);
+        else if (a.u) adjoint_pair<1 | ADJ_CTL, FC>(m, b, o, a);
         else adjoint_pair<1, FC>(m, b, o, a);
     } else {
-        if (a.u) adjoint_pair<2 | ADJ_CTL, FC>(m, b, o, a);
+        if (a.trk) adjoint_pair<2 | ADJ_CTL | ADJ_TRK, FC>(m, b, o, a);
+        else if (a.u) adjoint_pair<2 | ADJ_CTL, FC>(m, b, o, a);
         else adjoint_pair<2, FC>(m, b, o, a);
     }
 }

@@ -1329,17 +1329,27 @@ extern "C" int rmx_step_euler(rmx_batch* b, double h, int nsteps, double* hT, do
 
 
 // controls (rmx_adjoint_controls): p is u[B][nsteps][nr], dPdp is dPdu of the same shape or null (the forward sweep alone)
+// track (rmx_adjoint_track, with controls; task is null then): the terms of the objective; xtarget is its target table, a device array
+// when on_device.  The term table (rmx_track.h), the step offsets and, in the host form, the targets go into the workspace behind
+// the parts it has, and dPdq holds one row per step.
 static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rmx_task_pointpos* task, const double* p, double* P,
-                        double* dPdp, rmx_stats* stats, const int integ, const bool on_device = false, const bool controls = false) {
-    if (!b || !task || !p || !P || (!dPdp && !controls)) return fail(RMX_E_INVALID, "null argument");
+                        double* dPdp, rmx_stats* stats, const int integ, const bool on_device = false, const bool controls = false,
+                        const rmx_task_track* track = nullptr, const double* xtarget = nullptr) {
+    if (!b || (!task && !track) || !p || !P || (!dPdp && !controls)) return fail(RMX_E_INVALID, "null argument");
     rmx_model* m = b->m;
     if (nsteps < 1) return fail(RMX_E_INVALID, "nsteps < 1");
     if (m->dm.con) return fail(RMX_E_INVALID, "rmx_adjoint: ground contact is outside the adjoint path (SURVEY.md 8(f))");
     if (m->dm.nsph) return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
     if (m->big) return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
     if (m->dpf) return fail(RMX_E_INVALID, "rmx_adjoint: point forces (rmx_model_set_point_forces) are outside the adjoint path");
-    if (task->body < 0 || task->body >= m->nlist) return fail(RMX_E_INVALID, "task body out of range");
-    if (task->step < 1 || task->step > nsteps) return fail(RMX_E_INVALID, "task step must be in [1, nsteps]");
+    rmx_track::Plan tplan;
+    if (track) {
+        tplan = rmx_track::plan_terms(track->terms, track->nterms, nsteps, m->nlist, m->node_of_listing.data());
+        if (!tplan.error.empty()) return fail(RMX_E_INVALID, "rmx_adjoint_track: " + tplan.error);
+    } else {
+        if (task->body < 0 || task->body >= m->nlist) return fail(RMX_E_INVALID, "task body out of range");
+        if (task->step < 1 || task->step > nsteps) return fail(RMX_E_INVALID, "task step must be in [1, nsteps]");
+    }
     HIPCHK(hipSetDevice(m->device));
     DevOpts o;
     int rc = make_opts(b, opts, o);
@@ -1350,19 +1360,29 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
     const size_t hist = (size_t)b->B * nsteps * nn * sizeof(double);
     if (3 * hist > ((size_t)200 << 30)) return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
     AdjArgs a{};
-    a.B = b->B; a.nsteps = nsteps; a.task_step = task->step; a.task_node = m->node_of_listing[task->body];
-    for (int c = 0; c < 3; ++c) { a.xl[c] = task->xlocal[c]; a.xt[c] = task->xtarget[c]; }
-    a.pscale = task->pscale; a.wreg = task->wreg; a.wpos = task->wpos;
+    a.B = b->B; a.nsteps = nsteps;
+    if (track) {
+        a.pscale = track->pscale; a.wreg = track->wreg;
+    } else {
+        a.task_step = task->step; a.task_node = m->node_of_listing[task->body];
+        for (int c = 0; c < 3; ++c) { a.xl[c] = task->xlocal[c]; a.xt[c] = task->xtarget[c]; }
+        a.pscale = task->pscale; a.wreg = task->wreg; a.wpos = task->wpos;
+    }
     a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp; a.p = b->tmpA;
     a.it = stats ? b->it : nullptr; a.status = b->status;
     // (the constant parameters are staged in tmpA; the per-step controls, nsteps times as many, in the workspace behind the gradient)
-    void* bufs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t sizes[7] = {hist, hist, hist, (size_t)b->B * m->n * sizeof(double), (size_t)b->B * sizeof(double),
-                             (on_device && controls) ? 0 : nv * sizeof(double), (controls && !on_device) ? nv * sizeof(double) : 0};
+    constexpr int NBUF = 10;
+    void* bufs[NBUF] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t nterms = track ? (size_t)track->nterms : 0;
+    const size_t nxt = nterms * 3 * ((track && track->per_rollout) ? (size_t)b->B : 1);      // doubles of the target table
+    const size_t sizes[NBUF] = {hist, hist, hist, (size_t)b->B * m->n * (track ? (size_t)nsteps : 1) * sizeof(double), (size_t)b->B * sizeof(double),
+                                (on_device && controls) ? 0 : nv * sizeof(double), (controls && !on_device) ? nv * sizeof(double) : 0,
+                                nterms * sizeof(rmx_track::DevTerm), track ? ((size_t)nsteps + 1) * sizeof(int) : 0,
+                                (track && !on_device) ? nxt * sizeof(double) : 0};
     hipError_t e = hipSuccess;
     {   // one workspace per batch, kept between calls (grow-only): parts at 256-byte boundaries
-        size_t total = 0, offs[7];
-        for (int i = 0; i < 7; ++i) {
+        size_t total = 0, offs[NBUF];
+        for (int i = 0; i < NBUF; ++i) {
             offs[i] = total;
             total += (sizes[i] + 255) & ~(size_t)255;
         }
@@ -1386,11 +1406,18 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
             }
         }
         if (e == hipSuccess)
-            for (int i = 0; i < 7; ++i) bufs[i] = (char*)b->adjws + offs[i];
+            for (int i = 0; i < NBUF; ++i) bufs[i] = (char*)b->adjws + offs[i];
     }
     // (dPdq needs no fill: the task step lies in [1, nsteps] - checked above -, so the forward kernel writes every entry the backward
-    // kernel reads; one dispatch less ahead of a 0.83 ms launch pair)
+    // kernel reads; one dispatch less ahead of a 0.83 ms launch pair.  The tracking call: row k of dPdq is written and read where step k owns
+    // terms, and nowhere else)
     if (e == hipSuccess && !on_device) e = hipMemcpyAsync(controls ? bufs[6] : (void*)b->tmpA, p, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && track) {
+        e = hipMemcpyAsync(bufs[7], tplan.terms.data(), sizes[7], hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(bufs[8], tplan.begin.data(), sizes[8], hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(bufs[9], xtarget, sizes[9], hipMemcpyHostToDevice, b->stream);
+        if (e != hipSuccess) (void)hipStreamSynchronize(b->stream);      // (the plan's arrays must outlive the copies)
+    }
     if (e == hipSuccess) {
         a.Hs = (double*)bufs[0]; a.Ms = (double*)bufs[1]; a.Ds = (double*)bufs[2];
         a.dPdq = (double*)bufs[3]; a.P = (double*)bufs[4]; a.dPdp = (double*)bufs[5];
@@ -1401,6 +1428,12 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
             a.u = on_device ? p : (const double*)bufs[6];
             a.dPdu = dPdp ? a.dPdp : nullptr;
             a.p = nullptr; a.dPdp = nullptr;
+        }
+        if (track) {
+            a.trk = (const rmx_track::DevTerm*)bufs[7];
+            a.trk_begin = (const int*)bufs[8];
+            a.trk_xt = on_device ? xtarget : (const double*)bufs[9];
+            a.trk_xt_stride = track->per_rollout ? nterms * 3 : 0;
         }
         const rmx_select::AdjPlan plan = rmx_select::select_adjoint(step_traits(m), b->B, rmx_select::knobs_from_env());
         e = hipEventRecord(b->ev0, b->stream);
@@ -1420,6 +1453,7 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
             if (e == hipSuccess && stats->status) e = hipMemcpyAsync(stats->status, b->status, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
         }
         if (e == hipSuccess) e = wait_stream_short(b->stream);      // (configs[3]: a launch pair of 0.9 ms)
+        else if (track) (void)hipStreamSynchronize(b->stream);
         if (e == hipSuccess) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->last_ms = ms;
@@ -1457,6 +1491,25 @@ extern "C" int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, i
                                            const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats) {
     if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_adjoint_controls: integrator must be 1 (BDF1) or 2 (BDF2)");
     return adjoint_impl(b, opts, nsteps, task, d_u, d_P, d_dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, true, true);
+}
+
+static int track_refusal(const rmx_task_track* task, const double* xtarget, int integrator) {
+    if (!task) return fail(RMX_E_INVALID, "rmx_adjoint_track: null task");
+    if (!task->terms) return fail(RMX_E_INVALID, "rmx_adjoint_track: null terms");
+    if (!xtarget) return fail(RMX_E_INVALID, "rmx_adjoint_track: null xtarget");
+    if (task->nterms < 1) return fail(RMX_E_INVALID, "rmx_adjoint_track: nterms < 1");
+    if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_adjoint_track: integrator must be 1 (BDF1) or 2 (BDF2)");
+    return RMX_OK;
+}
+extern "C" int rmx_adjoint_track(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_track* task,
+                                 const double* u, double* P, double* dPdu, rmx_stats* stats) {
+    if (int rc = track_refusal(task, task ? task->xtarget : nullptr, integrator)) return rc;
+    return adjoint_impl(b, opts, nsteps, nullptr, u, P, dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, false, true, task, task->xtarget);
+}
+extern "C" int rmx_adjoint_track_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_track* task,
+                                        const double* d_xtarget, const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats) {
+    if (int rc = track_refusal(task, d_xtarget, integrator)) return rc;
+    return adjoint_impl(b, opts, nsteps, nullptr, d_u, d_P, d_dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, true, true, task, d_xtarget);
 }
 
 // simLoop of one batch enqueued on its stream, nothing waited for (include/redmax_hip.h "Asynchronous stepping")

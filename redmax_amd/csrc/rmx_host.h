@@ -15,6 +15,7 @@
 #include "rmx_device.h"
 #include "rmx_pf.h"
 #include "rmx_select.h"
+#include "rmx_track.h"
 
 using namespace rmx;
 
@@ -65,6 +66,11 @@ struct AdjArgs {
     // rmx_adjoint_controls (the CTL instantiations; behind the members the constant-parameter kernels read, whose offsets stay)
     const double* u;          // [B][nsteps][nr] one torque per step, or null: the constant parameters p
     double* dPdu;             // [B][nsteps][nr] (with u), or null: with u the forward sweep alone
+    // rmx_adjoint_track (the TRK instantiations; dPdq is [B][nsteps][n] there, row k written and read only where step k owns terms)
+    const rmx_track::DevTerm* trk;   // [nterms] the terms sorted by step (rmx_track.h)
+    const int* trk_begin;     // [nsteps + 1] step k owns terms trk_begin[k-1] .. trk_begin[k]-1
+    const double* trk_xt;     // targets, [nterms][3] or [B][nterms][3], indexed by the term's position in the caller's array
+    size_t trk_xt_stride;     // doubles from one rollout's target table to the next (0: one table for the batch)
 };
 
 struct rmx_model {

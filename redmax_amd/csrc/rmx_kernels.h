@@ -808,16 +808,29 @@ __device__ __forceinline__ void adj_md_helper(const DevModel& M, const AdjArgs& 
 // constant-parameter kernels keep their names and their instruction streams, which profiles/roofline_calibration.json is tied to
 // (bench.py load_calibration).
 constexpr int ADJ_CTL = 4;
+// TRK (rmx_adjoint_track, with CTL): the objective is a table of terms - a point of a body, a step, a weight, a target (a.trk, sorted
+// by step; a.trk_begin; a.trk_xt, shared or one table per rollout) - in place of the one term of a.task_step / a.task_node.  A step
+// that owns terms keeps what J of the last evaluated iterate is made of - every lane's sw, sv, the frames Rw, pw - in an LDS area of
+// its own behind the constants (and the helper wave's hand-over), runs the final-state front ONCE and loops over its terms; row
+// s-1 of a.dPdq ([B][nsteps][n] here) is their sum, which the backward kernel reads where the step owns terms.  J is formed once per
+// measured step from the kept iterate, not at every Newton iterate.  Compile-time like CTL: the other instantiations keep their code.
+constexpr int ADJ_TRK = 8;
+constexpr int ADJ_TRK_ROWS = 18;      // sw[3], sv[3], Rw[9], pw[3], one column per node
+__host__ __device__ constexpr size_t adj_trk_doubles(const int NP) { return (size_t)ADJ_TRK_ROWS * NP; }
 template <int NP, int MODE, bool HELP = false, bool FC = false>
 __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel Min, const DevOpts o, const AdjArgs a) {
     constexpr int INTEG = MODE & 3;
     constexpr bool CTL = (MODE & ADJ_CTL) != 0;
+    constexpr bool TRK = (MODE & ADJ_TRK) != 0;
     static_assert(INTEG == 1 || INTEG == 2, "BDF1 or BDF2");
+    static_assert(!TRK || CTL, "the tracking objective comes with per-step controls");
     static_assert(!HELP || NP <= 16, "the helper-wave form: trees of one DPP row");
     const DevModel M = model_view<NP, FC>(Min);
     double *sAcc, *sCol;
     smem_setup<NP>(M, sAcc, sCol);
     double* hand = nullptr;
+    // TRK: the kept iterate, behind the wave's scratch, the constants and (HELP) the hand-over buffers
+    double* const kept = TRK ? sAcc + acc_doubles(M.n, NP) + (size_t)(NCONST + NGROUND) * cstride(NP) + (HELP ? adj_hand_doubles(NP) : 0) : nullptr;
     if constexpr (HELP) {
         hand = sAcc + acc_doubles(M.n, NP) + (size_t)(NCONST + NGROUND) * cstride(NP);      // behind the wave's scratch and the constants
         if (threadIdx.x >= 64) {
@@ -838,7 +851,7 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     FrontState fs;
     fs.tau_add = a.pscale * pj;
     // does the task body hang below (or at) this lane's joint?  (rows of J(idxM_body, :) that are non-zero)
-    const bool on_path = lane < n && (lane == a.task_node || ((M.rel[MAXN + lane] >> a.task_node) & 1ull));
+    const bool on_path = !TRK && lane < n && (lane == a.task_node || ((M.rel[MAXN + lane] >> a.task_node) & 1ull));
     int iters = 0, status = 0;
     double Ptask = 0.0;
     const size_t nn = (size_t)n * n;
@@ -853,6 +866,12 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
         double* Mk = a.Ms + ((size_t)traj * a.nsteps + (s - 1)) * nn;
         double* Dk = a.Ds + ((size_t)traj * a.nsteps + (s - 1)) * nn;
         double Jw[3] = {0.0, 0.0, 0.0}, Jv[3] = {0.0, 0.0, 0.0};   // J(idxM_body, this joint) of the last evaluated iterate
+        int tb = 0, te = 0;                          // TRK: the terms this step owns
+        if constexpr (TRK) {
+            tb = a.trk_begin[s - 1];
+            te = a.trk_begin[s];
+        }
+        const bool measured = te > tb;
         const double q0 = (INTEG == 2 && s > 1) ? qp : q, qd0 = (INTEG == 2 && s > 1) ? qdp : qd;      // BDF2: step k-1
         const double q1 = q, qd1 = qd;                                                                  // BDF2: step k
         double qa = 0.0, qda = 0.0;                  // SDIRK2a's result
@@ -901,7 +920,19 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
                             if (i < n) Hk[(size_t)i * n + lane] = Hrow[i];
                     }
                 }
-                if (s == a.task_step && last_solve) {   // J(body rows, joint) = Ad(E_body^-1) s_joint : body-frame twist of the task body per unit qdot
+                if constexpr (TRK) {
+                    // the frames of the last evaluated iterate go to the kept area at every iterate of a measured step (the last store
+                    // wins), so that they are not live across the solve; sw, sv follow after the loop, where eval_MD has them anyway.
+                    // One store of all 18 rows after the loop instead: scratch per lane 180 -> 276 bytes in <16, 14>, 188 -> 288 in
+                    // <32, 14>, 2104 -> 2200 / 3832 -> 3960 in the 64-lane pair - more than the CTL siblings take (228, 244, 2156, 3880)
+                    if (measured && last_solve && lane < NP) {
+#pragma unroll
+                        for (int c = 0; c < 9; ++c) kept[(6 + c) * NP + lane] = fs.Rw[c];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) kept[(15 + c) * NP + lane] = fs.pw[c];
+                    }
+                }
+                if (!TRK && s == a.task_step && last_solve) {   // J(body rows, joint) = Ad(E_body^-1) s_joint : body-frame twist of the task body per unit qdot
                     double Rb[9], pb[3], t3[3], d3[3];
 #pragma unroll
                     for (int c = 0; c < 9; ++c) Rb[c] = readlane_d(fs.Rw[c], a.task_node);
@@ -1014,7 +1045,69 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
             qp = q1;
             qdp = qd1;
         }
-        if (s == a.task_step) {    // TaskBDF1PointPos.calcStep :67-107 (TaskBDF2PointPos.calcStep is the same) at the final state of this step
+        if constexpr (TRK) {
+            if (measured) {      // this step owns terms: calcStep of each of them, their sum in row s-1 of dPdq
+                // fs is still the state of the last evaluated iterate: keep what J needs of it before the final-state front overwrites it
+                // (the frames are in the area already)
+                if (lane < NP) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        kept[c * NP + lane] = fs.sw[c];
+                        kept[(3 + c) * NP + lane] = fs.sv[c];
+                    }
+                }
+                RMX_SYNC();
+                NodeOut e;
+                eval_front<NP, false>(M, sAcc, lane, q, qd, 0.0, 1.0, e, fs);
+                const int l = lane < NP ? lane : 0;      // (lanes past the tree: node 0's numbers, never on a path)
+                double swk[3], svk[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    swk[c] = kept[c * NP + l];
+                    svk[c] = kept[(3 + c) * NP + l];
+                }
+                double ysum = 0.0;
+                for (int t = tb; t < te; ++t) {
+                    const rmx_track::DevTerm& T = a.trk[t];
+                    const int node = __builtin_amdgcn_readfirstlane(T.node);      // (wave-uniform: the frame reads stay v_readlane)
+                    const double* xt = a.trk_xt + (size_t)traj * a.trk_xt_stride + (size_t)3 * (size_t)T.orig;
+                    const double xl[3] = {T.xl[0], T.xl[1], T.xl[2]}, wp = T.wpos;
+                    // M.rel's descendant mask of this lane as smem_setup staged it: the final-state eval_front above has just reloaded
+                    // fs.desc_m from there (the staged rows mirror M.rel[MAXN + lane]), so this relies on that call coming first
+                    const bool on = lane < n && (lane == node || ((fs.desc_m >> node) & 1ull));
+                    double Rb[9], pb[3], dxw[3], vl[3], t3[3], d3[3], Jw[3], Jv[3];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) Rb[c] = readlane_d(fs.Rw[c], node);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) pb[c] = readlane_d(fs.pw[c], node);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) dxw[c] = Rb[3 * c] * xl[0] + Rb[3 * c + 1] * xl[1] + Rb[3 * c + 2] * xl[2] + pb[c] - xt[c];
+                    Ptask += wp * 0.5 * dot3(dxw, dxw);
+                    // J(body rows, joint) of the kept iterate = Ad(E_body^-1) s_joint, as the single-term kernels form it per iterate
+                    double Rk[9], pk[3];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) Rk[c] = kept[(6 + c) * NP + node];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) pk[c] = kept[(15 + c) * NP + node];
+                    cross3(pk, swk, t3);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) d3[c] = svk[c] - t3[c];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {   // R' (.)
+                        Jw[c] = on ? (Rk[c] * swk[0] + Rk[3 + c] * swk[1] + Rk[6 + c] * swk[2]) : 0.0;
+                        Jv[c] = on ? (Rk[c] * d3[0] + Rk[3 + c] * d3[1] + Rk[6 + c] * d3[2]) : 0.0;
+                    }
+                    cross3(Jw, xl, t3);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) vl[c] = Jv[c] + t3[c];
+                    double g3[3];
+                    mat3v(Rb, vl, g3);
+                    ysum += wp * dot3(g3, dxw);
+                }
+                if (lane < n) a.dPdq[((size_t)traj * a.nsteps + (s - 1)) * n + lane] = ysum;
+                RMX_SYNC();      // (the kept iterate is read out before a later step writes the area again)
+            }
+        } else if (s == a.task_step) {    // TaskBDF1PointPos.calcStep :67-107 (TaskBDF2PointPos.calcStep is the same) at the final state of this step
             NodeOut e;
             eval_front<NP, false>(M, sAcc, lane, q, qd, 0.0, 1.0, e, fs);
             double Rb[9], pb[3], dxw[3], vl[3], t3[3];
@@ -1086,6 +1179,7 @@ template <int NP, int MODE, bool FC = false>
 __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const DevOpts o, const AdjArgs a) {
     constexpr int INTEG = MODE & 3;              // (MODE: as k_adjoint_fwd)
     constexpr bool CTL = (MODE & ADJ_CTL) != 0;
+    constexpr bool TRK = (MODE & ADJ_TRK) != 0;      // y_k: row k of dPdq where step k owns terms
     const DevModel M = model_view<NP, FC>(Min);
     const int lane = threadIdx.x, traj = blockIdx.x, n = M.n;
     const int id = (lane < n) ? M.idx[lane] : -1;
@@ -1097,7 +1191,9 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
     const double* Mb = a.Ms + (size_t)traj * a.nsteps * nn;
     const double* Db = a.Ds + (size_t)traj * a.nsteps * nn;
     for (int k = a.nsteps; k >= 1; --k) {
-        double y = (k == a.task_step && lane < n) ? a.dPdq[(size_t)traj * n + lane] : 0.0;
+        double y;
+        if constexpr (TRK) y = (a.trk_begin[k] > a.trk_begin[k - 1] && lane < n) ? a.dPdq[((size_t)traj * a.nsteps + (k - 1)) * n + lane] : 0.0;
+        else y = (k == a.task_step && lane < n) ? a.dPdq[(size_t)traj * n + lane] : 0.0;
         if (INTEG == 1) {
             // yk -= (-2 M_{k+1} + h D_{k+1})' z_{k+1}   TaskBDF1.m:58-64 ;   yk -= M_{k+2}' z_{k+2}   :65-70
             if (k < a.nsteps) adj_block<NP>(y, Mb + (size_t)k * nn, Db + (size_t)k * nn, n, lane, col, -2.0, h, z1);
