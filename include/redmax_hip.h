@@ -396,6 +396,47 @@ int rmx_adjoint_track(rmx_batch* b, const rmx_opts* opts, int nsteps, int integr
 int rmx_adjoint_track_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_track* task,
                              const double* d_xtarget, const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats);
 
+/* A differentiable controlled rollout (BDF1): the forward sweep records the trajectory and keeps H, M, D of every step (the
+ * "tape"), the backward sweep takes ANY cotangents dL/dq_k, dL/dqdot_k and returns dL/du, dL/dq0 and dL/dqdot0 - an objective of
+ * the caller's own (joint-space and velocity costs, a learned critic, a policy's loss), and the gradient with respect to the
+ * initial state that multiple shooting, receding-horizon control and chained rollouts need.  rmx_adjoint_controls / _track compute
+ * one objective inside the library; here there is none.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * rmx_rollout_tape: from the batch's current state, the forward sweep of rmx_adjoint_controls with integrator 1 - the
+ * line-search-free newton, the same guarded solve, the same compensated iterate - under the torques tau + pscale * u[b][k-1][:].
+ * u: host [batch][nsteps][nr] as in rmx_adjoint_controls.  qtraj, qdtraj: host [batch][nsteps][nr], trajectory-major, reduced DOF
+ * order (the layout of u); row k-1 is the state after step k; NULL together: no record.  H, M, D of every step's last evaluated
+ * iterate stay in the batch's adjoint workspace.  The batch is left at the end of the rollout; opts and stats as in
+ * rmx_adjoint_controls.  Refusals as rmx_adjoint_controls, with the same words (ground contact, spherical joints, more than 64
+ * nodes, point forces).
+ *
+ * rmx_rollout_vjp: reads the tape of the preceding rmx_rollout_tape on the same batch.  gq, gqd: host, shape of qtraj: dL/dq_k and
+ * dL/dqdot_k.  du: host, shape of u; dq0, dqd0: host [batch][nr], NULL together: not formed.  With z_{N+1} = z_{N+2} = 0,
+ * gqd_{N+1} = 0, N = nsteps, for k = N .. 1:
+ *     y_k  = gq_k + (gqd_k - gqd_{k+1})/h - (-2 M_{k+1} + h D_{k+1})' z_{k+1} - M_{k+2}' z_{k+2}
+ *     H_k' z_k = y_k
+ *     du_k = h^2 pscale z_k
+ *     dq0  = -gqd_1/h - (-M_1 + h D_1)' z_1 - M_2' z_2
+ *     dqd0 = h M_1' z_1
+ * The off-diagonal blocks are those of TaskBDF1.calcFinal (TaskBDF1.m:58-70); the gqd terms come from qdot_k = (q_k - q_{k-1})/h.
+ * The last two lines are the k = 0 row: -M_1 where the recursion has -2 M_1, because nothing precedes q0.  h and pscale are the
+ * tape's.  The call changes neither the batch's state nor the tape: it may be called again with other cotangents.
+ *
+ * The tape is valid until the next rmx_rollout_tape or rmx_adjoint_* call on that batch (both reuse the workspace); step calls and
+ * rmx_set_state leave it alone.  rmx_rollout_vjp refuses (RMX_E_INVALID) without a valid tape (the message says "no tape"), with
+ * an nsteps that differs from the tape's, and null arguments.
+ * BDF2 is not offered: the reference's adjoint only approximates its SDIRK2 start step (see rmx_adjoint_bdf2), and an exact
+ * gradient with respect to the initial state would need the SDIRK2 stages on the tape.
+ * The _device forms: the same with DEVICE pointers, nothing staged, nothing copied back; they return when the kernels have finished. */
+int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u,
+                     double* qtraj, double* qdtraj, rmx_stats* stats);
+int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const double* gqd,
+                    double* du, double* dq0, double* dqd0);
+int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u,
+                            double* d_qtraj, double* d_qdtraj, rmx_stats* stats);
+int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd,
+                           double* d_du, double* d_dq0, double* d_dqd0);
+
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.
  * hist_T/hist_V as in rmx_step_bdf1. */

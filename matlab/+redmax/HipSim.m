@@ -160,5 +160,19 @@ classdef HipSim < handle
 				[P, dPdu, stats] = redmax_hip_mex('adjoint_track', this.h, hstep, nsteps, task, u, itype);
 			end
 		end
+
+		function [qtraj, qdtraj, stats] = rolloutTape(this, hstep, nsteps, pscale, u)
+			% a controlled BDF1 rollout from the current state that records its trajectory and keeps the tape rolloutVjp
+			% reads: u, qtraj, qdtraj are nr x nsteps x B; at step k the joint torque is tau + pscale*u(:,k,b) and
+			% qtraj(:,k,b), qdtraj(:,k,b) is the state after it.  There is no objective: it is the caller's.
+			[qtraj, qdtraj, stats] = redmax_hip_mex('rollout_tape', this.h, hstep, nsteps, pscale, u);
+		end
+
+		function [du, dq0, dqd0] = rolloutVjp(this, nsteps, gq, gqd)
+			% the gradient of any loss L on the trajectory of the last rolloutTape: gq, gqd (nr x nsteps x B) are dL/dq and
+			% dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du, dL/dq0, dL/dqdot0.  May be
+			% repeated with other cotangents; an adjoint* call or another rolloutTape ends the tape.
+			[du, dq0, dqd0] = redmax_hip_mex('rollout_vjp', this.h, nsteps, gq, gqd);
+		end
 	end
 end

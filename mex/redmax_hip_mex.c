@@ -57,6 +57,12 @@
  *                  targets on several bodies at several steps.  task: struct terms (struct array: body 1-based, xlocal, step, wpos),
  *                  xtarget (3 x nterms, or 3 x nterms x B: one target table per rollout), pscale, wreg; u, dPdu, st, the one-output
  *                  form as 'adjoint_controls'.
+ *   [qtraj,qdtraj,st] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u)  rmx_rollout_tape: a controlled BDF1 rollout from
+ *                  the current state under the torques tau + pscale*u(:,k,b) that records its trajectory and keeps the tape
+ *                  'rollout_vjp' reads.  u, qtraj, qdtraj: nr x nsteps x B; column k is the state after step k; st as 'adjoint'.
+ *   [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)  rmx_rollout_vjp on the tape of the last 'rollout_tape': gq, gqd
+ *                  (nr x nsteps x B) are dL/dq and dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du,
+ *                  dL/dq0, dL/dqdot0.  May be repeated with other cotangents; any 'adjoint*' command ends the tape.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -542,6 +548,73 @@ static void cmd_adjoint_controls(int nlhs, mxArray* plhs[], int nrhs, const mxAr
     else mxDestroyArray(st);
 }
 
+/* an nr x nsteps x B argument of 'rollout_tape' / 'rollout_vjp' (the ABI's [B][nsteps][nr]) */
+static const double* traj_arg(const mxArray* a, const handle_t* h, int nsteps, const char* what) {
+    if (!mxIsDouble(a) || mxIsComplex(a) || mxGetNumberOfElements(a) != (size_t)h->nr * (size_t)nsteps * (size_t)h->B)
+        mexErrMsgIdAndTxt("redmax:hip", "%s must be a real double nr x nsteps x batch (%d x %d x %d) array", what, h->nr, nsteps, h->B);
+    return mxGetPr(a);
+}
+
+static void cmd_rollout_tape(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 6) die("usage: [qtraj,qdtraj,stats] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u)");
+    rmx_opts o;
+    rmx_opts_default(&o);
+    o.h = mxGetScalar(prhs[2]);
+    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    const int nsteps = (int)mxGetScalar(prhs[3]);
+    if (nsteps < 1) die("rollout_tape: nsteps must be at least 1");
+    const double pscale = mxGetScalar(prhs[4]);
+    const double* u = traj_arg(prhs[5], h, nsteps, "u");
+    const size_t per = (size_t)h->nr * (size_t)nsteps;
+    const size_t dims[3] = {(size_t)h->nr, (size_t)nsteps, (size_t)h->B};
+    mxArray* qt = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* qdt = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* st = new_i32((size_t)h->B, 2);
+    int* sp = (int*)mxGetData(st);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'adjoint_controls' */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_stats st_s;
+        st_s.newton_iters = sp + f;
+        st_s.ls_halvings = NULL;
+        st_s.status = sp + h->B + f;
+        if (rmx_rollout_tape(b, &o, nsteps, pscale, u + f * per, mxGetPr(qt) + f * per, mxGetPr(qdt) + f * per, &st_s))
+            die_rmx("rmx_rollout_tape");
+    }
+    plhs[0] = qt;
+    if (nlhs > 1) plhs[1] = qdt;
+    else mxDestroyArray(qdt);
+    if (nlhs > 2) plhs[2] = st;
+    else mxDestroyArray(st);
+}
+
+static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 5) die("usage: [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_vjp: nsteps must be at least 1");
+    const double* gq = traj_arg(prhs[3], h, nsteps, "gq");
+    const double* gqd = traj_arg(prhs[4], h, nsteps, "gqd");
+    const size_t per = (size_t)h->nr * (size_t)nsteps;
+    const size_t dims[3] = {(size_t)h->nr, (size_t)nsteps, (size_t)h->B};
+    mxArray* du = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* dq0 = mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL);
+    mxArray* dqd0 = mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        if (rmx_rollout_vjp(b, nsteps, gq + f * per, gqd + f * per, mxGetPr(du) + f * per, mxGetPr(dq0) + f * (size_t)h->nr,
+                            mxGetPr(dqd0) + f * (size_t)h->nr))
+            die_rmx("rmx_rollout_vjp");
+    }
+    plhs[0] = du;
+    if (nlhs > 1) plhs[1] = dq0;
+    else mxDestroyArray(dq0);
+    if (nlhs > 2) plhs[2] = dqd0;
+    else mxDestroyArray(dqd0);
+}
+
 /* field k of element i of the struct array task.terms */
 static const mxArray* term_field(const mxArray* terms, size_t i, const char* k) {
     const mxArray* f = mxGetField(terms, i, k);
@@ -641,7 +714,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * may name the handle ('step' / 'step_async' refuse with their own text).  Everything below reads or writes the state, the
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
-                                             "adjoint", "adjoint_controls", "adjoint_track", NULL};
+                                             "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -746,6 +819,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_adjoint_controls(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "adjoint_track")) {
         cmd_adjoint_track(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_tape")) {
+        cmd_rollout_tape(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_vjp")) {
+        cmd_rollout_vjp(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

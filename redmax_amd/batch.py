@@ -41,6 +41,7 @@ class BatchSim:
         _abi.check(self._L.rmx_batch_create(self._model, self.B, C.byref(self._batch)), "rmx_batch_create")
         self.opts = _abi.Opts()
         self._L.rmx_opts_default(C.byref(self.opts))
+        self.tape_count = 0                                # calls that rewrote the adjoint workspace (rollout_tape*, adjoint_*): see diff.rollout
 
     def close(self):
         if getattr(self, "_batch", None):
@@ -252,6 +253,7 @@ class BatchSim:
         C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
         opts.h = float(h)
         opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        self.tape_count += 1                        # (every adjoint_* call comes through here or _track_task: it ends a rollout_tape's tape)
         return tk, opts
 
     def adjoint_controls(self, nsteps, h, task, u, integrator=1, stats=False, gradient=True):
@@ -332,6 +334,7 @@ class BatchSim:
         C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
         opts.h = float(h)
         opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        self.tape_count += 1
         return tk, opts, (arr, xt)
 
     def adjoint_track(self, nsteps, h, task, u, integrator=1, stats=False, gradient=True):
@@ -384,6 +387,82 @@ class BatchSim:
         del keep
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
+
+    def _tape_opts(self, h):
+        opts = _abi.Opts()
+        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
+        if h is not None:
+            opts.h = float(h)
+        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108, as the adjoint_* calls
+        return opts
+
+    def _tape_stats(self, stats):
+        info, st = {}, None
+        if stats:
+            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
+            info["status"] = np.zeros(self.B, dtype=np.int32)
+            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        return info, st
+
+    def rollout_tape(self, nsteps, h, u, pscale=1.0, stats=False, trajectory=True):
+        """rmx_rollout_tape: a controlled BDF1 rollout from the current state that records its trajectory and keeps H, M, D of every
+        step (the tape rollout_vjp reads).  u: [B][nsteps][nr] (a [nsteps][nr] array holds for every trajectory); at step k the joint
+        torque is tau + pscale*u[:, k-1].  Returns (qtraj[B][nsteps][nr], qdtraj[B][nsteps][nr], info), row k-1 the state after step
+        k; trajectory=False returns None for both."""
+        nsteps = int(nsteps)
+        if u is None:
+            raise ValueError("rollout_tape: u is None")
+        u = np.asarray(u, dtype=np.float64)
+        if u.shape == (nsteps, self.nr):
+            u = np.broadcast_to(u, (self.B, nsteps, self.nr))
+        if u.shape != (self.B, nsteps, self.nr):
+            raise ValueError("rollout_tape: u must have shape (%d, %d, %d) or (%d, %d), got %r"
+                             % (self.B, nsteps, self.nr, nsteps, self.nr, u.shape))
+        u = np.ascontiguousarray(u)
+        opts = self._tape_opts(h)
+        qtraj = np.empty((self.B, nsteps, self.nr)) if trajectory else None
+        qdtraj = np.empty((self.B, nsteps, self.nr)) if trajectory else None
+        info, st = self._tape_stats(stats)
+        self.tape_count += 1
+        _abi.check(self._L.rmx_rollout_tape(self._batch, C.byref(opts), nsteps, float(pscale), _abi.dptr(u), _abi.dptr(qtraj),
+                                            _abi.dptr(qdtraj), C.byref(st) if st is not None else None), "rmx_rollout_tape")
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return qtraj, qdtraj, info
+
+    def rollout_tape_device(self, nsteps, h, u_ptr, qtraj_ptr, qdtraj_ptr, pscale=1.0, stats=False):
+        """rollout_tape with DEVICE pointers (integers) for u, qtraj and qdtraj, all [B][nsteps][nr]; qtraj_ptr and qdtraj_ptr 0 /
+        None together: no record.  Returns info."""
+        opts = self._tape_opts(h)
+        info, st = self._tape_stats(stats)
+        self.tape_count += 1
+        _abi.check(self._L.rmx_rollout_tape_device(self._batch, C.byref(opts), int(nsteps), float(pscale), C.c_void_p(u_ptr or None),
+                                                   C.c_void_p(qtraj_ptr or None), C.c_void_p(qdtraj_ptr or None),
+                                                   C.byref(st) if st is not None else None), "rmx_rollout_tape_device")
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return info
+
+    def rollout_vjp(self, nsteps, gq, gqd, initial_state=True):
+        """rmx_rollout_vjp on the tape of the last rollout_tape: gq, gqd [B][nsteps][nr] are dL/dq_k, dL/dqdot_k.  Returns
+        (du[B][nsteps][nr], dq0[B][nr], dqd0[B][nr]) = dL/du, dL/dq0, dL/dqdot0; initial_state=False returns None for the last two.
+        Neither the state nor the tape changes: the call may be repeated with other cotangents."""
+        nsteps = int(nsteps)
+        sh = (self.B, nsteps, self.nr)
+        gq = np.ascontiguousarray(gq, dtype=np.float64)
+        gqd = np.ascontiguousarray(gqd, dtype=np.float64)
+        if gq.shape != sh or gqd.shape != sh:
+            raise ValueError("rollout_vjp: gq and gqd must have shape %r, got %r and %r" % (sh, gq.shape, gqd.shape))
+        du = np.empty(sh)
+        dq0 = np.empty((self.B, self.nr)) if initial_state else None
+        dqd0 = np.empty((self.B, self.nr)) if initial_state else None
+        _abi.check(self._L.rmx_rollout_vjp(self._batch, nsteps, _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(du), _abi.dptr(dq0),
+                                           _abi.dptr(dqd0)), "rmx_rollout_vjp")
+        return du, dq0, dqd0
+
+    def rollout_vjp_device(self, nsteps, gq_ptr, gqd_ptr, du_ptr, dq0_ptr=None, dqd0_ptr=None):
+        """rollout_vjp with DEVICE pointers (integers): gq, gqd, du [B][nsteps][nr]; dq0, dqd0 [B][nr], 0 / None together: not formed."""
+        _abi.check(self._L.rmx_rollout_vjp_device(self._batch, int(nsteps), C.c_void_p(gq_ptr or None), C.c_void_p(gqd_ptr or None),
+                                                  C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None)),
+                   "rmx_rollout_vjp_device")
 
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent

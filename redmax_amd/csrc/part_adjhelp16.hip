@@ -16,9 +16,19 @@ static void adjoint_help_pair(const rmx_model* m, const rmx_batch* b, const DevO
     RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, true, FC>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
     if (!(MODE & ADJ_CTL) || a.dPdu) k_adjoint_bwd<RMX_NP, MODE, FC><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
 }
+// rmx_rollout_tape / rmx_rollout_vjp: the two kernels of the TAPE instantiation, one per call (a.tape: 1 forward, 2 backward; BDF1)
+template <bool FC>
+static void adjoint_help_tape(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B);
+    const size_t smem_bytes = m->smem_bytes + sizeof(double) * adj_hand_doubles(RMX_NP);
+    if (a.tape == 1) RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE, true, FC>), grid, dim3(128), smem_bytes, b->stream, m->dm, o, a);
+    else k_adjoint_bwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE, FC><<<grid, dim3(64), 0, b->stream>>>(m->dm, o, a);
+}
 template <bool FC>
 static void adjoint_help_pairs(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
-    if (integ == INTEG_BDF1) {
+    if (a.tape) {
+        adjoint_help_tape<FC>(m, b, o, a);
+    } else if (integ == INTEG_BDF1) {
         if (a.trk) adjoint_help_pair<1 | ADJ_CTL | ADJ_TRK, FC>(m, b, o, a);
         else if (a.u) adjoint_help_pair<1 | ADJ_CTL, FC>(m, b, o, a);
         else adjoint_help_pair<1, FC>(m, b, o, a);

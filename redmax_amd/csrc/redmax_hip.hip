@@ -1328,6 +1328,38 @@ extern "C" int rmx_step_euler(rmx_batch* b, double h, int nsteps, double* hT, do
 }
 
 
+// the models the adjoint path does not take (every rmx_adjoint_* entry and rmx_rollout_tape)
+static int adjoint_model_refusal(const rmx_model* m) {
+    if (m->dm.con) return fail(RMX_E_INVALID, "rmx_adjoint: ground contact is outside the adjoint path (SURVEY.md 8(f))");
+    if (m->dm.nsph) return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
+    if (m->big) return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
+    if (m->dpf) return fail(RMX_E_INVALID, "rmx_adjoint: point forces (rmx_model_set_point_forces) are outside the adjoint path");
+    return RMX_OK;
+}
+
+// the adjoint workspace of a batch: one allocation, kept between calls, that only ever grows
+static hipError_t adjws_reserve(rmx_batch* b, const size_t total) {
+    if (total <= b->adjws_bytes) return hipSuccess;
+    void* fresh = nullptr;
+    hipError_t e = hipMalloc(&fresh, total);      // the new buffer first: a failed regrow keeps the old workspace usable
+    if (e != hipSuccess && b->adjws) {      // ... unless old + new do not fit side by side: then the old one has to go first
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(b->stream);
+        (void)hipFree(b->adjws);
+        b->adjws = nullptr;
+        b->adjws_bytes = 0;
+        e = hipMalloc(&fresh, total);
+    }
+    if (e == hipSuccess) {
+        if (b->adjws) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->adjws); }
+        b->adjws = fresh;
+        b->adjws_bytes = total;
+    } else {
+        (void)hipGetLastError();       // an out-of-memory here must not be taken for a failed launch by the next call
+    }
+    return e;
+}
+
 // controls (rmx_adjoint_controls): p is u[B][nsteps][nr], dPdp is dPdu of the same shape or null (the forward sweep alone)
 // track (rmx_adjoint_track, with controls; task is null then): the terms of the objective; xtarget is its target table, a device array
 // when on_device.  The term table (rmx_track.h), the step offsets and, in the host form, the targets go into the workspace behind
@@ -1338,10 +1370,7 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
     if (!b || (!task && !track) || !p || !P || (!dPdp && !controls)) return fail(RMX_E_INVALID, "null argument");
     rmx_model* m = b->m;
     if (nsteps < 1) return fail(RMX_E_INVALID, "nsteps < 1");
-    if (m->dm.con) return fail(RMX_E_INVALID, "rmx_adjoint: ground contact is outside the adjoint path (SURVEY.md 8(f))");
-    if (m->dm.nsph) return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
-    if (m->big) return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
-    if (m->dpf) return fail(RMX_E_INVALID, "rmx_adjoint: point forces (rmx_model_set_point_forces) are outside the adjoint path");
+    if (int rc = adjoint_model_refusal(m)) return rc;
     rmx_track::Plan tplan;
     if (track) {
         tplan = rmx_track::plan_terms(track->terms, track->nterms, nsteps, m->nlist, m->node_of_listing.data());
@@ -1386,25 +1415,8 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
             offs[i] = total;
             total += (sizes[i] + 255) & ~(size_t)255;
         }
-        if (total > b->adjws_bytes) {
-            void* fresh = nullptr;
-            e = hipMalloc(&fresh, total);      // the new buffer first: a failed regrow keeps the old workspace usable
-            if (e != hipSuccess && b->adjws) {      // ... unless old + new do not fit side by side: then the old one has to go first
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(b->stream);
-                (void)hipFree(b->adjws);
-                b->adjws = nullptr;
-                b->adjws_bytes = 0;
-                e = hipMalloc(&fresh, total);
-            }
-            if (e == hipSuccess) {
-                if (b->adjws) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->adjws); }
-                b->adjws = fresh;
-                b->adjws_bytes = total;
-            } else {
-                (void)hipGetLastError();       // an out-of-memory here must not be taken for a failed launch by the next call
-            }
-        }
+        b->tape_nsteps = 0;      // (the workspace is about to be rewritten: a tape of rmx_rollout_tape ends here)
+        e = adjws_reserve(b, total);
         if (e == hipSuccess)
             for (int i = 0; i < NBUF; ++i) bufs[i] = (char*)b->adjws + offs[i];
     }
@@ -1491,6 +1503,162 @@ extern "C" int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, i
                                            const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats) {
     if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_adjoint_controls: integrator must be 1 (BDF1) or 2 (BDF2)");
     return adjoint_impl(b, opts, nsteps, task, d_u, d_P, d_dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, true, true);
+}
+
+// rmx_rollout_tape / rmx_rollout_vjp (include/redmax_hip.h): the parts of the workspace.  H, M, D first, where every adjoint call has
+// them; behind them the staging areas of the host forms - three arrays shaped as u (u, qtraj, qdtraj of the tape; gq, gqd, du of the
+// vjp) and two of [B][nr] (dq0, dqd0).  The tape call reserves all of it, so that a vjp never regrows (and so loses) the tape.
+struct TapeParts {
+    size_t off[8], bytes_traj, bytes_state, total;
+};
+static TapeParts tape_parts(const rmx_batch* b, const int nsteps) {
+    const rmx_model* m = b->m;
+    TapeParts t{};
+    const size_t hist = (size_t)b->B * nsteps * m->n * m->n * sizeof(double);
+    t.bytes_traj = (size_t)b->B * nsteps * m->nr * sizeof(double);
+    t.bytes_state = (size_t)b->B * m->nr * sizeof(double);
+    const size_t sizes[8] = {hist, hist, hist, t.bytes_traj, t.bytes_traj, t.bytes_traj, t.bytes_state, t.bytes_state};
+    for (int i = 0; i < 8; ++i) {
+        t.off[i] = t.total;
+        t.total += (sizes[i] + 255) & ~(size_t)255;
+    }
+    return t;
+}
+static void launch_adjoint_plan(rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
+    rmx_model* m = b->m;
+    const rmx_select::AdjPlan plan = rmx_select::select_adjoint(step_traits(m), b->B, rmx_select::knobs_from_env());
+    switch (plan.kernel) {
+        case AdjKernel::Help16: launch_adjoint_help_16(m, b, INTEG_BDF1, o, a, plan.fullchain); break;
+        case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, INTEG_BDF1, o, a); break;
+        case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, INTEG_BDF1, o, a); break;
+    }
+}
+
+static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
+                             double* qdtraj, rmx_stats* stats, const bool on_device) {
+    if (!b || !u) return fail(RMX_E_INVALID, "rmx_rollout_tape: null argument");
+    if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
+    rmx_model* m = b->m;
+    if (nsteps < 1) return fail(RMX_E_INVALID, "nsteps < 1");
+    if (int rc = adjoint_model_refusal(m)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    DevOpts o;
+    int rc = make_opts(b, opts, o);
+    if (rc) return rc;
+    rc = pending_error_check(b, "rmx_rollout_tape");
+    if (rc) return rc;
+    if ((size_t)b->B * nsteps * m->n * m->n * sizeof(double) * 3 > ((size_t)200 << 30))
+        return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
+    const TapeParts t = tape_parts(b, nsteps);
+    b->tape_nsteps = 0;
+    hipError_t e = adjws_reserve(b, t.total);
+    if (e == hipSuccess) {
+        char* ws = (char*)b->adjws;
+        if (!on_device) e = hipMemcpyAsync(ws + t.off[3], u, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
+        AdjArgs a{};
+        a.B = b->B; a.nsteps = nsteps; a.pscale = pscale;
+        a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp;
+        a.it = stats ? b->it : nullptr; a.status = b->status;
+        a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
+        a.u = on_device ? u : (const double*)(ws + t.off[3]);
+        a.tape = 1;
+        if (qtraj) {
+            a.qtraj = on_device ? qtraj : (double*)(ws + t.off[4]);
+            a.qdtraj = on_device ? qdtraj : (double*)(ws + t.off[5]);
+        }
+        if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
+        if (e == hipSuccess) {
+            launch_adjoint_plan(b, o, a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+        if (e == hipSuccess) e = set_started(b, 0);      // (a BDF1 rollout: rmx_step_bdf2 takes its start step again)
+        if (e == hipSuccess && !on_device && qtraj) {
+            e = hipMemcpyAsync(qtraj, a.qtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(qdtraj, a.qdtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
+        }
+        if (e == hipSuccess && stats) {
+            if (stats->newton_iters) e = hipMemcpyAsync(stats->newton_iters, b->it, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
+            if (e == hipSuccess && stats->status) e = hipMemcpyAsync(stats->status, b->status, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
+        }
+        if (e == hipSuccess) e = wait_stream_short(b->stream);
+        else (void)hipStreamSynchronize(b->stream);      // (u must outlive its copy)
+        if (e == hipSuccess) {
+            take_event_time(b);
+            b->tape_nsteps = nsteps;
+            b->tape_h = o.h;
+            b->tape_pscale = pscale;
+        }
+    }
+    if (e == hipErrorOutOfMemory) return fail(RMX_E_NOMEM, "rmx_rollout_tape: no device memory for the tape (H, M, D per step and rollout)");
+    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_tape: ") + hipGetErrorString(e));
+    return RMX_OK;
+}
+
+static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                            const bool on_device) {
+    if (!b || !gq || !gqd || !du) return fail(RMX_E_INVALID, "rmx_rollout_vjp: null argument");
+    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_vjp: dq0 and dqd0 must be given together");
+    rmx_model* m = b->m;
+    if (b->tape_nsteps < 1 || !b->adjws)
+        return fail(RMX_E_INVALID, "rmx_rollout_vjp: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_vjp: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+    HIPCHK(hipSetDevice(m->device));
+    int rc = pending_error_check(b, "rmx_rollout_vjp");
+    if (rc) return rc;
+    const TapeParts t = tape_parts(b, nsteps);
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp: no tape (the workspace is smaller than the tape)");
+    char* ws = (char*)b->adjws;
+    DevOpts o{};
+    o.h = b->tape_h;
+    AdjArgs a{};
+    a.B = b->B; a.nsteps = nsteps; a.pscale = b->tape_pscale;
+    a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
+    a.tape = 2;
+    a.gq = on_device ? gq : (const double*)(ws + t.off[3]);
+    a.gqd = on_device ? gqd : (const double*)(ws + t.off[4]);
+    a.dPdu = on_device ? du : (double*)(ws + t.off[5]);
+    if (dq0) {
+        a.dq0 = on_device ? dq0 : (double*)(ws + t.off[6]);
+        a.dqd0 = on_device ? dqd0 : (double*)(ws + t.off[7]);
+    }
+    hipError_t e = hipSuccess;
+    if (!on_device) {
+        e = hipMemcpyAsync(ws + t.off[3], gq, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[4], gqd, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
+    if (e == hipSuccess) {
+        launch_adjoint_plan(b, o, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+    if (e == hipSuccess && !on_device) {
+        e = hipMemcpyAsync(du, a.dPdu, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dq0, a.dq0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dqd0, a.dqd0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
+    }
+    if (e == hipSuccess) e = wait_stream_short(b->stream);
+    else (void)hipStreamSynchronize(b->stream);      // (the cotangents must outlive their copies)
+    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp: ") + hipGetErrorString(e));
+    take_event_time(b);
+    return RMX_OK;
+}
+
+extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
+                                double* qdtraj, rmx_stats* stats) {
+    return rollout_tape_impl(b, opts, nsteps, pscale, u, qtraj, qdtraj, stats, false);
+}
+extern "C" int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u, double* d_qtraj,
+                                       double* d_qdtraj, rmx_stats* stats) {
+    return rollout_tape_impl(b, opts, nsteps, pscale, d_u, d_qtraj, d_qdtraj, stats, true);
+}
+extern "C" int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0) {
+    return rollout_vjp_impl(b, nsteps, gq, gqd, du, dq0, dqd0, false);
+}
+extern "C" int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
+                                      double* d_dqd0) {
+    return rollout_vjp_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, true);
 }
 
 static int track_refusal(const rmx_task_track* task, const double* xtarget, int integrator) {

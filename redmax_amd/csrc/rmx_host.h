@@ -71,6 +71,11 @@ struct AdjArgs {
     const int* trk_begin;     // [nsteps + 1] step k owns terms trk_begin[k-1] .. trk_begin[k]-1
     const double* trk_xt;     // targets, [nterms][3] or [B][nterms][3], indexed by the term's position in the caller's array
     size_t trk_xt_stride;     // doubles from one rollout's target table to the next (0: one table for the batch)
+    // rmx_rollout_tape / rmx_rollout_vjp (the TAPE instantiations: u as above, dPdu is du; no task, no P, no dPdq)
+    int tape;                 // 0: an adjoint pair; 1: the forward sweep alone (rmx_rollout_tape); 2: the backward sweep alone (rmx_rollout_vjp)
+    double *qtraj, *qdtraj;   // [B][nsteps][nr] q, qdot after every step (out), or null together
+    const double *gq, *gqd;   // [B][nsteps][nr] the cotangents dL/dq_k, dL/dqdot_k
+    double *dq0, *dqd0;       // [B][nr] dL/dq0, dL/dqdot0 (out), or null together
 };
 
 struct rmx_model {
@@ -119,6 +124,8 @@ struct rmx_batch {
     size_t bigws_stride = 0;        // doubles per rollout
     void* adjws = nullptr;          // rmx_adjoint_*: H, M, D of every step and rollout, dP/dq, P, dP/dp - one allocation that is kept
     size_t adjws_bytes = 0;         // between calls and only ever grows (hipMalloc + hipFree of 3 x 20 MB cost more than the kernels)
+    int tape_nsteps = 0;            // rmx_rollout_tape: steps of the tape H, M, D in adjws hold (0: none - every rmx_adjoint_* call rewrites them)
+    double tape_h = 0.0, tape_pscale = 0.0;   // ... and the step size and torque scale it was recorded with
     double last_ms = 0.0;
     const char* last_kernel = "";   // label of the step kernel the last step call launched (rmx_last_step_kernel; StepPlan::label)
     bool async_pending = false;     // an rmx_step_*_async launch nobody has waited for yet (see pending_error_check)

@@ -815,6 +815,14 @@ constexpr int ADJ_CTL = 4;
 // s-1 of a.dPdq ([B][nsteps][n] here) is their sum, which the backward kernel reads where the step owns terms.  J is formed once per
 // measured step from the kept iterate, not at every Newton iterate.  Compile-time like CTL: the other instantiations keep their code.
 constexpr int ADJ_TRK = 8;
+// TAPE (rmx_rollout_tape / rmx_rollout_vjp, with CTL, BDF1 only, never with TRK): no objective at all.  The forward kernel is the CTL
+// sweep with a.task_step = 0 - no step is the task step, so no J is formed, no final-state front runs, no dPdq is written - without
+// the regulariser and P, and records q, qdot of every step (a.qtraj / a.qdtraj).  The task branches stay COMPILED in it: the sweep has
+// to be rmx_adjoint_controls' bit for bit, and with them compiled out the compiler contracts a few products of the front differently
+// (1 ulp in q on the 7-joint tree and the 32-link chain, measured; either branch alone restores the bits);
+// the backward kernel takes y_k from the caller's cotangents (a.gq / a.gqd), stores du per step and forms the k = 0 row (dL/dq0,
+// dL/dqdot0) behind the loop.  The two kernels are launched by different calls (a.tape).  Compile-time like CTL and TRK.
+constexpr int ADJ_TAPE = 16;
 constexpr int ADJ_TRK_ROWS = 18;      // sw[3], sv[3], Rw[9], pw[3], one column per node
 __host__ __device__ constexpr size_t adj_trk_doubles(const int NP) { return (size_t)ADJ_TRK_ROWS * NP; }
 template <int NP, int MODE, bool HELP = false, bool FC = false>
@@ -822,8 +830,10 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     constexpr int INTEG = MODE & 3;
     constexpr bool CTL = (MODE & ADJ_CTL) != 0;
     constexpr bool TRK = (MODE & ADJ_TRK) != 0;
+    constexpr bool TAPE = (MODE & ADJ_TAPE) != 0;
     static_assert(INTEG == 1 || INTEG == 2, "BDF1 or BDF2");
     static_assert(!TRK || CTL, "the tracking objective comes with per-step controls");
+    static_assert(!TAPE || (CTL && !TRK && INTEG == 1), "the taped rollout: per-step controls, no objective, BDF1");
     static_assert(!HELP || NP <= 16, "the helper-wave form: trees of one DPP row");
     const DevModel M = model_view<NP, FC>(Min);
     double *sAcc, *sCol;
@@ -860,7 +870,7 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
         if constexpr (CTL) {                 // (under BDF2 step 1's torque holds for both SDIRK2 solves)
             const double us = id >= 0 ? uj[(size_t)(s - 1) * M.nr] : 0.0;
             fs.tau_add = a.pscale * us;
-            ureg += us * us;
+            if constexpr (!TAPE) ureg += us * us;
         }
         double* Hk = a.Hs + ((size_t)traj * a.nsteps + (s - 1)) * nn;
         double* Mk = a.Ms + ((size_t)traj * a.nsteps + (s - 1)) * nn;
@@ -1045,6 +1055,13 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
             qp = q1;
             qdp = qd1;
         }
+        if constexpr (TAPE) {             // the record of the rollout: row s-1 is the state after step s, in the layout of u
+            if (a.qtraj && id >= 0) {
+                const size_t offs = ((size_t)traj * a.nsteps + (s - 1)) * M.nr + id;
+                a.qtraj[offs] = q;
+                a.qdtraj[offs] = qd;
+            }
+        }
         if constexpr (TRK) {
             if (measured) {      // this step owns terms: calcStep of each of them, their sum in row s-1 of dPdq
                 // fs is still the state of the last evaluated iterate: keep what J needs of it before the final-state front overwrites it
@@ -1138,7 +1155,7 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     }
     const double preg = wave_sum(CTL ? ureg : pj * pj);
     if (lane == 0) {
-        a.P[traj] = Ptask + a.wreg * 0.5 * preg;      // TaskBDF1.calcFinal :49 / TaskBDF2.calcFinal :49
+        if constexpr (!TAPE) a.P[traj] = Ptask + a.wreg * 0.5 * preg;      // TaskBDF1.calcFinal :49 / TaskBDF2.calcFinal :49
         if (a.it) {
             a.it[traj] = iters;
             a.status[traj] = status;
@@ -1180,6 +1197,8 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
     constexpr int INTEG = MODE & 3;              // (MODE: as k_adjoint_fwd)
     constexpr bool CTL = (MODE & ADJ_CTL) != 0;
     constexpr bool TRK = (MODE & ADJ_TRK) != 0;      // y_k: row k of dPdq where step k owns terms
+    constexpr bool TAPE = (MODE & ADJ_TAPE) != 0;    // y_k: the caller's cotangents; du per step; the k = 0 row behind the loop
+    static_assert(!TAPE || (CTL && !TRK && INTEG == 1), "the taped rollout: per-step controls, no objective, BDF1");
     const DevModel M = model_view<NP, FC>(Min);
     const int lane = threadIdx.x, traj = blockIdx.x, n = M.n;
     const int id = (lane < n) ? M.idx[lane] : -1;
@@ -1190,9 +1209,17 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
     double z1 = 0.0, z2 = 0.0, z3 = 0.0, z4 = 0.0, zs = 0.0;      // z of steps k+1 .. k+4
     const double* Mb = a.Ms + (size_t)traj * a.nsteps * nn;
     const double* Db = a.Ds + (size_t)traj * a.nsteps * nn;
+    double gdn = 0.0;                                // TAPE: dL/dqdot of step k+1
     for (int k = a.nsteps; k >= 1; --k) {
         double y;
-        if constexpr (TRK) y = (a.trk_begin[k] > a.trk_begin[k - 1] && lane < n) ? a.dPdq[((size_t)traj * a.nsteps + (k - 1)) * n + lane] : 0.0;
+        if constexpr (TAPE) {
+            // y_k = dL/dq_k + (dL/dqdot_k - dL/dqdot_{k+1}) / h, from qdot_k = (q_k - q_{k-1}) / h; mapped through M.idx as u is, zero on
+            // lanes without a DOF (the loads unconditional, the index clamped: see adj_block)
+            const size_t offk = ((size_t)traj * a.nsteps + (k - 1)) * M.nr + (id >= 0 ? id : 0);
+            const double gqk = a.gq[offk], gdk = a.gqd[offk];
+            y = id >= 0 ? gqk + (gdk - gdn) / h : 0.0;
+            gdn = gdk;
+        } else if constexpr (TRK) y = (a.trk_begin[k] > a.trk_begin[k - 1] && lane < n) ? a.dPdq[((size_t)traj * a.nsteps + (k - 1)) * n + lane] : 0.0;
         else y = (k == a.task_step && lane < n) ? a.dPdq[(size_t)traj * n + lane] : 0.0;
         if (INTEG == 1) {
             // yk -= (-2 M_{k+1} + h D_{k+1})' z_{k+1}   TaskBDF1.m:58-64 ;   yk -= M_{k+2}' z_{k+2}   :65-70
@@ -1236,7 +1263,9 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
         } else {
             z = lu_solve_neg<NP, true>(n, lane, Hrow, -y);
         }
-        if constexpr (CTL) {    // the constant-parameter formula below before its sum over the steps, one row per step
+        if constexpr (TAPE) {   // du_k = -z_k' dg_k/du_k, dg_k/du_k = -h^2 pscale I
+            if (id >= 0) a.dPdu[((size_t)traj * a.nsteps + (k - 1)) * M.nr + id] = h * h * a.pscale * z;
+        } else if constexpr (CTL) {    // the constant-parameter formula below before its sum over the steps, one row per step
             if (id >= 0) {
                 const size_t offk = ((size_t)traj * a.nsteps + (k - 1)) * M.nr + id;
                 a.dPdu[offk] = a.wreg * a.u[offk] + (INTEG == 1 ? h * h : (4.0 / 9.0) * h * h) * a.pscale * z;
@@ -1248,6 +1277,22 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
         z3 = z2;
         z2 = z1;
         z1 = z;
+    }
+    if constexpr (TAPE) {
+        // the k = 0 row.  g_1 = M (q_1 - q_0 - h qdot_0) - h^2 f(q_1, (q_1 - q_0) / h): dg_1/dq_0 = -M_1 + h D_1 (where the recursion has
+        // -2 M: nothing precedes q_0), dg_1/dqdot_0 = -h M_1, dg_2/dq_0 = M_2; and qdot_1 = (q_1 - q_0) / h reads q_0 directly.
+        // z1, z2 are z of steps 1 and 2 here, gdn is dL/dqdot_1.
+        if (a.dq0) {
+            double y0 = id >= 0 ? -gdn / h : 0.0, yd0 = 0.0;
+            adj_block<NP>(y0, Mb, Db, n, lane, col, -1.0, h, z1);
+            if (a.nsteps > 1) adj_block<NP>(y0, Mb + nn, Db + nn, n, lane, col, 1.0, 0.0, z2);
+            adj_block<NP>(yd0, Mb, Db, n, lane, col, -h, 0.0, z1);      // dL/dqdot_0 = h M_1' z_1
+            if (id >= 0) {
+                const size_t off = (size_t)traj * M.nr + id;
+                a.dq0[off] = y0;
+                a.dqd0[off] = yd0;
+            }
+        }
     }
     if (id >= 0 && !CTL) {   // dPdp = wreg*p' - z'*dgdp, dgdp(kk,:) = -eta^2*pscale*I with eta^2 = h^2 (TaskBDF1PointPos.m:104-105) or (4/9) h^2 for
         const size_t off = (size_t)traj * M.nr + id;                 // EVERY step (TaskBDF2PointPos.m:97-106)

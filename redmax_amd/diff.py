@@ -1,0 +1,81 @@
+"""A differentiable controlled BDF1 rollout for PyTorch: ``rollout(sim, q0, qdot0, u)`` returns the trajectory, and
+``backward()`` of any loss on it yields dL/du, dL/dq0 and dL/dqdot0.
+
+Forward is rmx_rollout_tape_device, backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
+objective lives wholly on the PyTorch side.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
+"""
+from __future__ import annotations
+
+_BAD_STATUS = 1 | 2 | 4      # RMX_ST_DIVERGED, RMX_ST_MAXITER, RMX_ST_NAN
+
+_Function = None
+
+
+def _function():
+    """The torch.autograd.Function, made on first use (torch is not imported before)."""
+    global _Function
+    if _Function is not None:
+        return _Function
+    import torch
+
+    class _Rollout(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, q0, qdot0, u, sim, h, pscale, check):
+            B, nsteps, nr = u.shape
+            q0c, qd0c, uc = q0.contiguous(), qdot0.contiguous(), u.contiguous()
+            qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
+            qdtraj = torch.empty_like(qtraj)
+            # the library works on a stream of its own and returns when its kernels have finished: what torch has queued for the
+            # inputs must be done before it starts
+            torch.cuda.current_stream(u.device).synchronize()
+            sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
+            info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=pscale, stats=check)
+            ctx.sim, ctx.nsteps, ctx.tape = sim, nsteps, sim.tape_count
+            if check and (info["status"] & _BAD_STATUS).any():
+                bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
+                raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+            return qtraj, qdtraj
+
+        @staticmethod
+        def backward(ctx, gq, gqd):
+            sim, nsteps = ctx.sim, ctx.nsteps
+            if sim.tape_count != ctx.tape:
+                raise RuntimeError("the tape of this rollout has been replaced")
+            dev = torch.device("cuda", sim.device)
+            sh = (sim.B, nsteps, sim.nr)
+            gq = torch.zeros(sh, dtype=torch.float64, device=dev) if gq is None else gq.contiguous()
+            gqd = torch.zeros(sh, dtype=torch.float64, device=dev) if gqd is None else gqd.contiguous()
+            du = torch.empty(sh, dtype=torch.float64, device=dev)
+            dq0 = torch.empty((sim.B, sim.nr), dtype=torch.float64, device=dev)
+            dqd0 = torch.empty_like(dq0)
+            torch.cuda.current_stream(dev).synchronize()
+            sim.rollout_vjp_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr())
+            return dq0, dqd0, du, None, None, None, None
+
+    _Function = _Rollout
+    return _Function
+
+
+def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True):
+    """A controlled BDF1 rollout of every trajectory of ``sim`` (a BatchSim) that autograd can differentiate.
+
+    q0, qdot0: [B][nr]; u: [B][nsteps][nr], one torque per joint and step (tau + pscale*u at step k) - float64 tensors on the sim's
+    device.  h: step size (None: sim.opts.h).  Returns (qtraj, qdtraj), both [B][nsteps][nr]: row k-1 is the state after step k.
+    The sim is left at the end of the rollout.  check=True raises RuntimeError when a rollout's Newton solve diverged, hit its
+    iteration limit or met a NaN.  backward() must run before the next rollout or adjoint_* call on the same sim: both replace
+    the tape, and backward raises RuntimeError("the tape of this rollout has been replaced") then."""
+    import torch
+    dev = torch.device("cuda", sim.device)
+    for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("rollout: %s must be float64, got %s" % (name, t.dtype))
+        if t.device != dev:
+            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+    if u.dim() != 3 or u.shape[0] != sim.B or u.shape[2] != sim.nr or u.shape[1] < 1:
+        raise ValueError("rollout: u must have shape (%d, nsteps, %d), got %r" % (sim.B, sim.nr, tuple(u.shape)))
+    for name, t in (("q0", q0), ("qdot0", qdot0)):
+        if tuple(t.shape) != (sim.B, sim.nr):
+            raise ValueError("rollout: %s must have shape (%d, %d), got %r" % (name, sim.B, sim.nr, tuple(t.shape)))
+    return _function().apply(q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check))

@@ -21,6 +21,10 @@ ROWS = (  # (name fragment, what it runs)
     ("k_adjoint_fwd<16, 13, true, true>", "rmx_adjoint_track (per-step controls + tracking objective), BDF1: forward sweep, full 16-link chain, second wavefront"),
     ("k_adjoint_bwd<16, 13, true>", "rmx_adjoint_track: backward sweep, full 16-link chain"),
     ("k_adjoint_fwd<64, 13, false, false>", "rmx_adjoint_track: forward sweep, 33..64 nodes"),
+    ("k_adjoint_fwd<16, 21, true, true>", "rmx_rollout_tape (taped forward sweep, BDF1): full 16-link chain, second wavefront"),
+    ("k_adjoint_bwd<16, 21, true>", "rmx_rollout_vjp (cotangents in, du, dq0, dqd0 out): full 16-link chain"),
+    ("k_adjoint_fwd<64, 21, false, false>", "rmx_rollout_tape: 33..64 nodes"),
+    ("k_adjoint_bwd<32, 21, false>", "rmx_rollout_vjp: 17..32 nodes"),
     ("k_step_bdf1<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF1"),
     ("k_step_bdf2<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF2"),
     ("k_big_step", "trees of 65..256 nodes (one workgroup per rollout)"),
