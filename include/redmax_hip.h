@@ -396,7 +396,7 @@ int rmx_adjoint_track(rmx_batch* b, const rmx_opts* opts, int nsteps, int integr
 int rmx_adjoint_track_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, const rmx_task_track* task,
                              const double* d_xtarget, const double* d_u, double* d_P, double* d_dPdu, rmx_stats* stats);
 
-/* A differentiable controlled rollout (BDF1): the forward sweep records the trajectory and keeps H, M, D of every step (the
+/* A differentiable controlled rollout (BDF1, BDF2): the forward sweep records the trajectory and keeps H, M, D of every step (the
  * "tape"), the backward sweep takes ANY cotangents dL/dq_k, dL/dqdot_k and returns dL/du, dL/dq0 and dL/dqdot0 - an objective of
  * the caller's own (joint-space and velocity costs, a learned critic, a policy's loss), and the gradient with respect to the
  * initial state that multiple shooting, receding-horizon control and chained rollouts need.  rmx_adjoint_controls / _track compute
@@ -422,14 +422,42 @@ int rmx_adjoint_track_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int
  * The last two lines are the k = 0 row: -M_1 where the recursion has -2 M_1, because nothing precedes q0.  h and pscale are the
  * tape's.  The call changes neither the batch's state nor the tape: it may be called again with other cotangents.
  *
- * The tape is valid until the next rmx_rollout_tape or rmx_adjoint_* call on that batch (both reuse the workspace); step calls and
+ * The tape is valid until the next rmx_rollout_tape / rmx_rollout_tape_bdf2 or rmx_adjoint_* call on that batch (both reuse the workspace); step calls and
  * rmx_set_state leave it alone.  rmx_rollout_vjp refuses (RMX_E_INVALID) without a valid tape (the message says "no tape"), with
  * an nsteps that differs from the tape's, and null arguments.
- * BDF2 is not offered: the reference's adjoint only approximates its SDIRK2 start step (see rmx_adjoint_bdf2), and an exact
- * gradient with respect to the initial state would need the SDIRK2 stages on the tape.
+ *
+ * rmx_rollout_tape_bdf2: the same under BDF2 - arguments, layouts, refusals and words are rmx_rollout_tape's.  The call starts from
+ * the batch's current (q, qdot) and ALWAYS takes the SDIRK2 start step (as rmx_adjoint_bdf2 does), so (q0, qdot0) is the complete
+ * state and dq0, dqd0 are well defined; row k-1 of qtraj is the state after step k, step 1 being the start step.  The batch is
+ * left at the end of the rollout with the BDF2 history in place: rmx_step_bdf2 may continue it.  The tape holds H, M, D of every
+ * step's final solve AND of the SDIRK2a stage (nsteps + 1 slots per rollout), and rmx_rollout_vjp - which follows the integrator
+ * of the tape it finds - differentiates every solve exactly.  Every solve is the same implicit function: given qA, qB, eta and
+ * the step's torque, x solves g = M(x)(x - qB) - eta^2 (f(x, (x - qA)/eta) + pscale u) = 0, and v = (x - qA)/eta.  With H = dg/dx,
+ * M, D = df/dqdot at the solution, cotangents xbar, vbar of x, v go back as
+ *     solve_bwd:  H' z = xbar + vbar/eta ;  A = -vbar/eta - eta D' z (of qA) ;  Bq = M' z (of qB) ;  ubar = eta^2 pscale z
+ * With al = (2 - sqrt 2)/2 the solves are (driverRedMaxBDF2.m:64-117)
+ *     SDIRK2a: eta = al h, qA = q0, qB = q0 + al h qd0                                         -> qa, qda = (qa - q0)/(al h)
+ *     SDIRK2b: eta = al h, qA = q0 + (1-al) h qda, qB = q0 + (2al-1) h qd0 + 2(1-al) h qda     -> q1, qd1
+ *     BDF2   : eta = 2h/3, qA = 4/3 q_k - 1/3 q_{k-1}, qB = qA + 8/9 h qd_k - 2/9 h qd_{k-1}   -> q_{k+1}, qd_{k+1}
+ * and the sweep carries qbar[k], vbar[k], which start as gq_k, gqd_k (zero for k = 0).  For k = N-1 .. 1:
+ *     (A, Bq, z) = solve_bwd(step k+1; qbar[k+1], vbar[k+1]) ;  du_{k+1} = (2h/3)^2 pscale z ;  s = A + Bq
+ *     qbar[k]   += 4/3 s ;  vbar[k]   += 8/9 h Bq ;  qbar[k-1] -= 1/3 s ;  vbar[k-1] -= 2/9 h Bq
+ * then the start step:
+ *     (A, Bq, zb) = solve_bwd(SDIRK2b; qbar[1], vbar[1])
+ *     qbar[0] += A + Bq ;  vbar[0] += (2al-1) h Bq ;  qdabar = (1-al) h A + 2(1-al) h Bq
+ *     (A2, B2, za) = solve_bwd(SDIRK2a; 0, qdabar)               (qa is read only through qda)
+ *     qbar[0] += A2 + B2 ;  vbar[0] += al h B2
+ *     du_1 = (al h)^2 pscale (za + zb)                           (step 1's torque holds for both solves)
+ *     dq0 = qbar[0] ;  dqd0 = vbar[0]
+ * rmx_adjoint_bdf2 and rmx_adjoint_controls / _track with integrator 2 keep the reference's APPROXIMATE k = 1 row (dg/dp =
+ * -(4/9) h^2 for the start step, dg/dqa dropped: TaskBDF2.calcFinal); only the taped rollout is exact there.
  * The _device forms: the same with DEVICE pointers, nothing staged, nothing copied back; they return when the kernels have finished. */
 int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u,
                      double* qtraj, double* qdtraj, rmx_stats* stats);
+int rmx_rollout_tape_bdf2(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u,
+                          double* qtraj, double* qdtraj, rmx_stats* stats);
+int rmx_rollout_tape_bdf2_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u,
+                                 double* d_qtraj, double* d_qdtraj, rmx_stats* stats);
 int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const double* gqd,
                     double* du, double* dq0, double* dqd0);
 int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u,

@@ -161,11 +161,16 @@ classdef HipSim < handle
 			end
 		end
 
-		function [qtraj, qdtraj, stats] = rolloutTape(this, hstep, nsteps, pscale, u)
-			% a controlled BDF1 rollout from the current state that records its trajectory and keeps the tape rolloutVjp
+		function [qtraj, qdtraj, stats] = rolloutTape(this, hstep, nsteps, pscale, u, integrator)
+			% a controlled BDF1 (or, integrator 2, BDF2) rollout from the current state that records its trajectory and keeps the tape rolloutVjp
 			% reads: u, qtraj, qdtraj are nr x nsteps x B; at step k the joint torque is tau + pscale*u(:,k,b) and
 			% qtraj(:,k,b), qdtraj(:,k,b) is the state after it.  There is no objective: it is the caller's.
-			[qtraj, qdtraj, stats] = redmax_hip_mex('rollout_tape', this.h, hstep, nsteps, pscale, u);
+			% integrator (optional, default 1) 2: the BDF2 rollout, self-started with SDIRK2 from the current state (step 1,
+			% whose torque holds for both stages); rolloutVjp then differentiates the start step exactly as well.
+			if nargin < 6
+				integrator = 1;
+			end
+			[qtraj, qdtraj, stats] = redmax_hip_mex('rollout_tape', this.h, hstep, nsteps, pscale, u, integrator);
 		end
 
 		function [du, dq0, dqd0] = rolloutVjp(this, nsteps, gq, gqd)

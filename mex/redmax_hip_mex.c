@@ -57,9 +57,10 @@
  *                  targets on several bodies at several steps.  task: struct terms (struct array: body 1-based, xlocal, step, wpos),
  *                  xtarget (3 x nterms, or 3 x nterms x B: one target table per rollout), pscale, wreg; u, dPdu, st, the one-output
  *                  form as 'adjoint_controls'.
- *   [qtraj,qdtraj,st] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u)  rmx_rollout_tape: a controlled BDF1 rollout from
- *                  the current state under the torques tau + pscale*u(:,k,b) that records its trajectory and keeps the tape
- *                  'rollout_vjp' reads.  u, qtraj, qdtraj: nr x nsteps x B; column k is the state after step k; st as 'adjoint'.
+ *   [qtraj,qdtraj,st] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u [, integrator])  rmx_rollout_tape: a controlled BDF1
+ *                  rollout from the current state under the torques tau + pscale*u(:,k,b) that records its trajectory and keeps the
+ *                  tape 'rollout_vjp' reads.  u, qtraj, qdtraj: nr x nsteps x B; column k is the state after step k; st as 'adjoint'.
+ *                  integrator (default 1) 2: rmx_rollout_tape_bdf2, the BDF2 rollout, self-started with SDIRK2 (step 1).
  *   [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)  rmx_rollout_vjp on the tape of the last 'rollout_tape': gq, gqd
  *                  (nr x nsteps x B) are dL/dq and dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du,
  *                  dL/dq0, dL/dqdot0.  May be repeated with other cotangents; any 'adjoint*' command ends the tape.
@@ -557,7 +558,10 @@ static const double* traj_arg(const mxArray* a, const handle_t* h, int nsteps, c
 
 static void cmd_rollout_tape(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 6) die("usage: [qtraj,qdtraj,stats] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u)");
+    if (nrhs < 6) die("usage: [qtraj,qdtraj,stats] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u [, integrator])");
+    const double integ_arg = nrhs > 6 ? mxGetScalar(prhs[6]) : 1.0;
+    if (integ_arg != 1.0 && integ_arg != 2.0) die("rollout_tape: integrator must be 1 (BDF1) or 2 (BDF2)");
+    const int integ = integ_arg == 2.0 ? 2 : 1;
     rmx_opts o;
     rmx_opts_default(&o);
     o.h = mxGetScalar(prhs[2]);
@@ -579,8 +583,9 @@ static void cmd_rollout_tape(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
         st_s.newton_iters = sp + f;
         st_s.ls_halvings = NULL;
         st_s.status = sp + h->B + f;
-        if (rmx_rollout_tape(b, &o, nsteps, pscale, u + f * per, mxGetPr(qt) + f * per, mxGetPr(qdt) + f * per, &st_s))
-            die_rmx("rmx_rollout_tape");
+        if ((integ == 2 ? rmx_rollout_tape_bdf2 : rmx_rollout_tape)(b, &o, nsteps, pscale, u + f * per, mxGetPr(qt) + f * per,
+                                                                    mxGetPr(qdt) + f * per, &st_s))
+            die_rmx(integ == 2 ? "rmx_rollout_tape_bdf2" : "rmx_rollout_tape");
     }
     plhs[0] = qt;
     if (nlhs > 1) plhs[1] = qdt;

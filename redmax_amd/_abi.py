@@ -25,6 +25,7 @@ SYMBOLS = (
     "rmx_set_state", "rmx_get_state", "rmx_set_state_device", "rmx_get_state_device",
     "rmx_eval", "rmx_eval_mfd", "rmx_compute_values", "rmx_step_bdf1", "rmx_step_bdf2", "rmx_step_history", "rmx_step_euler", "rmx_adjoint_bdf1", "rmx_adjoint_bdf2", "rmx_adjoint_bdf1_device", "rmx_adjoint_bdf2_device", "rmx_adjoint_controls", "rmx_adjoint_controls_device", "rmx_adjoint_track", "rmx_adjoint_track_device", "rmx_energy",
     "rmx_rollout_tape", "rmx_rollout_vjp", "rmx_rollout_tape_device", "rmx_rollout_vjp_device",
+    "rmx_rollout_tape_bdf2", "rmx_rollout_tape_bdf2_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -141,6 +142,8 @@ def lib():
     L.rmx_adjoint_track_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.POINTER(TaskTrack), vp, vp, vp, vp, C.POINTER(Stats)]
     L.rmx_rollout_tape.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_double, _dp, _dp, _dp, C.POINTER(Stats)]
     L.rmx_rollout_tape_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_double, vp, vp, vp, C.POINTER(Stats)]
+    L.rmx_rollout_tape_bdf2.argtypes = L.rmx_rollout_tape.argtypes
+    L.rmx_rollout_tape_bdf2_device.argtypes = L.rmx_rollout_tape_device.argtypes
     L.rmx_rollout_vjp.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.rmx_rollout_vjp_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

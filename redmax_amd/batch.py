@@ -404,11 +404,21 @@ class BatchSim:
             st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
         return info, st
 
-    def rollout_tape(self, nsteps, h, u, pscale=1.0, stats=False, trajectory=True):
+    def _tape_entry(self, integrator, device):
+        """(function, name) of the rollout_tape entry of an integrator: 1 BDF1, 2 BDF2 (rmx_rollout_tape_bdf2)."""
+        if integrator not in (1, 2):
+            raise ValueError("rollout_tape: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+        name = ("rmx_rollout_tape" if integrator == 1 else "rmx_rollout_tape_bdf2") + ("_device" if device else "")
+        return getattr(self._L, name), name
+
+    def rollout_tape(self, nsteps, h, u, pscale=1.0, stats=False, trajectory=True, integrator=1):
         """rmx_rollout_tape: a controlled BDF1 rollout from the current state that records its trajectory and keeps H, M, D of every
         step (the tape rollout_vjp reads).  u: [B][nsteps][nr] (a [nsteps][nr] array holds for every trajectory); at step k the joint
         torque is tau + pscale*u[:, k-1].  Returns (qtraj[B][nsteps][nr], qdtraj[B][nsteps][nr], info), row k-1 the state after step
-        k; trajectory=False returns None for both."""
+        k; trajectory=False returns None for both.  integrator=2: rmx_rollout_tape_bdf2 - the BDF2 rollout, which always takes its
+        SDIRK2 start step from the current state (step 1; its torque holds for both stages) and leaves the BDF2 history in place;
+        rollout_vjp follows the integrator of the tape."""
+        fn, fname = self._tape_entry(integrator, False)
         nsteps = int(nsteps)
         if u is None:
             raise ValueError("rollout_tape: u is None")
@@ -424,20 +434,20 @@ class BatchSim:
         qdtraj = np.empty((self.B, nsteps, self.nr)) if trajectory else None
         info, st = self._tape_stats(stats)
         self.tape_count += 1
-        _abi.check(self._L.rmx_rollout_tape(self._batch, C.byref(opts), nsteps, float(pscale), _abi.dptr(u), _abi.dptr(qtraj),
-                                            _abi.dptr(qdtraj), C.byref(st) if st is not None else None), "rmx_rollout_tape")
+        _abi.check(fn(self._batch, C.byref(opts), nsteps, float(pscale), _abi.dptr(u), _abi.dptr(qtraj), _abi.dptr(qdtraj),
+                      C.byref(st) if st is not None else None), fname)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return qtraj, qdtraj, info
 
-    def rollout_tape_device(self, nsteps, h, u_ptr, qtraj_ptr, qdtraj_ptr, pscale=1.0, stats=False):
+    def rollout_tape_device(self, nsteps, h, u_ptr, qtraj_ptr, qdtraj_ptr, pscale=1.0, stats=False, integrator=1):
         """rollout_tape with DEVICE pointers (integers) for u, qtraj and qdtraj, all [B][nsteps][nr]; qtraj_ptr and qdtraj_ptr 0 /
         None together: no record.  Returns info."""
+        fn, fname = self._tape_entry(integrator, True)
         opts = self._tape_opts(h)
         info, st = self._tape_stats(stats)
         self.tape_count += 1
-        _abi.check(self._L.rmx_rollout_tape_device(self._batch, C.byref(opts), int(nsteps), float(pscale), C.c_void_p(u_ptr or None),
-                                                   C.c_void_p(qtraj_ptr or None), C.c_void_p(qdtraj_ptr or None),
-                                                   C.byref(st) if st is not None else None), "rmx_rollout_tape_device")
+        _abi.check(fn(self._batch, C.byref(opts), int(nsteps), float(pscale), C.c_void_p(u_ptr or None), C.c_void_p(qtraj_ptr or None),
+                      C.c_void_p(qdtraj_ptr or None), C.byref(st) if st is not None else None), fname)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 

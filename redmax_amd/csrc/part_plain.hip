@@ -33,17 +33,23 @@ static void adjoint_pair(const rmx_model* m, const rmx_batch* b, const DevOpts& 
     RMX_LAUNCH((k_adjoint_fwd<RMX_NP, MODE, false, FC>), grid, block, smem_bytes, b->stream, m->dm, o, a);
     if (!(MODE & ADJ_CTL) || a.dPdu) k_adjoint_bwd<RMX_NP, MODE, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
 }
-// rmx_rollout_tape / rmx_rollout_vjp: the two kernels of the TAPE instantiation, one per call (a.tape: 1 forward, 2 backward; BDF1)
+// rmx_rollout_tape / rmx_rollout_tape_bdf2 / rmx_rollout_vjp: the two kernels of the TAPE instantiation, one per call (a.tape: 1 forward,
+// 2 backward).  The BDF2 tape (nsteps + 1 slots per rollout) has a backward kernel of its own.
 template <bool FC>
-static void adjoint_tape(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
+static void adjoint_tape(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
     const dim3 grid(b->B), block(64);
-    if (a.tape == 1) RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE, false, FC>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
-    else k_adjoint_bwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    if (integ == INTEG_BDF1) {
+        if (a.tape == 1) RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE, false, FC>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        else k_adjoint_bwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    } else {
+        if (a.tape == 1) RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2 | ADJ_CTL | ADJ_TAPE, false, FC>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+        else k_rollout_bwd_bdf2<RMX_NP, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    }
 }
 template <bool FC>
 static void adjoint_pairs(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
     if (a.tape) {
-        adjoint_tape<FC>(m, b, o, a);
+        adjoint_tape<FC>(m, b, integ, o, a);
     } else if (integ == INTEG_BDF1) {
         if (a.trk) adjoint_pair<1 | ADJ_CTL | ADJ_TRK, FC>(m, b, o, a);
         else if (a.u) adjoint_pair<1 | ADJ_CTL, FC>(m, b, o, a);

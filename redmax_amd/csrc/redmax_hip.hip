@@ -1508,13 +1508,14 @@ extern "C" int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, i
 // rmx_rollout_tape / rmx_rollout_vjp (include/redmax_hip.h): the parts of the workspace.  H, M, D first, where every adjoint call has
 // them; behind them the staging areas of the host forms - three arrays shaped as u (u, qtraj, qdtraj of the tape; gq, gqd, du of the
 // vjp) and two of [B][nr] (dq0, dqd0).  The tape call reserves all of it, so that a vjp never regrows (and so loses) the tape.
+// A BDF2 tape has nsteps + 1 slots per rollout: the last one holds the SDIRK2a solve.
 struct TapeParts {
     size_t off[8], bytes_traj, bytes_state, total;
 };
-static TapeParts tape_parts(const rmx_batch* b, const int nsteps) {
+static TapeParts tape_parts(const rmx_batch* b, const int nsteps, const int integ) {
     const rmx_model* m = b->m;
     TapeParts t{};
-    const size_t hist = (size_t)b->B * nsteps * m->n * m->n * sizeof(double);
+    const size_t hist = (size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * m->n * sizeof(double);
     t.bytes_traj = (size_t)b->B * nsteps * m->nr * sizeof(double);
     t.bytes_state = (size_t)b->B * m->nr * sizeof(double);
     const size_t sizes[8] = {hist, hist, hist, t.bytes_traj, t.bytes_traj, t.bytes_traj, t.bytes_state, t.bytes_state};
@@ -1524,18 +1525,19 @@ static TapeParts tape_parts(const rmx_batch* b, const int nsteps) {
     }
     return t;
 }
-static void launch_adjoint_plan(rmx_batch* b, const DevOpts& o, const AdjArgs& a) {
+static rmx_select::AdjPlan launch_adjoint_plan(rmx_batch* b, const int integ, const DevOpts& o, const AdjArgs& a) {
     rmx_model* m = b->m;
-    const rmx_select::AdjPlan plan = rmx_select::select_adjoint(step_traits(m), b->B, rmx_select::knobs_from_env());
+    const rmx_select::AdjPlan plan = rmx_select::select_rollout_tape(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
     switch (plan.kernel) {
-        case AdjKernel::Help16: launch_adjoint_help_16(m, b, INTEG_BDF1, o, a, plan.fullchain); break;
-        case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, INTEG_BDF1, o, a); break;
-        case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, INTEG_BDF1, o, a); break;
+        case AdjKernel::Help16: launch_adjoint_help_16(m, b, INTEG_BDF1, o, a, plan.fullchain); break;      // (BDF1 only: select_rollout_tape)
+        case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, integ, o, a); break;
+        case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, integ, o, a); break;
     }
+    return plan;
 }
 
 static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
-                             double* qdtraj, rmx_stats* stats, const bool on_device) {
+                             double* qdtraj, rmx_stats* stats, const bool on_device, const int integ = INTEG_BDF1) {
     if (!b || !u) return fail(RMX_E_INVALID, "rmx_rollout_tape: null argument");
     if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
     rmx_model* m = b->m;
@@ -1547,9 +1549,9 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
     if (rc) return rc;
     rc = pending_error_check(b, "rmx_rollout_tape");
     if (rc) return rc;
-    if ((size_t)b->B * nsteps * m->n * m->n * sizeof(double) * 3 > ((size_t)200 << 30))
+    if ((size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * m->n * sizeof(double) * 3 > ((size_t)200 << 30))
         return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
-    const TapeParts t = tape_parts(b, nsteps);
+    const TapeParts t = tape_parts(b, nsteps, integ);
     b->tape_nsteps = 0;
     hipError_t e = adjws_reserve(b, t.total);
     if (e == hipSuccess) {
@@ -1568,11 +1570,13 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         }
         if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
         if (e == hipSuccess) {
-            launch_adjoint_plan(b, o, a);
+            const rmx_select::AdjPlan plan = launch_adjoint_plan(b, integ, o, a);
+            if (integ == INTEG_BDF2) b->last_kernel = rmx_select::label_rollout_tape_bdf2(plan);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
-        if (e == hipSuccess) e = set_started(b, 0);      // (a BDF1 rollout: rmx_step_bdf2 takes its start step again)
+        // a BDF1 rollout: rmx_step_bdf2 takes its start step again; after a BDF2 rollout (q, qdot) of step k-1 are in place
+        if (e == hipSuccess) e = set_started(b, integ == INTEG_BDF2 ? 1 : 0);
         if (e == hipSuccess && !on_device && qtraj) {
             e = hipMemcpyAsync(qtraj, a.qtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(qdtraj, a.qdtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
@@ -1586,6 +1590,7 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         if (e == hipSuccess) {
             take_event_time(b);
             b->tape_nsteps = nsteps;
+            b->tape_integ = integ;
             b->tape_h = o.h;
             b->tape_pscale = pscale;
         }
@@ -1606,7 +1611,7 @@ static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const do
     HIPCHK(hipSetDevice(m->device));
     int rc = pending_error_check(b, "rmx_rollout_vjp");
     if (rc) return rc;
-    const TapeParts t = tape_parts(b, nsteps);
+    const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
     if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp: no tape (the workspace is smaller than the tape)");
     char* ws = (char*)b->adjws;
     DevOpts o{};
@@ -1629,7 +1634,7 @@ static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const do
     }
     if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
     if (e == hipSuccess) {
-        launch_adjoint_plan(b, o, a);
+        launch_adjoint_plan(b, b->tape_integ, o, a);      // (the backward sweep of the integrator that recorded the tape)
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
@@ -1652,6 +1657,14 @@ extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, 
 extern "C" int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u, double* d_qtraj,
                                        double* d_qdtraj, rmx_stats* stats) {
     return rollout_tape_impl(b, opts, nsteps, pscale, d_u, d_qtraj, d_qdtraj, stats, true);
+}
+extern "C" int rmx_rollout_tape_bdf2(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
+                                     double* qdtraj, rmx_stats* stats) {
+    return rollout_tape_impl(b, opts, nsteps, pscale, u, qtraj, qdtraj, stats, false, INTEG_BDF2);
+}
+extern "C" int rmx_rollout_tape_bdf2_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u, double* d_qtraj,
+                                            double* d_qdtraj, rmx_stats* stats) {
+    return rollout_tape_impl(b, opts, nsteps, pscale, d_u, d_qtraj, d_qdtraj, stats, true, INTEG_BDF2);
 }
 extern "C" int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0) {
     return rollout_vjp_impl(b, nsteps, gq, gqd, du, dq0, dqd0, false);

@@ -125,6 +125,7 @@ struct rmx_batch {
     void* adjws = nullptr;          // rmx_adjoint_*: H, M, D of every step and rollout, dP/dq, P, dP/dp - one allocation that is kept
     size_t adjws_bytes = 0;         // between calls and only ever grows (hipMalloc + hipFree of 3 x 20 MB cost more than the kernels)
     int tape_nsteps = 0;            // rmx_rollout_tape: steps of the tape H, M, D in adjws hold (0: none - every rmx_adjoint_* call rewrites them)
+    int tape_integ = 0;             // ... the integrator that recorded it (INTEG_BDF2: nsteps + 1 slots per rollout, rmx_rollout_tape_bdf2)
     double tape_h = 0.0, tape_pscale = 0.0;   // ... and the step size and torque scale it was recorded with
     double last_ms = 0.0;
     const char* last_kernel = "";   // label of the step kernel the last step call launched (rmx_last_step_kernel; StepPlan::label)

@@ -815,13 +815,16 @@ constexpr int ADJ_CTL = 4;
 // s-1 of a.dPdq ([B][nsteps][n] here) is their sum, which the backward kernel reads where the step owns terms.  J is formed once per
 // measured step from the kept iterate, not at every Newton iterate.  Compile-time like CTL: the other instantiations keep their code.
 constexpr int ADJ_TRK = 8;
-// TAPE (rmx_rollout_tape / rmx_rollout_vjp, with CTL, BDF1 only, never with TRK): no objective at all.  The forward kernel is the CTL
+// TAPE (rmx_rollout_tape / rmx_rollout_vjp, with CTL, never with TRK): no objective at all.  The forward kernel is the CTL
 // sweep with a.task_step = 0 - no step is the task step, so no J is formed, no final-state front runs, no dPdq is written - without
 // the regulariser and P, and records q, qdot of every step (a.qtraj / a.qdtraj).  The task branches stay COMPILED in it: the sweep has
 // to be rmx_adjoint_controls' bit for bit, and with them compiled out the compiler contracts a few products of the front differently
 // (1 ulp in q on the 7-joint tree and the 32-link chain, measured; either branch alone restores the bits);
 // the backward kernel takes y_k from the caller's cotangents (a.gq / a.gqd), stores du per step and forms the k = 0 row (dL/dq0,
 // dL/dqdot0) behind the loop.  The two kernels are launched by different calls (a.tape).  Compile-time like CTL and TRK.
+// Under BDF2 (rmx_rollout_tape_bdf2) the tape has nsteps + 1 slots per rollout: step s in slot s-1 as everywhere, and H, M, D of the
+// SDIRK2a solve - which the adjoint pairs drop, with the reference - in slot nsteps; its backward sweep is a kernel of its own
+// (k_rollout_bwd_bdf2) that differentiates every solve exactly.  One wavefront per rollout, never the helper-wave form.
 constexpr int ADJ_TAPE = 16;
 constexpr int ADJ_TRK_ROWS = 18;      // sw[3], sv[3], Rw[9], pw[3], one column per node
 __host__ __device__ constexpr size_t adj_trk_doubles(const int NP) { return (size_t)ADJ_TRK_ROWS * NP; }
@@ -833,7 +836,9 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     constexpr bool TAPE = (MODE & ADJ_TAPE) != 0;
     static_assert(INTEG == 1 || INTEG == 2, "BDF1 or BDF2");
     static_assert(!TRK || CTL, "the tracking objective comes with per-step controls");
-    static_assert(!TAPE || (CTL && !TRK && INTEG == 1), "the taped rollout: per-step controls, no objective, BDF1");
+    static_assert(!TAPE || (CTL && !TRK), "the taped rollout: per-step controls, no objective");
+    constexpr bool TAPE2 = TAPE && INTEG == 2;       // the BDF2 tape: H, M, D of the SDIRK2a solve too, in a slot of its own
+    static_assert(!TAPE2 || !HELP, "the BDF2 tape runs one wavefront per rollout (two hand-overs in step 1 only: see select_rollout_tape)");
     static_assert(!HELP || NP <= 16, "the helper-wave form: trees of one DPP row");
     const DevModel M = model_view<NP, FC>(Min);
     double *sAcc, *sCol;
@@ -905,7 +910,15 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
                 qB = (4.0 / 3.0) * q1 - (1.0 / 3.0) * q0 + (8.0 / 9.0) * h * qd1 - (2.0 / 9.0) * h * qd0;
             }
             xlo = 0.0;
-            const bool last_solve = sv + 1 == nsolve;    // the SDIRK2a solve leaves nothing in the history
+            if constexpr (TAPE2) {      // nsteps + 1 slots per rollout: step s in slot s-1, the SDIRK2a solve in slot nsteps
+                const size_t slot = (size_t)traj * (a.nsteps + 1) + ((s == 1 && sv == 0) ? a.nsteps : s - 1);
+                Hk = a.Hs + slot * nn;
+                Mk = a.Ms + slot * nn;
+                Dk = a.Ds + slot * nn;
+            }
+            // the SDIRK2a solve leaves nothing in the history - but on the BDF2 tape, where it has a slot of its own: there every use
+            // below is a store to the slot (no step is the task step, no terms, no helper wave)
+            const bool last_solve = TAPE2 || sv + 1 == nsolve;
             int iter = 1;
             // Scene.saveHistory keeps H, M, D of the LAST evaluated iterate of the step (driverRedMaxAdjointBDF1.m:100, 127).  Up to 32
             // nodes H rides in registers through the Newton loop (the solve destroys its working copy) and M, D are formed ONCE, after
@@ -1298,6 +1311,140 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
         const size_t off = (size_t)traj * M.nr + id;                 // EVERY step (TaskBDF2PointPos.m:97-106)
         const double e2 = INTEG == 1 ? h * h : (4.0 / 9.0) * h * h;
         a.dPdp[off] = a.wreg * a.p[off] + e2 * a.pscale * zs;
+    }
+}
+
+// The backward sweep of the BDF2 tape (rmx_rollout_tape_bdf2 / rmx_rollout_vjp; the recursion is in include/redmax_hip.h).  Every solve
+// of the BDF2 loop is x(qA, qB, u): g = M(x)(x - qB) - eta^2 (f(x, (x - qA)/eta) + pscale u) = 0 with v = (x - qA)/eta, and with H,
+// M, D of the tape dg/dqB = -M, dg/dqA = eta D, dg/du = -eta^2 pscale.  Cotangents (xbar, vbar) on (x, v) go back through
+//     H' z = xbar + vbar/eta,   qAbar = -vbar/eta - eta D' z,   qBbar = M' z,   ubar = eta^2 pscale z.
+
+// (M' z, D' z) of one slot, from one pass over column `col` of M and of D (this lane's entries).  The load discipline of adj_block:
+// every load before the first use, none under a lane condition, index and column clamped into the block, the padding selected afterwards.
+template <int NP>
+__device__ __forceinline__ void adj_block_md(double& mz, double& dz, const double* __restrict__ Mj, const double* __restrict__ Dj, const int n,
+                                             const int lane, const int col, const double z) {
+    const double* Mc = Mj + (size_t)col * n;
+    const double* Dc = Dj + (size_t)col * n;
+    double mc[NP], dc[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) mc[j] = Mc[j < n ? j : 0];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) dc[j] = Dc[j < n ? j : 0];
+    __builtin_amdgcn_sched_barrier(0);
+    mz = 0.0;
+    dz = 0.0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const bool in = j < n && lane < n;
+        const double zj = readlane_d(z, j);
+        mz += (in ? mc[j] : 0.0) * zj;
+        dz += (in ? dc[j] : 0.0) * zj;
+    }
+}
+
+// one taped solve backwards: z, and the cotangents A of qA and Bq of qB.  Lanes without a DOF carry zeros.
+template <int NP>
+__device__ __forceinline__ void tape_solve_bwd(const double* __restrict__ Hj, const double* __restrict__ Mj, const double* __restrict__ Dj, const int n,
+                                               const int lane, const int col, const bool dof, const double eta, const double xbar,
+                                               const double vbar, double& A, double& Bq, double& z) {
+    const double y = dof ? xbar + vbar / eta : 0.0;
+    // z = H'^-1 y: this lane's "row" of H' is column `lane` of H (as k_adjoint_bwd: unconditional loads, all in flight together)
+    double Hrow[NP];
+    const double* Hc = Hj + (size_t)col * n;
+    {
+        double hv[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) hv[i] = Hc[i < n ? i : 0];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) Hrow[i] = (i < n && lane < n) ? hv[i] : ((i == lane) ? 1.0 : 0.0);
+    }
+    // Up to 16 nodes: diagonal pivots under the growth guard first, partial pivoting on a fresh copy when it trips (k_adjoint_bwd's
+    // policy).  At 16 lanes that solve is lu_diag_tail from its first pivot on: its DPP broadcasts read Hrow[] and the right-hand side
+    // straight away, so both are materialised and two wait states pass first (dpp_settle; the hazard note at fmsub_rowbcast).
+    // From 17 nodes on the pivoted solve, which has no DPP sequence: at 32 lanes the guarded solve gave wrong results in the two
+    // start-step solves of this kernel - zero cotangents came back as a non-zero du_1 on an MI355X, the loop's solve being right -,
+    // which fits a broadcast that reads a register too soon after its write; the offending pair was not isolated.
+    if constexpr (NP <= 16) {
+        double yv = y;
+        if constexpr (NP == 16) {
+            asm volatile("" : "+v"(yv));
+            dpp_settle(Hrow);
+        }
+        const double hdl = Hc[col];
+        const double hd = lane < n ? hdl : 1.0;
+        bool lu_ok;
+        z = lu_solve_neg_diag<NP>(lane, Hrow, -yv, hd, lu_ok);
+        if (!lu_ok) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i) Hrow[i] = (i < n && lane < n) ? Hc[i] : ((i == lane) ? 1.0 : 0.0);
+            z = lu_solve_neg<NP, true>(n, lane, Hrow, -y);
+        }
+    } else {
+        z = lu_solve_neg<NP, true>(n, lane, Hrow, -y);
+    }
+    double mz, dz;
+    adj_block_md<NP>(mz, dz, Mj, Dj, n, lane, col, z);
+    A = dof ? -vbar / eta - eta * dz : 0.0;
+    Bq = dof ? mz : 0.0;
+}
+
+// One wavefront per rollout, lane = node.  qbar, vbar of steps k+1 (complete) and k (still collecting) ride in registers; the solve that
+// produced step k+1 (slot k; eta = 2h/3, qA = 4/3 q_k - 1/3 q_{k-1}, qB = qA + 8/9 h qd_k - 2/9 h qd_{k-1}) feeds steps k and k-1.  H, M,
+// D are read once each per step.  The SDIRK2 start step runs behind the loop: stage b (slot 0) reads q0, qd0 and qda, stage a (slot
+// nsteps) is read through qda alone; step 1's torque holds for both.
+template <int NP, bool FC = false>
+__global__ void __launch_bounds__(64) k_rollout_bwd_bdf2(const DevModel Min, const DevOpts o, const AdjArgs a) {
+    const DevModel M = model_view<NP, FC>(Min);
+    const int lane = threadIdx.x, traj = blockIdx.x, n = M.n, N = a.nsteps;
+    const int id = (lane < n) ? M.idx[lane] : -1;
+    const bool dof = id >= 0;
+    const size_t nn = (size_t)n * n;
+    const double h = o.h;
+    const int col = lane < n ? lane : 0;
+    const double al = (2.0 - sqrt(2.0)) / 2.0;
+    const double* Hb = a.Hs + (size_t)traj * (N + 1) * nn;
+    const double* Mb = a.Ms + (size_t)traj * (N + 1) * nn;
+    const double* Db = a.Ds + (size_t)traj * (N + 1) * nn;
+    const size_t row0 = (size_t)traj * N * M.nr + (dof ? id : 0);      // this lane's entry of row 0 (step 1) of gq, gqd, du
+    // (the cotangent loads unconditional, the row clamped, lanes without a DOF and rows that do not exist selected to zero afterwards)
+    const double gqN = a.gq[row0 + (size_t)(N - 1) * M.nr], gdN = a.gqd[row0 + (size_t)(N - 1) * M.nr];
+    const double gqP = a.gq[row0 + (size_t)(N >= 2 ? N - 2 : 0) * M.nr], gdP = a.gqd[row0 + (size_t)(N >= 2 ? N - 2 : 0) * M.nr];
+    double qb1 = dof ? gqN : 0.0, vb1 = dof ? gdN : 0.0;                        // step k+1
+    double qb0 = (dof && N >= 2) ? gqP : 0.0, vb0 = (dof && N >= 2) ? gdP : 0.0;      // step k (step 0 has no cotangent of its own)
+    const double eta = (2.0 / 3.0) * h;
+    for (int k = N - 1; k >= 1; --k) {
+        const size_t rowm = row0 + (size_t)(k >= 2 ? k - 2 : 0) * M.nr;          // step k-1, in flight across the solve
+        const double gqm = a.gq[rowm], gdm = a.gqd[rowm];
+        double A, Bq, z;
+        tape_solve_bwd<NP>(Hb + (size_t)k * nn, Mb + (size_t)k * nn, Db + (size_t)k * nn, n, lane, col, dof, eta, qb1, vb1, A, Bq, z);
+        if (dof) a.dPdu[row0 + (size_t)k * M.nr] = eta * eta * a.pscale * z;
+        const double s = A + Bq;
+        qb0 += (4.0 / 3.0) * s;
+        vb0 += (8.0 / 9.0) * h * Bq;
+        qb1 = qb0;
+        vb1 = vb0;
+        qb0 = ((dof && k >= 2) ? gqm : 0.0) - (1.0 / 3.0) * s;
+        vb0 = ((dof && k >= 2) ? gdm : 0.0) - (2.0 / 9.0) * h * Bq;
+    }
+    // the start step: qb1, vb1 are the cotangents of step 1, qb0, vb0 of the initial state
+    const double etas = al * h;
+    double A, Bq, zb, A2, B2, za;
+    tape_solve_bwd<NP>(Hb, Mb, Db, n, lane, col, dof, etas, qb1, vb1, A, Bq, zb);                   // SDIRK2b
+    qb0 += A + Bq;
+    vb0 += (2.0 * al - 1.0) * h * Bq;
+    const double qdab = (1.0 - al) * h * A + 2.0 * (1.0 - al) * h * Bq;
+    tape_solve_bwd<NP>(Hb + (size_t)N * nn, Mb + (size_t)N * nn, Db + (size_t)N * nn, n, lane, col, dof, etas, 0.0, qdab, A2, B2, za);      // SDIRK2a
+    qb0 += A2 + B2;
+    vb0 += al * h * B2;
+    if (dof) {
+        a.dPdu[row0] = etas * etas * a.pscale * (za + zb);
+        if (a.dq0) {
+            const size_t off = (size_t)traj * M.nr + id;
+            a.dq0[off] = qb0;
+            a.dqd0[off] = vb0;
+        }
     }
 }
 

@@ -154,4 +154,16 @@ inline AdjPlan select_adjoint(const StepTraits& t, const int B, const StepKnobs&
     return p;
 }
 
+// The taped rollout (rmx_rollout_tape / rmx_rollout_tape_bdf2 and the rmx_rollout_vjp that follows): BDF1 runs what the adjoint pair
+// runs.  The BDF2 tape also keeps H, M, D of the SDIRK2a solve; a second hand-over in step 1 only would make the barrier counts of the
+// two wavefronts depend on the step, for a saving in one solve of the rollout, so it never takes the helper-wave form.
+inline AdjPlan select_rollout_tape(const StepTraits& t, const int B, const int integ, const StepKnobs& k) {
+    AdjPlan p = select_adjoint(t, B, k);
+    if (integ == BDF2 && p.kernel == AdjKernel::Help16) p.kernel = p.fullchain ? AdjKernel::FullChain16 : AdjKernel::Generic;
+    return p;
+}
+inline const char* label_rollout_tape_bdf2(const AdjPlan& p) {      // what rmx_last_step_kernel reports after rmx_rollout_tape_bdf2
+    return p.kernel == AdjKernel::FullChain16 ? "k_adjoint_fwd<16,bdf2,tape,fullchain>" : "k_adjoint_fwd<bdf2,tape>";
+}
+
 }      // namespace rmx_select

@@ -1,7 +1,7 @@
-"""A differentiable controlled BDF1 rollout for PyTorch: ``rollout(sim, q0, qdot0, u)`` returns the trajectory, and
+"""A differentiable controlled BDF1 or BDF2 rollout for PyTorch: ``rollout(sim, q0, qdot0, u)`` returns the trajectory, and
 ``backward()`` of any loss on it yields dL/du, dL/dq0 and dL/dqdot0.
 
-Forward is rmx_rollout_tape_device, backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
+Forward is rmx_rollout_tape_device (rmx_rollout_tape_bdf2_device under integrator=2), backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
 objective lives wholly on the PyTorch side.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
 """
 from __future__ import annotations
@@ -20,7 +20,7 @@ def _function():
 
     class _Rollout(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, q0, qdot0, u, sim, h, pscale, check):
+        def forward(ctx, q0, qdot0, u, sim, h, pscale, check, integrator):
             B, nsteps, nr = u.shape
             q0c, qd0c, uc = q0.contiguous(), qdot0.contiguous(), u.contiguous()
             qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
@@ -29,7 +29,8 @@ def _function():
             # inputs must be done before it starts
             torch.cuda.current_stream(u.device).synchronize()
             sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
-            info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=pscale, stats=check)
+            info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=pscale, stats=check,
+                                           integrator=integrator)
             ctx.sim, ctx.nsteps, ctx.tape = sim, nsteps, sim.tape_count
             if check and (info["status"] & _BAD_STATUS).any():
                 bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
@@ -50,21 +51,26 @@ def _function():
             dqd0 = torch.empty_like(dq0)
             torch.cuda.current_stream(dev).synchronize()
             sim.rollout_vjp_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr())
-            return dq0, dqd0, du, None, None, None, None
+            return dq0, dqd0, du, None, None, None, None, None
 
     _Function = _Rollout
     return _Function
 
 
-def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True):
-    """A controlled BDF1 rollout of every trajectory of ``sim`` (a BatchSim) that autograd can differentiate.
+def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
+    """A controlled BDF1 (integrator=1) or BDF2 (integrator=2) rollout of every trajectory of ``sim`` (a BatchSim) that autograd can differentiate.
 
     q0, qdot0: [B][nr]; u: [B][nsteps][nr], one torque per joint and step (tau + pscale*u at step k) - float64 tensors on the sim's
     device.  h: step size (None: sim.opts.h).  Returns (qtraj, qdtraj), both [B][nsteps][nr]: row k-1 is the state after step k.
     The sim is left at the end of the rollout.  check=True raises RuntimeError when a rollout's Newton solve diverged, hit its
     iteration limit or met a NaN.  backward() must run before the next rollout or adjoint_* call on the same sim: both replace
-    the tape, and backward raises RuntimeError("the tape of this rollout has been replaced") then."""
+    the tape, and backward raises RuntimeError("the tape of this rollout has been replaced") then.
+    Under integrator=2 the rollout starts itself with SDIRK2 from (q0, qdot0): row 0 is the state after the two-stage start step
+    (u[:, 0] holds for both stages), row k-1 for k >= 2 the state after the BDF2 step from steps k-1 and k-2; the gradients are
+    exact through the start step too.  Any other integrator raises ValueError."""
     import torch
+    if integrator not in (1, 2):
+        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
     dev = torch.device("cuda", sim.device)
     for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
         if not isinstance(t, torch.Tensor):
@@ -78,4 +84,4 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True):
     for name, t in (("q0", q0), ("qdot0", qdot0)):
         if tuple(t.shape) != (sim.B, sim.nr):
             raise ValueError("rollout: %s must have shape (%d, %d), got %r" % (name, sim.B, sim.nr, tuple(t.shape)))
-    return _function().apply(q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check))
+    return _function().apply(q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check), integrator)

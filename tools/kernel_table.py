@@ -25,6 +25,10 @@ ROWS = (  # (name fragment, what it runs)
     ("k_adjoint_bwd<16, 21, true>", "rmx_rollout_vjp (cotangents in, du, dq0, dqd0 out): full 16-link chain"),
     ("k_adjoint_fwd<64, 21, false, false>", "rmx_rollout_tape: 33..64 nodes"),
     ("k_adjoint_bwd<32, 21, false>", "rmx_rollout_vjp: 17..32 nodes"),
+    ("k_adjoint_fwd<16, 22, false, true>", "rmx_rollout_tape_bdf2 (taped forward sweep, BDF2, SDIRK2a stage on the tape): full 16-link chain"),
+    ("k_rollout_bwd_bdf2<16, true>", "rmx_rollout_vjp on a BDF2 tape: full 16-link chain"),
+    ("k_adjoint_fwd<64, 22, false, false>", "rmx_rollout_tape_bdf2: 33..64 nodes"),
+    ("k_rollout_bwd_bdf2<64, false>", "rmx_rollout_vjp on a BDF2 tape: 33..64 nodes"),
     ("k_step_bdf1<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF1"),
     ("k_step_bdf2<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF2"),
     ("k_big_step", "trees of 65..256 nodes (one workgroup per rollout)"),

@@ -7,8 +7,11 @@ in one process, device pointers throughout, the two alternating; one rehearsal r
 the host wall clock (the calls return when their kernels have finished) and the kernel time by the library's HIP events
 (rmx_last_step_ms).  (a) is untouched by the work that added (b), so it stands for the parent commit.
 Writes profiles/rollout_vjp_bench.json.
+--integrator 2: the same under BDF2 (rmx_rollout_tape_bdf2_device: the SDIRK2a stage on the tape, one wavefront per rollout).
+--integrator 1 2: BDF1 with its helper wave, BDF1 without (RMX_ADJ_HELP=0, what the BDF2 tape always runs) and BDF2 alternate in
+one process, and the ratios BDF2 / BDF1 are formed; writes profiles/rollout_vjp_bench_bdf2.json.
 
-    python tools/rollout_vjp_bench.py [--reps 20]"""
+    python tools/rollout_vjp_bench.py [--reps 20] [--integrator 1 2]"""
 import argparse
 import ctypes as C
 import json
@@ -44,51 +47,99 @@ class Dev:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rollout_vjp_bench.json"))
+    ap.add_argument("--integrator", type=int, nargs="+", choices=(1, 2), default=[1],
+                    help="1 BDF1, 2 BDF2; both: they alternate in one process and the ratios BDF2 / BDF1 are formed")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    integs = sorted(set(args.integrator))
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "rollout_vjp_bench.json" if integs == [1] else "rollout_vjp_bench_bdf2.json")
     sys.path.insert(0, ROOT)
     from redmax_amd import BatchSim
     from redmax_amd.scenes import sceneAdjointChain
-    sc = sceneAdjointChain(N)
-    sc.init()
+    # the variants that alternate: (name, integrator, RMX_ADJ_HELP).  With both integrators BDF1 also runs without its helper wave
+    # (the knob is read at every call): the BDF2 tape never has one, so that is the like-for-like pair
+    # (helper None: RMX_ADJ_HELP is left as the caller set it - the single-integrator runs, and BDF2, which the knob does not reach)
+    variants = [("bdf%d" % i, i, None) for i in integs]
+    if integs == [1, 2]:
+        variants = [("bdf1", 1, "1"), ("bdf1_one_wave", 1, "0"), ("bdf2", 2, None)]
+    caller_help = os.environ.get("RMX_ADJ_HELP")
     rng = np.random.default_rng(20240)
-    u = 0.1 * rng.standard_normal((B, K, sc.nr))
-    task = dict(sc.task, step=K)
-    q0, qd0 = sc.getQ()
-    q0d, qd0d = Dev(np.repeat(q0[None], B, axis=0)), Dev(np.repeat(qd0[None], B, axis=0))
+    scenes = {}
+    for i in integs:
+        scenes[i] = sceneAdjointChain(N, bdf2=i == 2)
+        scenes[i].init()
+    nr = scenes[integs[0]].nr
+    u = 0.1 * rng.standard_normal((B, K, nr))
     ud, Pd, dPdud = Dev(u), Dev(np.zeros(B)), Dev(np.zeros_like(u))
     qt, qdt, dud = Dev(np.zeros_like(u)), Dev(np.zeros_like(u)), Dev(np.zeros_like(u))
     gq, gqd = Dev(rng.standard_normal(u.shape)), Dev(rng.standard_normal(u.shape))
-    dq0, dqd0 = Dev(np.zeros((B, sc.nr))), Dev(np.zeros((B, sc.nr)))
-    sim = BatchSim(sc, batch=B)
-    rows = {"adjoint_controls": [], "rollout_tape": [], "rollout_vjp": []}
+    dq0, dqd0 = Dev(np.zeros((B, nr))), Dev(np.zeros((B, nr)))
+    sims, starts, rows, checks = {}, {}, {}, {}
+    for name, i, _ in variants:
+        sc = scenes[i]
+        if i not in sims:
+            q0, qd0 = sc.getQ()
+            sims[i] = BatchSim(sc, batch=B)
+            starts[i] = (Dev(np.repeat(q0[None], B, axis=0)), Dev(np.repeat(qd0[None], B, axis=0)))
+        rows[name] = {"adjoint_controls": [], "rollout_tape": [], "rollout_vjp": []}
 
-    def timed(name, fn):
+    def timed(name, call, sim, fn):
         t0 = time.perf_counter()
         fn()
         wall = (time.perf_counter() - t0) * 1e3
-        rows[name].append((wall, sim._L.rmx_last_step_ms(sim._batch)))
+        rows[name][call].append((wall, sim._L.rmx_last_step_ms(sim._batch)))
 
     for rep in range(1 + args.reps):                   # (round 0: the rehearsal)
-        sim.set_state_device(q0d.ptr, qd0d.ptr)
-        timed("adjoint_controls", lambda: sim.adjoint_controls_device(K, sc.h, task, ud.ptr, Pd.ptr, dPdud.ptr))
-        qa = sim.get_state()[0]
-        sim.set_state_device(q0d.ptr, qd0d.ptr)
-        timed("rollout_tape", lambda: sim.rollout_tape_device(K, sc.h, ud.ptr, qt.ptr, qdt.ptr, pscale=task["pscale"]))
-        timed("rollout_vjp", lambda: sim.rollout_vjp_device(K, gq.ptr, gqd.ptr, dud.ptr, dq0.ptr, dqd0.ptr))
-        qb = sim.get_state()[0]
-    same = bool(np.array_equal(qa, qb) and np.array_equal(qt.get()[:, -1], qb))
-    finite = bool(np.isfinite(dud.get()).all() and np.isfinite(dq0.get()).all() and np.isfinite(dqd0.get()).all())
-    sim.close()
-    med = {k: {"wall_ms": float(np.median([r[0] for r in v[1:]])), "kernel_ms": float(np.median([r[1] for r in v[1:]])),
-               "wall_min_ms": float(min(r[0] for r in v[1:])), "wall_max_ms": float(max(r[0] for r in v[1:]))} for k, v in rows.items()}
-    pair = {k: med["rollout_tape"][k] + med["rollout_vjp"][k] for k in ("wall_ms", "kernel_ms")}
-    out = {"workload": "configs[3]: %d-link chain, %d rollouts, %d steps, BDF1; device pointers; median of %d rounds after one rehearsal"
-                       % (N, B, K, args.reps),
-           "adjoint_controls_device": med["adjoint_controls"], "rollout_tape_device": med["rollout_tape"],
-           "rollout_vjp_device": med["rollout_vjp"], "tape_plus_vjp": pair,
-           "tape_plus_vjp_over_adjoint_controls": {k: pair[k] / med["adjoint_controls"][k] for k in pair},
-           "same_final_state": same, "gradients_finite": finite}
+        for name, i, helper in variants:
+            if helper is not None:
+                os.environ["RMX_ADJ_HELP"] = helper
+            elif caller_help is None:
+                os.environ.pop("RMX_ADJ_HELP", None)
+            else:
+                os.environ["RMX_ADJ_HELP"] = caller_help
+            sim, sc, (q0d, qd0d) = sims[i], scenes[i], starts[i]
+            task = dict(sc.task, step=K)
+            sim.set_state_device(q0d.ptr, qd0d.ptr)
+            timed(name, "adjoint_controls", sim, lambda: sim.adjoint_controls_device(K, sc.h, task, ud.ptr, Pd.ptr, dPdud.ptr, integrator=i))
+            qa = sim.get_state()[0]
+            sim.set_state_device(q0d.ptr, qd0d.ptr)
+            timed(name, "rollout_tape", sim,
+                  lambda: sim.rollout_tape_device(K, sc.h, ud.ptr, qt.ptr, qdt.ptr, pscale=task["pscale"], integrator=i))
+            timed(name, "rollout_vjp", sim, lambda: sim.rollout_vjp_device(K, gq.ptr, gqd.ptr, dud.ptr, dq0.ptr, dqd0.ptr))
+            qb = sim.get_state()[0]
+            checks[name] = {"same_final_state": bool(np.array_equal(qa, qb) and np.array_equal(qt.get()[:, -1], qb)),
+                            "final_state_rel_diff": float(np.linalg.norm(qa - qb) / np.linalg.norm(qa)),
+                            "gradients_finite": bool(np.isfinite(dud.get()).all() and np.isfinite(dq0.get()).all()
+                                                     and np.isfinite(dqd0.get()).all())}
+    if caller_help is None:
+        os.environ.pop("RMX_ADJ_HELP", None)
+    else:
+        os.environ["RMX_ADJ_HELP"] = caller_help
+    for sim in sims.values():
+        sim.close()
+
+    def summary(name, i, helper):
+        med = {k: {"wall_ms": float(np.median([r[0] for r in v[1:]])), "kernel_ms": float(np.median([r[1] for r in v[1:]])),
+                   "wall_min_ms": float(min(r[0] for r in v[1:])), "wall_max_ms": float(max(r[0] for r in v[1:]))}
+               for k, v in rows[name].items()}
+        pair = {k: med["rollout_tape"][k] + med["rollout_vjp"][k] for k in ("wall_ms", "kernel_ms")}
+        return dict({"integrator": i, "RMX_ADJ_HELP": None if helper is None else int(helper),
+                     "adjoint_controls_device": med["adjoint_controls"], "rollout_tape_device": med["rollout_tape"],
+                     "rollout_vjp_device": med["rollout_vjp"], "tape_plus_vjp": pair,
+                     "tape_plus_vjp_over_adjoint_controls": {k: pair[k] / med["adjoint_controls"][k] for k in pair}}, **checks[name])
+
+    res = {name: summary(name, i, helper) for name, i, helper in variants}
+    workload = ("configs[3]: %d-link chain, %d rollouts, %d steps, %s; device pointers; median of %d rounds after one rehearsal"
+                % (N, B, K, " / ".join("BDF%d" % i for i in integs), args.reps))
+    if len(variants) == 1:
+        out = dict({"workload": workload}, **{k: v for k, v in res[variants[0][0]].items() if k not in ("integrator", "RMX_ADJ_HELP", "final_state_rel_diff")})
+    else:
+        out = dict({"workload": workload + "; the variants alternate within every round"}, **res)
+        if integs == [1, 2]:
+            for base in ("bdf1", "bdf1_one_wave"):
+                out["bdf2_over_" + base] = {call: {k: res["bdf2"][call][k] / res[base][call][k] for k in ("wall_ms", "kernel_ms")}
+                                            for call in ("rollout_tape_device", "rollout_vjp_device", "tape_plus_vjp")}
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
