@@ -465,6 +465,40 @@ int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, doub
 int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd,
                            double* d_du, double* d_dq0, double* d_dqd0);
 
+/* The linearisation of the taped rollout: the forward sensitivities of every taped solve, from which a host assembles the per-step
+ * A_k = d(q_k, qdot_k)/d(q_{k-1}, qdot_{k-1}) and B_k = d(q_k, qdot_k)/du_k that iLQR / DDP, time-varying LQR, Gauss-Newton shooting
+ * and SQP-style MPC work with.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * Every taped solve is x(qA, qB, u): g = M(x)(x - qB) - eta^2 (f(x, (x - qA)/eta) + pscale u) = 0 with H = dg/dx, dg/dqA = eta D,
+ * dg/dqB = -M, dg/du = -eta^2 pscale I (the implicit function of rmx_rollout_tape_bdf2 above).  Its forward sensitivities are
+ *     XA = dx/dqA = -eta H^-1 D        XB = dx/dqB = H^-1 M        XU = dx/du = eta^2 pscale H^-1
+ * the forward-mode counterparts of solve_bwd: with w = xbar + vbar/eta,  A = -vbar/eta + XA' w,  Bq = XB' w,  ubar = XU' w.
+ * With v = (x - qA)/eta:  dv/dqA = (XA - I)/eta,  dv/dqB = XB/eta,  dv/du = XU/eta.
+ *
+ * rmx_rollout_linearize reads the tape of the preceding rmx_rollout_tape / rmx_rollout_tape_bdf2 on the same batch and follows the
+ * integrator of the tape it finds, as rmx_rollout_vjp does.  XA, XB, XU: host [batch][nslots][nr*nr], column-major in the last
+ * index (the convention of rmx_eval and rmx_eval_mfd): entry j*nr + i is dx_i/d(.)_j, reduced DOF order.  Any of them may be NULL -
+ * that output is neither computed nor stored - but not all three.  nslots = nsteps for a BDF1 tape, nsteps + 1 for a BDF2 tape: slot
+ * s-1 is step s (step 1 of a BDF2 tape is the SDIRK2b solve), slot nsteps the SDIRK2a solve.  eta per slot: h under BDF1; under BDF2
+ * al h for slot 0 and slot nsteps, al = (2 - sqrt 2)/2, and 2h/3 for the others.  h and pscale are the tape's.
+ *
+ * BDF1 (qA = q_{k-1}, qB = q_{k-1} + h qdot_{k-1}, eta = h, qdot_k = (q_k - q_{k-1})/h), state order (q, qdot), slot k-1:
+ *     A_k = [ XA + XB          h XB ]        B_k = [ XU   ]
+ *           [ (XA + XB - I)/h    XB ]              [ XU/h ]
+ * BDF2: with dqA, dqB the variations of a solve's qA, qB, its results vary as dx = XA dqA + XB dqB + XU du, dv = (dx - dqA)/eta, and
+ *     SDIRK2a (slot nsteps): dqA = dq0 ;  dqB = dq0 + al h dqd0                                              -> dqa, dqda
+ *     SDIRK2b (slot 0)     : dqA = dq0 + (1-al) h dqda ;  dqB = dq0 + (2al-1) h dqd0 + 2(1-al) h dqda        -> dq1, dqd1
+ *     BDF2    (slot k)     : dqA = 4/3 dq_k - 1/3 dq_{k-1} ;  dqB = dqA + 8/9 h dqd_k - 2/9 h dqd_{k-1}      -> dq_{k+1}, dqd_{k+1}
+ * (du = du_1 in both SDIRK2 solves), which gives the blocks of the augmented state (q_k, qdot_k, q_{k-1}, qdot_{k-1}).
+ *
+ * The call changes neither the batch's state nor the tape: it may be repeated, and rmx_rollout_vjp before and after it returns the
+ * same bits.  Refusals (RMX_E_INVALID), in rmx_rollout_vjp's words where they coincide: "no tape", an nsteps that differs from the
+ * tape's, a null batch, all outputs null.  The slots of a rollout whose tape call reported a failed Newton solve (stats->status) are
+ * unspecified.  The host form stages through a device allocation of its own, freed before it returns; the tape's workspace does not
+ * grow.  The _device form: DEVICE pointers, nothing staged; it returns when the kernel has finished. */
+int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU);
+int rmx_rollout_linearize_device(rmx_batch* b, int nsteps, double* d_XA, double* d_XB, double* d_XU);
+
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.
  * hist_T/hist_V as in rmx_step_bdf1. */

@@ -179,5 +179,21 @@ classdef HipSim < handle
 			% repeated with other cotangents; an adjoint* call or another rolloutTape ends the tape.
 			[du, dq0, dqd0] = redmax_hip_mex('rollout_vjp', this.h, nsteps, gq, gqd);
 		end
+
+		function [XA, XB, XU] = rolloutLinearize(this, nsteps)
+			% the linearisation of the last rolloutTape: the sensitivities XA = dx/dqA, XB = dx/dqB, XU = dx/du of every taped
+			% solve x(qA, qB, u), each nr x nr x nslots x B with (i,j,s,b) = dx_i/d(.)_j of slot s; nslots = nsteps, or
+			% nsteps + 1 after a BDF2 rolloutTape (the last slot is the SDIRK2a solve).  Under BDF1, with h the step size,
+			%   A_k = [XA+XB, h*XB; (XA+XB-I)/h, XB]   B_k = [XU; XU/h]   (state order (q, qdot); slices (:,:,k,b))
+			% Outputs that are not asked for are not computed.  The tape and the state stay as they are.
+			XA = []; XB = []; XU = [];
+			if nargout <= 1
+				XA = redmax_hip_mex('rollout_linearize', this.h, nsteps);
+			elseif nargout == 2
+				[XA, XB] = redmax_hip_mex('rollout_linearize', this.h, nsteps);
+			else
+				[XA, XB, XU] = redmax_hip_mex('rollout_linearize', this.h, nsteps);
+			end
+		end
 	end
 end

@@ -64,6 +64,10 @@
  *   [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)  rmx_rollout_vjp on the tape of the last 'rollout_tape': gq, gqd
  *                  (nr x nsteps x B) are dL/dq and dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du,
  *                  dL/dq0, dL/dqdot0.  May be repeated with other cotangents; any 'adjoint*' command ends the tape.
+ *   [XA,XB,XU] = redmax_hip_mex('rollout_linearize', h, nsteps)  rmx_rollout_linearize on the tape of the last 'rollout_tape': the
+ *                  sensitivities dx/dqA, dx/dqB, dx/du of every taped solve, nr x nr x nslots x B with (i,j,s,b) = dx_i/d(.)_j of slot s
+ *                  (nslots = nsteps, or nsteps + 1 after a BDF2 'rollout_tape': the last slot is the SDIRK2a solve).  Outputs that are
+ *                  not asked for are not computed.  include/redmax_hip.h has the assembly of A_k, B_k from them.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -81,6 +85,7 @@ typedef struct {
     int pending_nsteps;    /* 'step_async' in flight: its nsteps and record mask ('sync' shapes its outputs from them) */
     int pending_record;
     int pending;
+    int tape_integ;        /* the integrator of the last 'rollout_tape' (2: its tape has nsteps + 1 slots; 'rollout_linearize' shapes its outputs) */
 } handle_t;
 
 #define HANDLE_MAGIC 0x726d78686970ull /* "rmxhip" */
@@ -587,6 +592,7 @@ static void cmd_rollout_tape(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
                                                                     mxGetPr(qdt) + f * per, &st_s))
             die_rmx(integ == 2 ? "rmx_rollout_tape_bdf2" : "rmx_rollout_tape");
     }
+    h->tape_integ = integ;
     plhs[0] = qt;
     if (nlhs > 1) plhs[1] = qdt;
     else mxDestroyArray(qdt);
@@ -618,6 +624,27 @@ static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     else mxDestroyArray(dq0);
     if (nlhs > 2) plhs[2] = dqd0;
     else mxDestroyArray(dqd0);
+}
+
+static void cmd_rollout_linearize(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 3) die("usage: [XA,XB,XU] = redmax_hip_mex('rollout_linearize', h, nsteps)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_linearize: nsteps must be at least 1");
+    const size_t nslots = (size_t)nsteps + (h->tape_integ == 2 ? 1 : 0);
+    const size_t per = (size_t)h->nr * (size_t)h->nr * nslots;
+    const size_t dims[4] = {(size_t)h->nr, (size_t)h->nr, nslots, (size_t)h->B};
+    const int nout = nlhs < 1 ? 1 : (nlhs > 3 ? 3 : nlhs);      /* outputs nobody asked for are not computed */
+    mxArray* X[3] = {NULL, NULL, NULL};
+    for (int i = 0; i < nout; ++i) X[i] = mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        if (rmx_rollout_linearize(b, nsteps, mxGetPr(X[0]) + f * per, X[1] ? mxGetPr(X[1]) + f * per : NULL,
+                                  X[2] ? mxGetPr(X[2]) + f * per : NULL))
+            die_rmx("rmx_rollout_linearize");
+    }
+    for (int i = 0; i < nout; ++i) plhs[i] = X[i];
 }
 
 /* field k of element i of the struct array task.terms */
@@ -719,7 +746,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * may name the handle ('step' / 'step_async' refuse with their own text).  Everything below reads or writes the state, the
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
-                                             "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", NULL};
+                                             "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
+                                             NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -828,6 +856,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_tape(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp")) {
         cmd_rollout_vjp(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_linearize")) {
+        cmd_rollout_linearize(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

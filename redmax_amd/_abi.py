@@ -26,6 +26,7 @@ SYMBOLS = (
     "rmx_eval", "rmx_eval_mfd", "rmx_compute_values", "rmx_step_bdf1", "rmx_step_bdf2", "rmx_step_history", "rmx_step_euler", "rmx_adjoint_bdf1", "rmx_adjoint_bdf2", "rmx_adjoint_bdf1_device", "rmx_adjoint_bdf2_device", "rmx_adjoint_controls", "rmx_adjoint_controls_device", "rmx_adjoint_track", "rmx_adjoint_track_device", "rmx_energy",
     "rmx_rollout_tape", "rmx_rollout_vjp", "rmx_rollout_tape_device", "rmx_rollout_vjp_device",
     "rmx_rollout_tape_bdf2", "rmx_rollout_tape_bdf2_device",
+    "rmx_rollout_linearize", "rmx_rollout_linearize_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -146,6 +147,8 @@ def lib():
     L.rmx_rollout_tape_bdf2_device.argtypes = L.rmx_rollout_tape_device.argtypes
     L.rmx_rollout_vjp.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.rmx_rollout_vjp_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.rmx_rollout_linearize.argtypes = [vp, C.c_int, _dp, _dp, _dp]
+    L.rmx_rollout_linearize_device.argtypes = [vp, C.c_int, vp, vp, vp]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.rmx_energy.argtypes = [vp, _dp, _dp]
     L.rmx_last_step_ms.argtypes = [vp]

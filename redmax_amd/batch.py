@@ -41,6 +41,7 @@ class BatchSim:
         _abi.check(self._L.rmx_batch_create(self._model, self.B, C.byref(self._batch)), "rmx_batch_create")
         self.opts = _abi.Opts()
         self._L.rmx_opts_default(C.byref(self.opts))
+        self._tape_integrator = 1                          # the integrator of the last rollout_tape* call: the slots rollout_linearize returns
         self.tape_count = 0                                # calls that rewrote the adjoint workspace (rollout_tape*, adjoint_*): see diff.rollout
 
     def close(self):
@@ -434,6 +435,7 @@ class BatchSim:
         qdtraj = np.empty((self.B, nsteps, self.nr)) if trajectory else None
         info, st = self._tape_stats(stats)
         self.tape_count += 1
+        self._tape_integrator = integrator
         _abi.check(fn(self._batch, C.byref(opts), nsteps, float(pscale), _abi.dptr(u), _abi.dptr(qtraj), _abi.dptr(qdtraj),
                       C.byref(st) if st is not None else None), fname)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
@@ -446,6 +448,7 @@ class BatchSim:
         opts = self._tape_opts(h)
         info, st = self._tape_stats(stats)
         self.tape_count += 1
+        self._tape_integrator = integrator
         _abi.check(fn(self._batch, C.byref(opts), int(nsteps), float(pscale), C.c_void_p(u_ptr or None), C.c_void_p(qtraj_ptr or None),
                       C.c_void_p(qdtraj_ptr or None), C.byref(st) if st is not None else None), fname)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
@@ -473,6 +476,28 @@ class BatchSim:
         _abi.check(self._L.rmx_rollout_vjp_device(self._batch, int(nsteps), C.c_void_p(gq_ptr or None), C.c_void_p(gqd_ptr or None),
                                                   C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None)),
                    "rmx_rollout_vjp_device")
+
+    def rollout_linearize(self, nsteps, which=("XA", "XB", "XU")):
+        """rmx_rollout_linearize on the tape of the last rollout_tape: the forward sensitivities of every taped solve x(qA, qB, u),
+        XA = dx/dqA, XB = dx/dqB, XU = dx/du (include/redmax_hip.h has the assembly of A_k, B_k from them).  Returns one array per
+        name in `which`, in that order, each [B][nslots][nr][nr] with [.., i, j] = dx_i/d(.)_j; nslots = nsteps for a BDF1 tape,
+        nsteps + 1 for a BDF2 tape (slot nsteps: the SDIRK2a solve).  Neither the state nor the tape changes."""
+        nsteps = int(nsteps)
+        which = (which,) if isinstance(which, str) else tuple(which)
+        if any(w not in ("XA", "XB", "XU") for w in which) or len(set(which)) != len(which):
+            raise ValueError("rollout_linearize: which must name distinct outputs among 'XA', 'XB', 'XU', got %r" % (which,))
+        nslots = max(nsteps, 0) + (1 if self._tape_integrator == 2 else 0)
+        out = {w: np.empty((self.B, nslots, self.nr, self.nr)) for w in which}
+        _abi.check(self._L.rmx_rollout_linearize(self._batch, nsteps, _abi.dptr(out.get("XA")), _abi.dptr(out.get("XB")),
+                                                 _abi.dptr(out.get("XU"))), "rmx_rollout_linearize")
+        # the ABI's last index is column-major (j*nr + i): [.., j, i] as numpy reads it
+        return tuple(np.ascontiguousarray(out[w].transpose(0, 1, 3, 2)) for w in which)
+
+    def rollout_linearize_device(self, nsteps, XA_ptr, XB_ptr, XU_ptr):
+        """rollout_linearize with DEVICE pointers (integers), each [B][nslots][nr*nr] with entry j*nr + i = dx_i/d(.)_j (column-major
+        in the last index); 0 / None: that output is neither computed nor stored (not all three)."""
+        _abi.check(self._L.rmx_rollout_linearize_device(self._batch, int(nsteps), C.c_void_p(XA_ptr or None), C.c_void_p(XB_ptr or None),
+                                                        C.c_void_p(XU_ptr or None)), "rmx_rollout_linearize_device")
 
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent

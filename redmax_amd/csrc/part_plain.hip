@@ -1,6 +1,7 @@
 // part_plain.hip (part 0 of the former rmx_kernels.hip) -- the plain kernels for ONE padded tree size RMX_NP (every scene without ForceGroundCuboid /
 // JointSpherical) plus Euler, adjoint, phase timing.
 #include "rmx_kernels.h"
+#include "rmx_linearize.h"
 
 void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
     const dim3 grid(b->B), block(64);
@@ -70,6 +71,12 @@ void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int int
     adjoint_pairs<true>(m, b, integ, o, a);
 }
 #endif
+
+// rmx_rollout_linearize: every slot of the tape at once
+void RMX_CAT(launch_linearize_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LinArgs& a) {
+    const dim3 grid((unsigned)((size_t)b->B * a.nslots)), block(64);
+    k_rollout_linearize<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+}
 
 void RMX_CAT(launch_mfd_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD) {
     const dim3 grid(b->B), block(64);

@@ -1650,6 +1650,65 @@ static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const do
     return RMX_OK;
 }
 
+// rmx_rollout_linearize: XA, XB, XU of every slot of the tape, one kernel over B * nslots wavefronts (rmx_linearize.h).  The host form
+// stages through an allocation of its own: the adjoint workspace holds the tape, a regrow would lose it, and tapes that are never
+// linearised do not pay for three more histories.
+static int rollout_linearize_impl(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU, const bool on_device) {
+    if (!b) return fail(RMX_E_INVALID, "rmx_rollout_linearize: null batch");
+    if (!XA && !XB && !XU) return fail(RMX_E_INVALID, "rmx_rollout_linearize: all outputs are null");
+    rmx_model* m = b->m;
+    if (b->tape_nsteps < 1 || !b->adjws)
+        return fail(RMX_E_INVALID, "rmx_rollout_linearize: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_linearize: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+    HIPCHK(hipSetDevice(m->device));
+    int rc = pending_error_check(b, "rmx_rollout_linearize");
+    if (rc) return rc;
+    const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_linearize: no tape (the workspace is smaller than the tape)");
+    char* ws = (char*)b->adjws;
+    LinArgs a{};
+    a.nslots = nsteps + (b->tape_integ == INTEG_BDF2 ? 1 : 0);
+    a.bdf2 = b->tape_integ == INTEG_BDF2 ? 1 : 0;
+    a.h = b->tape_h;
+    a.pscale = b->tape_pscale;
+    a.Hs = (const double*)(ws + t.off[0]); a.Ms = (const double*)(ws + t.off[1]); a.Ds = (const double*)(ws + t.off[2]);
+    if ((size_t)b->B * a.nslots > (size_t)0x7fffffff) return fail(RMX_E_INVALID, "rmx_rollout_linearize: batch * slots exceeds the grid");
+    double* host[3] = {XA, XB, XU};
+    const size_t bytes = (size_t)b->B * a.nslots * m->nr * m->nr * sizeof(double), pitch = (bytes + 255) & ~(size_t)255;
+    char* stage = nullptr;
+    if (!on_device) {
+        size_t want = 0;
+        for (double* p : host) want += p ? pitch : 0;
+        const hipError_t em = hipMalloc((void**)&stage, want ? want : 256);
+        if (em == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, "rmx_rollout_linearize: no device memory for the staging of the outputs"); }
+        if (em != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_linearize: ") + hipGetErrorString(em));
+    }
+    double* dev[3] = {XA, XB, XU};
+    if (!on_device) {
+        size_t at = 0;
+        for (int i = 0; i < 3; ++i)
+            if (host[i]) { dev[i] = (double*)(stage + at); at += pitch; }
+    }
+    a.XA = dev[0]; a.XB = dev[1]; a.XU = dev[2];
+    hipError_t e = hipSuccess;
+    if (bytes) {
+        e = hipEventRecord(b->ev0, b->stream);
+        if (e == hipSuccess) {
+            DISPATCH_NP(m->NP, launch_linearize, m, b, a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+        for (int i = 0; i < 3 && !on_device; ++i)
+            if (e == hipSuccess && host[i]) e = hipMemcpyAsync(host[i], dev[i], bytes, hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess) e = wait_stream_short(b->stream);
+        else (void)hipStreamSynchronize(b->stream);
+    }
+    if (stage) (void)hipFree(stage);
+    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_linearize: ") + hipGetErrorString(e));
+    if (bytes) take_event_time(b);
+    return RMX_OK;
+}
+
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                 double* qdtraj, rmx_stats* stats) {
     return rollout_tape_impl(b, opts, nsteps, pscale, u, qtraj, qdtraj, stats, false);
@@ -1672,6 +1731,12 @@ extern "C" int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const
 extern "C" int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
                                       double* d_dqd0) {
     return rollout_vjp_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, true);
+}
+extern "C" int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU) {
+    return rollout_linearize_impl(b, nsteps, XA, XB, XU, false);
+}
+extern "C" int rmx_rollout_linearize_device(rmx_batch* b, int nsteps, double* d_XA, double* d_XB, double* d_XU) {
+    return rollout_linearize_impl(b, nsteps, d_XA, d_XB, d_XU, true);
 }
 
 static int track_refusal(const rmx_task_track* task, const double* xtarget, int integrator) {

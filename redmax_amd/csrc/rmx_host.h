@@ -78,6 +78,15 @@ struct AdjArgs {
     double *dq0, *dqd0;       // [B][nr] dL/dq0, dL/dqdot0 (out), or null together
 };
 
+// rmx_rollout_linearize (rmx_linearize.h): one wavefront per (rollout, slot) of the tape
+struct LinArgs {
+    int nslots;               // per rollout: nsteps (BDF1) or nsteps + 1 (BDF2: slot nsteps holds the SDIRK2a solve)
+    int bdf2;                 // the tape's integrator: eta per slot
+    double h, pscale;         // the tape's
+    const double *Hs, *Ms, *Ds;   // [B][nslots][n*n], entry (row r, column c) at c*n + r
+    double *XA, *XB, *XU;     // [B][nslots][nr*nr], entry j*nr + i = dx_i/d(.)_j in reduced order; null: not wanted
+};
+
 struct rmx_model {
     int device = 0;
     int n = 0, nr = 0, nm = 0, NP = 0;   // n: 1-DOF nodes on the device (after lowering multi-DOF joints)
@@ -156,6 +165,7 @@ struct rmx_batch {
     void RMX_CAT(launch_euler_, NPV)(const rmx_model* m, const rmx_batch* b, double h, const StepArgs& a); \
     void RMX_CAT(launch_energy_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_adjoint_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
+    void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_phase_, NPV)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d); \
     void RMX_CAT(launch_mfd_, NPV)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD); \
     void RMX_CAT(launch_mfd_ct_, NPV)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD); \

@@ -57,6 +57,24 @@ def _function():
     return _Function
 
 
+def _check_inputs(sim, q0, qdot0, u):
+    """The argument checks rollout and linearize share (and their words)."""
+    import torch
+    dev = torch.device("cuda", sim.device)
+    for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("rollout: %s must be float64, got %s" % (name, t.dtype))
+        if t.device != dev:
+            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+    if u.dim() != 3 or u.shape[0] != sim.B or u.shape[2] != sim.nr or u.shape[1] < 1:
+        raise ValueError("rollout: u must have shape (%d, nsteps, %d), got %r" % (sim.B, sim.nr, tuple(u.shape)))
+    for name, t in (("q0", q0), ("qdot0", qdot0)):
+        if tuple(t.shape) != (sim.B, sim.nr):
+            raise ValueError("rollout: %s must have shape (%d, %d), got %r" % (name, sim.B, sim.nr, tuple(t.shape)))
+
+
 def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     """A controlled BDF1 (integrator=1) or BDF2 (integrator=2) rollout of every trajectory of ``sim`` (a BatchSim) that autograd can differentiate.
 
@@ -71,17 +89,46 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     import torch
     if integrator not in (1, 2):
         raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
-    dev = torch.device("cuda", sim.device)
-    for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("rollout: %s must be float64, got %s" % (name, t.dtype))
-        if t.device != dev:
-            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
-    if u.dim() != 3 or u.shape[0] != sim.B or u.shape[2] != sim.nr or u.shape[1] < 1:
-        raise ValueError("rollout: u must have shape (%d, nsteps, %d), got %r" % (sim.B, sim.nr, tuple(u.shape)))
-    for name, t in (("q0", q0), ("qdot0", qdot0)):
-        if tuple(t.shape) != (sim.B, sim.nr):
-            raise ValueError("rollout: %s must have shape (%d, %d), got %r" % (name, sim.B, sim.nr, tuple(t.shape)))
+    _check_inputs(sim, q0, qdot0, u)
     return _function().apply(q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check), integrator)
+
+
+def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
+    """The controlled BDF1 rollout of ``rollout`` and its linearisation, step by step: (qtraj, qdtraj, A, Bm) with
+
+        A[b, k-1]  = d(q_k, qdot_k)/d(q_{k-1}, qdot_{k-1})   [B][nsteps][2nr][2nr]
+        Bm[b, k-1] = d(q_k, qdot_k)/du_k                      [B][nsteps][2nr][nr]
+
+    in the state order (q, qdot) - what iLQR / DDP, time-varying LQR and Gauss-Newton shooting take.  Arguments, checks and words
+    are rollout's; no autograd graph is made.  Forward is rmx_rollout_tape_device, the per-solve sensitivities XA, XB, XU come
+    from rmx_rollout_linearize_device (include/redmax_hip.h) and are assembled here with torch ops:
+
+        A = [[XA + XB, h XB], [(XA + XB - I)/h, XB]]        Bm = [[XU], [XU/h]]
+
+    The call replaces the sim's tape, as rollout does, and leaves the sim at the end of the rollout.  integrator=2 raises
+    ValueError: BDF2 needs the augmented state (q_k, qdot_k, q_{k-1}, qdot_{k-1}) and a composite start step; the per-solve
+    sensitivities of a BDF2 tape are available from BatchSim.rollout_linearize, their assembly is left to a later change."""
+    import torch
+    if integrator != 1:
+        raise ValueError("linearize: integrator must be 1 (BDF1), got %r: the BDF2 assembly needs the augmented state "
+                         "(BatchSim.rollout_linearize returns the per-solve sensitivities of a BDF2 tape)" % (integrator,))
+    _check_inputs(sim, q0, qdot0, u)
+    h = float(sim.opts.h if h is None else h)
+    B, nsteps, nr = u.shape
+    q0c, qd0c, uc = q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous()
+    qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
+    qdtraj = torch.empty_like(qtraj)
+    X = torch.empty((3, B, nsteps, nr, nr), dtype=torch.float64, device=u.device)
+    torch.cuda.current_stream(u.device).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
+    info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=float(pscale), stats=bool(check))
+    if check and (info["status"] & _BAD_STATUS).any():
+        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
+        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+    sim.rollout_linearize_device(nsteps, X[0].data_ptr(), X[1].data_ptr(), X[2].data_ptr())
+    XA, XB, XU = (X[i].transpose(-1, -2) for i in range(3))      # the ABI's last index is column-major: [.., i, j] = dx_i/d(.)_j
+    S = XA + XB
+    eye = torch.eye(nr, dtype=torch.float64, device=u.device)
+    A = torch.cat([torch.cat([S, h * XB], dim=-1), torch.cat([(S - eye) / h, XB], dim=-1)], dim=-2)
+    Bm = torch.cat([XU, XU / h], dim=-2)
+    return qtraj, qdtraj, A, Bm

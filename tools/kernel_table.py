@@ -29,6 +29,11 @@ ROWS = (  # (name fragment, what it runs)
     ("k_rollout_bwd_bdf2<16, true>", "rmx_rollout_vjp on a BDF2 tape: full 16-link chain"),
     ("k_adjoint_fwd<64, 22, false, false>", "rmx_rollout_tape_bdf2: 33..64 nodes"),
     ("k_rollout_bwd_bdf2<64, false>", "rmx_rollout_vjp on a BDF2 tape: 33..64 nodes"),
+    ("k_rollout_linearize<4>", "rmx_rollout_linearize (XA, XB, XU of every slot of a tape; one wavefront per rollout and slot): <= 4 nodes"),
+    ("k_rollout_linearize<8>", "rmx_rollout_linearize: 5..8 nodes"),
+    ("k_rollout_linearize<16>", "rmx_rollout_linearize: 9..16 nodes"),
+    ("k_rollout_linearize<32>", "rmx_rollout_linearize: 17..32 nodes, the four blocks in one pass"),
+    ("k_rollout_linearize<64>", "rmx_rollout_linearize: 33..64 nodes, half a right-hand block per pass"),
     ("k_step_bdf1<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF1"),
     ("k_step_bdf2<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF2"),
     ("k_big_step", "trees of 65..256 nodes (one workgroup per rollout)"),
