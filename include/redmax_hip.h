@@ -499,6 +499,55 @@ int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const d
 int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU);
 int rmx_rollout_linearize_device(rmx_batch* b, int nsteps, double* d_XA, double* d_XB, double* d_XU);
 
+/* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
+ * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of
+ * RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * Every taped solve is the implicit function g(x; qA, qB, u, theta) = 0 of rmx_rollout_tape_bdf2 above, and the backward sweep forms
+ * the adjoint vector z of every solve (the z of solve_bwd; under BDF2 the SDIRK2a and SDIRK2b solves of step 1 each have their own).
+ * g is linear in each of these parameters, so
+ *     dL/dtheta = - sum over all slots s of the tape   z_s' dg_s/dtheta
+ * with dg_s/dtheta taken at the slot's solution x_s with its qA, qB and eta - the rule that gives du = eta^2 pscale z.  With
+ * v = (x - qA)/eta, and per body i, in the BODY frame (where the inertia is diag(I_i[0..5])), w = (J z)_i, phi = (J v)_i,
+ * beta = (J (x - qB) + eta^2 Jdot v)_i:
+ *     d(z'g)/dstiffness_j = eta^2 z_j (x_j - qRest_j)      d(z'g)/ddamping_j = eta^2 z_j v_j      d(z'g)/dqRest_j = -eta^2 k_j z_j
+ *     d(z'g)/dI_i[c]      = w_c beta_c - eta^2 (ad(phi) w)_c phi_c   ( - eta^2 w_lin . R_i' grav  for c = 3 )      c = 0 .. 5
+ *     d(z'g)/dgrav_k      = -eta^2 sum_i m_i (R_i w_i,lin)_k
+ * The weight of a body is I_i[3] R_i' grav (the reference reads the mass from that entry alone, Body.m:104-109), so the gravity term
+ * belongs to c = 3; the entries 3 .. 5 must be equal (rmx_model_create), and the gradient of the mass is the sum of the three.
+ * A body on a fixed joint has no DOF of its own and still gets its inertia row, through its ancestors' columns of J.  Joint-limit
+ * constants, axes, frames and the constant tau are not parameters here (dL/dtau is the sum over the steps of du / pscale).
+ *
+ * rmx_rollout_vjp_params reads the tape of the preceding rmx_rollout_tape / rmx_rollout_tape_bdf2 on the batch and follows its
+ * integrator.  gq, gqd, du, dq0, dqd0: as rmx_rollout_vjp, and du, dq0, dqd0 are the bits rmx_rollout_vjp returns for the same tape and
+ * cotangents (dq0, dqd0 NULL together: not formed).  out: one row per rollout - the gradient of a parameter the rollouts share is the
+ * caller's sum over the batch (the rows stay apart because a loss may weight rollouts).  stiffness, damping and qrest are per reduced
+ * DOF: a value set per joint reaches every DOF of a multi-DOF joint, and its gradient is the sum of those DOFs' entries.  Any of the
+ * five pointers may be NULL - that output is neither computed nor stored - but not all of them; an output has the same bits
+ * whichever others are asked for.  The sum over the slots runs in a fixed order: repeated calls return the same bits.
+ *
+ * The tape keeps the states it differentiates at - q0, qdot0 and the trajectory, copied on the batch's stream by the tape call
+ * (recorded in place where the caller asked for no record) - exactly as long as it keeps H, M, D; the SDIRK2a result qa of a BDF2
+ * tape is rebuilt from them: qda = (q1 - al h qd1 - q0)/((1 - al) h), qa = q0 + al h qda.
+ *
+ * The call changes neither the batch's state nor the tape: it may be repeated, and rmx_rollout_vjp and rmx_rollout_linearize return
+ * the same bits before and after it.  Refusals (RMX_E_INVALID), in rmx_rollout_vjp's words where they coincide: "no tape", an nsteps
+ * that differs from the tape's, a null batch, gq, gqd, du or out ("null argument"), "all outputs are null".  The rows of a rollout whose
+ * tape call reported a failed Newton solve (stats->status) are unspecified.
+ * The _device form: every array a DEVICE pointer (the struct itself is a host object), nothing staged; it returns when the kernels
+ * have finished. */
+typedef struct rmx_param_grads {   /* every pointer may be NULL (not formed), but not all five */
+    double* stiffness;   /* [batch][nr]          reduced DOF order                         */
+    double* damping;     /* [batch][nr]                                                    */
+    double* qrest;       /* [batch][nr]                                                    */
+    double* inertia;     /* [batch][njoints][6]  listing order, the layout of desc.I_i     */
+    double* grav;        /* [batch][3]                                                     */
+} rmx_param_grads;
+int rmx_rollout_vjp_params(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                           const rmx_param_grads* out);
+int rmx_rollout_vjp_params_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
+                                  double* d_dqd0, const rmx_param_grads* out);
+
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.
  * hist_T/hist_V as in rmx_step_bdf1. */

@@ -180,6 +180,15 @@ classdef HipSim < handle
 			[du, dq0, dqd0] = redmax_hip_mex('rollout_vjp', this.h, nsteps, gq, gqd);
 		end
 
+		function [du, dq0, dqd0, grads] = rolloutVjpParams(this, nsteps, gq, gqd)
+			% rolloutVjp (the same du, dq0, dqd0) and the gradient of the loss with respect to the model's parameters, one column
+			% per rollout: grads.stiffness, grads.damping, grads.qrest (nr x B, reduced DOF order), grads.inertia (6 x njoints x B,
+			% the layout of desc.I_i) and grads.grav (3 x B).  The gradient of a parameter the rollouts share is the sum over B;
+			% of a stiffness or damping set per joint the sum over that joint's DOFs.  The tape and the state stay as they are.
+			[du, dq0, dqd0, dk, dd, dr, dI, dg] = redmax_hip_mex('rollout_vjp_params', this.h, nsteps, gq, gqd);
+			grads = struct('stiffness', dk, 'damping', dd, 'qrest', dr, 'inertia', dI, 'grav', dg);
+		end
+
 		function [XA, XB, XU] = rolloutLinearize(this, nsteps)
 			% the linearisation of the last rolloutTape: the sensitivities XA = dx/dqA, XB = dx/dqB, XU = dx/du of every taped
 			% solve x(qA, qB, u), each nr x nr x nslots x B with (i,j,s,b) = dx_i/d(.)_j of slot s; nslots = nsteps, or

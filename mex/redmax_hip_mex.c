@@ -68,6 +68,11 @@
  *                  sensitivities dx/dqA, dx/dqB, dx/du of every taped solve, nr x nr x nslots x B with (i,j,s,b) = dx_i/d(.)_j of slot s
  *                  (nslots = nsteps, or nsteps + 1 after a BDF2 'rollout_tape': the last slot is the SDIRK2a solve).  Outputs that are
  *                  not asked for are not computed.  include/redmax_hip.h has the assembly of A_k, B_k from them.
+ *   [du,dq0,dqd0,dk,dd,dqrest,dI,dgrav] = redmax_hip_mex('rollout_vjp_params', h, nsteps, gq, gqd)  rmx_rollout_vjp_params on the tape
+ *                  of the last 'rollout_tape': 'rollout_vjp' (the same du, dq0, dqd0) and the gradient of the loss with respect to
+ *                  the model's parameters, one column per rollout: joint stiffness dk, damping dd and rest position dqrest (nr x B,
+ *                  reduced DOF order), body inertia dI (6 x njoints x B, the layout of desc.I_i) and gravity dgrav (3 x B).  The
+ *                  gradient of a parameter the rollouts share is the sum over B.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -626,6 +631,40 @@ static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     else mxDestroyArray(dqd0);
 }
 
+static void cmd_rollout_vjp_params(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 5) die("usage: [du,dq0,dqd0,dk,dd,dqrest,dI,dgrav] = redmax_hip_mex('rollout_vjp_params', h, nsteps, gq, gqd)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_vjp_params: nsteps must be at least 1");
+    const double* gq = traj_arg(prhs[3], h, nsteps, "gq");
+    const double* gqd = traj_arg(prhs[4], h, nsteps, "gqd");
+    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps, perI = 6 * (size_t)h->njoints;
+    const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B}, dimsI[3] = {6, (size_t)h->njoints, (size_t)h->B};
+    mxArray* out[8];
+    out[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    for (int i = 1; i < 6; ++i) out[i] = mxCreateDoubleMatrix(nr, (size_t)h->B, mxREAL);      /* dq0, dqd0, dk, dd, dqrest */
+    out[6] = mxCreateNumericArray(3, dimsI, mxDOUBLE_CLASS, mxREAL);
+    out[7] = mxCreateDoubleMatrix(3, (size_t)h->B, mxREAL);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_param_grads pg;
+        pg.stiffness = mxGetPr(out[3]) + f * nr;
+        pg.damping = mxGetPr(out[4]) + f * nr;
+        pg.qrest = mxGetPr(out[5]) + f * nr;
+        pg.inertia = mxGetPr(out[6]) + f * perI;
+        pg.grav = mxGetPr(out[7]) + f * 3;
+        if (rmx_rollout_vjp_params(b, nsteps, gq + f * per, gqd + f * per, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * nr,
+                                   mxGetPr(out[2]) + f * nr, &pg))
+            die_rmx("rmx_rollout_vjp_params");
+    }
+    plhs[0] = out[0];
+    for (int i = 1; i < 8; ++i) {
+        if (nlhs > i) plhs[i] = out[i];
+        else mxDestroyArray(out[i]);
+    }
+}
+
 static void cmd_rollout_linearize(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
     if (nrhs < 3) die("usage: [XA,XB,XU] = redmax_hip_mex('rollout_linearize', h, nsteps)");
@@ -747,7 +786,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             NULL};
+                                             "rollout_vjp_params", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -858,6 +897,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_vjp(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_linearize")) {
         cmd_rollout_linearize(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_vjp_params")) {
+        cmd_rollout_vjp_params(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

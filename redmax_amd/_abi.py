@@ -27,6 +27,7 @@ SYMBOLS = (
     "rmx_rollout_tape", "rmx_rollout_vjp", "rmx_rollout_tape_device", "rmx_rollout_vjp_device",
     "rmx_rollout_tape_bdf2", "rmx_rollout_tape_bdf2_device",
     "rmx_rollout_linearize", "rmx_rollout_linearize_device",
+    "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -81,6 +82,13 @@ class GroundContact(C.Structure):
 class PointForce(C.Structure):
     _fields_ = [("kind", C.c_int), ("npts", C.c_int), ("body", _ip), ("x", _dp), ("stiffness", C.c_double), ("damping", C.c_double),
                 ("L", C.c_double)]
+
+
+class ParamGrads(C.Structure):
+    _fields_ = [("stiffness", C.c_void_p), ("damping", C.c_void_p), ("qrest", C.c_void_p), ("inertia", C.c_void_p), ("grav", C.c_void_p)]
+
+
+PARAM_NAMES = ("stiffness", "damping", "qrest", "inertia", "grav")      # the members of rmx_param_grads, in their order
 
 
 class History(C.Structure):
@@ -149,6 +157,8 @@ def lib():
     L.rmx_rollout_vjp_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.rmx_rollout_linearize.argtypes = [vp, C.c_int, _dp, _dp, _dp]
     L.rmx_rollout_linearize_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
+    L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.rmx_energy.argtypes = [vp, _dp, _dp]
     L.rmx_last_step_ms.argtypes = [vp]

@@ -477,6 +477,51 @@ class BatchSim:
                                                   C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None)),
                    "rmx_rollout_vjp_device")
 
+    def _param_shapes(self):
+        """The shape of one rollout's row of every rmx_param_grads member."""
+        return {"stiffness": (self.nr,), "damping": (self.nr,), "qrest": (self.nr,), "inertia": (int(self._desc.njoints), 6), "grav": (3,)}
+
+    @staticmethod
+    def _param_names(want, who):
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in _abi.PARAM_NAMES for w in want) or len(set(want)) != len(want):
+            raise ValueError("%s: want must name distinct outputs among %s, got %r" % (who, ", ".join(repr(n) for n in _abi.PARAM_NAMES), want))
+        return want
+
+    def rollout_vjp_params(self, nsteps, gq, gqd, want=_abi.PARAM_NAMES, initial_state=True):
+        """rmx_rollout_vjp_params on the tape of the last rollout_tape: rollout_vjp's sweep for the cotangents gq, gqd [B][nsteps][nr],
+        and the gradient with respect to the model's parameters.  Returns (du, dq0, dqd0, grads): the first three are rollout_vjp's
+        (the same bits), grads maps every name in `want` to one row per rollout - stiffness, damping, qrest [B][nr] in reduced DOF
+        order, inertia [B][njoints][6] in listing order (the layout of desc.I_i: the rotational inertia, then three times the mass),
+        grav [B][3].  The gradient of a parameter the rollouts share is the sum over the batch; of a stiffness or damping set per
+        joint the sum over that joint's DOFs.  Neither the state nor the tape changes."""
+        nsteps = int(nsteps)
+        want = self._param_names(want, "rollout_vjp_params")
+        sh = (self.B, nsteps, self.nr)
+        gq = np.ascontiguousarray(gq, dtype=np.float64)
+        gqd = np.ascontiguousarray(gqd, dtype=np.float64)
+        if gq.shape != sh or gqd.shape != sh:
+            raise ValueError("rollout_vjp_params: gq and gqd must have shape %r, got %r and %r" % (sh, gq.shape, gqd.shape))
+        du = np.empty(sh)
+        dq0 = np.empty((self.B, self.nr)) if initial_state else None
+        dqd0 = np.empty((self.B, self.nr)) if initial_state else None
+        shapes = self._param_shapes()
+        grads = {w: np.zeros((self.B,) + shapes[w]) for w in want}
+        pg = _abi.ParamGrads(*[grads[n].ctypes.data if n in grads else None for n in _abi.PARAM_NAMES])
+        _abi.check(self._L.rmx_rollout_vjp_params(self._batch, nsteps, _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(du), _abi.dptr(dq0),
+                                                  _abi.dptr(dqd0), C.byref(pg)), "rmx_rollout_vjp_params")
+        return du, dq0, dqd0, grads
+
+    def rollout_vjp_params_device(self, nsteps, gq_ptr, gqd_ptr, du_ptr, dq0_ptr=None, dqd0_ptr=None, stiffness_ptr=None, damping_ptr=None,
+                                  qrest_ptr=None, inertia_ptr=None, grav_ptr=None):
+        """rollout_vjp_params with DEVICE pointers (integers): gq, gqd, du [B][nsteps][nr]; dq0, dqd0 [B][nr], 0 / None together: not
+        formed; stiffness, damping, qrest [B][nr], inertia [B][njoints][6], grav [B][3], 0 / None: that output is neither computed
+        nor stored (not all five)."""
+        pg = _abi.ParamGrads(stiffness_ptr or None, damping_ptr or None, qrest_ptr or None, inertia_ptr or None, grav_ptr or None)
+        _abi.check(self._L.rmx_rollout_vjp_params_device(self._batch, int(nsteps), C.c_void_p(gq_ptr or None), C.c_void_p(gqd_ptr or None),
+                                                         C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None),
+                                                         C.byref(pg)), "rmx_rollout_vjp_params_device")
+
     def rollout_linearize(self, nsteps, which=("XA", "XB", "XU")):
         """rmx_rollout_linearize on the tape of the last rollout_tape: the forward sensitivities of every taped solve x(qA, qB, u),
         XA = dx/dqA, XB = dx/dqB, XU = dx/du (include/redmax_hip.h has the assembly of A_k, B_k from them).  Returns one array per

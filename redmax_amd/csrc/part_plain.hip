@@ -2,6 +2,7 @@
 // JointSpherical) plus Euler, adjoint, phase timing.
 #include "rmx_kernels.h"
 #include "rmx_linearize.h"
+#include "rmx_params.h"
 
 void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
     const dim3 grid(b->B), block(64);
@@ -76,6 +77,30 @@ void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int int
 void RMX_CAT(launch_linearize_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LinArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nslots)), block(64);
     k_rollout_linearize<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+}
+
+// rmx_rollout_vjp_params: the backward sweep of the tape's integrator in its ADJ_ZS instantiation (du, dq0, dqd0 as rmx_rollout_vjp's
+// kernel, and z of every slot to a.zs), then the contraction over the slots.  fullchain: the instantiation rmx_rollout_vjp's plan runs
+// for the full 16-link chain.
+template <bool FC>
+static void vjp_zs(const rmx_batch* b, const rmx_model* m, int integ, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) k_adjoint_bwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE | ADJ_ZS, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    else k_rollout_bwd_bdf2_zs<RMX_NP, FC><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+}
+void RMX_CAT(launch_vjp_zs_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain) {
+#if RMX_NP == 16
+    if (fullchain) {
+        vjp_zs<true>(b, m, integ, o, a);
+        return;
+    }
+#endif
+    (void)fullchain;
+    vjp_zs<false>(b, m, integ, o, a);
+}
+void RMX_CAT(launch_param_grad_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a) {
+    const dim3 grid(b->B), block(64);
+    RMX_LAUNCH((k_rollout_param_grad<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, a);
 }
 
 void RMX_CAT(launch_mfd_, RMX_NP)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD) {

@@ -1509,8 +1509,13 @@ extern "C" int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, i
 // them; behind them the staging areas of the host forms - three arrays shaped as u (u, qtraj, qdtraj of the tape; gq, gqd, du of the
 // vjp) and two of [B][nr] (dq0, dqd0).  The tape call reserves all of it, so that a vjp never regrows (and so loses) the tape.
 // A BDF2 tape has nsteps + 1 slots per rollout: the last one holds the SDIRK2a solve.
+// Behind those, what rmx_rollout_vjp_params needs: the states the tape differentiates at - q0, qdot0 ([B][nr] each) and the recorded
+// trajectory (two arrays shaped as u), (2 nsteps + 2) nr doubles per rollout, kept as long as the tape (no vjp stages over them) -,
+// z of every slot ([B][nslots][n], written by the ADJ_ZS backward kernels) and the staging of the five gradient arrays.
+enum { TP_Q0 = 8, TP_QD0, TP_QT, TP_QDT, TP_ZS, TP_PG, TP_NPARTS };
 struct TapeParts {
-    size_t off[8], bytes_traj, bytes_state, total;
+    size_t off[TP_NPARTS], bytes_traj, bytes_state, total;
+    size_t pg_off[5], pg_bytes[5];      // stiffness, damping, qrest, inertia, grav inside part TP_PG
 };
 static TapeParts tape_parts(const rmx_batch* b, const int nsteps, const int integ) {
     const rmx_model* m = b->m;
@@ -1518,8 +1523,17 @@ static TapeParts tape_parts(const rmx_batch* b, const int nsteps, const int inte
     const size_t hist = (size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * m->n * sizeof(double);
     t.bytes_traj = (size_t)b->B * nsteps * m->nr * sizeof(double);
     t.bytes_state = (size_t)b->B * m->nr * sizeof(double);
-    const size_t sizes[8] = {hist, hist, hist, t.bytes_traj, t.bytes_traj, t.bytes_traj, t.bytes_state, t.bytes_state};
-    for (int i = 0; i < 8; ++i) {
+    const size_t zbytes = (size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * sizeof(double);
+    const size_t pg[5] = {t.bytes_state, t.bytes_state, t.bytes_state, (size_t)b->B * m->nlist * 6 * sizeof(double), (size_t)b->B * 3 * sizeof(double)};
+    size_t pgtotal = 0;
+    for (int i = 0; i < 5; ++i) {
+        t.pg_off[i] = pgtotal;
+        t.pg_bytes[i] = pg[i];
+        pgtotal += (pg[i] + 255) & ~(size_t)255;
+    }
+    const size_t sizes[TP_NPARTS] = {hist, hist, hist, t.bytes_traj, t.bytes_traj, t.bytes_traj, t.bytes_state, t.bytes_state,
+                                     t.bytes_state, t.bytes_state, t.bytes_traj, t.bytes_traj, zbytes, pgtotal};
+    for (int i = 0; i < TP_NPARTS; ++i) {
         t.off[i] = t.total;
         t.total += (sizes[i] + 255) & ~(size_t)255;
     }
@@ -1564,10 +1578,18 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
         a.u = on_device ? u : (const double*)(ws + t.off[3]);
         a.tape = 1;
+        // the states rmx_rollout_vjp_params differentiates at stay with the tape: (q0, qdot0) is copied on the stream ahead of the sweep;
+        // the trajectory is recorded by the kernel as ever - into the caller's arrays (or their staging) and copied behind the sweep,
+        // or, where the caller wants no record, straight into the tape's own rows
         if (qtraj) {
             a.qtraj = on_device ? qtraj : (double*)(ws + t.off[4]);
             a.qdtraj = on_device ? qdtraj : (double*)(ws + t.off[5]);
+        } else {
+            a.qtraj = (double*)(ws + t.off[TP_QT]);
+            a.qdtraj = (double*)(ws + t.off[TP_QDT]);
         }
+        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_Q0], b->q, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_QD0], b->qd, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
         if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
         if (e == hipSuccess) {
             const rmx_select::AdjPlan plan = launch_adjoint_plan(b, integ, o, a);
@@ -1577,6 +1599,10 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
         // a BDF1 rollout: rmx_step_bdf2 takes its start step again; after a BDF2 rollout (q, qdot) of step k-1 are in place
         if (e == hipSuccess) e = set_started(b, integ == INTEG_BDF2 ? 1 : 0);
+        if (e == hipSuccess && qtraj) {
+            e = hipMemcpyAsync(ws + t.off[TP_QT], a.qtraj, t.bytes_traj, hipMemcpyDeviceToDevice, b->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_QDT], a.qdtraj, t.bytes_traj, hipMemcpyDeviceToDevice, b->stream);
+        }
         if (e == hipSuccess && !on_device && qtraj) {
             e = hipMemcpyAsync(qtraj, a.qtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(qdtraj, a.qdtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
@@ -1646,6 +1672,83 @@ static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const do
     if (e == hipSuccess) e = wait_stream_short(b->stream);
     else (void)hipStreamSynchronize(b->stream);      // (the cotangents must outlive their copies)
     if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp: ") + hipGetErrorString(e));
+    take_event_time(b);
+    return RMX_OK;
+}
+
+// rmx_rollout_vjp_params: rmx_rollout_vjp's sweep in the instantiation that also stores z of every slot, then the contraction of
+// rmx_params.h over the slots with the states the tape kept.  Everything it stages lies in parts the tape call reserved.
+static int rollout_vjp_params_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                                   const rmx_param_grads* out, const bool on_device) {
+    if (!b || !gq || !gqd || !du || !out) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: null argument");
+    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: dq0 and dqd0 must be given together");
+    double* host[5] = {out->stiffness, out->damping, out->qrest, out->inertia, out->grav};
+    if (!host[0] && !host[1] && !host[2] && !host[3] && !host[4]) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: all outputs are null");
+    rmx_model* m = b->m;
+    if (b->tape_nsteps < 1 || !b->adjws)
+        return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+    HIPCHK(hipSetDevice(m->device));
+    int rc = pending_error_check(b, "rmx_rollout_vjp_params");
+    if (rc) return rc;
+    const int integ = b->tape_integ;
+    const TapeParts t = tape_parts(b, nsteps, integ);
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: no tape (the workspace is smaller than the tape)");
+    char* ws = (char*)b->adjws;
+    DevOpts o{};
+    o.h = b->tape_h;
+    AdjArgs a{};
+    a.B = b->B; a.nsteps = nsteps; a.pscale = b->tape_pscale;
+    a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
+    a.tape = 2;
+    a.gq = on_device ? gq : (const double*)(ws + t.off[3]);
+    a.gqd = on_device ? gqd : (const double*)(ws + t.off[4]);
+    a.dPdu = on_device ? du : (double*)(ws + t.off[5]);
+    if (dq0) {
+        a.dq0 = on_device ? dq0 : (double*)(ws + t.off[6]);
+        a.dqd0 = on_device ? dqd0 : (double*)(ws + t.off[7]);
+    }
+    a.zs = (double*)(ws + t.off[TP_ZS]);
+    ParamArgs pa{};
+    pa.nsteps = nsteps; pa.nslots = nsteps + (integ == INTEG_BDF2 ? 1 : 0); pa.bdf2 = integ == INTEG_BDF2 ? 1 : 0;
+    pa.njoints = m->nlist; pa.h = b->tape_h;
+    pa.q0 = (const double*)(ws + t.off[TP_Q0]); pa.qd0 = (const double*)(ws + t.off[TP_QD0]);
+    pa.qt = (const double*)(ws + t.off[TP_QT]); pa.qdt = (const double*)(ws + t.off[TP_QDT]);
+    pa.zs = a.zs;
+    double* dev[5];
+    for (int i = 0; i < 5; ++i) dev[i] = !host[i] ? nullptr : on_device ? host[i] : (double*)(ws + t.off[TP_PG] + t.pg_off[i]);
+    pa.stiffness = dev[0]; pa.damping = dev[1]; pa.qrest = dev[2]; pa.inertia = dev[3]; pa.grav = dev[4];
+    for (int i = 0; i < MAXN; ++i) pa.lst[i] = -1;
+    for (int L = 0; L < m->nlist; ++L) {
+        const int k = m->node_of_listing[L];
+        if (k >= 0 && k < MAXN) pa.lst[k] = (short)L;
+    }
+    hipError_t e = hipSuccess;
+    if (!on_device) {
+        e = hipMemcpyAsync(ws + t.off[3], gq, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[4], gqd, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
+    if (e == hipSuccess) {
+        const rmx_select::AdjPlan plan = rmx_select::select_rollout_tape(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
+        DISPATCH_NP(m->NP, launch_vjp_zs, m, b, integ, o, a, plan.fullchain);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        DISPATCH_NP(m->NP, launch_param_grad, m, b, pa);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+    if (e == hipSuccess && !on_device) {
+        e = hipMemcpyAsync(du, a.dPdu, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dq0, a.dq0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dqd0, a.dqd0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
+        for (int i = 0; i < 5; ++i)
+            if (e == hipSuccess && host[i] && t.pg_bytes[i]) e = hipMemcpyAsync(host[i], dev[i], t.pg_bytes[i], hipMemcpyDeviceToHost, b->stream);
+    }
+    if (e == hipSuccess) e = wait_stream_short(b->stream);
+    else (void)hipStreamSynchronize(b->stream);      // (the cotangents must outlive their copies)
+    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp_params: ") + hipGetErrorString(e));
     take_event_time(b);
     return RMX_OK;
 }
@@ -1731,6 +1834,14 @@ extern "C" int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const
 extern "C" int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
                                       double* d_dqd0) {
     return rollout_vjp_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, true);
+}
+extern "C" int rmx_rollout_vjp_params(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                                      const rmx_param_grads* out) {
+    return rollout_vjp_params_impl(b, nsteps, gq, gqd, du, dq0, dqd0, out, false);
+}
+extern "C" int rmx_rollout_vjp_params_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
+                                             double* d_dqd0, const rmx_param_grads* out) {
+    return rollout_vjp_params_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, out, true);
 }
 extern "C" int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU) {
     return rollout_linearize_impl(b, nsteps, XA, XB, XU, false);

@@ -76,6 +76,23 @@ struct AdjArgs {
     double *qtraj, *qdtraj;   // [B][nsteps][nr] q, qdot after every step (out), or null together
     const double *gq, *gqd;   // [B][nsteps][nr] the cotangents dL/dq_k, dL/dqdot_k
     double *dq0, *dqd0;       // [B][nr] dL/dq0, dL/dqdot0 (out), or null together
+    // rmx_rollout_vjp_params (the ADJ_ZS instantiations of the two backward kernels, launched by that entry alone)
+    double* zs;               // [B][nslots][n] the adjoint vector z of every taped solve, lane = node (out); slots as the tape's
+};
+
+// rmx_rollout_vjp_params (rmx_params.h): one wavefront per rollout walks the slots of its tape
+struct ParamArgs {
+    int nsteps, nslots;       // nslots per rollout: nsteps (BDF1) or nsteps + 1 (BDF2: slot nsteps holds the SDIRK2a solve)
+    int bdf2;                 // the tape's integrator
+    int njoints;              // joints / bodies in the caller's listing (the rows of `inertia`)
+    double h;                 // the tape's
+    const double *q0, *qd0;   // [B][nr] the state the tape started from
+    const double *qt, *qdt;   // [B][nsteps][nr] q, qdot after every step
+    const double* zs;         // [B][nslots][n] z of every slot (AdjArgs::zs)
+    double *stiffness, *damping, *qrest;   // [B][nr] reduced DOF order; null: not wanted
+    double* inertia;          // [B][njoints][6] listing order; null: not wanted
+    double* grav;             // [B][3]; null: not wanted
+    short lst[MAXN];          // listing index of the body each node carries, -1: none (the inner nodes of a lowered multi-DOF joint)
 };
 
 // rmx_rollout_linearize (rmx_linearize.h): one wavefront per (rollout, slot) of the tape
@@ -166,6 +183,8 @@ struct rmx_batch {
     void RMX_CAT(launch_energy_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_adjoint_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
+    void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \
+    void RMX_CAT(launch_param_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a); \
     void RMX_CAT(launch_phase_, NPV)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d); \
     void RMX_CAT(launch_mfd_, NPV)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD); \
     void RMX_CAT(launch_mfd_ct_, NPV)(const rmx_model* m, const rmx_batch* b, double* dM, double* df, double* dD); \

@@ -826,6 +826,9 @@ constexpr int ADJ_TRK = 8;
 // SDIRK2a solve - which the adjoint pairs drop, with the reference - in slot nsteps; its backward sweep is a kernel of its own
 // (k_rollout_bwd_bdf2) that differentiates every solve exactly.  One wavefront per rollout, never the helper-wave form.
 constexpr int ADJ_TAPE = 16;
+// ZS (rmx_rollout_vjp_params, with TAPE; backward kernels only): the backward sweep also stores z of every solve (a.zs), which the
+// parameter contraction of rmx_params.h reads.  Compile-time: rmx_rollout_vjp keeps the instantiations it had.
+constexpr int ADJ_ZS = 32;
 constexpr int ADJ_TRK_ROWS = 18;      // sw[3], sv[3], Rw[9], pw[3], one column per node
 __host__ __device__ constexpr size_t adj_trk_doubles(const int NP) { return (size_t)ADJ_TRK_ROWS * NP; }
 template <int NP, int MODE, bool HELP = false, bool FC = false>
@@ -1211,7 +1214,9 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
     constexpr bool CTL = (MODE & ADJ_CTL) != 0;
     constexpr bool TRK = (MODE & ADJ_TRK) != 0;      // y_k: row k of dPdq where step k owns terms
     constexpr bool TAPE = (MODE & ADJ_TAPE) != 0;    // y_k: the caller's cotangents; du per step; the k = 0 row behind the loop
+    constexpr bool ZS = (MODE & ADJ_ZS) != 0;        // z_k of every step to a.zs as well
     static_assert(!TAPE || (CTL && !TRK && INTEG == 1), "the taped rollout: per-step controls, no objective, BDF1");
+    static_assert(!ZS || TAPE, "z per slot: the taped rollout");
     const DevModel M = model_view<NP, FC>(Min);
     const int lane = threadIdx.x, traj = blockIdx.x, n = M.n;
     const int id = (lane < n) ? M.idx[lane] : -1;
@@ -1278,6 +1283,9 @@ __global__ void __launch_bounds__(64) k_adjoint_bwd(const DevModel Min, const De
         }
         if constexpr (TAPE) {   // du_k = -z_k' dg_k/du_k, dg_k/du_k = -h^2 pscale I
             if (id >= 0) a.dPdu[((size_t)traj * a.nsteps + (k - 1)) * M.nr + id] = h * h * a.pscale * z;
+            if constexpr (ZS) {
+                if (lane < n) a.zs[((size_t)traj * a.nsteps + (k - 1)) * n + lane] = z;      // (nodes without a DOF: an identity row, z = 0)
+            }
         } else if constexpr (CTL) {    // the constant-parameter formula below before its sum over the steps, one row per step
             if (id >= 0) {
                 const size_t offk = ((size_t)traj * a.nsteps + (k - 1)) * M.nr + id;
@@ -1445,6 +1453,69 @@ __global__ void __launch_bounds__(64) k_rollout_bwd_bdf2(const DevModel Min, con
             a.dq0[off] = qb0;
             a.dqd0[off] = vb0;
         }
+    }
+}
+
+// k_rollout_bwd_bdf2 with z of every solve stored as well - a.zs, [B][nsteps + 1][n] in the tape's slots (zb in slot 0, za in slot
+// nsteps): the kernel of rmx_rollout_vjp_params.  A kernel of its own, statement for statement the one above plus the three stores:
+// as a flag of a shared body the compiler scheduled rmx_rollout_vjp's instantiation differently (other code, if the same results),
+// and that kernel keeps its code.
+template <int NP, bool FC = false>
+__global__ void __launch_bounds__(64) k_rollout_bwd_bdf2_zs(const DevModel Min, const DevOpts o, const AdjArgs a) {
+    const DevModel M = model_view<NP, FC>(Min);
+    const int lane = threadIdx.x, traj = blockIdx.x, n = M.n, N = a.nsteps;
+    const int id = (lane < n) ? M.idx[lane] : -1;
+    const bool dof = id >= 0;
+    const size_t nn = (size_t)n * n;
+    const double h = o.h;
+    const int col = lane < n ? lane : 0;
+    const double al = (2.0 - sqrt(2.0)) / 2.0;
+    const double* Hb = a.Hs + (size_t)traj * (N + 1) * nn;
+    const double* Mb = a.Ms + (size_t)traj * (N + 1) * nn;
+    const double* Db = a.Ds + (size_t)traj * (N + 1) * nn;
+    const size_t row0 = (size_t)traj * N * M.nr + (dof ? id : 0);      // this lane's entry of row 0 (step 1) of gq, gqd, du
+    // (the cotangent loads unconditional, the row clamped, lanes without a DOF and rows that do not exist selected to zero afterwards)
+    const double gqN = a.gq[row0 + (size_t)(N - 1) * M.nr], gdN = a.gqd[row0 + (size_t)(N - 1) * M.nr];
+    const double gqP = a.gq[row0 + (size_t)(N >= 2 ? N - 2 : 0) * M.nr], gdP = a.gqd[row0 + (size_t)(N >= 2 ? N - 2 : 0) * M.nr];
+    double qb1 = dof ? gqN : 0.0, vb1 = dof ? gdN : 0.0;                        // step k+1
+    double qb0 = (dof && N >= 2) ? gqP : 0.0, vb0 = (dof && N >= 2) ? gdP : 0.0;      // step k (step 0 has no cotangent of its own)
+    const double eta = (2.0 / 3.0) * h;
+    for (int k = N - 1; k >= 1; --k) {
+        const size_t rowm = row0 + (size_t)(k >= 2 ? k - 2 : 0) * M.nr;          // step k-1, in flight across the solve
+        const double gqm = a.gq[rowm], gdm = a.gqd[rowm];
+        double A, Bq, z;
+        tape_solve_bwd<NP>(Hb + (size_t)k * nn, Mb + (size_t)k * nn, Db + (size_t)k * nn, n, lane, col, dof, eta, qb1, vb1, A, Bq, z);
+        if (dof) a.dPdu[row0 + (size_t)k * M.nr] = eta * eta * a.pscale * z;
+        if (lane < n) a.zs[((size_t)traj * (N + 1) + k) * n + lane] = z;
+        const double s = A + Bq;
+        qb0 += (4.0 / 3.0) * s;
+        vb0 += (8.0 / 9.0) * h * Bq;
+        qb1 = qb0;
+        vb1 = vb0;
+        qb0 = ((dof && k >= 2) ? gqm : 0.0) - (1.0 / 3.0) * s;
+        vb0 = ((dof && k >= 2) ? gdm : 0.0) - (2.0 / 9.0) * h * Bq;
+    }
+    // the start step: qb1, vb1 are the cotangents of step 1, qb0, vb0 of the initial state
+    const double etas = al * h;
+    double A, Bq, zb, A2, B2, za;
+    tape_solve_bwd<NP>(Hb, Mb, Db, n, lane, col, dof, etas, qb1, vb1, A, Bq, zb);                   // SDIRK2b
+    qb0 += A + Bq;
+    vb0 += (2.0 * al - 1.0) * h * Bq;
+    const double qdab = (1.0 - al) * h * A + 2.0 * (1.0 - al) * h * Bq;
+    tape_solve_bwd<NP>(Hb + (size_t)N * nn, Mb + (size_t)N * nn, Db + (size_t)N * nn, n, lane, col, dof, etas, 0.0, qdab, A2, B2, za);      // SDIRK2a
+    qb0 += A2 + B2;
+    vb0 += al * h * B2;
+    if (dof) {
+        a.dPdu[row0] = etas * etas * a.pscale * (za + zb);
+        if (a.dq0) {
+            const size_t off = (size_t)traj * M.nr + id;
+            a.dq0[off] = qb0;
+            a.dqd0[off] = vb0;
+        }
+    }
+    if (lane < n) {
+        a.zs[(size_t)traj * (N + 1) * n + lane] = zb;
+        a.zs[((size_t)traj * (N + 1) + N) * n + lane] = za;
     }
 }
 

@@ -1,5 +1,6 @@
 """A differentiable controlled BDF1 or BDF2 rollout for PyTorch: ``rollout(sim, q0, qdot0, u)`` returns the trajectory, and
-``backward()`` of any loss on it yields dL/du, dL/dq0 and dL/dqdot0.
+``backward()`` of any loss on it yields dL/du, dL/dq0 and dL/dqdot0 - and, with ``params=model_params(sim)``, the gradient with respect to
+the model's own parameters (joint stiffness, damping and rest position, body inertia and mass, gravity; rmx_rollout_vjp_params_device).
 
 Forward is rmx_rollout_tape_device (rmx_rollout_tape_bdf2_device under integrator=2), backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
 objective lives wholly on the PyTorch side.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
@@ -20,7 +21,9 @@ def _function():
 
     class _Rollout(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, q0, qdot0, u, sim, h, pscale, check, integrator):
+        def forward(ctx, q0, qdot0, u, sim, h, pscale, check, integrator, names=(), *ptensors):
+            # (names, ptensors: the model parameters of rollout(params=...); the forward does not read their values)
+            ctx.names = tuple(names)
             B, nsteps, nr = u.shape
             q0c, qd0c, uc = q0.contiguous(), qdot0.contiguous(), u.contiguous()
             qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
@@ -50,8 +53,15 @@ def _function():
             dq0 = torch.empty((sim.B, sim.nr), dtype=torch.float64, device=dev)
             dqd0 = torch.empty_like(dq0)
             torch.cuda.current_stream(dev).synchronize()
-            sim.rollout_vjp_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr())
-            return dq0, dqd0, du, None, None, None, None, None
+            if not ctx.names:
+                sim.rollout_vjp_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr())
+                return dq0, dqd0, du, None, None, None, None, None
+            shapes = sim._param_shapes()
+            rows = {n: torch.zeros((sim.B,) + shapes[n], dtype=torch.float64, device=dev) for n in ctx.names}
+            sim.rollout_vjp_params_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr(),
+                                          **{n + "_ptr": rows[n].data_ptr() for n in ctx.names})
+            # one row per rollout from the library; the rollouts share the model, so the parameter's gradient is their sum
+            return (dq0, dqd0, du, None, None, None, None, None, None) + tuple(rows[n].sum(dim=0) for n in ctx.names)
 
     _Function = _Rollout
     return _Function
@@ -75,7 +85,63 @@ def _check_inputs(sim, q0, qdot0, u):
             raise ValueError("rollout: %s must have shape (%d, %d), got %r" % (name, sim.B, sim.nr, tuple(t.shape)))
 
 
-def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
+def model_params(sim):
+    """The model parameters of ``sim`` (a BatchSim) the taped rollout can be differentiated by, as float64 leaf tensors on the sim's
+    device that hold the model's values and require grad: "stiffness", "damping", "qrest" [nr] in reduced DOF order (a value the
+    scene sets per joint is repeated for every DOF of a multi-DOF joint), "inertia" [njoints][6] in listing order (the layout of
+    desc.I_i: the rotational inertia, then three times the mass) and "grav" [3].  Pass the dict, or part of it, as ``params`` of rollout."""
+    import numpy as np
+    import torch
+    from . import _abi
+    n, nr = int(sim._desc.njoints), sim.nr
+    idx = np.zeros(n, dtype=np.int32)
+    _abi.check(sim._L.rmx_model_idxR(sim._model, _abi.iptr(idx)), "rmx_model_idxR")
+    keep = sim._keep
+    qrr = keep.get("qRestR")
+    vals = {k: np.zeros(nr) for k in ("stiffness", "damping", "qrest")}
+    starts = sorted(int(i) for i in idx if i >= 0) + [nr]
+    for j in range(n):
+        if idx[j] < 0:
+            continue
+        end = starts[starts.index(int(idx[j])) + 1]      # the DOFs of joint j: idx[j] .. the next joint's first DOF
+        for k, r in enumerate(range(int(idx[j]), end)):
+            vals["stiffness"][r] = keep["stiffness"][j]
+            vals["damping"][r] = keep["damping"][j]
+            vals["qrest"][r] = qrr[r] if qrr is not None and len(qrr) == nr else (keep["qRest"][j] if k == 0 else 0.0)
+    vals["inertia"] = np.asarray(keep["I_i"], dtype=np.float64).reshape(n, 6)
+    vals["grav"] = np.array([sim._desc.grav[i] for i in range(3)])
+    dev = torch.device("cuda", sim.device)
+    return {k: torch.tensor(v, dtype=torch.float64, device=dev, requires_grad=True) for k, v in vals.items()}
+
+
+def _check_params(sim, params):
+    """params of rollout -> (names, tensors) in the order of rmx_param_grads; ValueError for anything the library cannot fill."""
+    import torch
+    from . import _abi
+    if not isinstance(params, dict):
+        raise ValueError("rollout: params must be a dict of tensors (model_params(sim) or part of it), got %s" % type(params).__name__)
+    unknown = [k for k in params if k not in _abi.PARAM_NAMES]
+    if unknown:
+        raise ValueError("rollout: unknown model parameter %r (known: %s)" % (unknown[0], ", ".join(_abi.PARAM_NAMES)))
+    if not params:
+        raise ValueError("rollout: params names no parameter (pass None for a rollout without parameter gradients)")
+    dev = torch.device("cuda", sim.device)
+    shapes = sim._param_shapes()
+    names = tuple(n for n in _abi.PARAM_NAMES if n in params)
+    for n in names:
+        t = params[n]
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("rollout: params[%r] must be a torch.Tensor, got %s" % (n, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("rollout: params[%r] must be float64, got %s" % (n, t.dtype))
+        if t.device != dev:
+            raise ValueError("rollout: params[%r] must be on %s (the sim's device), got %s" % (n, dev, t.device))
+        if tuple(t.shape) != shapes[n]:
+            raise ValueError("rollout: params[%r] must have shape %r, got %r" % (n, shapes[n], tuple(t.shape)))
+    return names, tuple(params[n] for n in names)
+
+
+def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, params=None):
     """A controlled BDF1 (integrator=1) or BDF2 (integrator=2) rollout of every trajectory of ``sim`` (a BatchSim) that autograd can differentiate.
 
     q0, qdot0: [B][nr]; u: [B][nsteps][nr], one torque per joint and step (tau + pscale*u at step k) - float64 tensors on the sim's
@@ -85,12 +151,21 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     the tape, and backward raises RuntimeError("the tape of this rollout has been replaced") then.
     Under integrator=2 the rollout starts itself with SDIRK2 from (q0, qdot0): row 0 is the state after the two-stage start step
     (u[:, 0] holds for both stages), row k-1 for k >= 2 the state after the BDF2 step from steps k-1 and k-2; the gradients are
-    exact through the start step too.  Any other integrator raises ValueError."""
+    exact through the start step too.  Any other integrator raises ValueError.
+    params: None, or a dict of model-parameter tensors - model_params(sim) or any part of it ("stiffness", "damping", "qrest",
+    "inertia", "grav").  backward() then also accumulates into each given tensor's .grad the gradient of the loss with respect to
+    that parameter, summed over the batch (one rmx_rollout_vjp_params call).  The forward does NOT read the tensors' values: the sim
+    simulates the model it was built from, so the tensors must describe that model, and a parameter update means building a new
+    BatchSim from the updated scene.  Unknown names and tensors of another shape, dtype or device raise ValueError."""
     import torch
     if integrator not in (1, 2):
         raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
     _check_inputs(sim, q0, qdot0, u)
-    return _function().apply(q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check), integrator)
+    args = (q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check), integrator)
+    if params is None:
+        return _function().apply(*args)
+    names, tensors = _check_params(sim, params)
+    return _function().apply(*args, names, *tensors)
 
 
 def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):

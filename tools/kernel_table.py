@@ -34,6 +34,16 @@ ROWS = (  # (name fragment, what it runs)
     ("k_rollout_linearize<16>", "rmx_rollout_linearize: 9..16 nodes"),
     ("k_rollout_linearize<32>", "rmx_rollout_linearize: 17..32 nodes, the four blocks in one pass"),
     ("k_rollout_linearize<64>", "rmx_rollout_linearize: 33..64 nodes, half a right-hand block per pass"),
+    ("k_rollout_param_grad<4>", "rmx_rollout_vjp_params (the contraction over the slots of a tape; one wavefront per rollout): <= 4 nodes"),
+    ("k_rollout_param_grad<8>", "rmx_rollout_vjp_params: 5..8 nodes"),
+    ("k_rollout_param_grad<16>", "rmx_rollout_vjp_params: 9..16 nodes"),
+    ("k_rollout_param_grad<32>", "rmx_rollout_vjp_params: 17..32 nodes"),
+    ("k_rollout_param_grad<64>", "rmx_rollout_vjp_params: 33..64 nodes"),
+    ("k_adjoint_bwd<16, 53, true>", "rmx_rollout_vjp_params: the BDF1 backward sweep that also stores z per slot, full 16-link chain"),
+    ("k_adjoint_bwd<32, 53, false>", "the same, 17..32 nodes"),
+    ("k_adjoint_bwd<64, 53, false>", "the same, 33..64 nodes"),
+    ("k_rollout_bwd_bdf2_zs<16, true>", "rmx_rollout_vjp_params on a BDF2 tape: backward sweep with z per slot, full 16-link chain"),
+    ("k_rollout_bwd_bdf2_zs<64, false>", "the same, 33..64 nodes"),
     ("k_step_bdf1<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF1"),
     ("k_step_bdf2<32, true, false, false, 0>", "generic contact / Euler-chart kernel, <= 32 nodes, BDF2"),
     ("k_big_step", "trees of 65..256 nodes (one workgroup per rollout)"),

@@ -15,7 +15,11 @@ one process, and the ratios BDF2 / BDF1 are formed; writes profiles/rollout_vjp_
 512 x 20 of the 16-link chain (the configs[3] shape), 512 x 20 of the 32-link chain and 256 x 20 of a 40-link chain; writes
 profiles/rollout_linearize_bench.json.
 
-    python tools/rollout_vjp_bench.py [--reps 20] [--integrator 1 2] [--linearize]"""
+--params: rmx_rollout_vjp_params_device (du, dq0, dqd0 and all five parameter gradients: the z-storing backward sweep and the
+contraction over the slots, one kernel each) beside the tape and vjp calls of the same run, BDF1, at 512 x 20 of the 16-, 32- and
+40-link chains; writes profiles/rollout_params_bench.json.
+
+    python tools/rollout_vjp_bench.py [--reps 20] [--integrator 1 2] [--linearize] [--params]"""
 import argparse
 import ctypes as C
 import json
@@ -101,6 +105,64 @@ def main_linearize(args):
     print(json.dumps(out, indent=1))
 
 
+PARAM_SHAPES = ((16, 512, 20), (32, 512, 20), (40, 512, 20))      # (links, rollouts, steps)
+
+
+def main_params(args):
+    """tape, vjp and vjp_params alternate per shape; one rehearsal round, then the median of --reps rounds of the kernel time by the
+    library's events (rmx_last_step_ms) and of the host wall clock."""
+    sys.path.insert(0, ROOT)
+    from redmax_amd import BatchSim
+    from redmax_amd.scenes import sceneAdjointChain
+    out = {"workload": "BDF1 tape of a serial chain; device pointers; vjp_params with all five outputs (and with the three joint "
+                       "outputs alone); median of %d rounds after one rehearsal" % args.reps, "shapes": {}}
+    rng = np.random.default_rng(20240)
+    for n, b, k in PARAM_SHAPES:
+        sc = sceneAdjointChain(n)
+        sc.init()
+        nr = sc.nr
+        q0, qd0 = sc.getQ()
+        sim = BatchSim(sc, batch=b)
+        u = 0.1 * rng.standard_normal((b, k, nr))
+        ud, qt, qdt, dud = Dev(u), Dev(np.zeros_like(u)), Dev(np.zeros_like(u)), Dev(np.zeros_like(u))
+        gq, gqd = Dev(rng.standard_normal(u.shape)), Dev(rng.standard_normal(u.shape))
+        dq0, dqd0 = Dev(np.zeros((b, nr))), Dev(np.zeros((b, nr)))
+        q0d, qd0d = Dev(np.repeat(q0[None], b, axis=0)), Dev(np.repeat(qd0[None], b, axis=0))
+        shapes = sim._param_shapes()
+        G = {name: Dev(np.zeros((b,) + sh)) for name, sh in shapes.items()}
+        rows = {"rollout_tape": [], "rollout_vjp": [], "rollout_vjp_params": [], "rollout_vjp_params_joints_only": []}
+
+        def timed(call, fn):
+            t0 = time.perf_counter()
+            fn()
+            rows[call].append(((time.perf_counter() - t0) * 1e3, sim._L.rmx_last_step_ms(sim._batch)))
+
+        for _ in range(1 + args.reps):
+            sim.set_state_device(q0d.ptr, qd0d.ptr)
+            timed("rollout_tape", lambda: sim.rollout_tape_device(k, sc.h, ud.ptr, qt.ptr, qdt.ptr, pscale=sc.task["pscale"]))
+            timed("rollout_vjp", lambda: sim.rollout_vjp_device(k, gq.ptr, gqd.ptr, dud.ptr, dq0.ptr, dqd0.ptr))
+            timed("rollout_vjp_params", lambda: sim.rollout_vjp_params_device(k, gq.ptr, gqd.ptr, dud.ptr, dq0.ptr, dqd0.ptr,
+                                                                              **{name + "_ptr": G[name].ptr for name in G}))
+            timed("rollout_vjp_params_joints_only", lambda: sim.rollout_vjp_params_device(
+                k, gq.ptr, gqd.ptr, dud.ptr, dq0.ptr, dqd0.ptr, stiffness_ptr=G["stiffness"].ptr, damping_ptr=G["damping"].ptr, qrest_ptr=G["qrest"].ptr))
+        finite = bool(all(np.isfinite(g.get()).all() and np.abs(g.get()).max() > 0 for g in G.values()))
+        sim.close()
+        for d in [ud, qt, qdt, dud, gq, gqd, dq0, dqd0, q0d, qd0d] + list(G.values()):
+            Dev.hip.hipFree(d.p)
+        med = {c + "_device": {"wall_ms": float(np.median([r[0] for r in v[1:]])), "kernel_ms": float(np.median([r[1] for r in v[1:]]))}
+               for c, v in rows.items()}
+        kp = med["rollout_vjp_params_device"]["kernel_ms"]
+        med["vjp_params_over_tape_kernel"] = kp / med["rollout_tape_device"]["kernel_ms"]
+        med["vjp_params_over_vjp_kernel"] = kp / med["rollout_vjp_device"]["kernel_ms"]
+        med["outputs_finite_and_nonzero"] = finite
+        out["shapes"]["%d-link chain, %d rollouts x %d steps" % (n, b, k)] = med
+    path = args.out or os.path.join(ROOT, "profiles", "rollout_params_bench.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -108,9 +170,12 @@ def main():
                     help="1 BDF1, 2 BDF2; both: they alternate in one process and the ratios BDF2 / BDF1 are formed")
     ap.add_argument("--out", default=None)
     ap.add_argument("--linearize", action="store_true", help="time rmx_rollout_linearize_device beside tape and vjp at three shapes")
+    ap.add_argument("--params", action="store_true", help="time rmx_rollout_vjp_params_device beside tape and vjp at three shapes")
     args = ap.parse_args()
     if args.linearize:
         return main_linearize(args)
+    if args.params:
+        return main_params(args)
     integs = sorted(set(args.integrator))
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "rollout_vjp_bench.json" if integs == [1] else "rollout_vjp_bench_bdf2.json")
