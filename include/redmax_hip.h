@@ -499,6 +499,43 @@ int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const d
 int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU);
 int rmx_rollout_linearize_device(rmx_batch* b, int nsteps, double* d_XA, double* d_XB, double* d_XU);
 
+/* Forward-mode tangents of the taped rollout: J t, the perturbation of the whole trajectory for a perturbation of the controls and of
+ * the initial state - what Gauss-Newton / Levenberg-Marquardt / CG shooting (J'(J t)), sensitivity analysis and forward-mode automatic
+ * differentiation ask for.  One sweep over the tape, one elimination of H per slot shared by all directions of the call; nothing but
+ * the tangent trajectory is written.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * Every taped solve is x(qA, qB, u) with dg/dx = H, dg/dqA = eta D, dg/dqB = -M, dg/du = -eta^2 pscale I (rmx_rollout_tape_bdf2 and
+ * rmx_rollout_linearize above), so
+ *     solve_fwd(slot; dqA, dqB, du):   H dx = -eta D dqA + M dqB + eta^2 pscale du ;   dv = (dx - dqA)/eta
+ * BDF1 (eta = h, slot k-1 is step k), for k = 1 .. N from (dq_0, dqd_0) = (tq0, tqd0):
+ *     (dq_k, dqd_k) = solve_fwd(slot k-1; dq_{k-1}, dq_{k-1} + h dqd_{k-1}, tu_k)
+ * BDF2 (al = (2 - sqrt 2)/2; eta = al h in slots 0 and N, 2h/3 in the others; step 1's tangent tu_1 holds for both start solves):
+ *     SDIRK2a (slot N): (dqa, dqda)   = solve_fwd(dq0, dq0 + al h dqd0, tu_1)
+ *     SDIRK2b (slot 0): (dq_1, dqd_1) = solve_fwd(dq0 + (1-al) h dqda, dq0 + (2al-1) h dqd0 + 2(1-al) h dqda, tu_1)
+ *     BDF2    (slot k, k = 1 .. N-1): dqA = 4/3 dq_k - 1/3 dq_{k-1} ;  dqB = dqA + 8/9 h dqd_k - 2/9 h dqd_{k-1}
+ *                                     (dq_{k+1}, dqd_{k+1}) = solve_fwd(dqA, dqB, tu_{k+1})
+ * It is the transpose of rmx_rollout_vjp on the same tape: for cotangents (gq, gqd) with (du, dq0, dqd0) = rmx_rollout_vjp(gq, gqd),
+ *     <gq, tq> + <gqd, tqd> = <du, tu> + <dq0, tq0> + <dqd0, tqd0>.
+ *
+ * rmx_rollout_jvp reads the tape of the preceding rmx_rollout_tape / rmx_rollout_tape_bdf2 on the batch and follows the integrator of
+ * the tape it finds, as rmx_rollout_vjp and rmx_rollout_linearize do; h and pscale are the tape's.  ntan >= 1 tangent directions per
+ * rollout.  tu: host [batch][ntan][nsteps][nr] (one direction has the layout of u); tq0, tqd0: [batch][ntan][nr].  Each of the three
+ * may be NULL - zero - but not all three.  tq, tqd: [batch][ntan][nsteps][nr], row k-1 the tangent of the state after step k; both
+ * required.  Reduced DOF order throughout.
+ *
+ * The call changes neither the batch's state nor the tape: it may be repeated, and rmx_rollout_vjp, rmx_rollout_linearize and
+ * rmx_rollout_vjp_params return the same bits before and after it.  The pivots of a slot's elimination depend on H alone and the
+ * directions never mix: one direction's result has the same bits whatever ntan is, wherever the direction stands in the call, and
+ * whether a zero input is NULL or an array of zeros.  Refusals (RMX_E_INVALID), in rmx_rollout_vjp's words where they coincide: "no
+ * tape", an nsteps that differs from the tape's, a null batch, tq or tqd ("null argument"), "ntan < 1", "all tangents are null".  The
+ * rows of a rollout whose tape call reported a failed Newton solve (stats->status) are unspecified.  The host form stages through a
+ * device allocation of its own, freed before it returns; the tape's workspace does not grow.  The _device form: DEVICE pointers,
+ * nothing staged; it returns when the kernel has finished. */
+int rmx_rollout_jvp(rmx_batch* b, int nsteps, int ntan, const double* tu, const double* tq0, const double* tqd0,
+                    double* tq, double* tqd);
+int rmx_rollout_jvp_device(rmx_batch* b, int nsteps, int ntan, const double* d_tu, const double* d_tq0, const double* d_tqd0,
+                           double* d_tq, double* d_tqd);
+
 /* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
  * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of
  * RMX_VERSION (it stays 111): probe for the symbols.

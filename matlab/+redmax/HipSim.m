@@ -204,5 +204,20 @@ classdef HipSim < handle
 				[XA, XB, XU] = redmax_hip_mex('rollout_linearize', this.h, nsteps);
 			end
 		end
+
+		function [tq, tqd] = rolloutJvp(this, nsteps, tu, tq0, tqd0)
+			% forward-mode tangents of the last rolloutTape: for tangents of the controls tu (nr x nsteps x T x B) and of the initial
+			% state tq0, tqd0 (nr x T x B), T directions per rollout in one sweep over the tape, tq and tqd (nr x nsteps x T x B)
+			% are the tangents of the state after every step.  [] for any of the three means zero (not all).  With du, dq0, dqd0
+			% of rolloutVjp for cotangents gq, gqd:  gq(:)'*tq(:) + gqd(:)'*tqd(:) == du(:)'*tu(:) + dq0(:)'*tq0(:) + dqd0(:)'*tqd0(:).
+			% The tape and the state stay as they are.
+			if nargin < 4
+				tq0 = [];
+			end
+			if nargin < 5
+				tqd0 = [];
+			end
+			[tq, tqd] = redmax_hip_mex('rollout_jvp', this.h, nsteps, tu, tq0, tqd0);
+		end
 	end
 end

@@ -73,6 +73,10 @@
  *                  the model's parameters, one column per rollout: joint stiffness dk, damping dd and rest position dqrest (nr x B,
  *                  reduced DOF order), body inertia dI (6 x njoints x B, the layout of desc.I_i) and gravity dgrav (3 x B).  The
  *                  gradient of a parameter the rollouts share is the sum over B.
+ *   [tq,tqd] = redmax_hip_mex('rollout_jvp', h, nsteps, tu, tq0, tqd0)  rmx_rollout_jvp on the tape of the last 'rollout_tape': the
+ *                  tangents of the whole trajectory, tq, tqd (nr x nsteps x ntan x B), for tangents of the controls tu (nr x nsteps x
+ *                  ntan x B) and of the initial state tq0, tqd0 (nr x ntan x B); ntan directions per rollout, taken from the arrays'
+ *                  sizes.  [] for any of the three: zero (not all three).
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -686,6 +690,44 @@ static void cmd_rollout_linearize(int nlhs, mxArray* plhs[], int nrhs, const mxA
     for (int i = 0; i < nout; ++i) plhs[i] = X[i];
 }
 
+/* one tangent argument of 'rollout_jvp': [] (NULL: zero) or a double array of `per` * ntan * B elements; *ntan is set by the first
+ * array given and the others must agree */
+static const double* tangent_arg(const mxArray* a, const handle_t* h, size_t per, size_t* ntan, const char* what) {
+    if (mxIsEmpty(a)) return NULL;
+    const size_t n = mxGetNumberOfElements(a), unit = per * (size_t)h->B;
+    if (!mxIsDouble(a) || mxIsComplex(a) || n % unit != 0 || (*ntan && n != unit * *ntan))
+        mexErrMsgIdAndTxt("redmax:hip", "rollout_jvp: %s must be a real double array of %d x ntan x %d elements, the same ntan in every array",
+                          what, (int)per, h->B);
+    *ntan = n / unit;
+    return mxGetPr(a);
+}
+
+static void cmd_rollout_jvp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 6) die("usage: [tq,tqd] = redmax_hip_mex('rollout_jvp', h, nsteps, tu, tq0, tqd0)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_jvp: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps;
+    size_t ntan = 0;
+    const double* tu = tangent_arg(prhs[3], h, per, &ntan, "tu");          /* nr x nsteps x ntan x B */
+    const double* tq0 = tangent_arg(prhs[4], h, nr, &ntan, "tq0");         /* nr x ntan x B */
+    const double* tqd0 = tangent_arg(prhs[5], h, nr, &ntan, "tqd0");
+    if (!ntan) ntan = 1;      /* (every tangent empty: the library refuses it in its own words) */
+    const size_t dims[4] = {nr, (size_t)nsteps, ntan, (size_t)h->B};
+    mxArray* tq = mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* tqd = mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        if (rmx_rollout_jvp(b, nsteps, (int)ntan, tu ? tu + f * ntan * per : NULL, tq0 ? tq0 + f * ntan * nr : NULL,
+                            tqd0 ? tqd0 + f * ntan * nr : NULL, mxGetPr(tq) + f * ntan * per, mxGetPr(tqd) + f * ntan * per))
+            die_rmx("rmx_rollout_jvp");
+    }
+    plhs[0] = tq;
+    if (nlhs > 1) plhs[1] = tqd;
+    else mxDestroyArray(tqd);
+}
+
 /* field k of element i of the struct array task.terms */
 static const mxArray* term_field(const mxArray* terms, size_t i, const char* k) {
     const mxArray* f = mxGetField(terms, i, k);
@@ -786,7 +828,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", NULL};
+                                             "rollout_vjp_params", "rollout_jvp", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -899,6 +941,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_linearize(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp_params")) {
         cmd_rollout_vjp_params(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_jvp")) {
+        cmd_rollout_jvp(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

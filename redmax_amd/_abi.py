@@ -28,6 +28,7 @@ SYMBOLS = (
     "rmx_rollout_tape_bdf2", "rmx_rollout_tape_bdf2_device",
     "rmx_rollout_linearize", "rmx_rollout_linearize_device",
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
+    "rmx_rollout_jvp", "rmx_rollout_jvp_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -157,6 +158,8 @@ def lib():
     L.rmx_rollout_vjp_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.rmx_rollout_linearize.argtypes = [vp, C.c_int, _dp, _dp, _dp]
     L.rmx_rollout_linearize_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.rmx_rollout_jvp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]
+    L.rmx_rollout_jvp_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

@@ -544,6 +544,38 @@ class BatchSim:
         _abi.check(self._L.rmx_rollout_linearize_device(self._batch, int(nsteps), C.c_void_p(XA_ptr or None), C.c_void_p(XB_ptr or None),
                                                         C.c_void_p(XU_ptr or None)), "rmx_rollout_linearize_device")
 
+    def rollout_jvp(self, nsteps, tu=None, tq0=None, tqd0=None):
+        """rmx_rollout_jvp on the tape of the last rollout_tape: the tangents of the whole trajectory for tangents of the controls,
+        tu [B][T][nsteps][nr], and of the initial state, tq0, tqd0 [B][T][nr] - T directions per rollout in one sweep over the tape.
+        Any of the three may be None (zero), not all.  Returns (tq, tqd), both [B][T][nsteps][nr]: row k-1 is the tangent of the state
+        after step k.  T comes from the inputs; a tu of [B][nsteps][nr] or a tq0 / tqd0 of [B][nr] is one direction, and the T axis is
+        dropped again in the result.  Neither the state nor the tape changes."""
+        nsteps = int(nsteps)
+        arrs = {n: np.ascontiguousarray(a, dtype=np.float64) for n, a in (("tu", tu), ("tq0", tq0), ("tqd0", tqd0)) if a is not None}
+        if not arrs:
+            raise ValueError("rollout_jvp: all tangents are None")
+        tail = {"tu": (nsteps, self.nr), "tq0": (self.nr,), "tqd0": (self.nr,)}
+        single = all(a.ndim == 1 + len(tail[n]) for n, a in arrs.items())
+        if single:
+            arrs = {n: np.ascontiguousarray(a[:, None]) for n, a in arrs.items()}
+        T = max([a.shape[1] for a in arrs.values() if a.ndim >= 2] + [1])
+        for n, a in arrs.items():
+            if a.shape != (self.B, T) + tail[n]:
+                raise ValueError("rollout_jvp: %s must have shape %r - or, every input alike, that shape without the direction axis -, "
+                                 "got %r" % (n, (self.B, T) + tail[n], a.shape[:1] + a.shape[2:] if single else a.shape))
+        tq = np.empty((self.B, T, nsteps, self.nr))
+        tqd = np.empty_like(tq)
+        _abi.check(self._L.rmx_rollout_jvp(self._batch, nsteps, T, _abi.dptr(arrs.get("tu")), _abi.dptr(arrs.get("tq0")),
+                                           _abi.dptr(arrs.get("tqd0")), _abi.dptr(tq), _abi.dptr(tqd)), "rmx_rollout_jvp")
+        return (tq[:, 0], tqd[:, 0]) if single else (tq, tqd)
+
+    def rollout_jvp_device(self, nsteps, ntan, tu_ptr, tq0_ptr, tqd0_ptr, tq_ptr, tqd_ptr):
+        """rollout_jvp with DEVICE pointers (integers): tu [B][ntan][nsteps][nr], tq0, tqd0 [B][ntan][nr], 0 / None: zero (not all
+        three); tq, tqd [B][ntan][nsteps][nr]."""
+        _abi.check(self._L.rmx_rollout_jvp_device(self._batch, int(nsteps), int(ntan), C.c_void_p(tu_ptr or None), C.c_void_p(tq0_ptr or None),
+                                                  C.c_void_p(tqd0_ptr or None), C.c_void_p(tq_ptr or None), C.c_void_p(tqd_ptr or None)),
+                   "rmx_rollout_jvp_device")
+
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent
         variant the library chose."""

@@ -2,6 +2,7 @@
 // JointSpherical) plus Euler, adjoint, phase timing.
 #include "rmx_kernels.h"
 #include "rmx_linearize.h"
+#include "rmx_jvp.h"
 #include "rmx_params.h"
 
 void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
@@ -77,6 +78,12 @@ void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int int
 void RMX_CAT(launch_linearize_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LinArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nslots)), block(64);
     k_rollout_linearize<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+}
+
+// rmx_rollout_jvp: one wavefront per rollout and chunk of tangent directions
+void RMX_CAT(launch_jvp_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a) {
+    const dim3 grid((unsigned)((size_t)b->B * a.nchunks)), block(64);
+    k_rollout_jvp<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
 
 // rmx_rollout_vjp_params: the backward sweep of the tape's integrator in its ADJ_ZS instantiation (du, dq0, dqd0 as rmx_rollout_vjp's

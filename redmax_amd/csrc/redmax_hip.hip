@@ -1812,6 +1812,77 @@ static int rollout_linearize_impl(rmx_batch* b, int nsteps, double* XA, double* 
     return RMX_OK;
 }
 
+// rmx_rollout_jvp: the forward sweep over the tape, one kernel over B * ceil(ntan / JVP_TW) wavefronts (rmx_jvp.h).  The host form
+// stages through an allocation of its own, as rmx_rollout_linearize does: the staging areas of the tape's workspace are shaped for one
+// direction, and a regrow would lose the tape.
+static int rollout_jvp_impl(rmx_batch* b, int nsteps, int ntan, const double* tu, const double* tq0, const double* tqd0, double* tq,
+                            double* tqd, const bool on_device) {
+    if (!b || !tq || !tqd) return fail(RMX_E_INVALID, "rmx_rollout_jvp: null argument");
+    if (ntan < 1) return fail(RMX_E_INVALID, "rmx_rollout_jvp: ntan < 1");
+    if (!tu && !tq0 && !tqd0) return fail(RMX_E_INVALID, "rmx_rollout_jvp: all tangents are null");
+    rmx_model* m = b->m;
+    if (b->tape_nsteps < 1 || !b->adjws)
+        return fail(RMX_E_INVALID, "rmx_rollout_jvp: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_jvp: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+    HIPCHK(hipSetDevice(m->device));
+    int rc = pending_error_check(b, "rmx_rollout_jvp");
+    if (rc) return rc;
+    const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_jvp: no tape (the workspace is smaller than the tape)");
+    char* ws = (char*)b->adjws;
+    JvpArgs a{};
+    a.nsteps = nsteps;
+    a.nslots = nsteps + (b->tape_integ == INTEG_BDF2 ? 1 : 0);
+    a.bdf2 = b->tape_integ == INTEG_BDF2 ? 1 : 0;
+    a.ntan = ntan;
+    a.nchunks = (ntan + JVP_CHUNK - 1) / JVP_CHUNK;
+    a.h = b->tape_h;
+    a.pscale = b->tape_pscale;
+    a.Hs = (const double*)(ws + t.off[0]); a.Ms = (const double*)(ws + t.off[1]); a.Ds = (const double*)(ws + t.off[2]);
+    if ((size_t)b->B * a.nchunks > (size_t)0x7fffffff) return fail(RMX_E_INVALID, "rmx_rollout_jvp: batch * chunks of directions exceeds the grid");
+    const size_t bytes_traj = (size_t)b->B * ntan * nsteps * m->nr * sizeof(double), bytes_state = (size_t)b->B * ntan * m->nr * sizeof(double);
+    const double* in[3] = {tu, tq0, tqd0};
+    const size_t in_bytes[3] = {bytes_traj, bytes_state, bytes_state};
+    const double* din[3] = {tu, tq0, tqd0};
+    double* dout[2] = {tq, tqd};
+    char* stage = nullptr;
+    if (!on_device) {
+        const size_t pitch_traj = (bytes_traj + 255) & ~(size_t)255, pitch_state = (bytes_state + 255) & ~(size_t)255;
+        const size_t want = 2 * pitch_traj + (tu ? pitch_traj : 0) + (tq0 ? pitch_state : 0) + (tqd0 ? pitch_state : 0);
+        const hipError_t em = hipMalloc((void**)&stage, want ? want : 256);
+        if (em == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, "rmx_rollout_jvp: no device memory for the staging of the tangents"); }
+        if (em != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_jvp: ") + hipGetErrorString(em));
+        dout[0] = (double*)stage;
+        dout[1] = (double*)(stage + pitch_traj);
+        size_t at = 2 * pitch_traj;
+        for (int i = 0; i < 3; ++i)
+            if (in[i]) { din[i] = (const double*)(stage + at); at += i == 0 ? pitch_traj : pitch_state; }
+    }
+    a.tu = din[0]; a.tq0 = din[1]; a.tqd0 = din[2];
+    a.tq = dout[0]; a.tqd = dout[1];
+    hipError_t e = hipSuccess;
+    if (bytes_traj) {
+        for (int i = 0; i < 3 && !on_device; ++i)
+            if (e == hipSuccess && in[i]) e = hipMemcpyAsync((void*)din[i], in[i], in_bytes[i], hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
+        if (e == hipSuccess) {
+            DISPATCH_NP(m->NP, launch_jvp, m, b, a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+        if (e == hipSuccess && !on_device) {
+            e = hipMemcpyAsync(tq, dout[0], bytes_traj, hipMemcpyDeviceToHost, b->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(tqd, dout[1], bytes_traj, hipMemcpyDeviceToHost, b->stream);
+        }
+        if (e == hipSuccess) e = wait_stream_short(b->stream);
+        else (void)hipStreamSynchronize(b->stream);      // (the tangents must outlive their copies)
+    }
+    if (stage) (void)hipFree(stage);
+    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_jvp: ") + hipGetErrorString(e));
+    if (bytes_traj) take_event_time(b);
+    return RMX_OK;
+}
+
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                 double* qdtraj, rmx_stats* stats) {
     return rollout_tape_impl(b, opts, nsteps, pscale, u, qtraj, qdtraj, stats, false);
@@ -1848,6 +1919,14 @@ extern "C" int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, doubl
 }
 extern "C" int rmx_rollout_linearize_device(rmx_batch* b, int nsteps, double* d_XA, double* d_XB, double* d_XU) {
     return rollout_linearize_impl(b, nsteps, d_XA, d_XB, d_XU, true);
+}
+extern "C" int rmx_rollout_jvp(rmx_batch* b, int nsteps, int ntan, const double* tu, const double* tq0, const double* tqd0, double* tq,
+                               double* tqd) {
+    return rollout_jvp_impl(b, nsteps, ntan, tu, tq0, tqd0, tq, tqd, false);
+}
+extern "C" int rmx_rollout_jvp_device(rmx_batch* b, int nsteps, int ntan, const double* d_tu, const double* d_tq0, const double* d_tqd0,
+                                      double* d_tq, double* d_tqd) {
+    return rollout_jvp_impl(b, nsteps, ntan, d_tu, d_tq0, d_tqd0, d_tq, d_tqd, true);
 }
 
 static int track_refusal(const rmx_task_track* task, const double* xtarget, int integrator) {

@@ -104,6 +104,19 @@ struct LinArgs {
     double *XA, *XB, *XU;     // [B][nslots][nr*nr], entry j*nr + i = dx_i/d(.)_j in reduced order; null: not wanted
 };
 
+// rmx_rollout_jvp (rmx_jvp.h): one wavefront per (rollout, chunk of JVP_CHUNK tangent directions) walks the slots of the tape forwards
+constexpr int JVP_CHUNK = 8;     // tangent directions per wavefront (rmx_jvp.h JVP_TW: the register budget at 64 lanes)
+struct JvpArgs {
+    int nsteps, nslots;       // nslots per rollout: nsteps (BDF1) or nsteps + 1 (BDF2: slot nsteps holds the SDIRK2a solve)
+    int bdf2;                 // the tape's integrator
+    int ntan, nchunks;        // tangent directions per rollout, and the chunks of JVP_CHUNK they make: the grid is B * nchunks
+    double h, pscale;         // the tape's
+    const double *Hs, *Ms, *Ds;   // [B][nslots][n*n], entry (row r, column c) at c*n + r
+    const double* tu;         // [B][ntan][nsteps][nr], or null: zero
+    const double *tq0, *tqd0; // [B][ntan][nr], or null: zero
+    double *tq, *tqd;         // [B][ntan][nsteps][nr] (out)
+};
+
 struct rmx_model {
     int device = 0;
     int n = 0, nr = 0, nm = 0, NP = 0;   // n: 1-DOF nodes on the device (after lowering multi-DOF joints)
@@ -183,6 +196,7 @@ struct rmx_batch {
     void RMX_CAT(launch_energy_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_adjoint_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
+    void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \
     void RMX_CAT(launch_param_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a); \
     void RMX_CAT(launch_phase_, NPV)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d); \

@@ -3,7 +3,9 @@
 the model's own parameters (joint stiffness, damping and rest position, body inertia and mass, gravity; rmx_rollout_vjp_params_device).
 
 Forward is rmx_rollout_tape_device (rmx_rollout_tape_bdf2_device under integrator=2), backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
-objective lives wholly on the PyTorch side.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
+objective lives wholly on the PyTorch side.  Forward mode (torch.autograd.forward_ad, torch.func.jvp, torch.func.jacfwd) runs
+rmx_rollout_jvp_device on the same tape; ``jvp(sim, q0, qdot0, u, ...)`` pushes several tangent directions through one tape in one
+call.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
 """
 from __future__ import annotations
 
@@ -21,9 +23,8 @@ def _function():
 
     class _Rollout(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, q0, qdot0, u, sim, h, pscale, check, integrator, names=(), *ptensors):
+        def forward(q0, qdot0, u, sim, h, pscale, check, integrator, names=(), *ptensors):
             # (names, ptensors: the model parameters of rollout(params=...); the forward does not read their values)
-            ctx.names = tuple(names)
             B, nsteps, nr = u.shape
             q0c, qd0c, uc = q0.contiguous(), qdot0.contiguous(), u.contiguous()
             qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
@@ -34,11 +35,17 @@ def _function():
             sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
             info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=pscale, stats=check,
                                            integrator=integrator)
-            ctx.sim, ctx.nsteps, ctx.tape = sim, nsteps, sim.tape_count
             if check and (info["status"] & _BAD_STATUS).any():
                 bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
                 raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
             return qtraj, qdtraj
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            # (forward and setup_context apart: the form torch.func's transforms ask of an autograd.Function)
+            u, sim = inputs[2], inputs[3]
+            ctx.names = tuple(inputs[8]) if len(inputs) > 8 else ()
+            ctx.sim, ctx.nsteps, ctx.tape = sim, u.shape[1], sim.tape_count
 
         @staticmethod
         def backward(ctx, gq, gqd):
@@ -55,7 +62,7 @@ def _function():
             torch.cuda.current_stream(dev).synchronize()
             if not ctx.names:
                 sim.rollout_vjp_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr())
-                return dq0, dqd0, du, None, None, None, None, None
+                return dq0, dqd0, du, None, None, None, None, None, None      # (apply binds forward's default names=())
             shapes = sim._param_shapes()
             rows = {n: torch.zeros((sim.B,) + shapes[n], dtype=torch.float64, device=dev) for n in ctx.names}
             sim.rollout_vjp_params_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr(),
@@ -63,12 +70,64 @@ def _function():
             # one row per rollout from the library; the rollouts share the model, so the parameter's gradient is their sum
             return (dq0, dqd0, du, None, None, None, None, None, None) + tuple(rows[n].sum(dim=0) for n in ctx.names)
 
+        @staticmethod
+        def jvp(ctx, tq0, tqd0, tu, *rest):
+            # forward mode (torch.autograd.forward_ad, torch.func.jvp): one rmx_rollout_jvp_device call on the tape of this rollout
+            sim, nsteps = ctx.sim, ctx.nsteps
+            if sim.tape_count != ctx.tape:
+                raise RuntimeError("the tape of this rollout has been replaced")
+            if any(t is not None for t in rest):
+                raise RuntimeError("rollout: forward-mode tangents of the model parameters are not available (rmx_rollout_jvp takes "
+                                   "tangents of q0, qdot0 and u)")
+            if tq0 is None and tqd0 is None and tu is None:
+                z = torch.zeros((sim.B, nsteps, sim.nr), dtype=torch.float64, device=torch.device("cuda", sim.device))
+                return z, z.clone()
+            return _Tangents.apply(tq0, tqd0, tu, sim, nsteps)
+
+        @staticmethod
+        def vmap(info, in_dims, *args):
+            # (torch.func.jacfwd is vmap over jvp: the rollout itself is reached with unbatched inputs and never gets here)
+            raise RuntimeError("rollout: torch.func.vmap over q0, qdot0 or u is not available - the batch axis of the sim is the batch")
+
+    class _Tangents(torch.autograd.Function):
+        """rmx_rollout_jvp_device on the sim's tape.  Under torch.func.vmap (jacfwd) the mapped axis becomes the directions of ONE call."""
+
+        @staticmethod
+        def forward(tq0, tqd0, tu, sim, nsteps):
+            return _Tangents.run(sim, nsteps, 1, tq0, tqd0, tu, (sim.B, nsteps, sim.nr))
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            pass
+
+        @staticmethod
+        def run(sim, nsteps, ntan, tq0, tqd0, tu, shape):
+            dev = torch.device("cuda", sim.device)
+            tq0, tqd0, tu = (None if t is None else t.contiguous() for t in (tq0, tqd0, tu))
+            tq = torch.empty(shape, dtype=torch.float64, device=dev)
+            tqd = torch.empty_like(tq)
+            torch.cuda.current_stream(dev).synchronize()
+            sim.rollout_jvp_device(nsteps, ntan, *(0 if t is None else t.data_ptr() for t in (tu, tq0, tqd0)), tq.data_ptr(), tqd.data_ptr())
+            return tq, tqd
+
+        @staticmethod
+        def vmap(info, in_dims, tq0, tqd0, tu, sim, nsteps):
+            T = info.batch_size
+
+            def directions(t, dim):      # [B][T][...]: the mapped axis behind the rollouts; an unmapped tangent is the same in all
+                if t is None:
+                    return None
+                return t.unsqueeze(1).expand(t.shape[:1] + (T,) + t.shape[1:]) if dim is None else t.movedim(dim, 1)
+
+            tq0, tqd0, tu = (directions(t, d) for t, d in zip((tq0, tqd0, tu), in_dims[:3]))
+            return _Tangents.run(sim, nsteps, T, tq0, tqd0, tu, (sim.B, T, nsteps, sim.nr)), (1, 1)
+
     _Function = _Rollout
     return _Function
 
 
 def _check_inputs(sim, q0, qdot0, u):
-    """The argument checks rollout and linearize share (and their words)."""
+    """The argument checks rollout, linearize and jvp share (and their words)."""
     import torch
     dev = torch.device("cuda", sim.device)
     for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
@@ -152,6 +211,9 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, par
     Under integrator=2 the rollout starts itself with SDIRK2 from (q0, qdot0): row 0 is the state after the two-stage start step
     (u[:, 0] holds for both stages), row k-1 for k >= 2 the state after the BDF2 step from steps k-1 and k-2; the gradients are
     exact through the start step too.  Any other integrator raises ValueError.
+    Forward mode works too: under torch.autograd.forward_ad or torch.func.jvp the tangents of q0, qdot0 and u (any subset) go through
+    one rmx_rollout_jvp_device call on the tape just recorded, and torch.func.jacfwd runs all its directions in ONE such call; a
+    tangent on a params tensor raises RuntimeError (parameter tangents are not built), torch.func.vmap over q0, qdot0 or u too.
     params: None, or a dict of model-parameter tensors - model_params(sim) or any part of it ("stiffness", "damping", "qrest",
     "inertia", "grav").  backward() then also accumulates into each given tensor's .grad the gradient of the loss with respect to
     that parameter, summed over the batch (one rmx_rollout_vjp_params call).  The forward does NOT read the tensors' values: the sim
@@ -207,3 +269,56 @@ def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     A = torch.cat([torch.cat([S, h * XB], dim=-1), torch.cat([(S - eye) / h, XB], dim=-1)], dim=-2)
     Bm = torch.cat([XU, XU / h], dim=-2)
     return qtraj, qdtraj, A, Bm
+
+
+def jvp(sim, q0, qdot0, u, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, check=True, integrator=1):
+    """The controlled rollout of ``rollout`` and the forward-mode tangents of its whole trajectory: (qtraj, qdtraj, tq, tqd).
+
+    tu: [B][T][nsteps][nr], tq0, tqdot0: [B][T][nr] - T tangent directions per rollout, float64 tensors on the sim's device; any of
+    them may be None (zero), not all.  tq, tqd: [B][T][nsteps][nr], row k-1 the tangent of the state after step k.  A tu of
+    [B][nsteps][nr] or a tq0 / tqdot0 of [B][nr] (every given input alike) is one direction, and tq, tqd come back without the T axis.
+    One tape (rmx_rollout_tape_device, or its BDF2 form under integrator=2) and one rmx_rollout_jvp_device call for all directions -
+    one elimination per step whatever T is; no autograd graph is made.  Arguments, checks and words are rollout's.  The call
+    replaces the sim's tape, as rollout does, and leaves the sim at the end of the rollout."""
+    import torch
+    if integrator not in (1, 2):
+        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    _check_inputs(sim, q0, qdot0, u)
+    B, nsteps, nr = u.shape
+    dev = torch.device("cuda", sim.device)
+    tans = {n: t for n, t in (("tu", tu), ("tq0", tq0), ("tqdot0", tqdot0)) if t is not None}
+    if not tans:
+        raise ValueError("rollout: all tangents are None")
+    tail = {"tu": (nsteps, nr), "tq0": (nr,), "tqdot0": (nr,)}
+    for n, t in tans.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (n, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("rollout: %s must be float64, got %s" % (n, t.dtype))
+        if t.device != dev:
+            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (n, dev, t.device))
+    single = all(t.dim() == 1 + len(tail[n]) for n, t in tans.items())
+    if single:
+        tans = {n: t.unsqueeze(1) for n, t in tans.items()}
+    T = max([t.shape[1] for t in tans.values() if t.dim() >= 2] + [1])
+    for n, t in tans.items():
+        if tuple(t.shape) != (B, T) + tail[n]:
+            raise ValueError("rollout: %s must have shape %r - or, every tangent alike, that shape without the direction axis -, got %r"
+                             % (n, (B, T) + tail[n], tuple(t.shape[:1] + t.shape[2:]) if single else tuple(t.shape)))
+    tans = {n: t.detach().contiguous() for n, t in tans.items()}
+    h = float(sim.opts.h if h is None else h)
+    q0c, qd0c, uc = q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous()
+    qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=dev)
+    qdtraj = torch.empty_like(qtraj)
+    tq = torch.empty((B, T, nsteps, nr), dtype=torch.float64, device=dev)
+    tqd = torch.empty_like(tq)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
+    info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=float(pscale), stats=bool(check),
+                                   integrator=integrator)
+    if check and (info["status"] & _BAD_STATUS).any():
+        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
+        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+    sim.rollout_jvp_device(nsteps, T, *(tans[n].data_ptr() if n in tans else 0 for n in ("tu", "tq0", "tqdot0")), tq.data_ptr(),
+                           tqd.data_ptr())
+    return (qtraj, qdtraj, tq[:, 0], tqd[:, 0]) if single else (qtraj, qdtraj, tq, tqd)

@@ -34,6 +34,11 @@ ROWS = (  # (name fragment, what it runs)
     ("k_rollout_linearize<16>", "rmx_rollout_linearize: 9..16 nodes"),
     ("k_rollout_linearize<32>", "rmx_rollout_linearize: 17..32 nodes, the four blocks in one pass"),
     ("k_rollout_linearize<64>", "rmx_rollout_linearize: 33..64 nodes, half a right-hand block per pass"),
+    ("k_rollout_jvp<4>", "rmx_rollout_jvp (forward sweep over a tape; one wavefront per rollout and chunk of 8 tangent directions): <= 4 nodes"),
+    ("k_rollout_jvp<8>", "rmx_rollout_jvp: 5..8 nodes"),
+    ("k_rollout_jvp<16>", "rmx_rollout_jvp: 9..16 nodes"),
+    ("k_rollout_jvp<32>", "rmx_rollout_jvp: 17..32 nodes"),
+    ("k_rollout_jvp<64>", "rmx_rollout_jvp: 33..64 nodes, H, 8 columns and the carried tangents in registers"),
     ("k_rollout_param_grad<4>", "rmx_rollout_vjp_params (the contraction over the slots of a tape; one wavefront per rollout): <= 4 nodes"),
     ("k_rollout_param_grad<8>", "rmx_rollout_vjp_params: 5..8 nodes"),
     ("k_rollout_param_grad<16>", "rmx_rollout_vjp_params: 9..16 nodes"),

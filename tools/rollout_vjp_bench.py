@@ -19,7 +19,11 @@ profiles/rollout_linearize_bench.json.
 contraction over the slots, one kernel each) beside the tape and vjp calls of the same run, BDF1, at 512 x 20 of the 16-, 32- and
 40-link chains; writes profiles/rollout_params_bench.json.
 
-    python tools/rollout_vjp_bench.py [--reps 20] [--integrator 1 2] [--linearize] [--params]"""
+--jvp: rmx_rollout_jvp_device with 1 and with 8 tangent directions (tu, tq0 and tqd0 all given) beside the tape, vjp (the same number
+of eliminations per direction-sweep) and linearize (the route the call replaces) calls of the same run, BDF1 and BDF2, at 1024 x 20 of
+the 32-link chain; writes profiles/rollout_jvp_bench.json.
+
+    python tools/rollout_vjp_bench.py [--reps 20] [--integrator 1 2] [--linearize] [--params] [--jvp]"""
 import argparse
 import ctypes as C
 import json
@@ -163,6 +167,69 @@ def main_params(args):
     print(json.dumps(out, indent=1))
 
 
+JVP_SHAPE = (32, 1024, 20)      # (links, rollouts, steps)
+JVP_NTAN = (1, 8)
+
+
+def main_jvp(args):
+    """tape, vjp, linearize and jvp (1 and 8 directions) alternate, under BDF1 and under BDF2; one rehearsal round, then the median of
+    --reps rounds of the kernel time by the library's events (rmx_last_step_ms) and of the host wall clock."""
+    sys.path.insert(0, ROOT)
+    from redmax_amd import BatchSim
+    from redmax_amd.scenes import sceneAdjointChain
+    n, b, k = JVP_SHAPE
+    out = {"workload": "%d-link chain, %d rollouts x %d steps; device pointers; jvp with tu, tq0 and tqd0 given, linearize with XA, XB, XU "
+                       "asked for; median of %d rounds after one rehearsal" % (n, b, k, args.reps), "integrators": {}}
+    rng = np.random.default_rng(20240)
+    for integ in (1, 2):
+        sc = sceneAdjointChain(n, bdf2=integ == 2)
+        sc.init()
+        nr = sc.nr
+        q0, qd0 = sc.getQ()
+        sim = BatchSim(sc, batch=b)
+        u = 0.1 * rng.standard_normal((b, k, nr))
+        ud, qt, qdt, dud = Dev(u), Dev(np.zeros_like(u)), Dev(np.zeros_like(u)), Dev(np.zeros_like(u))
+        gq, gqd = Dev(rng.standard_normal(u.shape)), Dev(rng.standard_normal(u.shape))
+        dq0, dqd0 = Dev(np.zeros((b, nr))), Dev(np.zeros((b, nr)))
+        q0d, qd0d = Dev(np.repeat(q0[None], b, axis=0)), Dev(np.repeat(qd0[None], b, axis=0))
+        nslots = k + (integ == 2)
+        X = [Dev(np.zeros((b, nslots, nr * nr))) for _ in range(3)]
+        T = {t: (Dev(rng.standard_normal((b, t, k, nr))), Dev(rng.standard_normal((b, t, nr))), Dev(rng.standard_normal((b, t, nr))),
+                 Dev(np.zeros((b, t, k, nr))), Dev(np.zeros((b, t, k, nr)))) for t in JVP_NTAN}
+        rows = dict({"rollout_tape": [], "rollout_vjp": [], "rollout_linearize": []}, **{"rollout_jvp_ntan%d" % t: [] for t in JVP_NTAN})
+
+        def timed(call, fn):
+            t0 = time.perf_counter()
+            fn()
+            rows[call].append(((time.perf_counter() - t0) * 1e3, sim._L.rmx_last_step_ms(sim._batch)))
+
+        for _ in range(1 + args.reps):
+            sim.set_state_device(q0d.ptr, qd0d.ptr)
+            timed("rollout_tape", lambda: sim.rollout_tape_device(k, sc.h, ud.ptr, qt.ptr, qdt.ptr, pscale=sc.task["pscale"], integrator=integ))
+            timed("rollout_vjp", lambda: sim.rollout_vjp_device(k, gq.ptr, gqd.ptr, dud.ptr, dq0.ptr, dqd0.ptr))
+            timed("rollout_linearize", lambda: sim.rollout_linearize_device(k, X[0].ptr, X[1].ptr, X[2].ptr))
+            for t in JVP_NTAN:
+                tu, tq0, tqd0, tq, tqd = T[t]
+                timed("rollout_jvp_ntan%d" % t, lambda: sim.rollout_jvp_device(k, t, tu.ptr, tq0.ptr, tqd0.ptr, tq.ptr, tqd.ptr))
+        finite = bool(all(np.isfinite(T[t][i].get()).all() and np.abs(T[t][i].get()).max() > 0 for t in JVP_NTAN for i in (3, 4)))
+        sim.close()
+        for d in [ud, qt, qdt, dud, gq, gqd, dq0, dqd0, q0d, qd0d] + X + [x for t in JVP_NTAN for x in T[t]]:
+            Dev.hip.hipFree(d.p)
+        med = {c + "_device": {"wall_ms": float(np.median([r[0] for r in v[1:]])), "kernel_ms": float(np.median([r[1] for r in v[1:]]))}
+               for c, v in rows.items()}
+        for t in JVP_NTAN:
+            kj = med["rollout_jvp_ntan%d_device" % t]["kernel_ms"]
+            med["jvp_ntan%d_over_vjp_kernel" % t] = kj / med["rollout_vjp_device"]["kernel_ms"]
+            med["jvp_ntan%d_over_linearize_kernel" % t] = kj / med["rollout_linearize_device"]["kernel_ms"]
+        med["outputs_finite_and_nonzero"] = finite
+        out["integrators"]["BDF%d" % integ] = med
+    path = args.out or os.path.join(ROOT, "profiles", "rollout_jvp_bench.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -171,7 +238,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--linearize", action="store_true", help="time rmx_rollout_linearize_device beside tape and vjp at three shapes")
     ap.add_argument("--params", action="store_true", help="time rmx_rollout_vjp_params_device beside tape and vjp at three shapes")
+    ap.add_argument("--jvp", action="store_true", help="time rmx_rollout_jvp_device (1 and 8 directions) beside tape, vjp and linearize")
     args = ap.parse_args()
+    if args.jvp:
+        return main_jvp(args)
     if args.linearize:
         return main_linearize(args)
     if args.params:
