@@ -465,6 +465,42 @@ int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, doub
 int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd,
                            double* d_du, double* d_dq0, double* d_dqd0);
 
+/* The taped rollout in CLOSED LOOP: time-varying affine state feedback evaluated on the device, inside the one launch - the forward
+ * pass of iLQR / DDP and time-varying-LQR tracking, u_k = uff_k + K_k (x_{k-1} - xref_{k-1}), where the torque of step k depends on
+ * the state the rollout itself has reached.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * rmx_rollout_tape_feedback is rmx_rollout_tape (integrator 1) / rmx_rollout_tape_bdf2 (integrator 2) with the torque of step k
+ *     uapp[b][k-1][i] = uff[b][k-1][i] + sum_j K_k[i][j] (x_j - xref_{k-1,j}),     x = (q, qdot) at the START of step k
+ * - for k = 1 the batch's state at the call, for k > 1 the bits of row k-2 of qtraj / qdtraj.  Under BDF2 the torque of step 1 holds
+ * for both SDIRK2 solves.  Reduced DOF order throughout; x has 2 nr entries, q first.
+ * K: one table of 2 nr nr doubles per step, column-major as everywhere in this header: entry j*nr + i of step k's table (row k-1) is
+ * du_i/dx_j, j in 0 .. 2nr-1.  xref: one row of 2 nr doubles per step.  per_rollout 0: [nsteps][..], shared by the batch; 1:
+ * [batch][nsteps][..].  The sum runs in one fixed order (the nodes of the tree ascending - depth first -, the q block before the
+ * qdot block), so a rollout's result does not depend on its position in the batch.  K NULL: no feedback, uapp == uff bit for bit
+ * (xref is not read).  uapp: host [batch][nsteps][nr], the applied torques (out), or NULL.  Everything else - opts, stats, qtraj,
+ * qdtraj, the state the batch is left in - as rmx_rollout_tape / _bdf2.
+ *
+ * The tape the call leaves has rmx_rollout_tape's layout and IS the open-loop tape under the torques uapp: rmx_rollout_vjp,
+ * rmx_rollout_linearize, rmx_rollout_jvp and rmx_rollout_vjp_params read it unchanged and differentiate the open-loop rollout at
+ * uapp - what iLQR re-linearises around.  Gradients through the feedback law itself (dL/dK, dL/dxref, the closed-loop dL/duff) are
+ * not formed by any entry.
+ *
+ * Refusals (RMX_E_INVALID): everything rmx_rollout_tape refuses, in its words; a null struct or uff ("null argument"); an integrator
+ * other than 1 or 2; per_rollout other than 0 or 1.  A refused call leaves an existing tape alone.  The host form stages K, xref
+ * and uapp through a device allocation of its own, freed before it returns.  The _device form: every array a DEVICE pointer (the
+ * struct itself is a host object), nothing staged; it returns when the kernel has finished. */
+typedef struct rmx_feedback {
+    const double* uff;   /* [batch][nsteps][nr]                 required                                  */
+    const double* K;     /* [nsteps][2*nr*nr] or [batch][..]    NULL: no feedback, uapp == uff bit for bit */
+    const double* xref;  /* [nsteps][2*nr] or [batch][..]       row k-1: (q, qdot) reference for the state
+                            at the START of step k; NULL: zero                                            */
+    int per_rollout;     /* 0: K and xref shared by the batch, 1: one table per rollout                   */
+} rmx_feedback;
+int rmx_rollout_tape_feedback(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
+                              const rmx_feedback* fb, double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats);
+int rmx_rollout_tape_feedback_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
+                                     const rmx_feedback* fb, double* d_qtraj, double* d_qdtraj, double* d_uapp, rmx_stats* stats);
+
 /* The linearisation of the taped rollout: the forward sensitivities of every taped solve, from which a host assembles the per-step
  * A_k = d(q_k, qdot_k)/d(q_{k-1}, qdot_{k-1}) and B_k = d(q_k, qdot_k)/du_k that iLQR / DDP, time-varying LQR, Gauss-Newton shooting
  * and SQP-style MPC work with.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.

@@ -173,6 +173,26 @@ classdef HipSim < handle
 			[qtraj, qdtraj, stats] = redmax_hip_mex('rollout_tape', this.h, hstep, nsteps, pscale, u, integrator);
 		end
 
+		function [qtraj, qdtraj, uapp, stats] = rolloutFeedback(this, hstep, nsteps, pscale, uff, K, xref, integrator)
+			% rolloutTape in closed loop (the forward pass of iLQR, time-varying LQR tracking): the torque of step k is
+			%   uapp(:,k,b) = uff(:,k,b) + K(:,:,k) * (x - xref(:,k)),   x = [q; qdot] at the START of step k,
+			% formed on the device from the state the rollout has reached - all steps in one launch.  uff: nr x nsteps x B.
+			% K: nr x 2nr x nsteps, shared by the batch, or nr x 2nr x nsteps x B, K(i,j,k) = du_i/dx_j; xref: 2nr x nsteps
+			% or 2nr x nsteps x B (K and xref alike); [] for either: no feedback / a zero reference.  uapp: the applied torques.
+			% The tape it leaves is the open-loop tape under uapp: rolloutVjp, rolloutLinearize and rolloutJvp differentiate
+			% that open-loop rollout, not the feedback law.
+			if nargin < 6
+				K = [];
+			end
+			if nargin < 7
+				xref = [];
+			end
+			if nargin < 8
+				integrator = 1;
+			end
+			[qtraj, qdtraj, uapp, stats] = redmax_hip_mex('rollout_feedback', this.h, hstep, nsteps, pscale, uff, K, xref, integrator);
+		end
+
 		function [du, dq0, dqd0] = rolloutVjp(this, nsteps, gq, gqd)
 			% the gradient of any loss L on the trajectory of the last rolloutTape: gq, gqd (nr x nsteps x B) are dL/dq and
 			% dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du, dL/dq0, dL/dqdot0.  May be

@@ -61,6 +61,11 @@
  *                  rollout from the current state under the torques tau + pscale*u(:,k,b) that records its trajectory and keeps the
  *                  tape 'rollout_vjp' reads.  u, qtraj, qdtraj: nr x nsteps x B; column k is the state after step k; st as 'adjoint'.
  *                  integrator (default 1) 2: rmx_rollout_tape_bdf2, the BDF2 rollout, self-started with SDIRK2 (step 1).
+ *   [qtraj,qdtraj,uapp,st] = redmax_hip_mex('rollout_feedback', h, hstep, nsteps, pscale, uff, K, xref [, integrator])
+ *                  rmx_rollout_tape_feedback: 'rollout_tape' in closed loop - the torque of step k is uapp(:,k,b) = uff(:,k,b) +
+ *                  K(:,:,k)*(x - xref(:,k)) with x = [q; qdot] at the START of step k, formed on the device.  uff: nr x nsteps x B.
+ *                  K: nr x 2nr x nsteps (shared) or nr x 2nr x nsteps x B, K(i,j,k) = du_i/dx_j; xref: 2nr x nsteps [x B]; [] for
+ *                  either: no feedback / a zero reference.  uapp: the applied torques.  The tape is the open-loop tape under uapp.
  *   [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)  rmx_rollout_vjp on the tape of the last 'rollout_tape': gq, gqd
  *                  (nr x nsteps x B) are dL/dq and dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du,
  *                  dL/dq0, dL/dqdot0.  May be repeated with other cotangents; any 'adjoint*' command ends the tape.
@@ -609,6 +614,69 @@ static void cmd_rollout_tape(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
     else mxDestroyArray(st);
 }
 
+/* a table argument of 'rollout_feedback': [] (NULL), `per` elements per step shared by the batch, or as many for every rollout;
+ * *per_rollout is set by the first table given and the other must agree */
+static const double* feedback_arg(const mxArray* a, const handle_t* h, size_t per, int nsteps, int* per_rollout, const char* what) {
+    if (mxIsEmpty(a)) return NULL;
+    const size_t n = mxGetNumberOfElements(a), shared = per * (size_t)nsteps;
+    const int pr = n == shared * (size_t)h->B && h->B > 1;
+    if (!mxIsDouble(a) || mxIsComplex(a) || (n != shared && !pr) || (*per_rollout >= 0 && pr != *per_rollout))
+        mexErrMsgIdAndTxt("redmax:hip", "rollout_feedback: %s must be a real double array of %d x nsteps or %d x nsteps x batch elements, K and xref alike",
+                          what, (int)per, (int)per);
+    *per_rollout = pr;
+    return mxGetPr(a);
+}
+
+static void cmd_rollout_feedback(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 8) die("usage: [qtraj,qdtraj,uapp,stats] = redmax_hip_mex('rollout_feedback', h, hstep, nsteps, pscale, uff, K, xref [, integrator])");
+    const double integ_arg = nrhs > 8 ? mxGetScalar(prhs[8]) : 1.0;
+    if (integ_arg != 1.0 && integ_arg != 2.0) die("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2)");
+    const int integ = integ_arg == 2.0 ? 2 : 1;
+    rmx_opts o;
+    rmx_opts_default(&o);
+    o.h = mxGetScalar(prhs[2]);
+    o.iterMaxPerDof = 5;                               /* as 'rollout_tape' */
+    const int nsteps = (int)mxGetScalar(prhs[3]);
+    if (nsteps < 1) die("rollout_feedback: nsteps must be at least 1");
+    const double pscale = mxGetScalar(prhs[4]);
+    const double* uff = traj_arg(prhs[5], h, nsteps, "uff");
+    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps;
+    int per_rollout = -1;
+    const double* K = feedback_arg(prhs[6], h, 2 * nr * nr, nsteps, &per_rollout, "K");            /* nr x 2nr x nsteps [x B] */
+    const double* xref = feedback_arg(prhs[7], h, 2 * nr, nsteps, &per_rollout, "xref");           /* 2nr x nsteps [x B] */
+    if (per_rollout < 0) per_rollout = 0;
+    const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B};
+    mxArray* out[3];
+    for (int i = 0; i < 3; ++i) out[i] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* st = new_i32((size_t)h->B, 2);
+    int* sp = (int*)mxGetData(st);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'rollout_tape' */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_stats st_s;
+        st_s.newton_iters = sp + f;
+        st_s.ls_halvings = NULL;
+        st_s.status = sp + h->B + f;
+        rmx_feedback fb;
+        fb.uff = uff + f * per;
+        fb.K = K ? K + (per_rollout ? f * (size_t)nsteps * 2 * nr * nr : 0) : NULL;
+        fb.xref = xref ? xref + (per_rollout ? f * (size_t)nsteps * 2 * nr : 0) : NULL;
+        fb.per_rollout = per_rollout;
+        if (rmx_rollout_tape_feedback(b, &o, nsteps, integ, pscale, &fb, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * per,
+                                      mxGetPr(out[2]) + f * per, &st_s))
+            die_rmx("rmx_rollout_tape_feedback");
+    }
+    h->tape_integ = integ;
+    plhs[0] = out[0];
+    for (int i = 1; i < 3; ++i) {
+        if (nlhs > i) plhs[i] = out[i];
+        else mxDestroyArray(out[i]);
+    }
+    if (nlhs > 3) plhs[3] = st;
+    else mxDestroyArray(st);
+}
+
 static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
     if (nrhs < 5) die("usage: [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)");
@@ -828,7 +896,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", "rollout_jvp", NULL};
+                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -935,6 +1003,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_adjoint_track(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_tape")) {
         cmd_rollout_tape(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_feedback")) {
+        cmd_rollout_feedback(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp")) {
         cmd_rollout_vjp(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_linearize")) {

@@ -26,6 +26,7 @@ SYMBOLS = (
     "rmx_eval", "rmx_eval_mfd", "rmx_compute_values", "rmx_step_bdf1", "rmx_step_bdf2", "rmx_step_history", "rmx_step_euler", "rmx_adjoint_bdf1", "rmx_adjoint_bdf2", "rmx_adjoint_bdf1_device", "rmx_adjoint_bdf2_device", "rmx_adjoint_controls", "rmx_adjoint_controls_device", "rmx_adjoint_track", "rmx_adjoint_track_device", "rmx_energy",
     "rmx_rollout_tape", "rmx_rollout_vjp", "rmx_rollout_tape_device", "rmx_rollout_vjp_device",
     "rmx_rollout_tape_bdf2", "rmx_rollout_tape_bdf2_device",
+    "rmx_rollout_tape_feedback", "rmx_rollout_tape_feedback_device",
     "rmx_rollout_linearize", "rmx_rollout_linearize_device",
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
@@ -87,6 +88,10 @@ class PointForce(C.Structure):
 
 class ParamGrads(C.Structure):
     _fields_ = [("stiffness", C.c_void_p), ("damping", C.c_void_p), ("qrest", C.c_void_p), ("inertia", C.c_void_p), ("grav", C.c_void_p)]
+
+
+class Feedback(C.Structure):      # rmx_feedback: host pointers in the host form, device pointers in the _device form
+    _fields_ = [("uff", C.c_void_p), ("K", C.c_void_p), ("xref", C.c_void_p), ("per_rollout", C.c_int)]
 
 
 PARAM_NAMES = ("stiffness", "damping", "qrest", "inertia", "grav")      # the members of rmx_param_grads, in their order
@@ -152,6 +157,8 @@ def lib():
     L.rmx_adjoint_track_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.POINTER(TaskTrack), vp, vp, vp, vp, C.POINTER(Stats)]
     L.rmx_rollout_tape.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_double, _dp, _dp, _dp, C.POINTER(Stats)]
     L.rmx_rollout_tape_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_double, vp, vp, vp, C.POINTER(Stats)]
+    L.rmx_rollout_tape_feedback.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), _dp, _dp, _dp, C.POINTER(Stats)]
+    L.rmx_rollout_tape_feedback_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), vp, vp, vp, C.POINTER(Stats)]
     L.rmx_rollout_tape_bdf2.argtypes = L.rmx_rollout_tape.argtypes
     L.rmx_rollout_tape_bdf2_device.argtypes = L.rmx_rollout_tape_device.argtypes
     L.rmx_rollout_vjp.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp]

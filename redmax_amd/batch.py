@@ -454,6 +454,80 @@ class BatchSim:
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
+    def _feedback_tables(self, nsteps, K, xref):
+        """K and xref of rollout_feedback as contiguous float64 arrays, and whether they hold one table per rollout.  K:
+        [nsteps][2nr][nr] or [B][nsteps][2nr][nr], K[.., k-1, j, i] = du_i/dx_j of step k with x = (q, qdot) - the ABI's column-major
+        table as a C array -; xref: [nsteps][2nr] or [B][nsteps][2nr].  Both shared or both per rollout."""
+        nr, B = self.nr, self.B
+        shapes = {}
+        for name, a, tail in (("K", K, (nsteps, 2 * nr, nr)), ("xref", xref, (nsteps, 2 * nr))):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape not in (tail, (B,) + tail):
+                raise ValueError("rollout_feedback: %s must have shape %r or %r, got %r" % (name, tail, (B,) + tail, a.shape))
+            shapes[name] = a
+        K, xref = shapes.get("K"), shapes.get("xref")
+        per = [a.ndim == len(t) + 1 for a, t in ((K, (0, 0, 0)), (xref, (0, 0))) if a is not None]
+        if len(set(per)) > 1:
+            raise ValueError("rollout_feedback: K and xref must both be shared by the batch or both hold one table per rollout")
+        return K, xref, int(bool(per and per[0]))
+
+    def rollout_feedback(self, nsteps, h, uff, K=None, xref=None, pscale=1.0, stats=False, integrator=1):
+        """rmx_rollout_tape_feedback: rollout_tape in closed loop - at step k the joint torque is tau + pscale*uapp[:, k-1] with
+            uapp[b, k-1] = uff[b, k-1] + K[k-1].T @ (x - xref[k-1]),    x = (q, qdot) at the START of step k,
+        formed on the device from the state the rollout has reached (one launch for all steps).  uff: [B][nsteps][nr] (or
+        [nsteps][nr] for every rollout).  K: [nsteps][2nr][nr] shared by the batch or [B][nsteps][2nr][nr], K[.., k-1, j, i] =
+        du_i/dx_j (the row index is the STATE entry, q block first: the memory is the ABI's column-major table); None: no feedback,
+        uapp is uff bit for bit.  xref: [nsteps][2nr] or [B][nsteps][2nr], None: zero.  Returns (qtraj, qdtraj, uapp[, info]) - info
+        with stats=True.  The tape it leaves is the open-loop tape under uapp: rollout_vjp, rollout_linearize, rollout_jvp and
+        rollout_vjp_params differentiate that open-loop rollout, not the feedback law."""
+        if integrator not in (1, 2):
+            raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+        nsteps = int(nsteps)
+        if uff is None:
+            raise ValueError("rollout_feedback: uff is None")
+        uff = np.asarray(uff, dtype=np.float64)
+        if uff.shape == (nsteps, self.nr):
+            uff = np.broadcast_to(uff, (self.B, nsteps, self.nr))
+        if uff.shape != (self.B, nsteps, self.nr):
+            raise ValueError("rollout_feedback: uff must have shape (%d, %d, %d) or (%d, %d), got %r"
+                             % (self.B, nsteps, self.nr, nsteps, self.nr, uff.shape))
+        uff = np.ascontiguousarray(uff)
+        K, xref, per = self._feedback_tables(nsteps, K, xref)
+        fb = _abi.Feedback(uff.ctypes.data, K.ctypes.data if K is not None else None, xref.ctypes.data if xref is not None else None, per)
+        opts = self._tape_opts(h)
+        qtraj, qdtraj, uapp = (np.empty((self.B, nsteps, self.nr)) for _ in range(3))
+        info, st = self._tape_stats(stats)
+        self.tape_count += 1
+        self._tape_integrator = integrator
+        _abi.check(self._L.rmx_rollout_tape_feedback(self._batch, C.byref(opts), nsteps, int(integrator), float(pscale), C.byref(fb),
+                                                     _abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp),
+                                                     C.byref(st) if st is not None else None), "rmx_rollout_tape_feedback")
+        if not stats:
+            return qtraj, qdtraj, uapp
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return qtraj, qdtraj, uapp, info
+
+    def rollout_feedback_device(self, nsteps, h, uff_ptr, K_ptr, xref_ptr, qtraj_ptr, qdtraj_ptr, uapp_ptr, per_rollout=False, pscale=1.0,
+                                stats=False, integrator=1):
+        """rollout_feedback with DEVICE pointers (integers): uff, qtraj, qdtraj, uapp [B][nsteps][nr]; K [nsteps][2nr][nr] and xref
+        [nsteps][2nr], or one table per rollout with per_rollout=True.  K_ptr 0 / None: no feedback; xref_ptr 0 / None: zero;
+        qtraj_ptr and qdtraj_ptr 0 / None together: no record; uapp_ptr 0 / None: not stored.  Returns info."""
+        if integrator not in (1, 2):
+            raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+        fb = _abi.Feedback(uff_ptr or None, K_ptr or None, xref_ptr or None, int(bool(per_rollout)))
+        opts = self._tape_opts(h)
+        info, st = self._tape_stats(stats)
+        self.tape_count += 1
+        self._tape_integrator = integrator
+        _abi.check(self._L.rmx_rollout_tape_feedback_device(self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale),
+                                                            C.byref(fb), C.c_void_p(qtraj_ptr or None), C.c_void_p(qdtraj_ptr or None),
+                                                            C.c_void_p(uapp_ptr or None), C.byref(st) if st is not None else None),
+                   "rmx_rollout_tape_feedback_device")
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return info
+
     def rollout_vjp(self, nsteps, gq, gqd, initial_state=True):
         """rmx_rollout_vjp on the tape of the last rollout_tape: gq, gqd [B][nsteps][nr] are dL/dq_k, dL/dqdot_k.  Returns
         (du[B][nsteps][nr], dq0[B][nr], dqd0[B][nr]) = dL/du, dL/dq0, dL/dqdot0; initial_state=False returns None for the last two.

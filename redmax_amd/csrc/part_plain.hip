@@ -74,6 +74,14 @@ void launch_adjoint_fullchain_16(const rmx_model* m, const rmx_batch* b, int int
 }
 #endif
 
+// rmx_rollout_tape_feedback: the forward sweep of the tape under per-step affine state feedback (ADJ_FB, rmx_feedback.h).  Always this
+// generic one-wavefront kernel (rmx_select.h select_rollout_feedback); the backward sweeps that read its tape are adjoint_tape's
+void RMX_CAT(launch_rollout_feedback_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 1 | ADJ_CTL | ADJ_TAPE | ADJ_FB, false, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+    else RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2 | ADJ_CTL | ADJ_TAPE | ADJ_FB, false, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
+}
+
 // rmx_rollout_linearize: every slot of the tape at once
 void RMX_CAT(launch_linearize_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LinArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nslots)), block(64);

@@ -1550,8 +1550,11 @@ static rmx_select::AdjPlan launch_adjoint_plan(rmx_batch* b, const int integ, co
     return plan;
 }
 
+// fb (rmx_rollout_tape_feedback): u is fb->uff, the sweep is the ADJ_FB kernel and uapp (or null) takes the applied torques.  The host
+// form stages K, xref and uapp through a device allocation of its own, freed before the return; the tape's workspace is the same.
 static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
-                             double* qdtraj, rmx_stats* stats, const bool on_device, const int integ = INTEG_BDF1) {
+                             double* qdtraj, rmx_stats* stats, const bool on_device, const int integ = INTEG_BDF1,
+                             const rmx_feedback* fb = nullptr, double* uapp = nullptr) {
     if (!b || !u) return fail(RMX_E_INVALID, "rmx_rollout_tape: null argument");
     if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
     rmx_model* m = b->m;
@@ -1566,12 +1569,37 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
     if ((size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * m->n * sizeof(double) * 3 > ((size_t)200 << 30))
         return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
     const TapeParts t = tape_parts(b, nsteps, integ);
+    // the feedback tables of the host form: K, xref, uapp, each at a 256-byte boundary of one allocation
+    const size_t fb_tables = fb ? (fb->per_rollout ? (size_t)b->B : 1) * nsteps : 0;
+    const size_t fbK_bytes = (fb && fb->K) ? fb_tables * 2 * m->nr * m->nr * sizeof(double) : 0;
+    const size_t fbx_bytes = (fb && fb->xref) ? fb_tables * 2 * m->nr * sizeof(double) : 0;
+    const size_t fbK_room = (fbK_bytes + 255) & ~(size_t)255, fbx_room = (fbx_bytes + 255) & ~(size_t)255;
+    char* fbbuf = nullptr;
+    if (fb && !on_device && fbK_room + fbx_room + (uapp ? t.bytes_traj : 0) > 0) {      // (ahead of everything that ends the present tape)
+        if (hipMalloc((void**)&fbbuf, fbK_room + fbx_room + (uapp ? t.bytes_traj : 0)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RMX_E_NOMEM, "rmx_rollout_tape_feedback: no device memory for the gain tables");
+        }
+    }
     b->tape_nsteps = 0;
     hipError_t e = adjws_reserve(b, t.total);
     if (e == hipSuccess) {
         char* ws = (char*)b->adjws;
         if (!on_device) e = hipMemcpyAsync(ws + t.off[3], u, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
         AdjArgs a{};
+        if (fb) {
+            a.fbK = fb->K;
+            a.fbx = fb->xref;
+            a.fb_stride = fb->per_rollout ? (size_t)nsteps : 0;
+            a.uapp = uapp;
+            if (!on_device) {
+                a.fbK = fb->K ? (const double*)fbbuf : nullptr;
+                a.fbx = fb->xref ? (const double*)(fbbuf + fbK_room) : nullptr;
+                a.uapp = uapp ? (double*)(fbbuf + fbK_room + fbx_room) : nullptr;
+                if (e == hipSuccess && fb->K) e = hipMemcpyAsync(fbbuf, fb->K, fbK_bytes, hipMemcpyHostToDevice, b->stream);
+                if (e == hipSuccess && fb->xref) e = hipMemcpyAsync(fbbuf + fbK_room, fb->xref, fbx_bytes, hipMemcpyHostToDevice, b->stream);
+            }
+        }
         a.B = b->B; a.nsteps = nsteps; a.pscale = pscale;
         a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp;
         a.it = stats ? b->it : nullptr; a.status = b->status;
@@ -1592,9 +1620,16 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_QD0], b->qd, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
         if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
         if (e == hipSuccess) {
-            const rmx_select::AdjPlan plan = launch_adjoint_plan(b, integ, o, a);
-            if (integ == INTEG_BDF2) b->last_kernel = rmx_select::label_rollout_tape_bdf2(plan);
-            e = hipGetLastError();
+            if (fb) {
+                const rmx_select::AdjPlan plan = rmx_select::select_rollout_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
+                if (plan.kernel == AdjKernel::Generic) DISPATCH_NP(m->NP, launch_rollout_feedback, m, b, integ, o, a)
+                else e = hipErrorInvalidDeviceFunction;      // (no other feedback kernel exists: never a silent substitute)
+                b->last_kernel = rmx_select::label_rollout_feedback(integ);
+            } else {
+                const rmx_select::AdjPlan plan = launch_adjoint_plan(b, integ, o, a);
+                if (integ == INTEG_BDF2) b->last_kernel = rmx_select::label_rollout_tape_bdf2(plan);
+            }
+            if (e == hipSuccess) e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
         // a BDF1 rollout: rmx_step_bdf2 takes its start step again; after a BDF2 rollout (q, qdot) of step k-1 are in place
@@ -1607,6 +1642,7 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
             e = hipMemcpyAsync(qtraj, a.qtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(qdtraj, a.qdtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
         }
+        if (e == hipSuccess && fb && !on_device && uapp) e = hipMemcpyAsync(uapp, a.uapp, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
         if (e == hipSuccess && stats) {
             if (stats->newton_iters) e = hipMemcpyAsync(stats->newton_iters, b->it, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess && stats->status) e = hipMemcpyAsync(stats->status, b->status, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
@@ -1620,6 +1656,10 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
             b->tape_h = o.h;
             b->tape_pscale = pscale;
         }
+    }
+    if (fbbuf) {
+        if (e != hipSuccess) (void)hipStreamSynchronize(b->stream);
+        (void)hipFree(fbbuf);
     }
     if (e == hipErrorOutOfMemory) return fail(RMX_E_NOMEM, "rmx_rollout_tape: no device memory for the tape (H, M, D per step and rollout)");
     if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_tape: ") + hipGetErrorString(e));
@@ -1890,6 +1930,21 @@ extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, 
 extern "C" int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* d_u, double* d_qtraj,
                                        double* d_qdtraj, rmx_stats* stats) {
     return rollout_tape_impl(b, opts, nsteps, pscale, d_u, d_qtraj, d_qdtraj, stats, true);
+}
+static int rollout_feedback_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale, const rmx_feedback* fb,
+                                 double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats, const bool on_device) {
+    if (!b || !fb || !fb->uff) return fail(RMX_E_INVALID, "rmx_rollout_tape_feedback: null argument");
+    if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_rollout_tape_feedback: integrator must be 1 (BDF1) or 2 (BDF2)");
+    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, "rmx_rollout_tape_feedback: per_rollout must be 0 or 1");
+    return rollout_tape_impl(b, opts, nsteps, pscale, fb->uff, qtraj, qdtraj, stats, on_device, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, fb, uapp);
+}
+extern "C" int rmx_rollout_tape_feedback(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale, const rmx_feedback* fb,
+                                         double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats) {
+    return rollout_feedback_impl(b, opts, nsteps, integrator, pscale, fb, qtraj, qdtraj, uapp, stats, false);
+}
+extern "C" int rmx_rollout_tape_feedback_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
+                                                const rmx_feedback* fb, double* d_qtraj, double* d_qdtraj, double* d_uapp, rmx_stats* stats) {
+    return rollout_feedback_impl(b, opts, nsteps, integrator, pscale, fb, d_qtraj, d_qdtraj, d_uapp, stats, true);
 }
 extern "C" int rmx_rollout_tape_bdf2(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                      double* qdtraj, rmx_stats* stats) {

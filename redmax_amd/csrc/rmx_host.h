@@ -78,6 +78,11 @@ struct AdjArgs {
     double *dq0, *dqd0;       // [B][nr] dL/dq0, dL/dqdot0 (out), or null together
     // rmx_rollout_vjp_params (the ADJ_ZS instantiations of the two backward kernels, launched by that entry alone)
     double* zs;               // [B][nslots][n] the adjoint vector z of every taped solve, lane = node (out); slots as the tape's
+    // rmx_rollout_tape_feedback (the ADJ_FB instantiations of the forward kernel; u is the feed-forward uff there)
+    const double* fbK;        // [nsteps][2 nr nr] or [B][..]: du_i/dx_j of step k at row k-1, entry j*nr + i, x = (q, qdot); null: no feedback
+    const double* fbx;        // [nsteps][2 nr] or [B][..]: row k-1 the reference (q, qdot) for the state at the start of step k; null: zero
+    size_t fb_stride;         // rows (steps) from one rollout's tables to the next: nsteps, or 0 for tables the batch shares
+    double* uapp;             // [B][nsteps][nr] the torque applied in every step (out), or null
 };
 
 // rmx_rollout_vjp_params (rmx_params.h): one wavefront per rollout walks the slots of its tape
@@ -195,6 +200,7 @@ struct rmx_batch {
     void RMX_CAT(launch_euler_, NPV)(const rmx_model* m, const rmx_batch* b, double h, const StepArgs& a); \
     void RMX_CAT(launch_energy_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_adjoint_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
+    void RMX_CAT(launch_rollout_feedback_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \

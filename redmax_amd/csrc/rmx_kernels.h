@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "rmx_host.h"
+#include "rmx_feedback.h"
 
 // ============================================================================ kernels
 
@@ -829,6 +830,12 @@ constexpr int ADJ_TAPE = 16;
 // ZS (rmx_rollout_vjp_params, with TAPE; backward kernels only): the backward sweep also stores z of every solve (a.zs), which the
 // parameter contraction of rmx_params.h reads.  Compile-time: rmx_rollout_vjp keeps the instantiations it had.
 constexpr int ADJ_ZS = 32;
+// FB (rmx_rollout_tape_feedback, with CTL and TAPE, never with TRK or the helper wave): the torque of step s is not a.u's row alone
+// but a.u's row (the feed-forward uff) plus an affine feedback on the state the rollout has reached at the START of the step - the
+// kernel's own q, qd registers, the bits of row s-2 of the record - formed at the top of the step loop (rmx_feedback.h) and stored to
+// a.uapp.  Nothing else of the sweep changes, and the tape it leaves is the open-loop tape under a.uapp.  A null a.fbK is no
+// feedback: the applied torque is a.u's bit for bit.  Compile-time like the others: every other instantiation keeps its code.
+constexpr int ADJ_FB = 64;
 constexpr int ADJ_TRK_ROWS = 18;      // sw[3], sv[3], Rw[9], pw[3], one column per node
 __host__ __device__ constexpr size_t adj_trk_doubles(const int NP) { return (size_t)ADJ_TRK_ROWS * NP; }
 template <int NP, int MODE, bool HELP = false, bool FC = false>
@@ -842,6 +849,8 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     static_assert(!TAPE || (CTL && !TRK), "the taped rollout: per-step controls, no objective");
     constexpr bool TAPE2 = TAPE && INTEG == 2;       // the BDF2 tape: H, M, D of the SDIRK2a solve too, in a slot of its own
     static_assert(!TAPE2 || !HELP, "the BDF2 tape runs one wavefront per rollout (two hand-overs in step 1 only: see select_rollout_tape)");
+    constexpr bool FB = (MODE & ADJ_FB) != 0;
+    static_assert(!FB || (TAPE && !HELP), "state feedback: the taped rollout, one wavefront per rollout (select_rollout_feedback)");
     static_assert(!HELP || NP <= 16, "the helper-wave form: trees of one DPP row");
     const DevModel M = model_view<NP, FC>(Min);
     double *sAcc, *sCol;
@@ -876,7 +885,15 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
     const double al = (2.0 - sqrt(2.0)) / 2.0;       // SDIRK2 (driverRedMaxAdjointBDF2.m:80)
     for (int s = 1; s <= a.nsteps; ++s) {
         if constexpr (CTL) {                 // (under BDF2 step 1's torque holds for both SDIRK2 solves)
-            const double us = id >= 0 ? uj[(size_t)(s - 1) * M.nr] : 0.0;
+            double us = id >= 0 ? uj[(size_t)(s - 1) * M.nr] : 0.0;
+            if constexpr (FB) {              // (q, qd: the state at the start of step s)
+                if (a.fbK) {
+                    const size_t row = (size_t)traj * a.fb_stride + (size_t)(s - 1);
+                    us = feedback_torque<NP>(us, a.fbK + row * ((size_t)2 * M.nr * M.nr), a.fbx ? a.fbx + row * ((size_t)2 * M.nr) : nullptr,
+                                             M.nr, n, id, q, qd);
+                }
+                if (a.uapp && id >= 0) a.uapp[((size_t)traj * a.nsteps + (s - 1)) * M.nr + id] = us;
+            }
             fs.tau_add = a.pscale * us;
             if constexpr (!TAPE) ureg += us * us;
         }

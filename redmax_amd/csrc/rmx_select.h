@@ -166,4 +166,14 @@ inline const char* label_rollout_tape_bdf2(const AdjPlan& p) {      // what rmx_
     return p.kernel == AdjKernel::FullChain16 ? "k_adjoint_fwd<16,bdf2,tape,fullchain>" : "k_adjoint_fwd<bdf2,tape>";
 }
 
+
+// The taped rollout under state feedback (rmx_rollout_tape_feedback): always the generic one-wavefront kernel of part_plain, for
+// both integrators - never the helper-wave form (the feedback stage reads the registers of the wave that integrates) and never the
+// full-chain instantiation (one kernel per size keeps the new code small; the stage is a few percent of a step).  The backward
+// sweeps that read its tape follow select_rollout_tape: the tape's layout does not depend on the kernel that wrote it.
+inline AdjPlan select_rollout_feedback(const StepTraits&, const int, const int, const StepKnobs&) { return AdjPlan{}; }
+inline const char* label_rollout_feedback(const int integ) {      // what rmx_last_step_kernel reports after rmx_rollout_tape_feedback
+    return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback>" : "k_adjoint_fwd<bdf1,tape,feedback>";
+}
+
 }      // namespace rmx_select

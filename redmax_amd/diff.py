@@ -127,7 +127,7 @@ def _function():
 
 
 def _check_inputs(sim, q0, qdot0, u):
-    """The argument checks rollout, linearize and jvp share (and their words)."""
+    """The argument checks rollout, linearize, jvp and rollout_feedback share (and their words)."""
     import torch
     dev = torch.device("cuda", sim.device)
     for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
@@ -269,6 +269,63 @@ def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     A = torch.cat([torch.cat([S, h * XB], dim=-1), torch.cat([(S - eye) / h, XB], dim=-1)], dim=-2)
     Bm = torch.cat([XU, XU / h], dim=-2)
     return qtraj, qdtraj, A, Bm
+
+
+def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0, check=True, integrator=1, status=False):
+    """The controlled rollout of ``rollout`` in CLOSED LOOP: (qtraj, qdtraj, uapp), with the torque of step k
+
+        uapp[b, k-1] = uff[b, k-1] + K[.., k-1].T @ (x - xref[.., k-1]),      x = (q, qdot) at the START of step k
+
+    formed on the device from the state the rollout itself has reached - all steps in one launch (rmx_rollout_tape_feedback_device):
+    the forward pass of iLQR / DDP, time-varying-LQR tracking.  uff: [B][nsteps][nr].  K: [nsteps][2nr][nr], shared by the batch,
+    or [B][nsteps][2nr][nr]; the index order is (step, STATE entry j, torque i): K[.., k-1, j, i] = du_i/dx_j with the q block
+    first - a tensor whose memory is the ABI's column-major table (for a gain matrix G[i, j] in the usual order pass
+    G.transpose(-1, -2)).  xref: [nsteps][2nr] or [B][nsteps][2nr], row k-1 the reference for the state at the start of step k (row
+    0 belongs to (q0, qdot0)); K and xref both shared or both per rollout.  None: no feedback / a zero reference.
+    No autograd graph is made: the tape the call leaves is the open-loop tape under uapp, and gradients through the feedback law
+    are not available.  Arguments, checks and words are rollout's (uff in the place of u).  The call replaces the sim's tape, as
+    rollout does, and leaves the sim at the end of the rollout.  status=True appends the rollouts' status words (a bool tensor [B] on
+    the sim's device: did a Newton solve diverge, hit its iteration limit or meet a NaN) - for a caller that passes check=False and
+    sorts the rollouts itself, as a line search does."""
+    import torch
+    if integrator not in (1, 2):
+        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    _check_inputs(sim, q0, qdot0, uff)
+    B, nsteps, nr = uff.shape
+    dev = torch.device("cuda", sim.device)
+    per = []
+    for name, t, tail in (("K", K, (nsteps, 2 * nr, nr)), ("xref", xref, (nsteps, 2 * nr))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("rollout: %s must be float64, got %s" % (name, t.dtype))
+        if t.device != dev:
+            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+        if tuple(t.shape) not in (tail, (B,) + tail):
+            raise ValueError("rollout: %s must have shape %r or %r, got %r" % (name, tail, (B,) + tail, tuple(t.shape)))
+        per.append(t.dim() == len(tail) + 1)
+    if len(set(per)) > 1:
+        raise ValueError("rollout: K and xref must both be shared by the batch or both hold one table per rollout")
+    h = float(sim.opts.h if h is None else h)
+    q0c, qd0c, uc = q0.detach().contiguous(), qdot0.detach().contiguous(), uff.detach().contiguous()
+    Kc = None if K is None else K.detach().contiguous()
+    xc = None if xref is None else xref.detach().contiguous()
+    qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=dev)
+    qdtraj = torch.empty_like(qtraj)
+    uapp = torch.empty_like(qtraj)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
+    info = sim.rollout_feedback_device(nsteps, h, uc.data_ptr(), 0 if Kc is None else Kc.data_ptr(), 0 if xc is None else xc.data_ptr(),
+                                       qtraj.data_ptr(), qdtraj.data_ptr(), uapp.data_ptr(), per_rollout=bool(per and per[0]),
+                                       pscale=float(pscale), stats=bool(check or status), integrator=integrator)
+    if check and (info["status"] & _BAD_STATUS).any():
+        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
+        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+    if status:
+        return qtraj, qdtraj, uapp, torch.as_tensor((info["status"] & _BAD_STATUS) != 0, device=dev)
+    return qtraj, qdtraj, uapp
 
 
 def jvp(sim, q0, qdot0, u, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, check=True, integrator=1):

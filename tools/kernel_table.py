@@ -29,6 +29,11 @@ ROWS = (  # (name fragment, what it runs)
     ("k_rollout_bwd_bdf2<16, true>", "rmx_rollout_vjp on a BDF2 tape: full 16-link chain"),
     ("k_adjoint_fwd<64, 22, false, false>", "rmx_rollout_tape_bdf2: 33..64 nodes"),
     ("k_rollout_bwd_bdf2<64, false>", "rmx_rollout_vjp on a BDF2 tape: 33..64 nodes"),
+    ("k_adjoint_fwd<16, 85, false, false>", "rmx_rollout_tape_feedback (taped forward sweep under per-step affine state feedback, BDF1): 9..16 nodes"),
+    ("k_adjoint_fwd<32, 85, false, false>", "rmx_rollout_tape_feedback, BDF1: 17..32 nodes"),
+    ("k_adjoint_fwd<64, 85, false, false>", "rmx_rollout_tape_feedback, BDF1: 33..64 nodes"),
+    ("k_adjoint_fwd<32, 86, false, false>", "rmx_rollout_tape_feedback, BDF2: 17..32 nodes"),
+    ("k_adjoint_fwd<32, 21, false, false>", "rmx_rollout_tape, 17..32 nodes: the open-loop sibling of the feedback kernel"),
     ("k_rollout_linearize<4>", "rmx_rollout_linearize (XA, XB, XU of every slot of a tape; one wavefront per rollout and slot): <= 4 nodes"),
     ("k_rollout_linearize<8>", "rmx_rollout_linearize: 5..8 nodes"),
     ("k_rollout_linearize<16>", "rmx_rollout_linearize: 9..16 nodes"),
