@@ -483,7 +483,7 @@ int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const d
  * The tape the call leaves has rmx_rollout_tape's layout and IS the open-loop tape under the torques uapp: rmx_rollout_vjp,
  * rmx_rollout_linearize, rmx_rollout_jvp and rmx_rollout_vjp_params read it unchanged and differentiate the open-loop rollout at
  * uapp - what iLQR re-linearises around.  Gradients through the feedback law itself (dL/dK, dL/dxref, the closed-loop dL/duff) are
- * not formed by any entry.
+ * formed by rmx_rollout_vjp_feedback below, from the same tape.
  *
  * Refusals (RMX_E_INVALID): everything rmx_rollout_tape refuses, in its words; a null struct or uff ("null argument"); an integrator
  * other than 1 or 2; per_rollout other than 0 or 1.  A refused call leaves an existing tape alone.  The host form stages K, xref
@@ -500,6 +500,61 @@ int rmx_rollout_tape_feedback(rmx_batch* b, const rmx_opts* opts, int nsteps, in
                               const rmx_feedback* fb, double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats);
 int rmx_rollout_tape_feedback_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
                                      const rmx_feedback* fb, double* d_qtraj, double* d_qdtraj, double* d_uapp, rmx_stats* stats);
+
+/* The closed-loop adjoint of the taped rollout: dL/duff, dL/dK, dL/dxref, dL/dq0, dL/dqdot0 of a rollout that ran under
+ * rmx_rollout_tape_feedback, for any cotangents of its states and of its applied torques - tuning a controller on the device: gain
+ * and reference learning, policy gradients, differentiating an iLQR / MPC result through its own feedback policy.  Added WITHOUT a
+ * change of RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * With uapp_k = uff_k + K_k (x_{k-1} - xref_{k-1}) the tape is the open-loop tape under uapp; the closed loop adds one term per step:
+ * the cotangent ubar_k of the applied torque goes back into the cotangent of the state the step started from.  K_k = (Kq_k, Kv_k), the
+ * q block and the qdot block of row k-1's table (entry j*nr + i is du_i/dx_j), and (K' ubar)_j = sum_i K[j*nr + i] ubar_i.  gu: the
+ * caller's cotangent of uapp (costs on the applied control), shape of uff, or NULL: zero.  solve_bwd and the notation are those of
+ * rmx_rollout_tape_bdf2 above; the sweep carries qbar[k], vbar[k], which start as gq_k, gqd_k (zero for k = 0).
+ *   BDF1 (eta = h, slot k-1 is step k, qA = q_{k-1}, qB = q_{k-1} + h qd_{k-1}), for k = N .. 1:
+ *     (A, Bq, z) = solve_bwd(slot k-1, h; qbar[k], vbar[k]) ;  ubar_k = h^2 pscale z + gu_k
+ *     qbar[k-1] += A + Bq + Kq_k' ubar_k ;  vbar[k-1] += h Bq + Kv_k' ubar_k
+ *   (without the K terms this is rmx_rollout_vjp's recursion in another arrangement.)
+ *   BDF2: the recursion at rmx_rollout_tape_bdf2 with two additions.  Behind the solve of step k+1:
+ *     ubar_{k+1} = (2h/3)^2 pscale z + gu_{k+1} ;  qbar[k] += Kq_{k+1}' ubar_{k+1} ;  vbar[k] += Kv_{k+1}' ubar_{k+1}
+ *   - before qbar[k] enters the solve of step k -, and in the start step
+ *     ubar_1 = (al h)^2 pscale (za + zb) + gu_1 ;  qbar[0] += Kq_1' ubar_1 ;  vbar[0] += Kv_1' ubar_1
+ *   (step 1's torque holds for both SDIRK2 solves and reads x_0 only.)
+ *   Outputs, both integrators:
+ *     duff_k = ubar_k ;  dxref_{k-1} = -(Kq_k' ubar_k, Kv_k' ubar_k)          (row k-1, 2 nr entries)
+ *     dK_k[j*nr + i] = (x_{k-1} - xref_{k-1})_j ubar_{k,i}     (x_0 = (q0, qdot0) of the tape; for k > 1 row k-2 of its trajectory)
+ *     dq0 = qbar[0] ;  dqd0 = vbar[0]
+ *
+ * The call reads the tape on the batch and follows its integrator, as rmx_rollout_vjp does; h and pscale are the tape's.  fb->K,
+ * fb->xref and fb->per_rollout are as in the forward call (xref NULL: a zero reference); fb->uff is not read.  gq, gqd: as
+ * rmx_rollout_vjp.  The call does NOT check that the tape was recorded under these gains - a replay under uapp leaves the identical
+ * tape, so it cannot: passing the K, xref of the forward call is the caller's contract.
+ * Gradient rows are ALWAYS per rollout, whether the tables are shared or not: for tables the batch shares the caller sums over the
+ * batch (the rule of rmx_rollout_vjp_params, for the same reason: a loss may weight rollouts).  dK is batch * nsteps * 2 nr^2 doubles;
+ * for a shared table it is cheaper formed as the caller's own contraction of duff with the states (sum_b dx_{b,k-1,j} duff_{b,k,i}),
+ * with dK NULL here.  Every output has the same bits whichever others are NULL, and a rollout's rows do not depend on its place in
+ * the batch or on the batch size (K' ubar runs in one fixed order: the nodes of the tree ascending, one fused multiply-add per term).
+ * fb->K NULL: no gains.  With gu NULL too the call IS rmx_rollout_vjp on that tape - the same kernel, the same bits in duff, dq0,
+ * dqd0 -; with gu, duff = du + gu and dq0, dqd0 are the open-loop ones up to rounding.  dK or dxref asked for without gains is refused.
+ *
+ * The call changes neither the batch's state nor the tape: it may be repeated with the same bits, and rmx_rollout_vjp,
+ * rmx_rollout_linearize, rmx_rollout_jvp and rmx_rollout_vjp_params return the same bits before and after it.  Refusals
+ * (RMX_E_INVALID), in rmx_rollout_vjp's words where they coincide: "no tape", an nsteps that differs from the tape's, a null batch,
+ * fb, gq, gqd or out ("null argument"), "all outputs are null", dq0 and dqd0 not given together, per_rollout other than 0 or 1, dK or
+ * dxref without K ("no gains").  The host form stages the cotangents, K, xref and the outputs through a device allocation of its own,
+ * made ahead of anything else and freed before it returns; the tape's workspace does not grow.  The _device form: every array a
+ * DEVICE pointer (both structs are host objects), nothing staged; it returns when the kernel has finished. */
+typedef struct rmx_feedback_grads {   /* every pointer may be NULL (not formed), but not all of duff, dK, dxref, dq0 */
+    double* duff;    /* [batch][nsteps][nr]                                                     */
+    double* dK;      /* [batch][nsteps][2*nr*nr]  one row per rollout, layout of a per-rollout K */
+    double* dxref;   /* [batch][nsteps][2*nr]     one row per rollout                            */
+    double* dq0;     /* [batch][nr]  \ NULL together                                             */
+    double* dqd0;    /* [batch][nr]  /                                                           */
+} rmx_feedback_grads;
+int rmx_rollout_vjp_feedback(rmx_batch* b, int nsteps, const rmx_feedback* fb, const double* gq, const double* gqd,
+                             const double* gu, const rmx_feedback_grads* out);
+int rmx_rollout_vjp_feedback_device(rmx_batch* b, int nsteps, const rmx_feedback* fb, const double* d_gq, const double* d_gqd,
+                                    const double* d_gu, const rmx_feedback_grads* out);
 
 /* The linearisation of the taped rollout: the forward sensitivities of every taped solve, from which a host assembles the per-step
  * A_k = d(q_k, qdot_k)/d(q_{k-1}, qdot_{k-1}) and B_k = d(q_k, qdot_k)/du_k that iLQR / DDP, time-varying LQR, Gauss-Newton shooting

@@ -180,7 +180,7 @@ classdef HipSim < handle
 			% K: nr x 2nr x nsteps, shared by the batch, or nr x 2nr x nsteps x B, K(i,j,k) = du_i/dx_j; xref: 2nr x nsteps
 			% or 2nr x nsteps x B (K and xref alike); [] for either: no feedback / a zero reference.  uapp: the applied torques.
 			% The tape it leaves is the open-loop tape under uapp: rolloutVjp, rolloutLinearize and rolloutJvp differentiate
-			% that open-loop rollout, not the feedback law.
+			% that open-loop rollout; rolloutVjpFeedback differentiates the closed loop (dL/dK, dL/dxref, dL/duff).
 			if nargin < 6
 				K = [];
 			end
@@ -198,6 +198,18 @@ classdef HipSim < handle
 			% dL/dqdot of every step; du (nr x nsteps x B), dq0, dqd0 (nr x B) are dL/du, dL/dq0, dL/dqdot0.  May be
 			% repeated with other cotangents; an adjoint* call or another rolloutTape ends the tape.
 			[du, dq0, dqd0] = redmax_hip_mex('rollout_vjp', this.h, nsteps, gq, gqd);
+		end
+
+		function [duff, dK, dxref, dq0, dqd0] = rolloutVjpFeedback(this, nsteps, gq, gqd, K, xref, gu)
+			% the closed-loop adjoint of the last rolloutFeedback: gq, gqd as rolloutVjp, gu (nr x nsteps x B, or []: zero) the
+			% cotangent of the applied torques uapp; K, xref: the tables of the forward call ([]: no gains / a zero reference).
+			% duff (nr x nsteps x B), dK (nr x 2nr x nsteps x B), dxref (2nr x nsteps x B), dq0, dqd0 (nr x B): ALWAYS one slice
+			% per rollout - for tables the batch shares, sum over B.  Outputs that are not asked for are not formed; without
+			% gains dK and dxref are [].  The tape and the state stay as they are.
+			if nargin < 7
+				gu = [];
+			end
+			[duff, dK, dxref, dq0, dqd0] = redmax_hip_mex('rollout_vjp_feedback', this.h, nsteps, gq, gqd, K, xref, gu);
 		end
 
 		function [du, dq0, dqd0, grads] = rolloutVjpParams(this, nsteps, gq, gqd)

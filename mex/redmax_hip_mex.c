@@ -703,6 +703,52 @@ static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     else mxDestroyArray(dqd0);
 }
 
+/* 'rollout_vjp_feedback': the closed-loop adjoint on the tape 'rollout_feedback' left.  K, xref as there ([]: none); gu [] or as gq.
+ * The gradient rows are per rollout whatever the tables are: dK nr x 2nr x nsteps x B, dxref 2nr x nsteps x B. */
+static void cmd_rollout_vjp_feedback(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 7) die("usage: [duff,dK,dxref,dq0,dqd0] = redmax_hip_mex('rollout_vjp_feedback', h, nsteps, gq, gqd, K, xref [, gu])");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_vjp_feedback: nsteps must be at least 1");
+    const double* gq = traj_arg(prhs[3], h, nsteps, "gq");
+    const double* gqd = traj_arg(prhs[4], h, nsteps, "gqd");
+    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps;
+    int per_rollout = -1;
+    const double* K = feedback_arg(prhs[5], h, 2 * nr * nr, nsteps, &per_rollout, "K");
+    const double* xref = feedback_arg(prhs[6], h, 2 * nr, nsteps, &per_rollout, "xref");
+    if (per_rollout < 0) per_rollout = 0;
+    const double* gu = (nrhs > 7 && !mxIsEmpty(prhs[7])) ? traj_arg(prhs[7], h, nsteps, "gu") : NULL;
+    const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B}, dimsK[4] = {nr, 2 * nr, (size_t)nsteps, (size_t)h->B};
+    const size_t dimsx[3] = {2 * nr, (size_t)nsteps, (size_t)h->B};
+    mxArray* out[5];
+    out[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    out[1] = (K && nlhs > 1) ? mxCreateNumericArray(4, dimsK, mxDOUBLE_CLASS, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    out[2] = (K && nlhs > 2) ? mxCreateNumericArray(3, dimsx, mxDOUBLE_CLASS, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    out[3] = mxCreateDoubleMatrix(nr, (size_t)h->B, mxREAL);
+    out[4] = mxCreateDoubleMatrix(nr, (size_t)h->B, mxREAL);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_feedback fb;
+        fb.uff = NULL;
+        fb.K = K ? K + (per_rollout ? f * (size_t)nsteps * 2 * nr * nr : 0) : NULL;
+        fb.xref = xref ? xref + (per_rollout ? f * (size_t)nsteps * 2 * nr : 0) : NULL;
+        fb.per_rollout = per_rollout;
+        rmx_feedback_grads g;
+        g.duff = mxGetPr(out[0]) + f * per;
+        g.dK = (K && nlhs > 1) ? mxGetPr(out[1]) + f * (size_t)nsteps * 2 * nr * nr : NULL;
+        g.dxref = (K && nlhs > 2) ? mxGetPr(out[2]) + f * (size_t)nsteps * 2 * nr : NULL;
+        g.dq0 = mxGetPr(out[3]) + f * nr;
+        g.dqd0 = mxGetPr(out[4]) + f * nr;
+        if (rmx_rollout_vjp_feedback(b, nsteps, &fb, gq + f * per, gqd + f * per, gu ? gu + f * per : NULL, &g)) die_rmx("rmx_rollout_vjp_feedback");
+    }
+    plhs[0] = out[0];
+    for (int i = 1; i < 5; ++i) {
+        if (nlhs > i) plhs[i] = out[i];
+        else mxDestroyArray(out[i]);
+    }
+}
+
 static void cmd_rollout_vjp_params(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
     if (nrhs < 5) die("usage: [du,dq0,dqd0,dk,dd,dqrest,dI,dgrav] = redmax_hip_mex('rollout_vjp_params', h, nsteps, gq, gqd)");
@@ -896,7 +942,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", NULL};
+                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -1007,6 +1053,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_feedback(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp")) {
         cmd_rollout_vjp(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_vjp_feedback")) {
+        cmd_rollout_vjp_feedback(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_linearize")) {
         cmd_rollout_linearize(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp_params")) {

@@ -27,6 +27,7 @@ SYMBOLS = (
     "rmx_rollout_tape", "rmx_rollout_vjp", "rmx_rollout_tape_device", "rmx_rollout_vjp_device",
     "rmx_rollout_tape_bdf2", "rmx_rollout_tape_bdf2_device",
     "rmx_rollout_tape_feedback", "rmx_rollout_tape_feedback_device",
+    "rmx_rollout_vjp_feedback", "rmx_rollout_vjp_feedback_device",
     "rmx_rollout_linearize", "rmx_rollout_linearize_device",
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
@@ -94,6 +95,11 @@ class Feedback(C.Structure):      # rmx_feedback: host pointers in the host form
     _fields_ = [("uff", C.c_void_p), ("K", C.c_void_p), ("xref", C.c_void_p), ("per_rollout", C.c_int)]
 
 
+class FeedbackGrads(C.Structure):      # rmx_feedback_grads: host pointers in the host form, device pointers in the _device form
+    _fields_ = [("duff", C.c_void_p), ("dK", C.c_void_p), ("dxref", C.c_void_p), ("dq0", C.c_void_p), ("dqd0", C.c_void_p)]
+
+
+FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
 PARAM_NAMES = ("stiffness", "damping", "qrest", "inertia", "grav")      # the members of rmx_param_grads, in their order
 
 
@@ -159,6 +165,8 @@ def lib():
     L.rmx_rollout_tape_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_double, vp, vp, vp, C.POINTER(Stats)]
     L.rmx_rollout_tape_feedback.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), _dp, _dp, _dp, C.POINTER(Stats)]
     L.rmx_rollout_tape_feedback_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), vp, vp, vp, C.POINTER(Stats)]
+    L.rmx_rollout_vjp_feedback.argtypes = [vp, C.c_int, C.POINTER(Feedback), _dp, _dp, _dp, C.POINTER(FeedbackGrads)]
+    L.rmx_rollout_vjp_feedback_device.argtypes = [vp, C.c_int, C.POINTER(Feedback), vp, vp, vp, C.POINTER(FeedbackGrads)]
     L.rmx_rollout_tape_bdf2.argtypes = L.rmx_rollout_tape.argtypes
     L.rmx_rollout_tape_bdf2_device.argtypes = L.rmx_rollout_tape_device.argtypes
     L.rmx_rollout_vjp.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp]

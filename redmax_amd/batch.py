@@ -454,7 +454,7 @@ class BatchSim:
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
-    def _feedback_tables(self, nsteps, K, xref):
+    def _feedback_tables(self, nsteps, K, xref, who="rollout_feedback"):
         """K and xref of rollout_feedback as contiguous float64 arrays, and whether they hold one table per rollout.  K:
         [nsteps][2nr][nr] or [B][nsteps][2nr][nr], K[.., k-1, j, i] = du_i/dx_j of step k with x = (q, qdot) - the ABI's column-major
         table as a C array -; xref: [nsteps][2nr] or [B][nsteps][2nr].  Both shared or both per rollout."""
@@ -465,12 +465,12 @@ class BatchSim:
                 continue
             a = np.ascontiguousarray(a, dtype=np.float64)
             if a.shape not in (tail, (B,) + tail):
-                raise ValueError("rollout_feedback: %s must have shape %r or %r, got %r" % (name, tail, (B,) + tail, a.shape))
+                raise ValueError("%s: %s must have shape %r or %r, got %r" % (who, name, tail, (B,) + tail, a.shape))
             shapes[name] = a
         K, xref = shapes.get("K"), shapes.get("xref")
         per = [a.ndim == len(t) + 1 for a, t in ((K, (0, 0, 0)), (xref, (0, 0))) if a is not None]
         if len(set(per)) > 1:
-            raise ValueError("rollout_feedback: K and xref must both be shared by the batch or both hold one table per rollout")
+            raise ValueError("%s: K and xref must both be shared by the batch or both hold one table per rollout" % who)
         return K, xref, int(bool(per and per[0]))
 
     def rollout_feedback(self, nsteps, h, uff, K=None, xref=None, pscale=1.0, stats=False, integrator=1):
@@ -481,7 +481,7 @@ class BatchSim:
         du_i/dx_j (the row index is the STATE entry, q block first: the memory is the ABI's column-major table); None: no feedback,
         uapp is uff bit for bit.  xref: [nsteps][2nr] or [B][nsteps][2nr], None: zero.  Returns (qtraj, qdtraj, uapp[, info]) - info
         with stats=True.  The tape it leaves is the open-loop tape under uapp: rollout_vjp, rollout_linearize, rollout_jvp and
-        rollout_vjp_params differentiate that open-loop rollout, not the feedback law."""
+        rollout_vjp_params differentiate that open-loop rollout, not the feedback law; rollout_vjp_feedback differentiates the closed loop."""
         if integrator not in (1, 2):
             raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
         nsteps = int(nsteps)
@@ -550,6 +550,52 @@ class BatchSim:
         _abi.check(self._L.rmx_rollout_vjp_device(self._batch, int(nsteps), C.c_void_p(gq_ptr or None), C.c_void_p(gqd_ptr or None),
                                                   C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None)),
                    "rmx_rollout_vjp_device")
+
+    def rollout_vjp_feedback(self, nsteps, gq, gqd, K=None, xref=None, gu=None, want=None):
+        """rmx_rollout_vjp_feedback on the tape of the last rollout_feedback: the closed-loop adjoint.  gq, gqd [B][nsteps][nr] are
+        dL/dq_k, dL/dqdot_k, gu (or None: zero) the cotangent of the applied torque uapp; K, xref: the tables of the forward call
+        (rollout_feedback's shapes; the library cannot check that the tape was recorded under them).  Returns a dict with the names in
+        `want` among "duff" [B][nsteps][nr], "dK" [B][nsteps][2nr][nr], "dxref" [B][nsteps][2nr], "dq0" (which brings "dqd0", both
+        [B][nr]; None: all of them with gains, "duff" and "dq0" without): ALWAYS one row per rollout - for tables the batch shares, sum over the batch.  K None: no gains ("dK", "dxref"
+        are refused); with gu None too the call is rollout_vjp, the same bits.  Neither the state nor the tape changes."""
+        nsteps = int(nsteps)
+        if want is None:
+            want = ("duff", "dq0") if K is None else ("duff", "dK", "dxref", "dq0")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        names = _abi.FEEDBACK_GRAD_NAMES
+        if any(w not in names for w in want) or len(set(want)) != len(want):
+            raise ValueError("rollout_vjp_feedback: want must name distinct outputs among %s, got %r" % (", ".join(repr(n) for n in names), want))
+        if "dq0" in want or "dqd0" in want:
+            want = tuple(w for w in want if w not in ("dq0", "dqd0")) + ("dq0", "dqd0")
+        sh = (self.B, nsteps, self.nr)
+        gq = np.ascontiguousarray(gq, dtype=np.float64)
+        gqd = np.ascontiguousarray(gqd, dtype=np.float64)
+        if gq.shape != sh or gqd.shape != sh:
+            raise ValueError("rollout_vjp_feedback: gq and gqd must have shape %r, got %r and %r" % (sh, gq.shape, gqd.shape))
+        if gu is not None:
+            gu = np.ascontiguousarray(gu, dtype=np.float64)
+            if gu.shape != sh:
+                raise ValueError("rollout_vjp_feedback: gu must have shape %r, got %r" % (sh, gu.shape))
+        K, xref, per = self._feedback_tables(nsteps, K, xref, who="rollout_vjp_feedback")
+        fb = _abi.Feedback(None, K.ctypes.data if K is not None else None, xref.ctypes.data if xref is not None else None, per)
+        shapes = {"duff": sh, "dK": (self.B, nsteps, 2 * self.nr, self.nr), "dxref": (self.B, nsteps, 2 * self.nr),
+                  "dq0": (self.B, self.nr), "dqd0": (self.B, self.nr)}
+        out = {w: np.zeros(shapes[w]) for w in want}
+        fg = _abi.FeedbackGrads(*[out[n].ctypes.data if n in out else None for n in names])
+        _abi.check(self._L.rmx_rollout_vjp_feedback(self._batch, nsteps, C.byref(fb), _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(gu),
+                                                    C.byref(fg)), "rmx_rollout_vjp_feedback")
+        return out
+
+    def rollout_vjp_feedback_device(self, nsteps, gq_ptr, gqd_ptr, gu_ptr=None, K_ptr=None, xref_ptr=None, per_rollout=False, duff_ptr=None,
+                                    dK_ptr=None, dxref_ptr=None, dq0_ptr=None, dqd0_ptr=None):
+        """rollout_vjp_feedback with DEVICE pointers (integers): gq, gqd, gu, duff [B][nsteps][nr]; K [nsteps][2nr][nr] and xref
+        [nsteps][2nr], or one table per rollout with per_rollout=True; dK [B][nsteps][2nr][nr], dxref [B][nsteps][2nr], dq0, dqd0
+        [B][nr].  0 / None: gu zero, no gains, a zero reference, that output not formed (dq0 and dqd0 together; not all outputs)."""
+        fb = _abi.Feedback(None, K_ptr or None, xref_ptr or None, int(bool(per_rollout)))
+        fg = _abi.FeedbackGrads(duff_ptr or None, dK_ptr or None, dxref_ptr or None, dq0_ptr or None, dqd0_ptr or None)
+        _abi.check(self._L.rmx_rollout_vjp_feedback_device(self._batch, int(nsteps), C.byref(fb), C.c_void_p(gq_ptr or None),
+                                                           C.c_void_p(gqd_ptr or None), C.c_void_p(gu_ptr or None), C.byref(fg)),
+                   "rmx_rollout_vjp_feedback_device")
 
     def _param_shapes(self):
         """The shape of one rollout's row of every rmx_param_grads member."""

@@ -82,6 +82,14 @@ void RMX_CAT(launch_rollout_feedback_, RMX_NP)(const rmx_model* m, const rmx_bat
     else RMX_LAUNCH((k_adjoint_fwd<RMX_NP, 2 | ADJ_CTL | ADJ_TAPE | ADJ_FB, false, false>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
 }
 
+// rmx_rollout_vjp_feedback: the closed-loop backward sweep of the tape (rmx_feedback_bwd.h).  Always this generic one-wavefront kernel
+// (rmx_select.h select_rollout_vjp_feedback)
+void RMX_CAT(launch_vjp_feedback_, RMX_NP)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a) {
+    const dim3 grid(b->B), block(64);
+    if (integ == INTEG_BDF1) k_rollout_bwd_fb<RMX_NP, 1><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+    else k_rollout_bwd_fb<RMX_NP, 2><<<grid, block, 0, b->stream>>>(m->dm, o, a);
+}
+
 // rmx_rollout_linearize: every slot of the tape at once
 void RMX_CAT(launch_linearize_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LinArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nslots)), block(64);

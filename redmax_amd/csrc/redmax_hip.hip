@@ -1667,18 +1667,18 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
 }
 
 static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
-                            const bool on_device) {
-    if (!b || !gq || !gqd || !du) return fail(RMX_E_INVALID, "rmx_rollout_vjp: null argument");
-    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_vjp: dq0 and dqd0 must be given together");
+                            const bool on_device, const std::string& who = "rmx_rollout_vjp") {
+    if (!b || !gq || !gqd || !du) return fail(RMX_E_INVALID, who + ": null argument");
+    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, who + ": dq0 and dqd0 must be given together");
     rmx_model* m = b->m;
     if (b->tape_nsteps < 1 || !b->adjws)
-        return fail(RMX_E_INVALID, "rmx_rollout_vjp: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
-    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_vjp: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+        return fail(RMX_E_INVALID, who + ": no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, who + ": nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
     HIPCHK(hipSetDevice(m->device));
-    int rc = pending_error_check(b, "rmx_rollout_vjp");
+    int rc = pending_error_check(b, who.c_str());
     if (rc) return rc;
     const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
-    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp: no tape (the workspace is smaller than the tape)");
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, who + ": no tape (the workspace is smaller than the tape)");
     char* ws = (char*)b->adjws;
     DevOpts o{};
     o.h = b->tape_h;
@@ -1711,8 +1711,102 @@ static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const do
     }
     if (e == hipSuccess) e = wait_stream_short(b->stream);
     else (void)hipStreamSynchronize(b->stream);      // (the cotangents must outlive their copies)
-    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RMX_E_HIP, who + ": " + hipGetErrorString(e));
     take_event_time(b);
+    return RMX_OK;
+}
+
+// rmx_rollout_vjp_feedback: the closed-loop backward sweep (rmx_feedback_bwd.h).  Without gains and without gu it IS rmx_rollout_vjp
+// (the same launch, the same bits).  Otherwise one launch of k_rollout_bwd_fb; the host form stages the cotangents, K, xref and the
+// outputs through a device allocation of its own, made ahead of anything else and freed before the return: the tape's workspace
+// neither grows nor is written.
+static int rollout_vjp_feedback_impl(rmx_batch* b, int nsteps, const rmx_feedback* fb, const double* gq, const double* gqd, const double* gu,
+                                     const rmx_feedback_grads* out, const bool on_device) {
+    if (!b || !fb || !gq || !gqd || !out) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: null argument");
+    if (!out->duff && !out->dK && !out->dxref && !out->dq0) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: all outputs are null");
+    if ((out->dq0 == nullptr) != (out->dqd0 == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: dq0 and dqd0 must be given together");
+    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: per_rollout must be 0 or 1");
+    if (!fb->K && (out->dK || out->dxref)) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: no gains (K is null): dK and dxref cannot be formed");
+    rmx_model* m = b->m;
+    if (b->tape_nsteps < 1 || !b->adjws)
+        return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+    HIPCHK(hipSetDevice(m->device));
+    int rc = pending_error_check(b, "rmx_rollout_vjp_feedback");
+    if (rc) return rc;
+    const int integ = b->tape_integ;
+    const TapeParts t = tape_parts(b, nsteps, integ);
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: no tape (the workspace is smaller than the tape)");
+    if (!fb->K && !gu) {      // rmx_rollout_vjp itself; a duff nobody asked for goes to a scratch array of the call's own
+        double* du = out->duff;
+        std::vector<double> hdu;
+        if (!du && !on_device) {
+            hdu.resize((size_t)b->B * nsteps * m->nr);
+            du = hdu.data();
+        } else if (!du && hipMalloc((void**)&du, t.bytes_traj ? t.bytes_traj : 256) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RMX_E_NOMEM, "rmx_rollout_vjp_feedback: no device memory for the staging");
+        }
+        rc = rollout_vjp_impl(b, nsteps, gq, gqd, du, out->dq0, out->dqd0, on_device, "rmx_rollout_vjp_feedback");
+        if (!out->duff && on_device) (void)hipFree(du);
+        if (rc == RMX_OK)      // (the plan launch_adjoint_plan has just executed: the selection is pure)
+            b->last_kernel = rmx_select::label_rollout_vjp(rmx_select::select_rollout_tape(step_traits(m), b->B, integ, rmx_select::knobs_from_env()), integ);
+        return rc;
+    }
+    const size_t nr = m->nr;
+    const size_t fb_tables = (fb->per_rollout ? (size_t)b->B : 1) * nsteps, rows = (size_t)b->B * nsteps;
+    // the staged arrays of the host form, each at a 256-byte boundary of one allocation: inputs gq, gqd, gu, K, xref, then the outputs
+    enum { S_GQ, S_GQD, S_GU, S_K, S_X, S_DUFF, S_DK, S_DX, S_DQ0, S_DQD0, S_N };
+    const void* hin[S_N] = {gq, gqd, gu, fb->K, fb->K ? fb->xref : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double* hout[S_N] = {nullptr, nullptr, nullptr, nullptr, nullptr, out->duff, out->dK, out->dxref, out->dq0, out->dqd0};
+    const size_t bytes[S_N] = {t.bytes_traj, t.bytes_traj, t.bytes_traj, fb_tables * 2 * nr * nr * sizeof(double), fb_tables * 2 * nr * sizeof(double),
+                               t.bytes_traj, rows * 2 * nr * nr * sizeof(double), rows * 2 * nr * sizeof(double), t.bytes_state, t.bytes_state};
+    char* stage = nullptr;
+    size_t at[S_N] = {};
+    if (!on_device) {
+        size_t want = 0;
+        for (int i = 0; i < S_N; ++i) {
+            at[i] = want;
+            if (hin[i] || hout[i]) want += (bytes[i] + 255) & ~(size_t)255;
+        }
+        const hipError_t em = hipMalloc((void**)&stage, want ? want : 256);
+        if (em == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, "rmx_rollout_vjp_feedback: no device memory for the staging"); }
+        if (em != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp_feedback: ") + hipGetErrorString(em));
+    }
+    auto din = [&](const int i) { return !hin[i] ? (const double*)nullptr : on_device ? (const double*)hin[i] : (const double*)(stage + at[i]); };
+    auto dout = [&](const int i) { return !hout[i] ? (double*)nullptr : on_device ? hout[i] : (double*)(stage + at[i]); };
+    char* ws = (char*)b->adjws;
+    DevOpts o{};
+    o.h = b->tape_h;
+    AdjArgs a{};
+    a.B = b->B; a.nsteps = nsteps; a.pscale = b->tape_pscale;
+    a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
+    a.tape = 2;
+    a.gq = din(S_GQ); a.gqd = din(S_GQD); a.gu = din(S_GU);
+    a.fbK = din(S_K); a.fbx = din(S_X);
+    a.fb_stride = fb->per_rollout ? (size_t)nsteps : 0;
+    a.dPdu = dout(S_DUFF); a.dK = dout(S_DK); a.dxref = dout(S_DX); a.dq0 = dout(S_DQ0); a.dqd0 = dout(S_DQD0);
+    a.fq0 = (const double*)(ws + t.off[TP_Q0]); a.fqd0 = (const double*)(ws + t.off[TP_QD0]);
+    a.fqt = (const double*)(ws + t.off[TP_QT]); a.fqdt = (const double*)(ws + t.off[TP_QDT]);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < S_N && !on_device; ++i)
+        if (e == hipSuccess && hin[i] && bytes[i]) e = hipMemcpyAsync(stage + at[i], hin[i], bytes[i], hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
+    if (e == hipSuccess) {
+        const rmx_select::AdjPlan plan = rmx_select::select_rollout_vjp_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
+        if (plan.kernel == AdjKernel::Generic) DISPATCH_NP(m->NP, launch_vjp_feedback, m, b, integ, o, a)
+        else e = hipErrorInvalidDeviceFunction;      // (no other kernel exists: never a silent substitute)
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+    for (int i = 0; i < S_N && !on_device; ++i)
+        if (e == hipSuccess && hout[i] && bytes[i]) e = hipMemcpyAsync(hout[i], stage + at[i], bytes[i], hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = wait_stream_short(b->stream);
+    else (void)hipStreamSynchronize(b->stream);      // (the inputs must outlive their copies)
+    if (stage) (void)hipFree(stage);
+    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp_feedback: ") + hipGetErrorString(e));
+    take_event_time(b);
+    b->last_kernel = rmx_select::label_rollout_vjp_feedback(integ);
     return RMX_OK;
 }
 
@@ -1960,6 +2054,14 @@ extern "C" int rmx_rollout_vjp(rmx_batch* b, int nsteps, const double* gq, const
 extern "C" int rmx_rollout_vjp_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
                                       double* d_dqd0) {
     return rollout_vjp_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, true);
+}
+extern "C" int rmx_rollout_vjp_feedback(rmx_batch* b, int nsteps, const rmx_feedback* fb, const double* gq, const double* gqd, const double* gu,
+                                        const rmx_feedback_grads* out) {
+    return rollout_vjp_feedback_impl(b, nsteps, fb, gq, gqd, gu, out, false);
+}
+extern "C" int rmx_rollout_vjp_feedback_device(rmx_batch* b, int nsteps, const rmx_feedback* fb, const double* d_gq, const double* d_gqd,
+                                               const double* d_gu, const rmx_feedback_grads* out) {
+    return rollout_vjp_feedback_impl(b, nsteps, fb, d_gq, d_gqd, d_gu, out, true);
 }
 extern "C" int rmx_rollout_vjp_params(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
                                       const rmx_param_grads* out) {

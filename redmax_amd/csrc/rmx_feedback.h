@@ -15,9 +15,9 @@
 // The loads of FB_CHUNK columns are issued together and unconditionally (column index clamped, the term selected afterwards: see
 // adj_block), not one dependent round trip per column.
 //
-// What is NOT here: gradients through the feedback law.  The tape a feedback rollout leaves is the open-loop tape under the applied
+// What is not here but in rmx_feedback_bwd.h: gradients through the feedback law.  The tape a feedback rollout leaves is the open-loop tape under the applied
 // torques uapp, and rmx_rollout_vjp / _linearize / _jvp / _vjp_params differentiate that open-loop rollout - what iLQR re-linearises
-// around.  dL/dK, dL/dxref and the closed-loop dL/duff are not formed anywhere.
+// around.  dL/dK, dL/dxref and the closed-loop dL/duff are formed by rmx_rollout_vjp_feedback: rmx_feedback_bwd.h.
 #pragma once
 
 constexpr int FB_CHUNK = 16;      // columns in flight at a time

@@ -83,6 +83,12 @@ struct AdjArgs {
     const double* fbx;        // [nsteps][2 nr] or [B][..]: row k-1 the reference (q, qdot) for the state at the start of step k; null: zero
     size_t fb_stride;         // rows (steps) from one rollout's tables to the next: nsteps, or 0 for tables the batch shares
     double* uapp;             // [B][nsteps][nr] the torque applied in every step (out), or null
+    // rmx_rollout_vjp_feedback (k_rollout_bwd_fb, rmx_feedback_bwd.h: fbK, fbx, fb_stride as above; dPdu is duff and may be null there)
+    const double* gu;         // [B][nsteps][nr] the cotangent of the applied torque, or null: zero
+    double* dK;               // [B][nsteps][2 nr nr] one table per rollout (out), or null
+    double* dxref;            // [B][nsteps][2 nr] one row per rollout (out), or null
+    const double *fq0, *fqd0; // [B][nr] the state the tape started from (its parts TP_Q0, TP_QD0): read for dK alone
+    const double *fqt, *fqdt; // [B][nsteps][nr] the tape's trajectory (TP_QT, TP_QDT): read for dK alone
 };
 
 // rmx_rollout_vjp_params (rmx_params.h): one wavefront per rollout walks the slots of its tape
@@ -201,6 +207,7 @@ struct rmx_batch {
     void RMX_CAT(launch_energy_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
     void RMX_CAT(launch_adjoint_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_rollout_feedback_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
+    void RMX_CAT(launch_vjp_feedback_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \

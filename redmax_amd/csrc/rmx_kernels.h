@@ -1536,6 +1536,8 @@ __global__ void __launch_bounds__(64) k_rollout_bwd_bdf2_zs(const DevModel Min, 
     }
 }
 
+#include "rmx_feedback_bwd.h"      /* k_rollout_bwd_fb: the closed-loop backward sweep, on tape_solve_bwd above */
+
 // Parity hook: one residual (+Hessian) evaluation per trajectory, results to HBM.
 template <int NP, bool WANT_H, bool CT>
 __global__ void __launch_bounds__(64) k_eval(const DevModel M, const int B, const double* __restrict__ q,

@@ -176,4 +176,18 @@ inline const char* label_rollout_feedback(const int integ) {      // what rmx_la
     return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback>" : "k_adjoint_fwd<bdf1,tape,feedback>";
 }
 
+// The closed-loop backward sweep (rmx_rollout_vjp_feedback with gains or a cotangent of the applied torque): always the generic
+// one-wavefront kernel of part_plain (rmx_feedback_bwd.h), for both integrators and every size - the K term sits between two solves
+// of the same wavefront, so there is no helper-wave form, and one kernel per size keeps the new code small.  Without gains and
+// without gu the entry IS rmx_rollout_vjp and follows select_rollout_tape: label_rollout_vjp names the backward kernel that plan runs.
+inline AdjPlan select_rollout_vjp_feedback(const StepTraits&, const int, const int, const StepKnobs&) { return AdjPlan{}; }
+inline const char* label_rollout_vjp_feedback(const int integ) {      // what rmx_last_step_kernel reports after rmx_rollout_vjp_feedback
+    return integ == BDF2 ? "k_rollout_bwd_fb<bdf2,vjp_feedback>" : "k_rollout_bwd_fb<bdf1,vjp_feedback>";
+}
+inline const char* label_rollout_vjp(const AdjPlan& p, const int integ) {      // ... after rmx_rollout_vjp_feedback without gains and gu
+    const bool fc = p.kernel == AdjKernel::FullChain16 || (p.kernel == AdjKernel::Help16 && p.fullchain);
+    if (integ == BDF2) return fc ? "k_rollout_bwd_bdf2<16,fullchain>" : "k_rollout_bwd_bdf2";
+    return fc ? "k_adjoint_bwd<16,bdf1,tape,fullchain>" : "k_adjoint_bwd<bdf1,tape>";
+}
+
 }      // namespace rmx_select

@@ -5,7 +5,9 @@ the model's own parameters (joint stiffness, damping and rest position, body ine
 Forward is rmx_rollout_tape_device (rmx_rollout_tape_bdf2_device under integrator=2), backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
 objective lives wholly on the PyTorch side.  Forward mode (torch.autograd.forward_ad, torch.func.jvp, torch.func.jacfwd) runs
 rmx_rollout_jvp_device on the same tape; ``jvp(sim, q0, qdot0, u, ...)`` pushes several tangent directions through one tape in one
-call.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
+call.  ``rollout_closed_loop`` is the same for a rollout under state feedback (rmx_rollout_tape_feedback_device forward,
+rmx_rollout_vjp_feedback_device backward): autograd reaches the gains K, the reference xref and the feed-forward uff through the
+closed loop.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
 """
 from __future__ import annotations
 
@@ -282,8 +284,8 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     first - a tensor whose memory is the ABI's column-major table (for a gain matrix G[i, j] in the usual order pass
     G.transpose(-1, -2)).  xref: [nsteps][2nr] or [B][nsteps][2nr], row k-1 the reference for the state at the start of step k (row
     0 belongs to (q0, qdot0)); K and xref both shared or both per rollout.  None: no feedback / a zero reference.
-    No autograd graph is made: the tape the call leaves is the open-loop tape under uapp, and gradients through the feedback law
-    are not available.  Arguments, checks and words are rollout's (uff in the place of u).  The call replaces the sim's tape, as
+    No autograd graph is made: the tape the call leaves is the open-loop tape under uapp.  Gradients through the feedback law
+    (dL/dK, dL/dxref, the closed-loop dL/duff) come from ``rollout_closed_loop``, the same rollout as an autograd function.  Arguments, checks and words are rollout's (uff in the place of u).  The call replaces the sim's tape, as
     rollout does, and leaves the sim at the end of the rollout.  status=True appends the rollouts' status words (a bool tensor [B] on
     the sim's device: did a Newton solve diverge, hit its iteration limit or meet a NaN) - for a caller that passes check=False and
     sorts the rollouts itself, as a line search does."""
@@ -326,6 +328,92 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     if status:
         return qtraj, qdtraj, uapp, torch.as_tensor((info["status"] & _BAD_STATUS) != 0, device=dev)
     return qtraj, qdtraj, uapp
+
+
+_ClosedLoop = None
+
+
+def _closed_loop_function():
+    """The torch.autograd.Function of rollout_closed_loop, made on first use."""
+    global _ClosedLoop
+    if _ClosedLoop is not None:
+        return _ClosedLoop
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _Closed(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, q0, qdot0, uff, K, xref, sim, h, pscale, check, integrator):
+            qtraj, qdtraj, uapp = rollout_feedback(sim, q0, qdot0, uff, K, xref, h=h, pscale=pscale, check=check, integrator=integrator)
+            ctx.sim, ctx.nsteps, ctx.tape = sim, uff.shape[1], sim.tape_count
+            ctx.per = K is not None and K.dim() == 4
+            ctx.has = (K is not None, xref is not None)
+            keep = [q0.detach(), qdot0.detach(), qtraj, qdtraj]
+            keep += [t.detach().contiguous() for t in (K, xref) if t is not None]
+            ctx.save_for_backward(*keep)
+            return qtraj, qdtraj, uapp
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gq, gqd, gu):
+            sim, nsteps = ctx.sim, ctx.nsteps
+            if sim.tape_count != ctx.tape:
+                raise RuntimeError("the tape of this rollout has been replaced")
+            saved = list(ctx.saved_tensors)
+            q0, qd0, qtraj, qdtraj = saved[:4]
+            K = saved[4] if ctx.has[0] else None
+            xref = saved[4 + int(ctx.has[0])] if ctx.has[1] else None
+            dev = torch.device("cuda", sim.device)
+            B, nr = sim.B, sim.nr
+            sh = (B, nsteps, nr)
+            gq = torch.zeros(sh, dtype=torch.float64, device=dev) if gq is None else gq.contiguous()
+            gqd = torch.zeros(sh, dtype=torch.float64, device=dev) if gqd is None else gqd.contiguous()
+            gu = None if gu is None else gu.contiguous()
+            need = ctx.needs_input_grad
+            duff = torch.empty(sh, dtype=torch.float64, device=dev)
+            dq0 = torch.empty((B, nr), dtype=torch.float64, device=dev)
+            dqd0 = torch.empty_like(dq0)
+            rows_K = torch.empty((B, nsteps, 2 * nr, nr), dtype=torch.float64, device=dev) if (K is not None and ctx.per and need[3]) else None
+            rows_x = torch.empty((B, nsteps, 2 * nr), dtype=torch.float64, device=dev) if (K is not None and xref is not None and need[4]) else None
+            torch.cuda.current_stream(dev).synchronize()
+            sim.rollout_vjp_feedback_device(nsteps, gq.data_ptr(), gqd.data_ptr(), 0 if gu is None else gu.data_ptr(),
+                                            0 if K is None else K.data_ptr(), 0 if (K is None or xref is None) else xref.data_ptr(),
+                                            per_rollout=ctx.per, duff_ptr=duff.data_ptr(), dK_ptr=0 if rows_K is None else rows_K.data_ptr(),
+                                            dxref_ptr=0 if rows_x is None else rows_x.data_ptr(), dq0_ptr=dq0.data_ptr(), dqd0_ptr=dqd0.data_ptr())
+            dK = dx = None
+            if K is not None and need[3]:
+                if ctx.per:
+                    dK = rows_K
+                else:      # a shared table: one contraction of duff with the states the steps started from, no [B][nsteps][2nr][nr] tensor
+                    x = torch.cat([torch.cat([q0[:, None], qtraj[:, :-1]], dim=1), torch.cat([qd0[:, None], qdtraj[:, :-1]], dim=1)], dim=2)
+                    if xref is not None:
+                        x = x - xref
+                    dK = torch.einsum("bkj,bki->kji", x, duff)
+            if xref is not None and need[4]:
+                if K is None:
+                    dx = torch.zeros_like(xref)
+                else:
+                    dx = rows_x if ctx.per else rows_x.sum(dim=0)
+            return dq0, dqd0, duff, dK, dx, None, None, None, None, None
+
+    _ClosedLoop = _Closed
+    return _ClosedLoop
+
+
+def rollout_closed_loop(sim, q0, qdot0, uff, K, xref=None, h=None, pscale=1.0, check=True, integrator=1):
+    """``rollout_feedback`` as a function autograd can differentiate: (qtraj, qdtraj, uapp), every one of them differentiable with
+    respect to q0, qdot0, uff, K and xref - gain tuning, learning a tracking reference, a torch policy that emits K, xref or uff,
+    differentiating an iLQR result through its own feedback policy.  Shapes and meaning are rollout_feedback's; K and xref may be
+    shared by the batch or hold one table per rollout (both alike).  Forward is rmx_rollout_tape_feedback_device, backward ONE
+    rmx_rollout_vjp_feedback_device call (include/redmax_hip.h) with the cotangent of uapp as gu.  The library returns one gradient row per
+    rollout: for a shared xref the rows are summed over the batch, and for a shared K the gradient is one einsum of duff with the
+    states the steps started from (no [B][nsteps][2nr][nr] tensor is made).  Arguments, checks and words are rollout_feedback's.
+    backward() must run before the next rollout or adjoint_* call on the same sim: those replace the tape, and backward raises
+    RuntimeError("the tape of this rollout has been replaced") then.  First derivatives only."""
+    if integrator not in (1, 2):
+        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    return _closed_loop_function().apply(q0, qdot0, uff, K, xref, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check),
+                                         integrator)
 
 
 def jvp(sim, q0, qdot0, u, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, check=True, integrator=1):

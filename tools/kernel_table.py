@@ -34,6 +34,12 @@ ROWS = (  # (name fragment, what it runs)
     ("k_adjoint_fwd<64, 85, false, false>", "rmx_rollout_tape_feedback, BDF1: 33..64 nodes"),
     ("k_adjoint_fwd<32, 86, false, false>", "rmx_rollout_tape_feedback, BDF2: 17..32 nodes"),
     ("k_adjoint_fwd<32, 21, false, false>", "rmx_rollout_tape, 17..32 nodes: the open-loop sibling of the feedback kernel"),
+    ("k_rollout_bwd_fb<16, 1>", "rmx_rollout_vjp_feedback (closed-loop backward sweep: duff, dK, dxref, dq0, dqd0), BDF1 tape: 9..16 nodes"),
+    ("k_rollout_bwd_fb<32, 1>", "rmx_rollout_vjp_feedback, BDF1 tape: 17..32 nodes"),
+    ("k_rollout_bwd_fb<64, 1>", "rmx_rollout_vjp_feedback, BDF1 tape: 33..64 nodes"),
+    ("k_rollout_bwd_fb<32, 2>", "rmx_rollout_vjp_feedback, BDF2 tape: 17..32 nodes"),
+    ("k_rollout_bwd_fb<64, 2>", "rmx_rollout_vjp_feedback, BDF2 tape: 33..64 nodes"),
+    ("k_rollout_bwd_bdf2<32, false>", "rmx_rollout_vjp on a BDF2 tape, 17..32 nodes: the open-loop sibling of `k_rollout_bwd_fb<32, 2>`"),
     ("k_rollout_linearize<4>", "rmx_rollout_linearize (XA, XB, XU of every slot of a tape; one wavefront per rollout and slot): <= 4 nodes"),
     ("k_rollout_linearize<8>", "rmx_rollout_linearize: 5..8 nodes"),
     ("k_rollout_linearize<16>", "rmx_rollout_linearize: 9..16 nodes"),
