@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rmx_host.h"
+#include "rmx_tape.h"
 
 // ============================================================================ host side
 
@@ -1230,6 +1231,29 @@ static void take_event_time(rmx_batch* b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->last_ms = ms;
 }
+// The tail of a synchronous call, in three pieces its callers put their copies between.  The timed part: record ev0, launch, check,
+// record ev1.  launch() enqueues the kernels and returns hipSuccess, or the error that kept it from launching; e is the call's
+// verdict so far (nothing is enqueued behind a failure).
+template <class Launch>
+static hipError_t timed_launch(rmx_batch* b, hipError_t e, Launch&& launch) {
+    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+    return e;
+}
+// ... the wait: short on success; after a failure the stream is drained where arrays of the caller must outlive their copies
+static hipError_t wait_or_drain(rmx_batch* b, hipError_t e, const bool drain = true) {
+    if (e == hipSuccess) e = wait_stream_short(b->stream);
+    else if (drain) (void)hipStreamSynchronize(b->stream);
+    return e;
+}
+// ... and the verdict: "who: text" of a HIP error, or the kernel time of a call that went through
+static int call_result(rmx_batch* b, const hipError_t e, const std::string& who) {
+    if (e != hipSuccess) return fail(RMX_E_HIP, who + ": " + hipGetErrorString(e));
+    take_event_time(b);
+    return RMX_OK;
+}
 
 static int step_sync(rmx_batch* b, const rmx_opts* opts, int nsteps, rmx_stats* st, double* hT, double* hV, int integ,
                      double* hQ = nullptr, double* hQd = nullptr, int* hC = nullptr) {
@@ -1307,20 +1331,14 @@ extern "C" int rmx_step_euler(rmx_batch* b, double h, int nsteps, double* hT, do
     }
     StepArgs a{};
     a.B = b->B; a.nsteps = nsteps; a.q = b->q; a.qd = b->qd; a.histT = dT; a.histV = dV;
-    hipError_t e = hipEventRecord(b->ev0, b->stream);
-    DISPATCH_NP(m->NP, launch_euler, m, b, h, a);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+    hipError_t e = timed_launch(b, hipSuccess, [&] { DISPATCH_NP(m->NP, launch_euler, m, b, h, a); return hipSuccess; });
     if (e == hipSuccess) e = set_started(b, 0);
     if (e == hipSuccess && hT) {
         e = hipMemcpyAsync(hT, dT, nh * sizeof(double), hipMemcpyDeviceToHost, b->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(hV, dV, nh * sizeof(double), hipMemcpyDeviceToHost, b->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    if (e == hipSuccess) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->last_ms = ms;
-    }
+    if (e == hipSuccess) take_event_time(b);
     if (dT) (void)hipFree(dT);
     if (dV) (void)hipFree(dV);
     if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_step_euler: ") + hipGetErrorString(e));
@@ -1358,6 +1376,16 @@ static hipError_t adjws_reserve(rmx_batch* b, const size_t total) {
         (void)hipGetLastError();       // an out-of-memory here must not be taken for a failed launch by the next call
     }
     return e;
+}
+
+// Executes an adjoint plan of rmx_select.h: the one switch from AdjKernel to a launcher.
+static void launch_adjoint_plan(rmx_batch* b, const rmx_select::AdjPlan& plan, const int integ, const DevOpts& o, const AdjArgs& a) {
+    rmx_model* m = b->m;
+    switch (plan.kernel) {
+        case AdjKernel::Help16: launch_adjoint_help_16(m, b, integ, o, a, plan.fullchain); break;      // (a taped rollout: BDF1 only, select_rollout_tape)
+        case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, integ, o, a); break;
+        case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, integ, o, a); break;
+    }
 }
 
 // controls (rmx_adjoint_controls): p is u[B][nsteps][nr], dPdp is dPdu of the same shape or null (the forward sweep alone)
@@ -1400,80 +1428,63 @@ static int adjoint_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, const rm
     a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp; a.p = b->tmpA;
     a.it = stats ? b->it : nullptr; a.status = b->status;
     // (the constant parameters are staged in tmpA; the per-step controls, nsteps times as many, in the workspace behind the gradient)
-    constexpr int NBUF = 10;
-    void* bufs[NBUF] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // one workspace per batch, kept between calls (grow-only): its parts at 256-byte boundaries, in this order
+    enum { W_H, W_M, W_D, W_DPDQ, W_P, W_DPDP, W_U, W_TRK, W_TRK_BEGIN, W_XT };
     const size_t nterms = track ? (size_t)track->nterms : 0;
     const size_t nxt = nterms * 3 * ((track && track->per_rollout) ? (size_t)b->B : 1);      // doubles of the target table
-    const size_t sizes[NBUF] = {hist, hist, hist, (size_t)b->B * m->n * (track ? (size_t)nsteps : 1) * sizeof(double), (size_t)b->B * sizeof(double),
-                                (on_device && controls) ? 0 : nv * sizeof(double), (controls && !on_device) ? nv * sizeof(double) : 0,
-                                nterms * sizeof(rmx_track::DevTerm), track ? ((size_t)nsteps + 1) * sizeof(int) : 0,
-                                (track && !on_device) ? nxt * sizeof(double) : 0};
-    hipError_t e = hipSuccess;
-    {   // one workspace per batch, kept between calls (grow-only): parts at 256-byte boundaries
-        size_t total = 0, offs[NBUF];
-        for (int i = 0; i < NBUF; ++i) {
-            offs[i] = total;
-            total += (sizes[i] + 255) & ~(size_t)255;
-        }
-        b->tape_nsteps = 0;      // (the workspace is about to be rewritten: a tape of rmx_rollout_tape ends here)
-        e = adjws_reserve(b, total);
-        if (e == hipSuccess)
-            for (int i = 0; i < NBUF; ++i) bufs[i] = (char*)b->adjws + offs[i];
-    }
+    rmx_tape::StagePlan ws;
+    for (int i = W_H; i <= W_D; ++i) ws.add(hist, true);
+    ws.add((size_t)b->B * m->n * (track ? (size_t)nsteps : 1) * sizeof(double), true);
+    ws.add((size_t)b->B * sizeof(double), true);
+    ws.add((on_device && controls) ? 0 : nv * sizeof(double), true);
+    ws.add((controls && !on_device) ? nv * sizeof(double) : 0, true);
+    ws.add(nterms * sizeof(rmx_track::DevTerm), true);
+    ws.add(track ? ((size_t)nsteps + 1) * sizeof(int) : 0, true);
+    ws.add((track && !on_device) ? nxt * sizeof(double) : 0, true);
+    auto part = [&](const int i) { return (void*)((char*)b->adjws + ws.off[i]); };
+    b->tape_nsteps = 0;      // (the workspace is about to be rewritten: a tape of rmx_rollout_tape ends here)
+    hipError_t e = adjws_reserve(b, ws.total);
     // (dPdq needs no fill: the task step lies in [1, nsteps] - checked above -, so the forward kernel writes every entry the backward
     // kernel reads; one dispatch less ahead of a 0.83 ms launch pair.  The tracking call: row k of dPdq is written and read where step k owns
     // terms, and nowhere else)
-    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(controls ? bufs[6] : (void*)b->tmpA, p, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(controls ? part(W_U) : (void*)b->tmpA, p, nv * sizeof(double), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess && track) {
-        e = hipMemcpyAsync(bufs[7], tplan.terms.data(), sizes[7], hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(bufs[8], tplan.begin.data(), sizes[8], hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(bufs[9], xtarget, sizes[9], hipMemcpyHostToDevice, b->stream);
+        e = hipMemcpyAsync(part(W_TRK), tplan.terms.data(), ws.bytes[W_TRK], hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(part(W_TRK_BEGIN), tplan.begin.data(), ws.bytes[W_TRK_BEGIN], hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(part(W_XT), xtarget, ws.bytes[W_XT], hipMemcpyHostToDevice, b->stream);
         if (e != hipSuccess) (void)hipStreamSynchronize(b->stream);      // (the plan's arrays must outlive the copies)
     }
     if (e == hipSuccess) {
-        a.Hs = (double*)bufs[0]; a.Ms = (double*)bufs[1]; a.Ds = (double*)bufs[2];
-        a.dPdq = (double*)bufs[3]; a.P = (double*)bufs[4]; a.dPdp = (double*)bufs[5];
+        a.Hs = (double*)part(W_H); a.Ms = (double*)part(W_M); a.Ds = (double*)part(W_D);
+        a.dPdq = (double*)part(W_DPDQ); a.P = (double*)part(W_P); a.dPdp = (double*)part(W_DPDP);
         if (on_device) {          // the caller's device arrays directly: nothing staged, nothing copied back
             a.p = p; a.P = P; a.dPdp = dPdp;
         }
         if (controls) {
-            a.u = on_device ? p : (const double*)bufs[6];
+            a.u = on_device ? p : (const double*)part(W_U);
             a.dPdu = dPdp ? a.dPdp : nullptr;
             a.p = nullptr; a.dPdp = nullptr;
         }
         if (track) {
-            a.trk = (const rmx_track::DevTerm*)bufs[7];
-            a.trk_begin = (const int*)bufs[8];
-            a.trk_xt = on_device ? xtarget : (const double*)bufs[9];
+            a.trk = (const rmx_track::DevTerm*)part(W_TRK);
+            a.trk_begin = (const int*)part(W_TRK_BEGIN);
+            a.trk_xt = on_device ? xtarget : (const double*)part(W_XT);
             a.trk_xt_stride = track->per_rollout ? nterms * 3 : 0;
         }
         const rmx_select::AdjPlan plan = rmx_select::select_adjoint(step_traits(m), b->B, rmx_select::knobs_from_env());
-        e = hipEventRecord(b->ev0, b->stream);
-        switch (plan.kernel) {
-            case AdjKernel::Help16: launch_adjoint_help_16(m, b, integ, o, a, plan.fullchain); break;
-            case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, integ, o, a); break;
-            case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, integ, o, a); break;
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+        e = timed_launch(b, e, [&] { launch_adjoint_plan(b, plan, integ, o, a); return hipSuccess; });
         // after a BDF2 rollout (q, qdot) of step k-1 are in place: rmx_step_bdf2 may continue it; a BDF1 rollout invalidates them
         if (e == hipSuccess) e = set_started(b, integ == INTEG_BDF2 ? 1 : 0);
-        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(P, a.P, sizes[4], hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess && !on_device && dPdp) e = hipMemcpyAsync(dPdp, bufs[5], sizes[5], hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(P, a.P, ws.bytes[W_P], hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess && !on_device && dPdp) e = hipMemcpyAsync(dPdp, part(W_DPDP), ws.bytes[W_DPDP], hipMemcpyDeviceToHost, b->stream);
         if (e == hipSuccess && stats) {
             if (stats->newton_iters) e = hipMemcpyAsync(stats->newton_iters, b->it, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess && stats->status) e = hipMemcpyAsync(stats->status, b->status, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
         }
-        if (e == hipSuccess) e = wait_stream_short(b->stream);      // (configs[3]: a launch pair of 0.9 ms)
-        else if (track) (void)hipStreamSynchronize(b->stream);
-        if (e == hipSuccess) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->last_ms = ms;
-        }
+        e = wait_or_drain(b, e, track != nullptr);      // (configs[3]: a launch pair of 0.9 ms; the tracking call drains after a failure, as above)
     }
     if (e == hipErrorOutOfMemory) return fail(RMX_E_NOMEM, "rmx_adjoint: no device memory for the history (H, M, D per step and rollout)");
-    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_adjoint: ") + hipGetErrorString(e));
-    return RMX_OK;
+    return call_result(b, e, "rmx_adjoint");
 }
 
 extern "C" int rmx_adjoint_bdf1(rmx_batch* b, const rmx_opts* opts, int nsteps, const rmx_task_pointpos* task, const double* p,
@@ -1505,49 +1516,117 @@ extern "C" int rmx_adjoint_controls_device(rmx_batch* b, const rmx_opts* opts, i
     return adjoint_impl(b, opts, nsteps, task, d_u, d_P, d_dPdu, stats, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, true, true);
 }
 
-// rmx_rollout_tape / rmx_rollout_vjp (include/redmax_hip.h): the parts of the workspace.  H, M, D first, where every adjoint call has
-// them; behind them the staging areas of the host forms - three arrays shaped as u (u, qtraj, qdtraj of the tape; gq, gqd, du of the
-// vjp) and two of [B][nr] (dq0, dqd0).  The tape call reserves all of it, so that a vjp never regrows (and so loses) the tape.
-// A BDF2 tape has nsteps + 1 slots per rollout: the last one holds the SDIRK2a solve.
-// Behind those, what rmx_rollout_vjp_params needs: the states the tape differentiates at - q0, qdot0 ([B][nr] each) and the recorded
-// trajectory (two arrays shaped as u), (2 nsteps + 2) nr doubles per rollout, kept as long as the tape (no vjp stages over them) -,
-// z of every slot ([B][nslots][n], written by the ADJ_ZS backward kernels) and the staging of the five gradient arrays.
-enum { TP_Q0 = 8, TP_QD0, TP_QT, TP_QDT, TP_ZS, TP_PG, TP_NPARTS };
-struct TapeParts {
-    size_t off[TP_NPARTS], bytes_traj, bytes_state, total;
-    size_t pg_off[5], pg_bytes[5];      // stiffness, damping, qrest, inertia, grav inside part TP_PG
-};
-static TapeParts tape_parts(const rmx_batch* b, const int nsteps, const int integ) {
-    const rmx_model* m = b->m;
-    TapeParts t{};
-    const size_t hist = (size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * m->n * sizeof(double);
-    t.bytes_traj = (size_t)b->B * nsteps * m->nr * sizeof(double);
-    t.bytes_state = (size_t)b->B * m->nr * sizeof(double);
-    const size_t zbytes = (size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * sizeof(double);
-    const size_t pg[5] = {t.bytes_state, t.bytes_state, t.bytes_state, (size_t)b->B * m->nlist * 6 * sizeof(double), (size_t)b->B * 3 * sizeof(double)};
-    size_t pgtotal = 0;
-    for (int i = 0; i < 5; ++i) {
-        t.pg_off[i] = pgtotal;
-        t.pg_bytes[i] = pg[i];
-        pgtotal += (pg[i] + 255) & ~(size_t)255;
-    }
-    const size_t sizes[TP_NPARTS] = {hist, hist, hist, t.bytes_traj, t.bytes_traj, t.bytes_traj, t.bytes_state, t.bytes_state,
-                                     t.bytes_state, t.bytes_state, t.bytes_traj, t.bytes_traj, zbytes, pgtotal};
-    for (int i = 0; i < TP_NPARTS; ++i) {
-        t.off[i] = t.total;
-        t.total += (sizes[i] + 255) & ~(size_t)255;
-    }
-    return t;
+// ---- The taped-rollout family.  rmx_rollout_tape* record a tape in the adjoint workspace (rmx_tape.h: the layout of its parts);
+// rmx_rollout_vjp*, _linearize and _jvp read it.  Three helpers carry what the entries share: the tape as an entry sees it
+// (TapeView), the arrays of a host form on the device (Staging) and the end of a call (tape_call_end, over the pieces of the tail).
+static_assert(INTEG_BDF2 == 2, "rmx_tape::layout takes the integrator as 1 or 2");
+static rmx_tape::Layout tape_layout(const rmx_batch* b, const int nsteps, const int integ) {
+    return rmx_tape::layout(b->B, nsteps, integ, b->m->n, b->m->nr, b->m->nlist);
 }
-static rmx_select::AdjPlan launch_adjoint_plan(rmx_batch* b, const int integ, const DevOpts& o, const AdjArgs& a) {
-    rmx_model* m = b->m;
-    const rmx_select::AdjPlan plan = rmx_select::select_rollout_tape(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
-    switch (plan.kernel) {
-        case AdjKernel::Help16: launch_adjoint_help_16(m, b, INTEG_BDF1, o, a, plan.fullchain); break;      // (BDF1 only: select_rollout_tape)
-        case AdjKernel::FullChain16: launch_adjoint_fullchain_16(m, b, integ, o, a); break;
-        case AdjKernel::Generic: DISPATCH_NP(m->NP, launch_adjoint, m, b, integ, o, a); break;
+static rmx_select::AdjPlan tape_plan(const rmx_batch* b, const int integ) {      // the sweeps of the open-loop tape, forward and backward
+    return rmx_select::select_rollout_tape(step_traits(b->m), b->B, integ, rmx_select::knobs_from_env());
+}
+
+// The parts of a tape's workspace, resolved, and what the tape was recorded with.
+struct TapeView {
+    rmx_tape::Layout t;
+    double *Hs, *Ms, *Ds;                        // [B][nslots][n*n]
+    double *stage_traj[3], *stage_state[2];      // the staging areas of the host forms that must not allocate
+    double *q0, *qd0, *qt, *qdt, *zs, *pg[5];    // what the tape keeps for rmx_rollout_vjp_params / _vjp_feedback; the staging of the five gradients
+    int integ, nslots, bdf2;
+    double h, pscale;
+};
+static TapeView tape_resolve(const rmx_batch* b, const rmx_tape::Layout& t, const int integ, const double h, const double pscale) {
+    auto at = [b](const size_t off) { return (double*)((char*)b->adjws + off); };
+    TapeView v{};
+    v.t = t;
+    v.Hs = at(t.H); v.Ms = at(t.M); v.Ds = at(t.D);
+    for (int i = 0; i < 3; ++i) v.stage_traj[i] = at(t.stage_traj[i]);
+    for (int i = 0; i < 2; ++i) v.stage_state[i] = at(t.stage_state[i]);
+    v.q0 = at(t.Q0); v.qd0 = at(t.QD0); v.qt = at(t.QT); v.qdt = at(t.QDT); v.zs = at(t.ZS);
+    for (int i = 0; i < 5; ++i) v.pg[i] = at(t.PG + t.pg_off[i]);
+    v.integ = integ; v.nslots = t.nslots; v.bdf2 = integ == INTEG_BDF2 ? 1 : 0;
+    v.h = h; v.pscale = pscale;
+    return v;
+}
+// The tape of a batch for the entry `who`, or that entry's refusal (the order of the refusals is part of the interface).
+static int tape_view(rmx_batch* b, const int nsteps, const std::string& who, TapeView& v) {
+    if (b->tape_nsteps < 1 || !b->adjws)
+        return fail(RMX_E_INVALID, who + ": no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
+    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, who + ": nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
+    HIPCHK(hipSetDevice(b->m->device));
+    if (int rc = pending_error_check(b, who.c_str())) return rc;
+    const rmx_tape::Layout t = tape_layout(b, nsteps, b->tape_integ);
+    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, who + ": no tape (the workspace is smaller than the tape)");
+    v = tape_resolve(b, t, b->tape_integ, b->tape_h, b->tape_pscale);
+    return RMX_OK;
+}
+// what the backward sweeps over a tape share (rmx_rollout_vjp, _vjp_params, _vjp_feedback)
+static AdjArgs vjp_args(const rmx_batch* b, const TapeView& v, DevOpts& o) {
+    o = DevOpts{};
+    o.h = v.h;
+    AdjArgs a{};
+    a.B = b->B; a.nsteps = b->tape_nsteps; a.pscale = v.pscale;
+    a.Hs = v.Hs; a.Ms = v.Ms; a.Ds = v.Ds;
+    a.tape = 2;
+    return a;
+}
+
+// The arrays of a call where the kernels find them.  Device form: the caller's pointers, nothing allocated or copied.  Host form: every
+// array that is given is staged on the device, copied in ahead of the launch (in) or out behind it (out) - in an area of the
+// workspace that the tape call reserved (`borrowed`: the entries that must not allocate), or in an allocation of the call's own
+// (allocate(): laid out by rmx_tape::StagePlan, an absent array takes no room there).
+struct Staging {
+    const bool on_device;
+    rmx_tape::StagePlan plan;
+    const void* in[rmx_tape::STAGE_MAX] = {};
+    void* out[rmx_tape::STAGE_MAX] = {};
+    void* at[rmx_tape::STAGE_MAX] = {};
+    char* own = nullptr;
+    explicit Staging(const bool on_device_) : on_device(on_device_) {}
+    int add(const size_t bytes, const void* in_, void* out_, void* borrowed = nullptr) {      // both null: absent
+        const int i = plan.add(bytes, in_ || out_);
+        in[i] = in_;
+        out[i] = out_;
+        at[i] = !plan.present[i] ? nullptr : !on_device ? borrowed : in_ ? const_cast<void*>(in_) : out_;
+        return i;
     }
-    return plan;
+    int allocate(const std::string& who, const char* what) {
+        if (on_device) return RMX_OK;
+        const hipError_t e = hipMalloc((void**)&own, plan.total ? plan.total : 256);
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, who + ": no device memory for " + what); }
+        if (e != hipSuccess) return fail(RMX_E_HIP, who + ": " + hipGetErrorString(e));
+        for (int i = 0; i < plan.n; ++i)
+            if (plan.present[i]) at[i] = own + plan.off[i];
+        return RMX_OK;
+    }
+    double* dev(const int i) const { return (double*)at[i]; }      // null: absent
+    hipError_t copy_in(const rmx_batch* b, hipError_t e) const {
+        for (int i = 0; i < plan.n && !on_device; ++i)
+            if (e == hipSuccess && in[i] && plan.bytes[i]) e = hipMemcpyAsync(at[i], in[i], plan.bytes[i], hipMemcpyHostToDevice, b->stream);
+        return e;
+    }
+    hipError_t copy_out(const rmx_batch* b, hipError_t e) const {
+        for (int i = 0; i < plan.n && !on_device; ++i)
+            if (e == hipSuccess && out[i] && plan.bytes[i]) e = hipMemcpyAsync(out[i], at[i], plan.bytes[i], hipMemcpyDeviceToHost, b->stream);
+        return e;
+    }
+    void release(const rmx_batch* b, const hipError_t e) {      // (after a failure copies may still be in flight)
+        if (!own) return;
+        if (e != hipSuccess) (void)hipStreamSynchronize(b->stream);
+        (void)hipFree(own);
+        own = nullptr;
+    }
+};
+// the end of a call that read a tape: wait (after a failure: drain - the caller's arrays must outlive their copies), free, verdict
+static int tape_call_end(rmx_batch* b, hipError_t e, Staging& st, const std::string& who) {
+    e = wait_or_drain(b, e);
+    st.release(b, e);
+    return call_result(b, e, who);
+}
+// The feedback sweeps exist as the generic kernel alone: a plan that names another one is an error, never a silent substitute.
+static hipError_t generic_only(const rmx_select::AdjPlan& plan) {
+    return plan.kernel == AdjKernel::Generic ? hipSuccess : hipErrorInvalidDeviceFunction;
 }
 
 // fb (rmx_rollout_tape_feedback): u is fb->uff, the sweep is the ADJ_FB kernel and uapp (or null) takes the applied torques.  The host
@@ -1566,89 +1645,72 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
     if (rc) return rc;
     rc = pending_error_check(b, "rmx_rollout_tape");
     if (rc) return rc;
-    if ((size_t)b->B * (nsteps + (integ == INTEG_BDF2 ? 1 : 0)) * m->n * m->n * sizeof(double) * 3 > ((size_t)200 << 30))
-        return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
-    const TapeParts t = tape_parts(b, nsteps, integ);
-    // the feedback tables of the host form: K, xref, uapp, each at a 256-byte boundary of one allocation
-    const size_t fb_tables = fb ? (fb->per_rollout ? (size_t)b->B : 1) * nsteps : 0;
-    const size_t fbK_bytes = (fb && fb->K) ? fb_tables * 2 * m->nr * m->nr * sizeof(double) : 0;
-    const size_t fbx_bytes = (fb && fb->xref) ? fb_tables * 2 * m->nr * sizeof(double) : 0;
-    const size_t fbK_room = (fbK_bytes + 255) & ~(size_t)255, fbx_room = (fbx_bytes + 255) & ~(size_t)255;
-    char* fbbuf = nullptr;
-    if (fb && !on_device && fbK_room + fbx_room + (uapp ? t.bytes_traj : 0) > 0) {      // (ahead of everything that ends the present tape)
-        if (hipMalloc((void**)&fbbuf, fbK_room + fbx_room + (uapp ? t.bytes_traj : 0)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RMX_E_NOMEM, "rmx_rollout_tape_feedback: no device memory for the gain tables");
-        }
+    const rmx_tape::Layout t = tape_layout(b, nsteps, integ);
+    if (3 * t.bytes_hist > ((size_t)200 << 30)) return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
+    enum { F_K, F_X, F_UAPP };
+    Staging fbst(on_device);
+    if (fb) {
+        const size_t row = (fb->per_rollout ? (size_t)b->B : 1) * nsteps * 2 * m->nr * sizeof(double);
+        fbst.add(row * m->nr, fb->K, nullptr);
+        fbst.add(row, fb->xref, nullptr);
+        fbst.add(t.bytes_traj, nullptr, uapp);
+        if (fbst.plan.total > 0)      // (ahead of everything that ends the present tape)
+            if ((rc = fbst.allocate("rmx_rollout_tape_feedback", "the gain tables"))) return rc;
     }
     b->tape_nsteps = 0;
     hipError_t e = adjws_reserve(b, t.total);
     if (e == hipSuccess) {
-        char* ws = (char*)b->adjws;
-        if (!on_device) e = hipMemcpyAsync(ws + t.off[3], u, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
+        const TapeView v = tape_resolve(b, t, integ, o.h, pscale);
+        enum { S_U, S_QT, S_QDT };
+        Staging st(on_device);
+        st.add(t.bytes_traj, u, nullptr, v.stage_traj[0]);
+        st.add(t.bytes_traj, nullptr, qtraj, v.stage_traj[1]);
+        st.add(t.bytes_traj, nullptr, qdtraj, v.stage_traj[2]);
+        e = fbst.copy_in(b, st.copy_in(b, e));
         AdjArgs a{};
         if (fb) {
-            a.fbK = fb->K;
-            a.fbx = fb->xref;
+            a.fbK = fbst.dev(F_K);
+            a.fbx = fbst.dev(F_X);
             a.fb_stride = fb->per_rollout ? (size_t)nsteps : 0;
-            a.uapp = uapp;
-            if (!on_device) {
-                a.fbK = fb->K ? (const double*)fbbuf : nullptr;
-                a.fbx = fb->xref ? (const double*)(fbbuf + fbK_room) : nullptr;
-                a.uapp = uapp ? (double*)(fbbuf + fbK_room + fbx_room) : nullptr;
-                if (e == hipSuccess && fb->K) e = hipMemcpyAsync(fbbuf, fb->K, fbK_bytes, hipMemcpyHostToDevice, b->stream);
-                if (e == hipSuccess && fb->xref) e = hipMemcpyAsync(fbbuf + fbK_room, fb->xref, fbx_bytes, hipMemcpyHostToDevice, b->stream);
-            }
+            a.uapp = fbst.dev(F_UAPP);
         }
         a.B = b->B; a.nsteps = nsteps; a.pscale = pscale;
         a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp;
         a.it = stats ? b->it : nullptr; a.status = b->status;
-        a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
-        a.u = on_device ? u : (const double*)(ws + t.off[3]);
+        a.Hs = v.Hs; a.Ms = v.Ms; a.Ds = v.Ds;
+        a.u = st.dev(S_U);
         a.tape = 1;
         // the states rmx_rollout_vjp_params differentiates at stay with the tape: (q0, qdot0) is copied on the stream ahead of the sweep;
         // the trajectory is recorded by the kernel as ever - into the caller's arrays (or their staging) and copied behind the sweep,
         // or, where the caller wants no record, straight into the tape's own rows
-        if (qtraj) {
-            a.qtraj = on_device ? qtraj : (double*)(ws + t.off[4]);
-            a.qdtraj = on_device ? qdtraj : (double*)(ws + t.off[5]);
-        } else {
-            a.qtraj = (double*)(ws + t.off[TP_QT]);
-            a.qdtraj = (double*)(ws + t.off[TP_QDT]);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_Q0], b->q, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_QD0], b->qd, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
-        if (e == hipSuccess) {
+        a.qtraj = qtraj ? st.dev(S_QT) : v.qt;
+        a.qdtraj = qtraj ? st.dev(S_QDT) : v.qdt;
+        if (e == hipSuccess) e = hipMemcpyAsync(v.q0, b->q, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(v.qd0, b->qd, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
+        e = timed_launch(b, e, [&] {
             if (fb) {
                 const rmx_select::AdjPlan plan = rmx_select::select_rollout_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
-                if (plan.kernel == AdjKernel::Generic) DISPATCH_NP(m->NP, launch_rollout_feedback, m, b, integ, o, a)
-                else e = hipErrorInvalidDeviceFunction;      // (no other feedback kernel exists: never a silent substitute)
+                if (generic_only(plan) == hipSuccess) DISPATCH_NP(m->NP, launch_rollout_feedback, m, b, integ, o, a)
                 b->last_kernel = rmx_select::label_rollout_feedback(integ);
-            } else {
-                const rmx_select::AdjPlan plan = launch_adjoint_plan(b, integ, o, a);
-                if (integ == INTEG_BDF2) b->last_kernel = rmx_select::label_rollout_tape_bdf2(plan);
+                return generic_only(plan);
             }
-            if (e == hipSuccess) e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
+            const rmx_select::AdjPlan plan = tape_plan(b, integ);
+            launch_adjoint_plan(b, plan, integ, o, a);
+            if (integ == INTEG_BDF2) b->last_kernel = rmx_select::label_rollout_tape_bdf2(plan);
+            return hipSuccess;
+        });
         // a BDF1 rollout: rmx_step_bdf2 takes its start step again; after a BDF2 rollout (q, qdot) of step k-1 are in place
         if (e == hipSuccess) e = set_started(b, integ == INTEG_BDF2 ? 1 : 0);
         if (e == hipSuccess && qtraj) {
-            e = hipMemcpyAsync(ws + t.off[TP_QT], a.qtraj, t.bytes_traj, hipMemcpyDeviceToDevice, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[TP_QDT], a.qdtraj, t.bytes_traj, hipMemcpyDeviceToDevice, b->stream);
+            e = hipMemcpyAsync(v.qt, a.qtraj, t.bytes_traj, hipMemcpyDeviceToDevice, b->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(v.qdt, a.qdtraj, t.bytes_traj, hipMemcpyDeviceToDevice, b->stream);
         }
-        if (e == hipSuccess && !on_device && qtraj) {
-            e = hipMemcpyAsync(qtraj, a.qtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(qdtraj, a.qdtraj, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
-        }
-        if (e == hipSuccess && fb && !on_device && uapp) e = hipMemcpyAsync(uapp, a.uapp, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
+        e = fbst.copy_out(b, st.copy_out(b, e));
         if (e == hipSuccess && stats) {
             if (stats->newton_iters) e = hipMemcpyAsync(stats->newton_iters, b->it, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
             if (e == hipSuccess && stats->status) e = hipMemcpyAsync(stats->status, b->status, sizeof(int) * b->B, hipMemcpyDeviceToHost, b->stream);
         }
-        if (e == hipSuccess) e = wait_stream_short(b->stream);
-        else (void)hipStreamSynchronize(b->stream);      // (u must outlive its copy)
+        e = wait_or_drain(b, e);      // (u must outlive its copy)
         if (e == hipSuccess) {
             take_event_time(b);
             b->tape_nsteps = nsteps;
@@ -1657,63 +1719,38 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
             b->tape_pscale = pscale;
         }
     }
-    if (fbbuf) {
-        if (e != hipSuccess) (void)hipStreamSynchronize(b->stream);
-        (void)hipFree(fbbuf);
-    }
+    fbst.release(b, e);
     if (e == hipErrorOutOfMemory) return fail(RMX_E_NOMEM, "rmx_rollout_tape: no device memory for the tape (H, M, D per step and rollout)");
     if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_tape: ") + hipGetErrorString(e));
     return RMX_OK;
+}
+
+// gq, gqd in and du, dq0, dqd0 out, as rmx_rollout_vjp and rmx_rollout_vjp_params take them: the host forms stage them in the areas
+// the tape call reserved.
+static void vjp_stage(Staging& st, const TapeView& v, AdjArgs& a, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0) {
+    a.gq = st.dev(st.add(v.t.bytes_traj, gq, nullptr, v.stage_traj[0]));
+    a.gqd = st.dev(st.add(v.t.bytes_traj, gqd, nullptr, v.stage_traj[1]));
+    a.dPdu = st.dev(st.add(v.t.bytes_traj, nullptr, du, v.stage_traj[2]));
+    a.dq0 = st.dev(st.add(v.t.bytes_state, nullptr, dq0, v.stage_state[0]));
+    a.dqd0 = st.dev(st.add(v.t.bytes_state, nullptr, dqd0, v.stage_state[1]));
 }
 
 static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
                             const bool on_device, const std::string& who = "rmx_rollout_vjp") {
     if (!b || !gq || !gqd || !du) return fail(RMX_E_INVALID, who + ": null argument");
     if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, who + ": dq0 and dqd0 must be given together");
-    rmx_model* m = b->m;
-    if (b->tape_nsteps < 1 || !b->adjws)
-        return fail(RMX_E_INVALID, who + ": no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
-    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, who + ": nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
-    HIPCHK(hipSetDevice(m->device));
-    int rc = pending_error_check(b, who.c_str());
-    if (rc) return rc;
-    const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
-    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, who + ": no tape (the workspace is smaller than the tape)");
-    char* ws = (char*)b->adjws;
-    DevOpts o{};
-    o.h = b->tape_h;
-    AdjArgs a{};
-    a.B = b->B; a.nsteps = nsteps; a.pscale = b->tape_pscale;
-    a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
-    a.tape = 2;
-    a.gq = on_device ? gq : (const double*)(ws + t.off[3]);
-    a.gqd = on_device ? gqd : (const double*)(ws + t.off[4]);
-    a.dPdu = on_device ? du : (double*)(ws + t.off[5]);
-    if (dq0) {
-        a.dq0 = on_device ? dq0 : (double*)(ws + t.off[6]);
-        a.dqd0 = on_device ? dqd0 : (double*)(ws + t.off[7]);
-    }
-    hipError_t e = hipSuccess;
-    if (!on_device) {
-        e = hipMemcpyAsync(ws + t.off[3], gq, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[4], gqd, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
-    }
-    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
-    if (e == hipSuccess) {
-        launch_adjoint_plan(b, b->tape_integ, o, a);      // (the backward sweep of the integrator that recorded the tape)
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
-    if (e == hipSuccess && !on_device) {
-        e = hipMemcpyAsync(du, a.dPdu, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dq0, a.dq0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dqd0, a.dqd0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
-    }
-    if (e == hipSuccess) e = wait_stream_short(b->stream);
-    else (void)hipStreamSynchronize(b->stream);      // (the cotangents must outlive their copies)
-    if (e != hipSuccess) return fail(RMX_E_HIP, who + ": " + hipGetErrorString(e));
-    take_event_time(b);
-    return RMX_OK;
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
+    DevOpts o;
+    AdjArgs a = vjp_args(b, v, o);
+    Staging st(on_device);
+    vjp_stage(st, v, a, gq, gqd, du, dq0, dqd0);
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] {
+        launch_adjoint_plan(b, tape_plan(b, v.integ), v.integ, o, a);      // (the backward sweep of the integrator that recorded the tape)
+        return hipSuccess;
+    });
+    return tape_call_end(b, st.copy_out(b, e), st, who);
 }
 
 // rmx_rollout_vjp_feedback: the closed-loop backward sweep (rmx_feedback_bwd.h).  Without gains and without gu it IS rmx_rollout_vjp
@@ -1722,228 +1759,131 @@ static int rollout_vjp_impl(rmx_batch* b, int nsteps, const double* gq, const do
 // neither grows nor is written.
 static int rollout_vjp_feedback_impl(rmx_batch* b, int nsteps, const rmx_feedback* fb, const double* gq, const double* gqd, const double* gu,
                                      const rmx_feedback_grads* out, const bool on_device) {
-    if (!b || !fb || !gq || !gqd || !out) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: null argument");
-    if (!out->duff && !out->dK && !out->dxref && !out->dq0) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: all outputs are null");
-    if ((out->dq0 == nullptr) != (out->dqd0 == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: dq0 and dqd0 must be given together");
-    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: per_rollout must be 0 or 1");
-    if (!fb->K && (out->dK || out->dxref)) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: no gains (K is null): dK and dxref cannot be formed");
+    const std::string who = "rmx_rollout_vjp_feedback";
+    if (!b || !fb || !gq || !gqd || !out) return fail(RMX_E_INVALID, who + ": null argument");
+    if (!out->duff && !out->dK && !out->dxref && !out->dq0) return fail(RMX_E_INVALID, who + ": all outputs are null");
+    if ((out->dq0 == nullptr) != (out->dqd0 == nullptr)) return fail(RMX_E_INVALID, who + ": dq0 and dqd0 must be given together");
+    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    if (!fb->K && (out->dK || out->dxref)) return fail(RMX_E_INVALID, who + ": no gains (K is null): dK and dxref cannot be formed");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
     rmx_model* m = b->m;
-    if (b->tape_nsteps < 1 || !b->adjws)
-        return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
-    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
-    HIPCHK(hipSetDevice(m->device));
-    int rc = pending_error_check(b, "rmx_rollout_vjp_feedback");
-    if (rc) return rc;
-    const int integ = b->tape_integ;
-    const TapeParts t = tape_parts(b, nsteps, integ);
-    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp_feedback: no tape (the workspace is smaller than the tape)");
     if (!fb->K && !gu) {      // rmx_rollout_vjp itself; a duff nobody asked for goes to a scratch array of the call's own
         double* du = out->duff;
         std::vector<double> hdu;
         if (!du && !on_device) {
             hdu.resize((size_t)b->B * nsteps * m->nr);
             du = hdu.data();
-        } else if (!du && hipMalloc((void**)&du, t.bytes_traj ? t.bytes_traj : 256) != hipSuccess) {
+        } else if (!du && hipMalloc((void**)&du, v.t.bytes_traj ? v.t.bytes_traj : 256) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(RMX_E_NOMEM, "rmx_rollout_vjp_feedback: no device memory for the staging");
+            return fail(RMX_E_NOMEM, who + ": no device memory for the staging");
         }
-        rc = rollout_vjp_impl(b, nsteps, gq, gqd, du, out->dq0, out->dqd0, on_device, "rmx_rollout_vjp_feedback");
+        const int rc = rollout_vjp_impl(b, nsteps, gq, gqd, du, out->dq0, out->dqd0, on_device, who);
         if (!out->duff && on_device) (void)hipFree(du);
-        if (rc == RMX_OK)      // (the plan launch_adjoint_plan has just executed: the selection is pure)
-            b->last_kernel = rmx_select::label_rollout_vjp(rmx_select::select_rollout_tape(step_traits(m), b->B, integ, rmx_select::knobs_from_env()), integ);
+        if (rc == RMX_OK) b->last_kernel = rmx_select::label_rollout_vjp(tape_plan(b, v.integ), v.integ);      // (the plan just executed: the selection is pure)
         return rc;
     }
-    const size_t nr = m->nr;
+    const size_t nr = m->nr, row = 2 * nr * sizeof(double);
     const size_t fb_tables = (fb->per_rollout ? (size_t)b->B : 1) * nsteps, rows = (size_t)b->B * nsteps;
-    // the staged arrays of the host form, each at a 256-byte boundary of one allocation: inputs gq, gqd, gu, K, xref, then the outputs
-    enum { S_GQ, S_GQD, S_GU, S_K, S_X, S_DUFF, S_DK, S_DX, S_DQ0, S_DQD0, S_N };
-    const void* hin[S_N] = {gq, gqd, gu, fb->K, fb->K ? fb->xref : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double* hout[S_N] = {nullptr, nullptr, nullptr, nullptr, nullptr, out->duff, out->dK, out->dxref, out->dq0, out->dqd0};
-    const size_t bytes[S_N] = {t.bytes_traj, t.bytes_traj, t.bytes_traj, fb_tables * 2 * nr * nr * sizeof(double), fb_tables * 2 * nr * sizeof(double),
-                               t.bytes_traj, rows * 2 * nr * nr * sizeof(double), rows * 2 * nr * sizeof(double), t.bytes_state, t.bytes_state};
-    char* stage = nullptr;
-    size_t at[S_N] = {};
-    if (!on_device) {
-        size_t want = 0;
-        for (int i = 0; i < S_N; ++i) {
-            at[i] = want;
-            if (hin[i] || hout[i]) want += (bytes[i] + 255) & ~(size_t)255;
-        }
-        const hipError_t em = hipMalloc((void**)&stage, want ? want : 256);
-        if (em == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, "rmx_rollout_vjp_feedback: no device memory for the staging"); }
-        if (em != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp_feedback: ") + hipGetErrorString(em));
-    }
-    auto din = [&](const int i) { return !hin[i] ? (const double*)nullptr : on_device ? (const double*)hin[i] : (const double*)(stage + at[i]); };
-    auto dout = [&](const int i) { return !hout[i] ? (double*)nullptr : on_device ? hout[i] : (double*)(stage + at[i]); };
-    char* ws = (char*)b->adjws;
-    DevOpts o{};
-    o.h = b->tape_h;
-    AdjArgs a{};
-    a.B = b->B; a.nsteps = nsteps; a.pscale = b->tape_pscale;
-    a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
-    a.tape = 2;
-    a.gq = din(S_GQ); a.gqd = din(S_GQD); a.gu = din(S_GU);
-    a.fbK = din(S_K); a.fbx = din(S_X);
+    enum { S_GQ, S_GQD, S_GU, S_K, S_X, S_DUFF, S_DK, S_DX, S_DQ0, S_DQD0 };      // the inputs, then the outputs
+    Staging st(on_device);
+    st.add(v.t.bytes_traj, gq, nullptr);
+    st.add(v.t.bytes_traj, gqd, nullptr);
+    st.add(v.t.bytes_traj, gu, nullptr);
+    st.add(fb_tables * row * nr, fb->K, nullptr);
+    st.add(fb_tables * row, fb->K ? fb->xref : nullptr, nullptr);
+    st.add(v.t.bytes_traj, nullptr, out->duff);
+    st.add(rows * row * nr, nullptr, out->dK);
+    st.add(rows * row, nullptr, out->dxref);
+    st.add(v.t.bytes_state, nullptr, out->dq0);
+    st.add(v.t.bytes_state, nullptr, out->dqd0);
+    if (int rc = st.allocate(who, "the staging")) return rc;
+    DevOpts o;
+    AdjArgs a = vjp_args(b, v, o);
+    a.gq = st.dev(S_GQ); a.gqd = st.dev(S_GQD); a.gu = st.dev(S_GU);
+    a.fbK = st.dev(S_K); a.fbx = st.dev(S_X);
     a.fb_stride = fb->per_rollout ? (size_t)nsteps : 0;
-    a.dPdu = dout(S_DUFF); a.dK = dout(S_DK); a.dxref = dout(S_DX); a.dq0 = dout(S_DQ0); a.dqd0 = dout(S_DQD0);
-    a.fq0 = (const double*)(ws + t.off[TP_Q0]); a.fqd0 = (const double*)(ws + t.off[TP_QD0]);
-    a.fqt = (const double*)(ws + t.off[TP_QT]); a.fqdt = (const double*)(ws + t.off[TP_QDT]);
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < S_N && !on_device; ++i)
-        if (e == hipSuccess && hin[i] && bytes[i]) e = hipMemcpyAsync(stage + at[i], hin[i], bytes[i], hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
-    if (e == hipSuccess) {
-        const rmx_select::AdjPlan plan = rmx_select::select_rollout_vjp_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
-        if (plan.kernel == AdjKernel::Generic) DISPATCH_NP(m->NP, launch_vjp_feedback, m, b, integ, o, a)
-        else e = hipErrorInvalidDeviceFunction;      // (no other kernel exists: never a silent substitute)
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
-    for (int i = 0; i < S_N && !on_device; ++i)
-        if (e == hipSuccess && hout[i] && bytes[i]) e = hipMemcpyAsync(hout[i], stage + at[i], bytes[i], hipMemcpyDeviceToHost, b->stream);
-    if (e == hipSuccess) e = wait_stream_short(b->stream);
-    else (void)hipStreamSynchronize(b->stream);      // (the inputs must outlive their copies)
-    if (stage) (void)hipFree(stage);
-    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp_feedback: ") + hipGetErrorString(e));
-    take_event_time(b);
-    b->last_kernel = rmx_select::label_rollout_vjp_feedback(integ);
-    return RMX_OK;
+    a.dPdu = st.dev(S_DUFF); a.dK = st.dev(S_DK); a.dxref = st.dev(S_DX); a.dq0 = st.dev(S_DQ0); a.dqd0 = st.dev(S_DQD0);
+    a.fq0 = v.q0; a.fqd0 = v.qd0; a.fqt = v.qt; a.fqdt = v.qdt;
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] {
+        const rmx_select::AdjPlan plan = rmx_select::select_rollout_vjp_feedback(step_traits(m), b->B, v.integ, rmx_select::knobs_from_env());
+        if (generic_only(plan) == hipSuccess) DISPATCH_NP(m->NP, launch_vjp_feedback, m, b, v.integ, o, a)
+        return generic_only(plan);
+    });
+    const int rc = tape_call_end(b, st.copy_out(b, e), st, who);
+    if (rc == RMX_OK) b->last_kernel = rmx_select::label_rollout_vjp_feedback(v.integ);
+    return rc;
 }
 
 // rmx_rollout_vjp_params: rmx_rollout_vjp's sweep in the instantiation that also stores z of every slot, then the contraction of
 // rmx_params.h over the slots with the states the tape kept.  Everything it stages lies in parts the tape call reserved.
 static int rollout_vjp_params_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
                                    const rmx_param_grads* out, const bool on_device) {
-    if (!b || !gq || !gqd || !du || !out) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: null argument");
-    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: dq0 and dqd0 must be given together");
-    double* host[5] = {out->stiffness, out->damping, out->qrest, out->inertia, out->grav};
-    if (!host[0] && !host[1] && !host[2] && !host[3] && !host[4]) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: all outputs are null");
+    const std::string who = "rmx_rollout_vjp_params";
+    if (!b || !gq || !gqd || !du || !out) return fail(RMX_E_INVALID, who + ": null argument");
+    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, who + ": dq0 and dqd0 must be given together");
+    double* const grads[5] = {out->stiffness, out->damping, out->qrest, out->inertia, out->grav};
+    if (!grads[0] && !grads[1] && !grads[2] && !grads[3] && !grads[4]) return fail(RMX_E_INVALID, who + ": all outputs are null");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
     rmx_model* m = b->m;
-    if (b->tape_nsteps < 1 || !b->adjws)
-        return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
-    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
-    HIPCHK(hipSetDevice(m->device));
-    int rc = pending_error_check(b, "rmx_rollout_vjp_params");
-    if (rc) return rc;
-    const int integ = b->tape_integ;
-    const TapeParts t = tape_parts(b, nsteps, integ);
-    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_vjp_params: no tape (the workspace is smaller than the tape)");
-    char* ws = (char*)b->adjws;
-    DevOpts o{};
-    o.h = b->tape_h;
-    AdjArgs a{};
-    a.B = b->B; a.nsteps = nsteps; a.pscale = b->tape_pscale;
-    a.Hs = (double*)(ws + t.off[0]); a.Ms = (double*)(ws + t.off[1]); a.Ds = (double*)(ws + t.off[2]);
-    a.tape = 2;
-    a.gq = on_device ? gq : (const double*)(ws + t.off[3]);
-    a.gqd = on_device ? gqd : (const double*)(ws + t.off[4]);
-    a.dPdu = on_device ? du : (double*)(ws + t.off[5]);
-    if (dq0) {
-        a.dq0 = on_device ? dq0 : (double*)(ws + t.off[6]);
-        a.dqd0 = on_device ? dqd0 : (double*)(ws + t.off[7]);
-    }
-    a.zs = (double*)(ws + t.off[TP_ZS]);
-    ParamArgs pa{};
-    pa.nsteps = nsteps; pa.nslots = nsteps + (integ == INTEG_BDF2 ? 1 : 0); pa.bdf2 = integ == INTEG_BDF2 ? 1 : 0;
-    pa.njoints = m->nlist; pa.h = b->tape_h;
-    pa.q0 = (const double*)(ws + t.off[TP_Q0]); pa.qd0 = (const double*)(ws + t.off[TP_QD0]);
-    pa.qt = (const double*)(ws + t.off[TP_QT]); pa.qdt = (const double*)(ws + t.off[TP_QDT]);
-    pa.zs = a.zs;
+    DevOpts o;
+    AdjArgs a = vjp_args(b, v, o);
+    Staging st(on_device);
+    vjp_stage(st, v, a, gq, gqd, du, dq0, dqd0);
     double* dev[5];
-    for (int i = 0; i < 5; ++i) dev[i] = !host[i] ? nullptr : on_device ? host[i] : (double*)(ws + t.off[TP_PG] + t.pg_off[i]);
+    for (int i = 0; i < 5; ++i) dev[i] = st.dev(st.add(v.t.pg_bytes[i], nullptr, grads[i], v.pg[i]));
+    a.zs = v.zs;
+    ParamArgs pa{};
+    pa.nsteps = nsteps; pa.nslots = v.nslots; pa.bdf2 = v.bdf2;
+    pa.njoints = m->nlist; pa.h = v.h;
+    pa.q0 = v.q0; pa.qd0 = v.qd0; pa.qt = v.qt; pa.qdt = v.qdt;
+    pa.zs = a.zs;
     pa.stiffness = dev[0]; pa.damping = dev[1]; pa.qrest = dev[2]; pa.inertia = dev[3]; pa.grav = dev[4];
     for (int i = 0; i < MAXN; ++i) pa.lst[i] = -1;
     for (int L = 0; L < m->nlist; ++L) {
         const int k = m->node_of_listing[L];
         if (k >= 0 && k < MAXN) pa.lst[k] = (short)L;
     }
-    hipError_t e = hipSuccess;
-    if (!on_device) {
-        e = hipMemcpyAsync(ws + t.off[3], gq, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ws + t.off[4], gqd, t.bytes_traj, hipMemcpyHostToDevice, b->stream);
-    }
-    if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
-    if (e == hipSuccess) {
-        const rmx_select::AdjPlan plan = rmx_select::select_rollout_tape(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
-        DISPATCH_NP(m->NP, launch_vjp_zs, m, b, integ, o, a, plan.fullchain);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        DISPATCH_NP(m->NP, launch_param_grad, m, b, pa);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
-    if (e == hipSuccess && !on_device) {
-        e = hipMemcpyAsync(du, a.dPdu, t.bytes_traj, hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dq0, a.dq0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess && dq0) e = hipMemcpyAsync(dqd0, a.dqd0, t.bytes_state, hipMemcpyDeviceToHost, b->stream);
-        for (int i = 0; i < 5; ++i)
-            if (e == hipSuccess && host[i] && t.pg_bytes[i]) e = hipMemcpyAsync(host[i], dev[i], t.pg_bytes[i], hipMemcpyDeviceToHost, b->stream);
-    }
-    if (e == hipSuccess) e = wait_stream_short(b->stream);
-    else (void)hipStreamSynchronize(b->stream);      // (the cotangents must outlive their copies)
-    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_vjp_params: ") + hipGetErrorString(e));
-    take_event_time(b);
-    return RMX_OK;
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] {
+        DISPATCH_NP(m->NP, launch_vjp_zs, m, b, v.integ, o, a, tape_plan(b, v.integ).fullchain);
+        const hipError_t el = hipGetLastError();
+        if (el == hipSuccess) DISPATCH_NP(m->NP, launch_param_grad, m, b, pa);
+        return el;
+    });
+    return tape_call_end(b, st.copy_out(b, e), st, who);
 }
 
 // rmx_rollout_linearize: XA, XB, XU of every slot of the tape, one kernel over B * nslots wavefronts (rmx_linearize.h).  The host form
 // stages through an allocation of its own: the adjoint workspace holds the tape, a regrow would lose it, and tapes that are never
 // linearised do not pay for three more histories.
 static int rollout_linearize_impl(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU, const bool on_device) {
-    if (!b) return fail(RMX_E_INVALID, "rmx_rollout_linearize: null batch");
-    if (!XA && !XB && !XU) return fail(RMX_E_INVALID, "rmx_rollout_linearize: all outputs are null");
+    const std::string who = "rmx_rollout_linearize";
+    if (!b) return fail(RMX_E_INVALID, who + ": null batch");
+    if (!XA && !XB && !XU) return fail(RMX_E_INVALID, who + ": all outputs are null");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
     rmx_model* m = b->m;
-    if (b->tape_nsteps < 1 || !b->adjws)
-        return fail(RMX_E_INVALID, "rmx_rollout_linearize: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
-    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_linearize: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
-    HIPCHK(hipSetDevice(m->device));
-    int rc = pending_error_check(b, "rmx_rollout_linearize");
-    if (rc) return rc;
-    const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
-    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_linearize: no tape (the workspace is smaller than the tape)");
-    char* ws = (char*)b->adjws;
     LinArgs a{};
-    a.nslots = nsteps + (b->tape_integ == INTEG_BDF2 ? 1 : 0);
-    a.bdf2 = b->tape_integ == INTEG_BDF2 ? 1 : 0;
-    a.h = b->tape_h;
-    a.pscale = b->tape_pscale;
-    a.Hs = (const double*)(ws + t.off[0]); a.Ms = (const double*)(ws + t.off[1]); a.Ds = (const double*)(ws + t.off[2]);
-    if ((size_t)b->B * a.nslots > (size_t)0x7fffffff) return fail(RMX_E_INVALID, "rmx_rollout_linearize: batch * slots exceeds the grid");
-    double* host[3] = {XA, XB, XU};
-    const size_t bytes = (size_t)b->B * a.nslots * m->nr * m->nr * sizeof(double), pitch = (bytes + 255) & ~(size_t)255;
-    char* stage = nullptr;
-    if (!on_device) {
-        size_t want = 0;
-        for (double* p : host) want += p ? pitch : 0;
-        const hipError_t em = hipMalloc((void**)&stage, want ? want : 256);
-        if (em == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, "rmx_rollout_linearize: no device memory for the staging of the outputs"); }
-        if (em != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_linearize: ") + hipGetErrorString(em));
+    a.nslots = v.nslots; a.bdf2 = v.bdf2; a.h = v.h; a.pscale = v.pscale;
+    a.Hs = v.Hs; a.Ms = v.Ms; a.Ds = v.Ds;
+    if ((size_t)b->B * a.nslots > (size_t)0x7fffffff) return fail(RMX_E_INVALID, who + ": batch * slots exceeds the grid");
+    const size_t bytes = (size_t)b->B * a.nslots * m->nr * m->nr * sizeof(double);
+    enum { S_XA, S_XB, S_XU };
+    Staging st(on_device);
+    st.add(bytes, nullptr, XA);
+    st.add(bytes, nullptr, XB);
+    st.add(bytes, nullptr, XU);
+    if (int rc = st.allocate(who, "the staging of the outputs")) return rc;
+    a.XA = st.dev(S_XA); a.XB = st.dev(S_XB); a.XU = st.dev(S_XU);
+    if (!bytes) {      // (no reduced DOF: nothing to compute, and no kernel time to take)
+        st.release(b, hipSuccess);
+        return RMX_OK;
     }
-    double* dev[3] = {XA, XB, XU};
-    if (!on_device) {
-        size_t at = 0;
-        for (int i = 0; i < 3; ++i)
-            if (host[i]) { dev[i] = (double*)(stage + at); at += pitch; }
-    }
-    a.XA = dev[0]; a.XB = dev[1]; a.XU = dev[2];
-    hipError_t e = hipSuccess;
-    if (bytes) {
-        e = hipEventRecord(b->ev0, b->stream);
-        if (e == hipSuccess) {
-            DISPATCH_NP(m->NP, launch_linearize, m, b, a);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
-        for (int i = 0; i < 3 && !on_device; ++i)
-            if (e == hipSuccess && host[i]) e = hipMemcpyAsync(host[i], dev[i], bytes, hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess) e = wait_stream_short(b->stream);
-        else (void)hipStreamSynchronize(b->stream);
-    }
-    if (stage) (void)hipFree(stage);
-    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_linearize: ") + hipGetErrorString(e));
-    if (bytes) take_event_time(b);
-    return RMX_OK;
+    const hipError_t e = timed_launch(b, hipSuccess, [&] { DISPATCH_NP(m->NP, launch_linearize, m, b, a); return hipSuccess; });
+    return tape_call_end(b, st.copy_out(b, e), st, who);
 }
 
 // rmx_rollout_jvp: the forward sweep over the tape, one kernel over B * ceil(ntan / JVP_TW) wavefronts (rmx_jvp.h).  The host form
@@ -1951,70 +1891,38 @@ static int rollout_linearize_impl(rmx_batch* b, int nsteps, double* XA, double* 
 // direction, and a regrow would lose the tape.
 static int rollout_jvp_impl(rmx_batch* b, int nsteps, int ntan, const double* tu, const double* tq0, const double* tqd0, double* tq,
                             double* tqd, const bool on_device) {
-    if (!b || !tq || !tqd) return fail(RMX_E_INVALID, "rmx_rollout_jvp: null argument");
-    if (ntan < 1) return fail(RMX_E_INVALID, "rmx_rollout_jvp: ntan < 1");
-    if (!tu && !tq0 && !tqd0) return fail(RMX_E_INVALID, "rmx_rollout_jvp: all tangents are null");
+    const std::string who = "rmx_rollout_jvp";
+    if (!b || !tq || !tqd) return fail(RMX_E_INVALID, who + ": null argument");
+    if (ntan < 1) return fail(RMX_E_INVALID, who + ": ntan < 1");
+    if (!tu && !tq0 && !tqd0) return fail(RMX_E_INVALID, who + ": all tangents are null");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
     rmx_model* m = b->m;
-    if (b->tape_nsteps < 1 || !b->adjws)
-        return fail(RMX_E_INVALID, "rmx_rollout_jvp: no tape (rmx_rollout_tape has not run on this batch, or a later rmx_adjoint_* call reused its workspace)");
-    if (nsteps != b->tape_nsteps) return fail(RMX_E_INVALID, "rmx_rollout_jvp: nsteps differs from the tape's (" + std::to_string(b->tape_nsteps) + ")");
-    HIPCHK(hipSetDevice(m->device));
-    int rc = pending_error_check(b, "rmx_rollout_jvp");
-    if (rc) return rc;
-    const TapeParts t = tape_parts(b, nsteps, b->tape_integ);
-    if (t.total > b->adjws_bytes) return fail(RMX_E_INVALID, "rmx_rollout_jvp: no tape (the workspace is smaller than the tape)");
-    char* ws = (char*)b->adjws;
     JvpArgs a{};
-    a.nsteps = nsteps;
-    a.nslots = nsteps + (b->tape_integ == INTEG_BDF2 ? 1 : 0);
-    a.bdf2 = b->tape_integ == INTEG_BDF2 ? 1 : 0;
+    a.nsteps = nsteps; a.nslots = v.nslots; a.bdf2 = v.bdf2;
     a.ntan = ntan;
     a.nchunks = (ntan + JVP_CHUNK - 1) / JVP_CHUNK;
-    a.h = b->tape_h;
-    a.pscale = b->tape_pscale;
-    a.Hs = (const double*)(ws + t.off[0]); a.Ms = (const double*)(ws + t.off[1]); a.Ds = (const double*)(ws + t.off[2]);
-    if ((size_t)b->B * a.nchunks > (size_t)0x7fffffff) return fail(RMX_E_INVALID, "rmx_rollout_jvp: batch * chunks of directions exceeds the grid");
-    const size_t bytes_traj = (size_t)b->B * ntan * nsteps * m->nr * sizeof(double), bytes_state = (size_t)b->B * ntan * m->nr * sizeof(double);
-    const double* in[3] = {tu, tq0, tqd0};
-    const size_t in_bytes[3] = {bytes_traj, bytes_state, bytes_state};
-    const double* din[3] = {tu, tq0, tqd0};
-    double* dout[2] = {tq, tqd};
-    char* stage = nullptr;
-    if (!on_device) {
-        const size_t pitch_traj = (bytes_traj + 255) & ~(size_t)255, pitch_state = (bytes_state + 255) & ~(size_t)255;
-        const size_t want = 2 * pitch_traj + (tu ? pitch_traj : 0) + (tq0 ? pitch_state : 0) + (tqd0 ? pitch_state : 0);
-        const hipError_t em = hipMalloc((void**)&stage, want ? want : 256);
-        if (em == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(RMX_E_NOMEM, "rmx_rollout_jvp: no device memory for the staging of the tangents"); }
-        if (em != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_jvp: ") + hipGetErrorString(em));
-        dout[0] = (double*)stage;
-        dout[1] = (double*)(stage + pitch_traj);
-        size_t at = 2 * pitch_traj;
-        for (int i = 0; i < 3; ++i)
-            if (in[i]) { din[i] = (const double*)(stage + at); at += i == 0 ? pitch_traj : pitch_state; }
+    a.h = v.h; a.pscale = v.pscale;
+    a.Hs = v.Hs; a.Ms = v.Ms; a.Ds = v.Ds;
+    if ((size_t)b->B * a.nchunks > (size_t)0x7fffffff) return fail(RMX_E_INVALID, who + ": batch * chunks of directions exceeds the grid");
+    const size_t bytes_traj = ntan * v.t.bytes_traj, bytes_state = ntan * v.t.bytes_state;
+    enum { S_TQ, S_TQD, S_TU, S_TQ0, S_TQD0 };      // the outputs first
+    Staging st(on_device);
+    st.add(bytes_traj, nullptr, tq);
+    st.add(bytes_traj, nullptr, tqd);
+    st.add(bytes_traj, tu, nullptr);
+    st.add(bytes_state, tq0, nullptr);
+    st.add(bytes_state, tqd0, nullptr);
+    if (int rc = st.allocate(who, "the staging of the tangents")) return rc;
+    a.tu = st.dev(S_TU); a.tq0 = st.dev(S_TQ0); a.tqd0 = st.dev(S_TQD0);
+    a.tq = st.dev(S_TQ); a.tqd = st.dev(S_TQD);
+    if (!bytes_traj) {      // (no reduced DOF: nothing to compute, and no kernel time to take)
+        st.release(b, hipSuccess);
+        return RMX_OK;
     }
-    a.tu = din[0]; a.tq0 = din[1]; a.tqd0 = din[2];
-    a.tq = dout[0]; a.tqd = dout[1];
-    hipError_t e = hipSuccess;
-    if (bytes_traj) {
-        for (int i = 0; i < 3 && !on_device; ++i)
-            if (e == hipSuccess && in[i]) e = hipMemcpyAsync((void*)din[i], in[i], in_bytes[i], hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipEventRecord(b->ev0, b->stream);
-        if (e == hipSuccess) {
-            DISPATCH_NP(m->NP, launch_jvp, m, b, a);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(b->ev1, b->stream);
-        if (e == hipSuccess && !on_device) {
-            e = hipMemcpyAsync(tq, dout[0], bytes_traj, hipMemcpyDeviceToHost, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(tqd, dout[1], bytes_traj, hipMemcpyDeviceToHost, b->stream);
-        }
-        if (e == hipSuccess) e = wait_stream_short(b->stream);
-        else (void)hipStreamSynchronize(b->stream);      // (the tangents must outlive their copies)
-    }
-    if (stage) (void)hipFree(stage);
-    if (e != hipSuccess) return fail(RMX_E_HIP, std::string("rmx_rollout_jvp: ") + hipGetErrorString(e));
-    if (bytes_traj) take_event_time(b);
-    return RMX_OK;
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] { DISPATCH_NP(m->NP, launch_jvp, m, b, a); return hipSuccess; });
+    return tape_call_end(b, st.copy_out(b, e), st, who);
 }
 
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,

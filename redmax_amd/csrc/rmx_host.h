@@ -87,8 +87,8 @@ struct AdjArgs {
     const double* gu;         // [B][nsteps][nr] the cotangent of the applied torque, or null: zero
     double* dK;               // [B][nsteps][2 nr nr] one table per rollout (out), or null
     double* dxref;            // [B][nsteps][2 nr] one row per rollout (out), or null
-    const double *fq0, *fqd0; // [B][nr] the state the tape started from (its parts TP_Q0, TP_QD0): read for dK alone
-    const double *fqt, *fqdt; // [B][nsteps][nr] the tape's trajectory (TP_QT, TP_QDT): read for dK alone
+    const double *fq0, *fqd0; // [B][nr] the state the tape started from (its parts Q0, QD0 of rmx_tape.h): read for dK alone
+    const double *fqt, *fqdt; // [B][nsteps][nr] the tape's trajectory (parts QT, QDT): read for dK alone
 };
 
 // rmx_rollout_vjp_params (rmx_params.h): one wavefront per rollout walks the slots of its tape
