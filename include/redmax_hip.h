@@ -627,6 +627,60 @@ int rmx_rollout_jvp(rmx_batch* b, int nsteps, int ntan, const double* tu, const 
 int rmx_rollout_jvp_device(rmx_batch* b, int nsteps, int ntan, const double* d_tu, const double* d_tq0, const double* d_tqd0,
                            double* d_tq, double* d_tqd);
 
+/* The Riccati sweep of iLQR / DDP over the taped rollout: the backward pass of one iteration for a quadratic model of the cost, the
+ * whole recursion in one launch, with the per-step sensitivities formed inside it.  Added WITHOUT a change of RMX_VERSION (it stays
+ * 111): probe for the symbols.
+ *
+ * rmx_rollout_lqr reads the BDF1 tape on the batch, left by rmx_rollout_tape or by rmx_rollout_tape_feedback with integrator 1 (the
+ * open-loop tape under the applied torques: what iLQR re-linearises around).  h and pscale are the tape's.  Per step k, with
+ * S = XA + XB, XB, XU of slot k-1 (rmx_rollout_linearize's definitions and bits) and x = (q, qdot),
+ *     A_k = [ S          h XB ]      B_k = [ XU   ]
+ *           [ (S - I)/h    XB ]            [ XU/h ]
+ * and with Vx_N = lx_N, Vxx_N = Q_N, for k = N .. 1:
+ *     Qx = A'Vx      Qu = lu_k + B'Vx      Qxx = A'Vxx A      Qux = B'Vxx A      Quu0 = R + B'Vxx B   (symmetric)
+ *     [k_k, K_k] = -(Quu0 + mu I)^-1 [Qu, Qux]
+ *     Vx  <- lx_{k-1} + Qx  + K'Quu0 k + K'Qu  + Qux'k            (lx_0 = 0, Q_0 = 0: x_0 is fixed)
+ *     Vxx <- Q_{k-1}  + Qxx + K'Quu0 K + K'Qux + Qux'K            (kept symmetric)
+ *     expected = -sum_k (Qu'k_k + 1/2 k_k'Quu0 k_k)
+ * expected is the decrease of the quadratic model under the full step.  Arrays over the steps hold step k in row k-1.
+ *
+ * K is written in the layout rmx_rollout_tape_feedback reads per rollout (rmx_feedback.K with per_rollout = 1), kff in the layout of
+ * uff: one iLQR trial is this call, uff = ubar + alpha kff, and the feedback call with xref the nominal states.
+ *
+ * Quu0 + mu I is factorised without pivoting (LDL').  A pivot that is not > 0 flags the rollout: status 1, every kff and K row of that
+ * rollout zero, expected 0 - with K = 0 around its own nominal the feedback call reproduces that nominal, so a flagged rollout takes
+ * no step.  The other rollouts of the batch are not affected, and the call still returns RMX_OK.
+ *
+ * The call changes neither the batch's state nor the tape: it may be repeated with the same bits, and rmx_rollout_vjp, _linearize,
+ * _jvp and _vjp_params return the same bits before and after it.  A rollout's rows do not depend on its place in the batch, on the
+ * batch size, on whether Q is shared or passed as per-rollout copies, on mu against a constant mu_b, or on expected / status being
+ * NULL.  The rows of a rollout whose tape call reported a failed Newton solve (stats->status) are unspecified.
+ * Refusals (RMX_E_INVALID), in rmx_rollout_vjp's words where they coincide: "no tape", an nsteps that differs from the tape's, a BDF2
+ * tape ("BDF1 tape"), a null batch, cost, out, lx, lu, Q, R, kff or K ("null argument"), per_rollout other than 0 or 1, mu negative or
+ * not finite (checked whether or not mu_b is given; the entries of mu_b are the caller's to keep >= 0), and nr > 32 (the message names
+ * the model's nr; a tree of more than 32 nodes is refused too): the kernel keeps Vxx and a step's temporaries in LDS and exists for
+ * the padded sizes up to 32.
+ * The host form stages through a device allocation of its own, made ahead of anything else and freed before it returns; the tape's
+ * workspace does not grow, and no scratch proportional to batch * nsteps * nr^2 is allocated by either form.  The _device form:
+ * every array a DEVICE pointer (both structs are host objects), nothing staged; it returns when the kernel has finished. */
+typedef struct rmx_lqr_cost {
+    const double* lx;    /* [batch][nsteps][2*nr]   dJ/dx_k at the nominal, row k-1: state after step k, (q, qdot)   required */
+    const double* lu;    /* [batch][nsteps][nr]     dJ/du_k at the nominal                                          required */
+    const double* Q;     /* [nsteps][2nr*2nr] or [batch][nsteps][2nr*2nr]  symmetric, column-major                   required */
+    const double* R;     /* [nr*nr] symmetric, shared by steps and rollouts                                          required */
+    int per_rollout;     /* 0: Q shared by the batch, 1: one table per rollout                                       */
+    double mu;           /* >= 0: regulariser of Quu                                                                 */
+    const double* mu_b;  /* [batch] or NULL; when given it replaces mu, rollout by rollout                           */
+} rmx_lqr_cost;
+typedef struct rmx_lqr_gains {          /* kff and K required */
+    double* kff;        /* [batch][nsteps][nr]                                                                         */
+    double* K;          /* [batch][nsteps][2*nr*nr]  entry j*nr + i of row k-1 is du_i/dx_j: rmx_feedback.K, per rollout */
+    double* expected;   /* [batch] or NULL                                                                             */
+    int* status;        /* [batch] or NULL: 0, or 1 = some Quu + mu I was not positive definite                        */
+} rmx_lqr_gains;
+int rmx_rollout_lqr(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out);
+int rmx_rollout_lqr_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out);
+
 /* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
  * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of
  * RMX_VERSION (it stays 111): probe for the symbols.

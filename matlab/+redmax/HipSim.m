@@ -251,5 +251,19 @@ classdef HipSim < handle
 			end
 			[tq, tqd] = redmax_hip_mex('rollout_jvp', this.h, nsteps, tu, tq0, tqd0);
 		end
+
+		function [kff, K, expected, notpd] = rolloutLqr(this, nsteps, lx, lu, Q, R, mu)
+			% the Riccati sweep of iLQR on the BDF1 tape of the last rolloutTape / rolloutFeedback, in one launch: for the cost's
+			% gradients at the nominal lx (2nr x nsteps x B), lu (nr x nsteps x B) and its Hessians Q (2nr x 2nr x nsteps, shared,
+			% or 2nr x 2nr x nsteps x B) and R (nr x nr), both symmetric, the feed-forward kff (nr x nsteps x B) and the gains
+			% K (nr x 2nr x nsteps x B, K(i,j,k,b) = du_i/dx_j) that rolloutFeedback takes as they are: one iLQR trial is
+			% rolloutFeedback(hstep, nsteps, pscale, ubar + alpha*kff, K, xbar).  mu >= 0 (default 0) regularises Quu.  expected
+			% (1 x B): the decrease of the quadratic model under the full step; notpd (1 x B): 1 where Quu + mu*I was not
+			% positive definite - that rollout's gains are zero.  The tape and the state stay as they are.
+			if nargin < 7
+				mu = 0;
+			end
+			[kff, K, expected, notpd] = redmax_hip_mex('rollout_lqr', this.h, nsteps, lx, lu, Q, R, mu);
+		end
 	end
 end

@@ -82,6 +82,11 @@
  *                  tangents of the whole trajectory, tq, tqd (nr x nsteps x ntan x B), for tangents of the controls tu (nr x nsteps x
  *                  ntan x B) and of the initial state tq0, tqd0 (nr x ntan x B); ntan directions per rollout, taken from the arrays'
  *                  sizes.  [] for any of the three: zero (not all three).
+ *   [kff,K,expected,notpd] = redmax_hip_mex('rollout_lqr', h, nsteps, lx, lu, Q, R [, mu])  rmx_rollout_lqr on the BDF1 tape of the
+ *                  last 'rollout_tape' / 'rollout_feedback': the Riccati sweep of iLQR.  lx (2nr x nsteps x B), lu (nr x nsteps x B):
+ *                  the cost's gradients at the nominal; Q: 2nr x 2nr x nsteps (shared) or 2nr x 2nr x nsteps x B, R: nr x nr, both
+ *                  symmetric; mu (default 0) regularises Quu.  kff: nr x nsteps x B; K: nr x 2nr x nsteps x B, K(i,j,k,b) = du_i/dx_j -
+ *                  what 'rollout_feedback' takes; expected, notpd: 1 x B (notpd 1: Quu + mu I was not positive definite, zero gains).
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -804,6 +809,61 @@ static void cmd_rollout_linearize(int nlhs, mxArray* plhs[], int nrhs, const mxA
     for (int i = 0; i < nout; ++i) plhs[i] = X[i];
 }
 
+/* a real double argument of 'rollout_lqr' with `want` elements (or, where alt != 0, `alt`) */
+static const double* lqr_arg(const mxArray* a, size_t want, size_t alt, const char* what, const char* shape) {
+    const size_t n = mxGetNumberOfElements(a);
+    if (!mxIsDouble(a) || mxIsComplex(a) || (n != want && !(alt && n == alt)))
+        mexErrMsgIdAndTxt("redmax:hip", "rollout_lqr: %s must be a real double %s array", what, shape);
+    return mxGetPr(a);
+}
+
+static void cmd_rollout_lqr(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 7) die("usage: [kff,K,expected,notpd] = redmax_hip_mex('rollout_lqr', h, nsteps, lx, lu, Q, R [, mu])");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_lqr: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
+    const size_t perq = 4 * nr * nr * N;
+    const double* lx = lqr_arg(prhs[3], 2 * nr * N * B, 0, "lx", "2nr x nsteps x batch");
+    const double* lu = lqr_arg(prhs[4], nr * N * B, 0, "lu", "nr x nsteps x batch");
+    const double* Q = lqr_arg(prhs[5], perq, perq * B, "Q", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
+    const double* R = lqr_arg(prhs[6], nr * nr, 0, "R", "nr x nr");
+    /* (a batch of one: Q is one table either way) */
+    const int per_rollout = mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
+    const size_t dk[3] = {nr, N, B}, dK[4] = {nr, 2 * nr, N, B};
+    mxArray* kff = mxCreateNumericArray(3, dk, mxDOUBLE_CLASS, mxREAL);
+    mxArray* K = mxCreateNumericArray(4, dK, mxDOUBLE_CLASS, mxREAL);
+    mxArray* ex = mxCreateDoubleMatrix(1, B, mxREAL);
+    mxArray* bad = mxCreateDoubleMatrix(1, B, mxREAL);
+    int* status = (int*)mxCalloc(B, sizeof *status);
+    rmx_lqr_cost cost;
+    memset(&cost, 0, sizeof cost);
+    cost.R = R;
+    cost.per_rollout = per_rollout;
+    cost.mu = nrhs > 7 ? mxGetScalar(prhs[7]) : 0.0;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_lqr_gains out;
+        cost.lx = lx + f * 2 * nr * N;
+        cost.lu = lu + f * nr * N;
+        cost.Q = per_rollout ? Q + f * perq : Q;
+        out.kff = mxGetPr(kff) + f * nr * N;
+        out.K = mxGetPr(K) + f * 2 * nr * nr * N;
+        out.expected = mxGetPr(ex) + f;
+        out.status = status + f;
+        if (rmx_rollout_lqr(b, nsteps, &cost, &out)) die_rmx("rmx_rollout_lqr");
+    }
+    for (size_t i = 0; i < B; ++i) mxGetPr(bad)[i] = status[i] ? 1.0 : 0.0;
+    mxFree(status);
+    mxArray* outs[4] = {kff, K, ex, bad};
+    plhs[0] = kff;
+    for (int i = 1; i < 4; ++i) {
+        if (nlhs > i) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
 /* one tangent argument of 'rollout_jvp': [] (NULL: zero) or a double array of `per` * ntan * B elements; *ntan is set by the first
  * array given and the others must agree */
 static const double* tangent_arg(const mxArray* a, const handle_t* h, size_t per, size_t* ntan, const char* what) {
@@ -942,7 +1002,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", NULL};
+                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr",
+                                             NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -1061,6 +1122,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_vjp_params(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_jvp")) {
         cmd_rollout_jvp(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_lqr")) {
+        cmd_rollout_lqr(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

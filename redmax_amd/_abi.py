@@ -31,6 +31,7 @@ SYMBOLS = (
     "rmx_rollout_linearize", "rmx_rollout_linearize_device",
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
+    "rmx_rollout_lqr", "rmx_rollout_lqr_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -97,6 +98,15 @@ class Feedback(C.Structure):      # rmx_feedback: host pointers in the host form
 
 class FeedbackGrads(C.Structure):      # rmx_feedback_grads: host pointers in the host form, device pointers in the _device form
     _fields_ = [("duff", C.c_void_p), ("dK", C.c_void_p), ("dxref", C.c_void_p), ("dq0", C.c_void_p), ("dqd0", C.c_void_p)]
+
+
+class LqrCost(C.Structure):      # rmx_lqr_cost: host pointers in the host form, device pointers in the _device form
+    _fields_ = [("lx", C.c_void_p), ("lu", C.c_void_p), ("Q", C.c_void_p), ("R", C.c_void_p), ("per_rollout", C.c_int), ("mu", C.c_double),
+                ("mu_b", C.c_void_p)]
+
+
+class LqrGains(C.Structure):      # rmx_lqr_gains
+    _fields_ = [("kff", C.c_void_p), ("K", C.c_void_p), ("expected", C.c_void_p), ("status", C.c_void_p)]
 
 
 FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
@@ -175,6 +185,8 @@ def lib():
     L.rmx_rollout_linearize_device.argtypes = [vp, C.c_int, vp, vp, vp]
     L.rmx_rollout_jvp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.rmx_rollout_jvp_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.rmx_rollout_lqr.argtypes = [vp, C.c_int, C.POINTER(LqrCost), C.POINTER(LqrGains)]
+    L.rmx_rollout_lqr_device.argtypes = L.rmx_rollout_lqr.argtypes
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

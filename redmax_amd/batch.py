@@ -696,6 +696,51 @@ class BatchSim:
                                                   C.c_void_p(tqd0_ptr or None), C.c_void_p(tq_ptr or None), C.c_void_p(tqd_ptr or None)),
                    "rmx_rollout_jvp_device")
 
+    def rollout_lqr(self, nsteps, lx, lu, Q, R, mu=0.0, mu_b=None):
+        """rmx_rollout_lqr on the BDF1 tape of the last rollout_tape / rollout_feedback: the Riccati sweep of iLQR (the recursion of
+        ilqr.backward_pass, include/redmax_hip.h) for the cost's gradients lx [B][nsteps][2nr], lu [B][nsteps][nr] at the nominal and
+        its Hessians Q [nsteps][2nr][2nr] (shared) or [B][nsteps][2nr][2nr], R [nr][nr], both symmetric; mu >= 0 regularises Quu,
+        mu_b [B] replaces it rollout by rollout.  Returns (kff [B][nsteps][nr], K [B][nsteps][2nr][nr], expected [B], notpd [B] bool):
+        K[b, k-1, j, i] = du_i/dx_j, the table rollout_feedback takes per rollout; a rollout whose Quu + mu I was not positive
+        definite has notpd set and zero gains.  Neither the state nor the tape changes."""
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        lx = np.ascontiguousarray(lx, dtype=np.float64)
+        lu = np.ascontiguousarray(lu, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if lx.shape != (B, nsteps, 2 * nr) or lu.shape != (B, nsteps, nr):
+            raise ValueError("rollout_lqr: lx and lu must have shapes %r and %r, got %r and %r"
+                             % ((B, nsteps, 2 * nr), (B, nsteps, nr), lx.shape, lu.shape))
+        tail = (nsteps, 2 * nr, 2 * nr)
+        if Q.shape not in (tail, (B,) + tail):
+            raise ValueError("rollout_lqr: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, Q.shape))
+        if R.shape != (nr, nr):
+            raise ValueError("rollout_lqr: R must have shape %r, got %r" % ((nr, nr), R.shape))
+        if mu_b is not None:
+            mu_b = np.ascontiguousarray(mu_b, dtype=np.float64)
+            if mu_b.shape != (B,):
+                raise ValueError("rollout_lqr: mu_b must have shape %r, got %r" % ((B,), mu_b.shape))
+        kff = np.empty((B, nsteps, nr))
+        K = np.empty((B, nsteps, 2 * nr, nr))
+        expected = np.empty(B)
+        status = np.zeros(B, dtype=np.int32)
+        # (Q and R are symmetric: their row-major memory is the ABI's column-major table)
+        cost = _abi.LqrCost(lx.ctypes.data, lu.ctypes.data, Q.ctypes.data, R.ctypes.data, int(Q.ndim == 4), float(mu),
+                            None if mu_b is None else mu_b.ctypes.data)
+        gains = _abi.LqrGains(kff.ctypes.data, K.ctypes.data, expected.ctypes.data, status.ctypes.data)
+        _abi.check(self._L.rmx_rollout_lqr(self._batch, nsteps, C.byref(cost), C.byref(gains)), "rmx_rollout_lqr")
+        return kff, K, expected, status != 0
+
+    def rollout_lqr_device(self, nsteps, lx_ptr, lu_ptr, Q_ptr, R_ptr, kff_ptr, K_ptr, expected_ptr=None, status_ptr=None, per_rollout=False,
+                           mu=0.0, mu_b_ptr=None):
+        """rollout_lqr with DEVICE pointers (integers): lx [B][nsteps][2nr], lu, kff [B][nsteps][nr], Q [nsteps][2nr*2nr] or, with
+        per_rollout=True, one table per rollout, R [nr*nr], K [B][nsteps][2nr*nr]; expected [B] doubles, status [B] int32 and mu_b
+        [B] doubles may be 0 / None."""
+        cost = _abi.LqrCost(lx_ptr or None, lu_ptr or None, Q_ptr or None, R_ptr or None, int(bool(per_rollout)), float(mu), mu_b_ptr or None)
+        gains = _abi.LqrGains(kff_ptr or None, K_ptr or None, expected_ptr or None, status_ptr or None)
+        _abi.check(self._L.rmx_rollout_lqr_device(self._batch, int(nsteps), C.byref(cost), C.byref(gains)), "rmx_rollout_lqr_device")
+
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent
         variant the library chose."""

@@ -4,6 +4,9 @@
 #include "rmx_linearize.h"
 #include "rmx_jvp.h"
 #include "rmx_params.h"
+#if RMX_NP <= 32
+#include "rmx_lqr.h"
+#endif
 
 void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
     const dim3 grid(b->B), block(64);
@@ -95,6 +98,14 @@ void RMX_CAT(launch_linearize_, RMX_NP)(const rmx_model* m, const rmx_batch* b, 
     const dim3 grid((unsigned)((size_t)b->B * a.nslots)), block(64);
     k_rollout_linearize<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
+
+#if RMX_NP <= 32
+// rmx_rollout_lqr: one workgroup per rollout, the whole sweep in LDS (rmx_select.h select_rollout_lqr: the sizes it exists for, its LDS)
+void RMX_CAT(launch_lqr_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes) {
+    const dim3 grid(b->B), block(LQR_THREADS);
+    RMX_LAUNCH((k_rollout_lqr<RMX_NP>), grid, block, lds_bytes, b->stream, m->dm, a);
+}
+#endif
 
 // rmx_rollout_jvp: one wavefront per rollout and chunk of tangent directions
 void RMX_CAT(launch_jvp_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a) {

@@ -1925,6 +1925,73 @@ static int rollout_jvp_impl(rmx_batch* b, int nsteps, int ntan, const double* tu
     return tape_call_end(b, st.copy_out(b, e), st, who);
 }
 
+// rmx_rollout_lqr: the Riccati sweep of iLQR over the BDF1 tape, one workgroup per rollout (rmx_lqr.h); the per-slot sensitivities
+// are formed inside the sweep, nothing proportional to B N nr^2 is allocated.  The host form stages through an allocation of its
+// own, as rmx_rollout_linearize does.
+static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out, const bool on_device) {
+    const std::string who = "rmx_rollout_lqr";
+    if (!b || !cost || !out || !cost->lx || !cost->lu || !cost->Q || !cost->R || !out->kff || !out->K)
+        return fail(RMX_E_INVALID, who + ": null argument");
+    if (cost->per_rollout != 0 && cost->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    if (!(cost->mu >= 0.0) || !std::isfinite(cost->mu)) return fail(RMX_E_INVALID, who + ": mu must be finite and >= 0");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
+    if (v.integ != INTEG_BDF1)
+        return fail(RMX_E_INVALID, who + ": needs a BDF1 tape (the tape on this batch is BDF2: its augmented state is not built)");
+    rmx_model* m = b->m;
+    const rmx_select::LqrPlan plan = rmx_select::select_rollout_lqr(step_traits(m), m->nr);
+    if (plan.kernel == rmx_select::LqrKernel::RefusedNr)
+        return fail(RMX_E_INVALID, who + ": nr > " + std::to_string(rmx_select::LQR_MAX_NR) + " (the model has nr = " + std::to_string(m->nr) +
+                                       "; the LDS-resident sweep stops at " + std::to_string(rmx_select::LQR_MAX_NR) + " reduced DOFs)");
+    if (plan.kernel != rmx_select::LqrKernel::Lds)
+        return fail(RMX_E_INVALID, who + ": more than " + std::to_string(rmx_select::LQR_MAX_NR) + " nodes (the model has " + std::to_string(m->n) +
+                                       " for nr = " + std::to_string(m->nr) + "; the LDS-resident sweep stops there)");
+    const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
+    const size_t bytes_q = (cost->per_rollout ? B : 1) * N * 4 * nr * nr * dbl;
+    enum { S_KFF, S_K, S_EXP, S_ST, S_LX, S_LU, S_Q, S_R, S_MUB };      // the outputs first
+    Staging st(on_device);
+    st.add(B * N * nr * dbl, nullptr, out->kff);
+    st.add(B * N * 2 * nr * nr * dbl, nullptr, out->K);
+    st.add(B * dbl, nullptr, out->expected);
+    st.add(B * sizeof(int), nullptr, out->status);
+    st.add(B * N * 2 * nr * dbl, cost->lx, nullptr);
+    st.add(B * N * nr * dbl, cost->lu, nullptr);
+    st.add(bytes_q, cost->Q, nullptr);
+    st.add(nr * nr * dbl, cost->R, nullptr);
+    st.add(B * dbl, cost->mu_b, nullptr);
+    if (int rc = st.allocate(who, "the staging of the cost and the gains")) return rc;
+    LqrArgs a{};
+    a.nsteps = nsteps; a.h = v.h; a.pscale = v.pscale; a.mu = cost->mu;
+    a.Hs = v.Hs; a.Ms = v.Ms; a.Ds = v.Ds;
+    a.lx = st.dev(S_LX); a.lu = st.dev(S_LU); a.Q = st.dev(S_Q); a.R = st.dev(S_R); a.mu_b = st.dev(S_MUB);
+    a.q_stride = cost->per_rollout ? N * 4 * nr * nr : 0;
+    a.kff = st.dev(S_KFF); a.K = st.dev(S_K); a.expected = st.dev(S_EXP); a.status = (int*)st.at[S_ST];
+    if (!nr) {      // (no reduced DOF: no gains to compute, and no kernel time to take)
+        hipError_t e = hipSuccess;
+        if (a.expected) e = hipMemsetAsync(a.expected, 0, B * dbl, b->stream);
+        if (e == hipSuccess && a.status) e = hipMemsetAsync(a.status, 0, B * sizeof(int), b->stream);
+        return tape_call_end(b, st.copy_out(b, e), st, who);
+    }
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] {
+        switch (m->NP) {
+            case 4: launch_lqr_4(m, b, a, plan.lds_bytes); break;
+            case 8: launch_lqr_8(m, b, a, plan.lds_bytes); break;
+            case 16: launch_lqr_16(m, b, a, plan.lds_bytes); break;
+            case 32: launch_lqr_32(m, b, a, plan.lds_bytes); break;
+            default: return hipErrorInvalidDeviceFunction;      // (the plan admits no other size: never a silent substitute)
+        }
+        return hipSuccess;
+    });
+    return tape_call_end(b, st.copy_out(b, e), st, who);
+}
+extern "C" int rmx_rollout_lqr(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out) {
+    return rollout_lqr_impl(b, nsteps, cost, out, false);
+}
+extern "C" int rmx_rollout_lqr_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out) {
+    return rollout_lqr_impl(b, nsteps, cost, out, true);
+}
+
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                 double* qdtraj, rmx_stats* stats) {
     return rollout_tape_impl(b, opts, nsteps, pscale, u, qtraj, qdtraj, stats, false);

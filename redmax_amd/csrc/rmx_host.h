@@ -128,6 +128,22 @@ struct JvpArgs {
     double *tq, *tqd;         // [B][ntan][nsteps][nr] (out)
 };
 
+// rmx_rollout_lqr (rmx_lqr.h): one workgroup per rollout walks the slots of its BDF1 tape backwards
+struct LqrArgs {
+    int nsteps;               // of the tape (BDF1: one slot per step)
+    double h, pscale;         // the tape's
+    double mu;                // the regulariser of Quu where mu_b is null
+    const double *Hs, *Ms, *Ds;   // [B][nsteps][n*n], entry (row r, column c) at c*n + r
+    const double *lx, *lu;    // [B][nsteps][2 nr], [B][nsteps][nr]
+    const double* Q;          // [nsteps][2nr * 2nr] or [B][..], column-major
+    size_t q_stride;          // doubles from one rollout's Q table to the next (0: one table for the batch)
+    const double* R;          // [nr * nr]
+    const double* mu_b;       // [B] or null
+    double *kff, *K;          // [B][nsteps][nr], [B][nsteps][2 nr nr] (entry j*nr + i of a row: du_i/dx_j)
+    double* expected;         // [B] or null
+    int* status;              // [B] or null
+};
+
 struct rmx_model {
     int device = 0;
     int n = 0, nr = 0, nm = 0, NP = 0;   // n: 1-DOF nodes on the device (after lowering multi-DOF joints)
@@ -247,6 +263,11 @@ size_t big_ws_doubles(const rmx_model* m);
 void launch_big_step(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a);
 void launch_big_eval(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH);
 void launch_big_energy(const rmx_model* m, const rmx_batch* b, double* dT, double* dV);
+// part_plain.hip: the Riccati sweep over the tape (rmx_lqr.h), the padded sizes its LDS-resident kernel exists for (select_rollout_lqr)
+void launch_lqr_4(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+void launch_lqr_8(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+void launch_lqr_16(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+void launch_lqr_32(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
 RMX_DECLARE_LAUNCHERS(4)
 RMX_DECLARE_LAUNCHERS(8)
 RMX_DECLARE_LAUNCHERS(16)

@@ -190,4 +190,28 @@ inline const char* label_rollout_vjp(const AdjPlan& p, const int integ) {      /
     return fc ? "k_adjoint_bwd<16,bdf1,tape,fullchain>" : "k_adjoint_bwd<bdf1,tape>";
 }
 
+// The Riccati sweep over the BDF1 tape (rmx_rollout_lqr): one workgroup of four wavefronts per rollout with Vxx and every temporary
+// of a step in LDS (rmx_lqr.h: 17 blocks of (NP + 1) NP doubles and 8 vectors of NP).  That kernel exists for the padded sizes up to
+// 32 - at 64 the blocks alone would be 17 * 33 280 bytes, over three times a CU's LDS -, so nr > 32 is refused, and with it a tree
+// of more than 32 nodes whose reduced DOFs are fewer (its elimination runs at the padded size of its NODES).
+constexpr int LQR_MAX_NR = 32, LQR_BLOCKS = 17, LQR_VECTORS = 8, LQR_BLOCK_THREADS = 256;
+enum class LqrKernel {
+    Lds,             // part_plain: k_rollout_lqr<NP>
+    RefusedNr,       // nr > LQR_MAX_NR
+    RefusedNodes,    // nr fits, the tree's padded size does not
+};
+struct LqrPlan {
+    LqrKernel kernel = LqrKernel::Lds;
+    int block = LQR_BLOCK_THREADS;      // threads per workgroup
+    size_t lds_bytes = 0;               // dynamic LDS of the workgroup
+};
+inline size_t lqr_lds_bytes(const int NP) { return sizeof(double) * ((size_t)LQR_BLOCKS * (NP + 1) * NP + (size_t)LQR_VECTORS * NP); }
+inline LqrPlan select_rollout_lqr(const StepTraits& t, const int nr) {
+    LqrPlan p;
+    if (nr > LQR_MAX_NR) p.kernel = LqrKernel::RefusedNr;
+    else if (t.big || t.NP > LQR_MAX_NR) p.kernel = LqrKernel::RefusedNodes;
+    else p.lds_bytes = lqr_lds_bytes(t.NP);
+    return p;
+}
+
 }      // namespace rmx_select

@@ -330,6 +330,46 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     return qtraj, qdtraj, uapp
 
 
+def lqr_backward(sim, lx, lu, Q, R, mu=0.0):
+    """The Riccati sweep of iLQR on the tape ``sim`` holds (rmx_rollout_lqr_device, include/redmax_hip.h): the recursion of
+    ``ilqr.backward_pass`` in one launch, the per-step linearisation formed inside it - no rollout is run and no A_k, B_k are written.
+
+    lx [B][N][2nr], lu [B][N][nr]: the cost's gradients at the nominal the tape was recorded at; Q [N][2nr][2nr], shared by the batch,
+    or [B][N][2nr][2nr]; R [nr][nr]; both symmetric; mu >= 0 - float64 tensors on the sim's device, N the tape's steps.  The tape must
+    be a BDF1 tape (rollout, linearize, rollout_feedback with integrator=1).  Returns (kff [B][N][nr], K [B][N][2nr][nr],
+    expected [B], notpd [B] bool): K is what ``rollout_feedback`` takes as is (K[b, k-1, j, i] = du_i/dx_j, the transpose of
+    backward_pass's), and a rollout whose Quu + mu I was not positive definite has notpd set, zero gains and expected 0."""
+    import torch
+    dev = torch.device("cuda", sim.device)
+    for name, t in (("lx", lx), ("lu", lu), ("Q", Q), ("R", R)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("lqr_backward: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("lqr_backward: %s must be float64, got %s" % (name, t.dtype))
+        if t.device != dev:
+            raise ValueError("lqr_backward: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+    B, nr = sim.B, sim.nr
+    if lu.dim() != 3 or lu.shape[0] != B or lu.shape[2] != nr or lu.shape[1] < 1:
+        raise ValueError("lqr_backward: lu must have shape (%d, nsteps, %d), got %r" % (B, nr, tuple(lu.shape)))
+    N = lu.shape[1]
+    if tuple(lx.shape) != (B, N, 2 * nr):
+        raise ValueError("lqr_backward: lx must have shape %r, got %r" % ((B, N, 2 * nr), tuple(lx.shape)))
+    tail = (N, 2 * nr, 2 * nr)
+    if tuple(Q.shape) not in (tail, (B,) + tail):
+        raise ValueError("lqr_backward: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, tuple(Q.shape)))
+    if tuple(R.shape) != (nr, nr):
+        raise ValueError("lqr_backward: R must have shape %r, got %r" % ((nr, nr), tuple(R.shape)))
+    lxc, luc, Qc, Rc = (t.detach().contiguous() for t in (lx, lu, Q, R))
+    kff = torch.empty((B, N, nr), dtype=torch.float64, device=dev)
+    K = torch.empty((B, N, 2 * nr, nr), dtype=torch.float64, device=dev)
+    expected = torch.empty(B, dtype=torch.float64, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    sim.rollout_lqr_device(N, lxc.data_ptr(), luc.data_ptr(), Qc.data_ptr(), Rc.data_ptr(), kff.data_ptr(), K.data_ptr(),
+                           expected.data_ptr(), status.data_ptr(), per_rollout=Q.dim() == 4, mu=float(mu))
+    return kff, K, expected, status != 0
+
+
 _ClosedLoop = None
 
 

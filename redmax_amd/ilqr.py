@@ -3,7 +3,9 @@
 The backward pass (``backward_pass``) is pure torch and runs on any device; the dynamics stay in the library: every iteration
 linearises the nominal rollout with ``diff.linearize`` (rmx_rollout_tape_device + rmx_rollout_linearize_device) and runs its line
 search in closed loop with ``diff.rollout_feedback`` (rmx_rollout_tape_feedback_device) - the whole batch, all steps, one launch
-per trial step length.  torch is imported inside the functions, as in ``diff``.
+per trial step length.  With ``solve(backward="device")`` the backward pass leaves torch too: one launch of the library's Riccati
+sweep on the tape the forward pass left (``diff.lqr_backward``, rmx_rollout_lqr_device), ``backward_pass`` staying the definition it
+is checked against.  torch is imported inside the functions, as in ``diff``.
 
 Conventions.  x = (q, qdot), 2nr entries.  Step k = 1 .. N takes x_{k-1} and the torque u_k to x_k; x_0 = (q0, qdot0) is fixed.
 Arrays over the steps hold step k in row k-1.  The feedback acts on the state at the START of the step:
@@ -92,7 +94,7 @@ def backward_pass(A, Bm, lx, lu, Q, R, mu=0.0):
 Result = namedtuple("Result", "u qtraj qdtraj cost alpha")
 
 
-def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0):
+def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0, backward="torch"):
     """Batched iLQR: one problem per rollout of ``sim`` (a BatchSim), BDF1.  Returns (result, history).
 
     q0, qdot0 [B][nr], u0 [B][N][nr]: float64 tensors on the sim's device; cost: a QuadraticCost on that device.  Each iteration
@@ -107,9 +109,16 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
     result: u [B][N][nr] (the applied torques of the last launch), qtraj, qdtraj, cost [B], alpha [B] (the last iteration's step
     lengths, 0: no step taken).  history: [iters+1][B], the cost before the first and after every iteration - non-increasing per
     rollout.  The sim is left at the end of the returned trajectories with their open-loop tape (rollout_vjp and the others may
-    follow)."""
+    follow).
+    backward: "torch" (the default) is step 1 as written above.  "device" runs the backward pass as ONE launch on the tape the
+    previous launch left (``diff.lqr_backward``, rmx_rollout_lqr_device): no ``diff.linearize``, no extra forward launch per
+    iteration and no A_k, B_k in memory; needs nr <= 32.  A rollout whose Quu + mu I is not positive definite there gets zero gains
+    and keeps alpha = 0 in that iteration.  The two paths evaluate one recursion in different summation orders: their results agree
+    to rounding, not bit for bit."""
     import torch
     from . import diff
+    if backward not in ("torch", "device"):
+        raise ValueError("solve: backward must be 'torch' or 'device', got %r" % (backward,))
     diff._check_inputs(sim, q0, qdot0, u0)
     B, N, nr = u0.shape
     if tuple(cost.Q.shape) != (N, 2 * nr, 2 * nr):
@@ -117,8 +126,11 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
     x0 = torch.cat([q0, qdot0], dim=-1).unsqueeze(1)
     kw = dict(h=h, pscale=pscale, integrator=1)
 
+    tape = [None]                                                      # sim.tape_count after the last launch
+
     def launch(uff, K, xref):
         qt, qdt, ua, failed = diff.rollout_feedback(sim, q0, qdot0, uff, K, xref, check=False, status=True, **kw)
+        tape[0] = sim.tape_count
         x = torch.cat([qt, qdt], dim=-1)
         J = cost.value(x, ua)
         return qt, qdt, ua, x, torch.where(torch.isfinite(J) & ~failed, J, torch.full_like(J, float("inf")))      # (a failed solve: never accepted)
@@ -129,10 +141,18 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
     history = [Jbar]
     alpha = torch.zeros(B, dtype=torch.float64, device=u0.device)
     for _ in range(int(iters)):
-        _, _, A, Bm = diff.linearize(sim, q0, qdot0, ubar, **{k: v for k, v in kw.items() if k != "integrator"})
-        lx, lu = cost.gradients(xbar, ubar)
-        kff, K, _ = backward_pass(A, Bm, lx, lu, cost.Q, cost.R, mu)
-        Kabi = K.transpose(-1, -2).contiguous()
+        if backward == "device":
+            # the last launch held the accepted trajectories only (points 2 and 4): its open-loop tape under ubar IS the nominal's
+            if sim.tape_count != tape[0]:
+                raise RuntimeError("the tape of this rollout has been replaced")
+            lx, lu = cost.gradients(xbar, ubar)
+            kff, Kabi, _, notpd = diff.lqr_backward(sim, lx, lu, cost.Q, cost.R, mu)
+        else:
+            _, _, A, Bm = diff.linearize(sim, q0, qdot0, ubar, **{k: v for k, v in kw.items() if k != "integrator"})
+            lx, lu = cost.gradients(xbar, ubar)
+            kff, K, _ = backward_pass(A, Bm, lx, lu, cost.Q, cost.R, mu)
+            Kabi = K.transpose(-1, -2).contiguous()
+            notpd = None
         xref = torch.cat([x0, xbar[:, :-1]], dim=1).contiguous()      # the nominal state at the START of every step
         alpha = torch.zeros(B, dtype=torch.float64, device=u0.device)
         accepted = torch.zeros(B, dtype=torch.bool, device=u0.device)
@@ -141,6 +161,8 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
             trial = torch.where(accepted, alpha, torch.full_like(alpha, float(al)))
             out = launch(ubar + trial[:, None, None] * kff, Kabi, xref)
             better = ~accepted & (out[4] < Jbar)
+            if notpd is not None:
+                better = better & ~notpd                               # (zero gains: no step to take)
             alpha = torch.where(better, trial, alpha)
             accepted = accepted | better
             clean = bool(accepted.all())

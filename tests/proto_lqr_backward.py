@@ -1,0 +1,126 @@
+"""The Riccati recursion of rmx_rollout_lqr (include/redmax_hip.h; redmax_amd.ilqr.backward_pass) in numpy ``longdouble``: the
+reference both float64 evaluations - backward_pass on the CPU and the device kernel - are judged against.
+
+numpy.linalg has no extended type, so the Quu solve is an elimination of its own (symmetric, no pivoting: LDL', as the kernel's).
+The module also states the structured identities the kernel's algebra rests on (``structured_step``): with A = [S hX; Z X],
+Z = (S - I)/h, B = [U; U/h] every product of a step is a product of nr x nr blocks.
+"""
+import numpy as np
+
+LD = np.longdouble
+assert np.finfo(LD).eps < 1e-18, "numpy.longdouble is not an extended type on this machine"
+
+
+def ldl_solve(Amat, rhs):
+    """(x, ok) with Amat x = rhs by LDL' without pivoting in longdouble; ok False where a pivot is not > 0."""
+    Amat = np.array(Amat, dtype=LD)
+    x = np.array(rhs, dtype=LD)
+    n = Amat.shape[0]
+    for k in range(n):
+        piv = Amat[k, k]
+        if not piv > 0:
+            return None, False
+        for j in range(k + 1, n):
+            Amat[j:, j] -= Amat[j:, k] * (Amat[j, k] / piv)
+    for i in range(n):           # forward with z = y / d
+        x[i] = (x[i] - Amat[i, :i] @ x[:i]) / Amat[i, i]
+    for i in range(n - 2, -1, -1):
+        x[i] = x[i] - (Amat[i + 1:, i] @ x[i + 1:]) / Amat[i, i]
+    return x, True
+
+
+def backward_pass_ext(A, Bm, lx, lu, Q, R, mu=0.0):
+    """One rollout: A [N][2nr][2nr], Bm [N][2nr][nr], lx [N][2nr], lu [N][nr], Q [N][2nr][2nr], R [nr][nr] (any float type; taken
+    to longdouble exactly).  Returns (kff [N][nr], K [N][nr][2nr] with K[k-1, i, j] = du_i/dx_j, expected, notpd, cond) in
+    longdouble; cond: the largest float64 condition number of Quu0 + mu I over the steps.  A flagged rollout: zeros, expected 0."""
+    A, Bm, lx, lu, Q, R = (np.asarray(a, dtype=LD) for a in (A, Bm, lx, lu, Q, R))
+    N, nx, nu = Bm.shape
+    kff, K = np.zeros((N, nu), dtype=LD), np.zeros((N, nu, nx), dtype=LD)
+    expected, cond = LD(0), 0.0
+    Vx, Vxx = lx[N - 1], Q[N - 1]
+    for s in range(N - 1, -1, -1):
+        Ak, Bk = A[s], Bm[s]
+        Qx, Qu = Ak.T @ Vx, lu[s] + Bk.T @ Vx
+        Qxx, Qux = Ak.T @ Vxx @ Ak, Bk.T @ Vxx @ Ak
+        Quu0 = R + Bk.T @ Vxx @ Bk
+        Quu0 = (Quu0 + Quu0.T) / 2
+        Quu = Quu0 + LD(mu) * np.eye(nu, dtype=LD)
+        cond = max(cond, float(np.linalg.cond(Quu.astype(np.float64))))
+        sol, ok = ldl_solve(Quu, np.concatenate([Qu[:, None], Qux], axis=1))
+        if not ok:
+            return np.zeros_like(kff), np.zeros_like(K), LD(0), True, cond
+        ks, Ks = -sol[:, 0], -sol[:, 1:]
+        kff[s], K[s] = ks, Ks
+        expected = expected - (Qu @ ks + (ks @ (Quu0 @ ks)) / 2)
+        Vx = Qx + Ks.T @ (Quu0 @ ks) + Ks.T @ Qu + Qux.T @ ks
+        Vxx = Qxx + Ks.T @ Quu0 @ Ks + Ks.T @ Qux + Qux.T @ Ks
+        Vxx = (Vxx + Vxx.T) / 2
+        if s > 0:
+            Vx, Vxx = Vx + lx[s - 1], Vxx + Q[s - 1]
+    return kff, K, expected, False, cond
+
+
+def assemble(S, X, U, h, dtype=np.float64):
+    """A_k, B_k of one step from S = XA + XB, X = XB, U = XU: the blocks diff.linearize assembles."""
+    S, X, U = (np.asarray(a, dtype=dtype) for a in (S, X, U))
+    nr = S.shape[0]
+    h = dtype(h)
+    A = np.block([[S, h * X], [(S - np.eye(nr, dtype=dtype)) / h, X]])
+    return A, np.concatenate([U, U / h], axis=0)
+
+
+def structured_step(S, X, U, h, Vx, Vxx, dtype=LD):
+    """(Qx, BtVx, Qxx, Qux, BtVB) of one step from nr x nr blocks alone, the form the kernel evaluates:
+        Z = (S - I)/h      W = Vqq + (Vqv + Vqv')/h + Vvv/h^2
+        T = Vxx A:  T11 = Vqq S + Vqv Z   T12 = h Vqq X + Vqv X   T21 = Vqv'S + Vvv Z   T22 = h Vqv'X + Vvv X
+        Qxx = [S'T11 + Z'T21, S'T12 + Z'T22; ., h X'T12 + X'T22]      Qux = [U'T11 + U'T21/h, U'T12 + U'T22/h]
+        B'Vxx B = U'W U      A'Vx = (S'p + Z'r, h X'p + X'r)      B'Vx = U'p + (U/h)'r
+    and the issue's W-only form of Qxx for comparison (``structured_step_w``)."""
+    S, X, U, Vx, Vxx = (np.asarray(a, dtype=dtype) for a in (S, X, U, Vx, Vxx))
+    nr = S.shape[0]
+    h = dtype(h)
+    p, r = Vx[:nr], Vx[nr:]
+    Vqq, Vqv, Vvv = Vxx[:nr, :nr], Vxx[:nr, nr:], Vxx[nr:, nr:]
+    Z = (S - np.eye(nr, dtype=dtype)) / h
+    W = Vqq + (Vqv + Vqv.T) / h + Vvv / h / h
+    T11, T12 = Vqq @ S + Vqv @ Z, h * (Vqq @ X) + Vqv @ X
+    T21, T22 = Vqv.T @ S + Vvv @ Z, h * (Vqv.T @ X) + Vvv @ X
+    Q12 = S.T @ T12 + Z.T @ T22
+    Qxx = np.block([[S.T @ T11 + Z.T @ T21, Q12], [Q12.T, h * (X.T @ T12) + X.T @ T22]])
+    Qux = np.concatenate([U.T @ T11 + (U.T @ T21) / h, U.T @ T12 + (U.T @ T22) / h], axis=1)
+    Qx = np.concatenate([S.T @ p + Z.T @ r, h * (X.T @ p) + X.T @ r])
+    return Qx, U.T @ p + (U / h).T @ r, Qxx, Qux, U.T @ W @ U
+
+
+def structured_step_w(S, X, U, h, Vx, Vxx, dtype=LD):
+    """The same five quantities in the W-only form: w = p + r/h, Gv = Vqv + Vvv/h, P = [S, hX],
+        B'Vx = U'w    A'Vx = (S'w - r/h, h X'w)    Qux = U'[W S - Gv/h, h W X]
+        Qxx = P'W P + P'[-Gv/h, 0] + [-Gv/h, 0]'P + [Vvv/h^2, 0; 0, 0]
+    (its Vvv/h^2 terms cancel against each other: the kernel uses the Z form)."""
+    S, X, U, Vx, Vxx = (np.asarray(a, dtype=dtype) for a in (S, X, U, Vx, Vxx))
+    nr = S.shape[0]
+    h = dtype(h)
+    p, r = Vx[:nr], Vx[nr:]
+    Vqq, Vqv, Vvv = Vxx[:nr, :nr], Vxx[:nr, nr:], Vxx[nr:, nr:]
+    w, Gv = p + r / h, Vqv + Vvv / h
+    W = Vqq + (Vqv + Vqv.T) / h + Vvv / h / h
+    P = np.concatenate([S, h * X], axis=1)
+    zero = np.zeros((nr, nr), dtype=dtype)
+    G0 = np.concatenate([-Gv / h, zero], axis=1)
+    Qxx = P.T @ W @ P + P.T @ G0 + G0.T @ P + np.block([[Vvv / h / h, zero], [zero, zero]])
+    Qux = U.T @ np.concatenate([W @ S - Gv / h, h * (W @ X)], axis=1)
+    Qx = np.concatenate([S.T @ w - r / h, h * (X.T @ w)])
+    return Qx, U.T @ w, Qxx, Qux, U.T @ W @ U
+
+
+def to_feedback_layout(K):
+    """K [.., nr, 2nr] (K[.., i, j] = du_i/dx_j, backward_pass's order) -> the table rmx_rollout_lqr writes and rmx_rollout_tape_feedback
+    reads, [.., 2nr, nr]: entry j*nr + i of a row is du_i/dx_j."""
+    return np.ascontiguousarray(np.swapaxes(K, -1, -2))
+
+
+def rel_err(x, ref):
+    """max |x - ref| / max |ref| in longdouble, as a float (0 where both are zero)."""
+    x, ref = np.asarray(x, dtype=LD), np.asarray(ref, dtype=LD)
+    den = np.abs(ref).max()
+    return float(np.abs(x - ref).max() / den) if den > 0 else float(np.abs(x - ref).max())
