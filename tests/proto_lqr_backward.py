@@ -11,28 +11,28 @@ LD = np.longdouble
 assert np.finfo(LD).eps < 1e-18, "numpy.longdouble is not an extended type on this machine"
 
 
-def ldl_solve(Amat, rhs):
-    """(x, ok) with Amat x = rhs by LDL' without pivoting in longdouble; ok False where a pivot is not > 0."""
+def ldl_solve(Amat, rhs, pivot=False):
+    """(x, ok) with Amat x = rhs by LDL' without pivoting in longdouble; ok False where a pivot is not > 0.  pivot=True: (x, ok, k), k
+    the index of the first pivot that is not > 0 (None where every pivot is)."""
     Amat = np.array(Amat, dtype=LD)
     x = np.array(rhs, dtype=LD)
     n = Amat.shape[0]
     for k in range(n):
         piv = Amat[k, k]
         if not piv > 0:
-            return None, False
+            return (None, False, k) if pivot else (None, False)
         for j in range(k + 1, n):
             Amat[j:, j] -= Amat[j:, k] * (Amat[j, k] / piv)
     for i in range(n):           # forward with z = y / d
         x[i] = (x[i] - Amat[i, :i] @ x[:i]) / Amat[i, i]
     for i in range(n - 2, -1, -1):
         x[i] = x[i] - (Amat[i + 1:, i] @ x[i + 1:]) / Amat[i, i]
-    return x, True
+    return (x, True, None) if pivot else (x, True)
 
 
-def backward_pass_ext(A, Bm, lx, lu, Q, R, mu=0.0):
-    """One rollout: A [N][2nr][2nr], Bm [N][2nr][nr], lx [N][2nr], lu [N][nr], Q [N][2nr][2nr], R [nr][nr] (any float type; taken
-    to longdouble exactly).  Returns (kff [N][nr], K [N][nr][2nr] with K[k-1, i, j] = du_i/dx_j, expected, notpd, cond) in
-    longdouble; cond: the largest float64 condition number of Quu0 + mu I over the steps.  A flagged rollout: zeros, expected 0."""
+def _sweep(A, Bm, lx, lu, Q, R, mu):
+    """The recursion itself: (kff, K, expected, flag, cond, Quu0 of the last step processed); flag None or (step, pivot) - the row of
+    the step and the index of the pivot of Quu0 + mu I that was not > 0."""
     A, Bm, lx, lu, Q, R = (np.asarray(a, dtype=LD) for a in (A, Bm, lx, lu, Q, R))
     N, nx, nu = Bm.shape
     kff, K = np.zeros((N, nu), dtype=LD), np.zeros((N, nu, nx), dtype=LD)
@@ -46,9 +46,9 @@ def backward_pass_ext(A, Bm, lx, lu, Q, R, mu=0.0):
         Quu0 = (Quu0 + Quu0.T) / 2
         Quu = Quu0 + LD(mu) * np.eye(nu, dtype=LD)
         cond = max(cond, float(np.linalg.cond(Quu.astype(np.float64))))
-        sol, ok = ldl_solve(Quu, np.concatenate([Qu[:, None], Qux], axis=1))
+        sol, ok, piv = ldl_solve(Quu, np.concatenate([Qu[:, None], Qux], axis=1), pivot=True)
         if not ok:
-            return np.zeros_like(kff), np.zeros_like(K), LD(0), True, cond
+            return np.zeros_like(kff), np.zeros_like(K), LD(0), (s, piv), cond, Quu0
         ks, Ks = -sol[:, 0], -sol[:, 1:]
         kff[s], K[s] = ks, Ks
         expected = expected - (Qu @ ks + (ks @ (Quu0 @ ks)) / 2)
@@ -57,7 +57,85 @@ def backward_pass_ext(A, Bm, lx, lu, Q, R, mu=0.0):
         Vxx = (Vxx + Vxx.T) / 2
         if s > 0:
             Vx, Vxx = Vx + lx[s - 1], Vxx + Q[s - 1]
-    return kff, K, expected, False, cond
+    return kff, K, expected, None, cond, Quu0
+
+
+def backward_pass_ext(A, Bm, lx, lu, Q, R, mu=0.0, flag=False):
+    """One rollout: A [N][2nr][2nr], Bm [N][2nr][nr], lx [N][2nr], lu [N][nr], Q [N][2nr][2nr], R [nr][nr] (any float type; taken
+    to longdouble exactly).  Returns (kff [N][nr], K [N][nr][2nr] with K[k-1, i, j] = du_i/dx_j, expected, notpd, cond) in
+    longdouble; cond: the largest float64 condition number of Quu0 + mu I over the steps.  A flagged rollout: zeros, expected 0.
+    flag=True: a sixth entry, None or (step, pivot) - where the recursion stopped: the row of the step (0 .. N-1) and the index of the
+    first pivot of its LDL' that was not > 0."""
+    kff, K, expected, where, cond, _ = _sweep(A, Bm, lx, lu, Q, R, mu)
+    out = (kff, K, expected, where is not None, cond)
+    return out + (where,) if flag else out
+
+
+# ---------------------------------------------------------------- cost families (the CPU and the GPU tests draw the same inputs)
+
+def _spd(rng, n, lo, hi):
+    """Symmetric positive definite: a random orthogonal basis times a log-uniform spectrum whose ends are lo and hi (n = 1: hi)."""
+    q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    lam = np.exp(rng.uniform(np.log(lo), np.log(hi), n))
+    lam[0], lam[-1] = lo, hi
+    M = (q * lam) @ q.T
+    return (M + M.T) / 2
+
+
+def dense_cost(seed, nr, N, B=None, r_spectrum=(0.03, 0.3), q_spectrum=(1e-2, 1.0)):
+    """(Q, R): Q [N][2nr][2nr], or [B][N][2nr][2nr] with B, every Q_k symmetric positive definite with a full q-qdot block - a random
+    orthogonal basis times a log-uniform spectrum with the ends q_spectrum, times (0.5 + k), so that no two steps (and, with B, no
+    two rollouts) share a table; R [nr][nr] dense SPD with the ends r_spectrum.  Both are symmetrised as (M + M')/2 exactly: their
+    row-major memory is the column-major table of the ABI."""
+    rng = np.random.default_rng(seed)
+    R = _spd(rng, nr, *r_spectrum)
+    Q = np.array([[(0.5 + k) * _spd(rng, 2 * nr, *q_spectrum) for k in range(N)] for _ in range(1 if B is None else B)])
+    return (Q[0] if B is None else Q), R
+
+
+def indefinite_at(A, Bm, lx, lu, Q, R, mu, s):
+    """(Q', c): Q [N][2nr][2nr] of ONE rollout with Q'[s] = Q[s] - c e e', a rank-one indefinite cost at step row s that the
+    recursion meets at a pivot k >= 1.  e is a unit vector of state space orthogonal to column 0 of B_s (the other columns of B_s,
+    summed, with their component along column 0 taken out), so w = B_s'e has w[0] = 0 up to rounding and Quu0 of step s, which
+    changes by -c w w', keeps its first pivot.  The steps behind s (processed first) do not see Q[s]: the recursion can stop at s
+    only.  c is doubled from 1 until the longdouble recursion stops at step s with a pivot index >= 1, then once more: the margin
+    that keeps a float64 evaluation on the same side of zero."""
+    Bs = np.asarray(Bm[s], dtype=np.float64)
+    assert Bs.shape[1] >= 2 and 0 <= s < len(Q)
+    b0 = Bs[:, 0] / np.linalg.norm(Bs[:, 0])
+    e = Bs[:, 1:].sum(axis=1)
+    e = e - b0 * (b0 @ e)
+    e = e - b0 * (b0 @ e)            # (twice: the second pass removes what rounding left of the first)
+    e = e / np.linalg.norm(e)
+    ee = np.outer(e, e)              # (exactly symmetric: e_i e_j is commutative)
+    c = 1.0
+    for _ in range(200):
+        Qi = np.array(Q, dtype=np.float64)
+        Qi[s] = Qi[s] - c * ee
+        where = _sweep(A, Bm, lx, lu, Qi, R, mu)[3]
+        if where is not None and where[0] == s:      # (a smaller c can pass step s and stop the recursion at a step before it)
+            assert where[1] >= 1, where
+            Qi[s] = Qi[s] - c * ee   # (= Q[s] - 2c e e' up to rounding; c below is what was subtracted in all)
+            where = _sweep(A, Bm, lx, lu, Qi, R, mu)[3]
+            assert where is not None and where[0] == s and where[1] >= 1, where
+            return Qi, 2 * c
+        c *= 2
+    raise AssertionError("indefinite_at: no c up to 2^200 stops the recursion at step %d" % s)
+
+
+def rescue_mu(A, Bm, lx, lu, Q, R, mu=0.0):
+    """The regulariser that makes a flagged problem positive definite again, as an iLQR's regularise-and-retry loop finds it: from
+    |lambda_min| of the Quu0 the recursion stopped at (with ``mu``), quadrupled until the longdouble recursion passes every step,
+    then once more (the margin of indefinite_at).  Returns (mu, rounds): rounds counts the quadruplings before the margin's."""
+    where, _, quu0 = _sweep(A, Bm, lx, lu, Q, R, mu)[3:]
+    assert where is not None, "rescue_mu: the problem is not flagged"
+    m = abs(float(np.linalg.eigvalsh(quu0.astype(np.float64)).min()))
+    for rounds in range(100):
+        if _sweep(A, Bm, lx, lu, Q, R, m)[3] is None:
+            assert _sweep(A, Bm, lx, lu, Q, R, 4 * m)[3] is None
+            return 4 * m, rounds
+        m *= 4
+    raise AssertionError("rescue_mu: not positive definite up to mu = %g" % m)
 
 
 def assemble(S, X, U, h, dtype=np.float64):

@@ -7,11 +7,15 @@ The checks, in the order of the sections below:
      correct float64 evaluations of one recursion with different summation orders and another factorisation differ by small
      constant factors in an error that is eps * conditioning for both; three bits allow that and do not allow a lost term;
   2. closing the loop through rmx_rollout_tape_feedback_device; 3. exact structure, bit for bit; 4. a rollout that is not positive
-     definite; 5. refusals; 6. ilqr.solve(backward="device").
+     definite - at the first step processed, and at an interior step behind a good pivot, then rescued by a larger mu of its own;
+     5. refusals; 6. ilqr.solve(backward="device").
 
 Scenes: sceneAdjointChain(5) (nr 5, padded to 8), sceneAdjointTree7, sceneAdjointChain(32) (the LDS limit); B = 3, N = 8 (N = 3
 for the 32-link chain); states from test_rollout_vjp_proto.case; the cost of test_gpu_ilqr._problem: Q = diag(1 on q, 0.01 on qdot),
-R = 0.1 I, mu = 1e-6.
+R = 0.1 I, mu = 1e-6 ("diag").  With the dense costs of proto_lqr_backward.dense_cost ("dense": every entry of Q and R set, another
+Q at every step and, per rollout, for every rollout) also sceneAdjointChain(2) and (3) (NP 4: one tile, and an odd d), "fixed" of
+test_rollout_feedback_proto (n 5, nr 3, NP 8: nodes without a DOF inside the tree), sceneAdjointChain(11) (NP 16, part-filled) and
+(16) (NP 16, full); N = 6, N = 3 for the 16-link chain.
 
 Measured on an MI355X (the worst rollout of each case; cond(Quu) the largest over steps and rollouts).  Every e_ref is below the
 floor of 16 eps = 3.6e-15, so the bound is 8 * 16 eps = 2.84e-14 throughout; per-rollout copies of Q give the figures of the shared Q:
@@ -28,6 +32,34 @@ floor of 16 eps = 3.6e-15, so the bound is 8 * 16 eps = 2.84e-14 throughout; per
     5       1   kff        3.78e-16   2.02e-16   5.9
     5       1   K          6.27e-16   6.55e-16   5.9
     5       1   expected   4.69e-16   2.35e-16   5.9
+The cases on dense costs, one line each (e_ref e_gpu per quantity, the rollout with the largest e_gpu; "per": one table per rollout).
+Where e_ref leaves the floor the bound is 8 e_ref; the largest e_gpu / bound of these lines is 0.33:
+    scene   N   cost                      kff                 K                   expected            cond(Quu)
+    2       6   dense                     1.06e-14 1.61e-14   8.27e-15 1.31e-14   3.90e-16 4.30e-16   561
+    2       6   dense per                 1.18e-14 1.04e-14   8.27e-15 1.31e-14   3.90e-16 4.30e-16   484
+    3       6   dense                     8.27e-15 1.09e-14   7.29e-15 1.01e-14   2.05e-16 1.32e-16   660
+    3       6   dense per                 1.11e-14 1.51e-14   4.64e-15 1.23e-14   5.69e-16 2.50e-16   640
+    fixed   6   dense                     8.35e-16 7.88e-16   6.60e-16 7.14e-16   2.22e-16 2.07e-16   7.7
+    fixed   6   dense per                 5.79e-16 9.86e-16   1.25e-15 1.49e-15   3.17e-16 2.66e-16   11.7
+    5       8   dense                     2.57e-14 5.73e-14   1.47e-14 3.48e-14   2.09e-16 2.09e-16   1.6e3
+    5       8   dense per                 9.56e-15 3.45e-14   2.56e-14 2.94e-14   2.09e-16 2.09e-16   1.6e3
+    tree7   8   dense                     7.59e-16 1.52e-15   2.12e-15 3.48e-15   3.64e-16 1.90e-16   2.6e3
+    tree7   8   dense per                 7.59e-16 1.52e-15   2.09e-15 2.29e-15   9.91e-17 2.63e-16   3.6e3
+    11      6   dense                     2.95e-14 3.41e-14   1.39e-14 3.57e-14   1.66e-15 9.49e-16   2.0e3
+    11      6   dense per                 5.07e-14 7.13e-14   1.39e-14 3.57e-14   5.95e-16 5.83e-16   3.4e3
+    16      3   dense                     1.75e-14 1.58e-14   2.89e-14 3.80e-14   3.26e-16 3.26e-16   788
+    16      3   dense per                 2.98e-14 2.67e-14   4.37e-14 4.75e-14   1.55e-15 2.86e-16   1.6e3
+    32      3   dense                     9.76e-15 1.05e-14   2.73e-14 4.59e-14   3.50e-16 6.50e-16   548
+    32      3   dense per                 9.76e-15 1.05e-14   3.01e-14 3.09e-14   4.01e-16 4.01e-16   580
+    3       6   dense, R not symmetric    1.05e-14 6.34e-15   7.30e-15 1.01e-14   3.07e-16 1.80e-16   660
+    5       8   dense, R not symmetric    2.56e-14 4.70e-14   2.56e-14 2.62e-14   2.93e-16 2.93e-16   1.6e3
+    5       8   ill-conditioned, mu 0     1.14e-11 8.36e-12   4.63e-11 3.29e-11   1.72e-15 8.76e-15   1.3e6  (Q x 1e-6; bound 8 eps cond = 1.8e-9)
+    16      3   ill-conditioned, mu 0     1.15e-10 1.55e-10   1.94e-10 1.70e-10   6.11e-17 6.11e-17   2.6e7  (Q x 1e-9; bound 4.4e-8)
+    5       8   rescued, mu 95.1272       4.53e-16 2.84e-16   2.19e-15 1.08e-15   3.56e-16 1.46e-16   2.5    (rollout 1)
+    11      6   rescued, mu 112.669       4.82e-16 4.06e-16   4.08e-16 7.81e-16   3.58e-17 2.37e-16   2.1    (rollout 1)
+The indefinite cases: scene 5, step row 4 of 8, c = 2, the recursion stops at pivot 1; scene 11, step row 3 of 6, c = 2, pivot 1; one
+quadrupling of mu from |lambda_min(Quu0)| makes each positive definite again, and the margin's makes the mu above.  Closing the loop
+with the dense cost: J 60.27, 60.99, 54.89 before, 0.989, 1.814, 1.941 after the full step with either path's gains.
 """
 import ctypes as C
 
@@ -37,10 +69,12 @@ import pytest
 import proto_lqr_backward as P
 import proto_rollout_linearize as lin
 from test_gpu_adjoint_controls import _DevArray, _scene
+from test_rollout_feedback_proto import scene as _scene_or_fixed
 from test_rollout_vjp_proto import case
 
 B, MU = 3, 1e-6
-STEPS = {5: 8, "tree7": 8, 32: 3}
+STEPS = {5: 8, "tree7": 8, 32: 3, 2: 6, 3: 6, "fixed": 6, 11: 6, 16: 3}
+SEED = {2: 2, 3: 3, "fixed": 4, 5: 5, "tree7": 7, 11: 11, 16: 16, 32: 32}      # of a size's dense cost
 EPS = np.finfo(np.float64).eps
 _CACHE = {}
 
@@ -49,7 +83,7 @@ def _setup(size, nsteps=None):
     nsteps = STEPS[size] if nsteps is None else nsteps
     key = (size, nsteps)
     if key not in _CACHE:
-        sc = _scene(size, 1)
+        sc = _scene_or_fixed(size, 1)
         _CACHE[key] = (sc, case(sc, 53, nsteps=nsteps, B=B), nsteps)
     return _CACHE[key]
 
@@ -61,14 +95,18 @@ def _tape(sim, sc, cs, sel=slice(None)):
     return qt, qdt
 
 
-def _cost(sc, cs, qt, qdt, sel=slice(None)):
-    """(lx, lu, Q, R) of test_gpu_ilqr._problem's cost at the nominal (qt, qdt, u)."""
+def _cost(sc, cs, qt, qdt, sel=slice(None), QR=None):
+    """(lx, lu, Q, R) of test_gpu_ilqr._problem's cost at the nominal (qt, qdt, u); QR = (Q, R): of that cost instead, Q [N][.][.] or
+    one table per rollout - lx = Q_k (x_k - goal), lu = R u_k for the same goal."""
     nr, N = sc.nr, qt.shape[1]
     q0, _ = sc.getQ()
     goal = np.concatenate([q0 - 0.1, np.zeros(nr)])
+    x = np.concatenate([qt, qdt], axis=-1)
+    if QR is not None:
+        Q, R = QR
+        return np.einsum("kij,bkj->bki" if Q.ndim == 3 else "bkij,bkj->bki", Q, x - goal), np.einsum("ij,bkj->bki", R, cs["u"][sel]), Q, R
     Q = np.tile(np.diag([1.0] * nr + [0.01] * nr), (N, 1, 1))
     R = 0.1 * np.eye(nr)
-    x = np.concatenate([qt, qdt], axis=-1)
     return np.einsum("kij,bkj->bki", Q, x - goal), np.einsum("ij,bkj->bki", R, cs["u"][sel]), Q, R
 
 
@@ -89,15 +127,74 @@ def _nominal(size, nsteps=None):
 
 # ---------------------------------------------------------------- 1. against the reference
 
+def _dense(size, nsteps=None, per=False, **spectra):
+    """(lx, lu, Q, R) of proto_lqr_backward.dense_cost at a size's nominal, shared or one table per rollout: computed once."""
+    key = ("dense", size, nsteps, per) + tuple(sorted(spectra.items()))
+    if key not in _CACHE:
+        sc, cs, N = _setup(size, nsteps)
+        nom = _nominal(size, nsteps)
+        _CACHE[key] = _cost(sc, cs, nom["qt"], nom["qdt"], QR=P.dense_cost(9000 + SEED[size], sc.nr, N, B if per else None, **spectra))
+    return _CACHE[key]
+
+
+def _table(Q, b):
+    return Q[b] if Q.ndim == 4 else Q
+
+
+def _backward_pass(nom, lx, lu, Q, R, mu, b):
+    """ilqr.backward_pass (float64, CPU) of rollout b with its own table and its own mu."""
+    import torch
+    from redmax_amd.ilqr import backward_pass
+    t = lambda a: torch.tensor(a, dtype=torch.float64)      # noqa: E731
+    return tuple(a.numpy()[0] for a in backward_pass(t(nom["A"][b:b + 1]), t(nom["Bm"][b:b + 1]), t(lx[b:b + 1]), t(lu[b:b + 1]),
+                                                     t(_table(Q, b)), t(R), float(mu)))
+
+
+def _judge(tag, b, ref, gpu, ext, cond, stability=False):
+    """The file's rule for one rollout: ref = backward_pass's (kff, K, expected), gpu = the device's with K as backward_pass orders it,
+    ext = the longdouble recursion's.  e_gpu <= 8 max(e_ref, 16 eps) per quantity; stability: eps * cond joins the maximum."""
+    ok = True
+    for name, r, g, e in zip(("kff", "K", "expected"), ref, gpu, ext):
+        e_ref, e_gpu = P.rel_err(r, e), P.rel_err(g, e)
+        bound = 8 * max(e_ref, 16 * EPS, EPS * cond if stability else 0.0)
+        print("%s b %d %-8s: e_ref %.3e e_gpu %.3e bound %.3e cond(Quu) %.3e%s"
+              % (tag, b, name, e_ref, e_gpu, bound, cond, "" if e_gpu <= bound else "   <-- over"))
+        ok = ok and e_gpu <= bound
+    return ok
+
+
+DENSE_SIZES = [2, 3, "fixed", 5, "tree7", 11, 16, 32]
+_DIAG = [(5, None, False), (5, None, True), ("tree7", None, False), (32, None, False), (32, None, True), (5, 1, False)]
+CASES = [pytest.param(s, n, p, "diag", id="%s-%s-%s" % (s, n, p)) for s, n, p in _DIAG] + \
+        [pytest.param(s, None, p, "dense", id="%s-dense-%s" % (s, "per-rollout" if p else "shared")) for s in DENSE_SIZES for p in (False, True)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("size,nsteps,per", [(5, None, False), (5, None, True), ("tree7", None, False), (32, None, False), (32, None, True),
-                                             (5, 1, False)])
-def test_gains_meet_the_extended_recursion_as_closely_as_backward_pass(size, nsteps, per):
+@pytest.mark.parametrize("size,nsteps,per,cost", CASES)
+def test_gains_meet_the_extended_recursion_as_closely_as_backward_pass(size, nsteps, per, cost):
+    """cost "diag": test_gpu_ilqr._problem's, per: B copies of its table.  "dense": proto_lqr_backward.dense_cost - every entry of Q
+    and R set, another table at every step and, with per, for every rollout; each rollout is judged on its own table."""
     import torch
     from redmax_amd import BatchSim
     from redmax_amd.ilqr import backward_pass
     sc, cs, N = _setup(size, nsteps)
     nom = _nominal(size, nsteps)
+    if cost == "dense":
+        lx, lu, Q, R = _dense(size, nsteps, per)
+        assert Q.ndim == (4 if per else 3) and np.abs(Q).min() > 0 and np.abs(R).min() > 0
+        sim = BatchSim(sc, batch=B)
+        _tape(sim, sc, cs)
+        kff, K, expected, notpd = sim.rollout_lqr(N, lx, lu, Q, R, mu=MU)
+        sim.close()
+        assert kff.shape == (B, N, sc.nr) and K.shape == (B, N, 2 * sc.nr, sc.nr) and expected.shape == (B,) and not notpd.any()
+        ok = True
+        for b in range(B):
+            ext = P.backward_pass_ext(nom["A"][b], nom["Bm"][b], lx[b], lu[b], _table(Q, b), R, MU)
+            assert not ext[3]
+            ok = _judge("size %s N %d dense per %d" % (size, N, per), b, _backward_pass(nom, lx, lu, Q, R, MU, b),
+                        (kff[b], K[b].transpose(0, 2, 1), expected[b]), ext[:3], ext[4]) and ok
+        assert ok
+        return
     lx, lu, Q, R = nom["cost"]
     sim = BatchSim(sc, batch=B)
     _tape(sim, sc, cs)
@@ -116,6 +213,38 @@ def test_gains_meet_the_extended_recursion_as_closely_as_backward_pass(size, nst
             print("size %s N %d per %d b %d %-8s: e_ref %.3e e_gpu %.3e bound %.3e cond(Quu) %.3e%s"
                   % (size, N, per, b, name, e_ref, e_gpu, bound, cond, "" if e_gpu <= bound else "   <-- over"))
             ok = ok and e_gpu <= bound
+    assert ok
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [5, 16])
+def test_ill_conditioned_quu_within_the_stability_bound_of_an_spd_solve(size):
+    """mu = 0, R with the spectrum 1e-9 .. 0.1, and Q scaled down by factors of 1e-3 until cond(Quu) >= 1e6 in every rollout (Quu -> R,
+    cond 1e8, as Q -> 0).  The rule gains the term eps * cond: the backward-stability bound of an SPD solve; 8 stays the allowance
+    between two correct float64 evaluations."""
+    from redmax_amd import BatchSim
+    sc, cs, N = _setup(size)
+    nom = _nominal(size)
+    Q0, R = P.dense_cost(9100 + SEED[size], sc.nr, N, r_spectrum=(1e-9, 0.1))
+    for power in range(7):
+        lx, lu, Q, R = _cost(sc, cs, nom["qt"], nom["qdt"], QR=(Q0 * 1e-3 ** power, R))
+        exts = [P.backward_pass_ext(nom["A"][b], nom["Bm"][b], lx[b], lu[b], Q, R, 0.0) for b in range(B)]
+        if min(e[4] for e in exts) >= 1e6:
+            break
+    print("size %s: Q scaled by 1e-%d, cond(Quu) per rollout %s" % (size, 3 * power, [e[4] for e in exts]))
+    assert min(e[4] for e in exts) >= 1e6 and not any(e[3] for e in exts)
+    refs = [_backward_pass(nom, lx, lu, Q, R, 0.0, b) for b in range(B)]
+    assert all(np.isfinite(a).all() for r in refs for a in r)                       # (float64 on the CPU takes the step too)
+    assert all(np.linalg.eigvalsh(R + nom["Bm"][b, N - 1].T @ Q[N - 1] @ nom["Bm"][b, N - 1]).min() > 0 for b in range(B))
+    sim = BatchSim(sc, batch=B)
+    _tape(sim, sc, cs)
+    kff, K, expected, notpd = sim.rollout_lqr(N, lx, lu, Q, R, mu=0.0)
+    sim.close()
+    assert not notpd.any()
+    ok = True
+    for b in range(B):
+        ok = _judge("size %s N %d ill-conditioned" % (size, N), b, refs[b], (kff[b], K[b].transpose(0, 2, 1), expected[b]), exts[b][:3],
+                    exts[b][4], stability=True) and ok
     assert ok
 
 
@@ -147,6 +276,44 @@ def test_gains_close_the_loop_through_the_feedback_kernel():
     J1 = cost.value(torch.cat([q2, qd2], dim=-1), u2)
     print("J before %s\nJ after the full step %s\nexpected decrease %s" % (J0.cpu().numpy(), J1.cpu().numpy(), expected.cpu().numpy()))
     assert (J1 < J0).all()
+    sim.close()
+
+
+@pytest.mark.gpu
+def test_gains_close_the_loop_through_the_feedback_kernel_with_a_dense_cost():
+    """The same loop with a QuadraticCost built from dense_cost.  alpha = 0 is bit for bit as before.  alpha = 1: a full iLQR step on
+    a nonlinear rollout need not lower the cost, so J1 < J0 is asserted where it holds for ilqr.backward_pass's gains (diff.linearize
+    on the same nominal) through the same feedback kernel; otherwise the two paths must agree on the sign of J1 - J0 per rollout."""
+    import torch
+    from redmax_amd import BatchSim, diff
+    from redmax_amd.ilqr import QuadraticCost, backward_pass
+    sc, cs, t, diag = _torch_problem()
+    N, ps = t["u"].shape[1], sc.task["pscale"]
+    dev = t["u"].device
+    Q, R = P.dense_cost(9200, sc.nr, N)
+    cost = QuadraticCost(torch.tensor(Q, device=dev), torch.tensor(R, device=dev), diag.xgoal)
+    sim = BatchSim(sc, batch=B)
+    qt, qdt, ubar = diff.rollout_feedback(sim, t["q0"], t["qd0"], t["u"], h=sc.h, pscale=ps)
+    xbar = torch.cat([qt, qdt], dim=-1)
+    J0 = cost.value(xbar, ubar)
+    lx, lu = cost.gradients(xbar, ubar)
+    kff, K, expected, notpd = diff.lqr_backward(sim, lx, lu, cost.Q, cost.R, MU)
+    assert K.shape == (B, N, 2 * sc.nr, sc.nr) and not notpd.any() and (expected > 0).all()
+    xref = torch.cat([torch.cat([t["q0"], t["qd0"]], dim=-1).unsqueeze(1), xbar[:, :-1]], dim=1).contiguous()
+    q1, qd1, u1 = diff.rollout_feedback(sim, t["q0"], t["qd0"], ubar, K, xref, h=sc.h, pscale=ps)
+    assert torch.equal(q1, qt) and torch.equal(qd1, qdt) and torch.equal(u1, ubar)
+    q2, qd2, u2 = diff.rollout_feedback(sim, t["q0"], t["qd0"], ubar + kff, K, xref, h=sc.h, pscale=ps)
+    J1 = cost.value(torch.cat([q2, qd2], dim=-1), u2)
+    _, _, A, Bm = diff.linearize(sim, t["q0"], t["qd0"], ubar, h=sc.h, pscale=ps)
+    rk, rK, rexp = backward_pass(A, Bm, lx, lu, cost.Q, cost.R, MU)
+    q3, qd3, u3 = diff.rollout_feedback(sim, t["q0"], t["qd0"], ubar + rk, rK.transpose(-1, -2).contiguous(), xref, h=sc.h, pscale=ps)
+    J1r = cost.value(torch.cat([q3, qd3], dim=-1), u3)
+    print("J before %s\nJ after the full step %s\n  with backward_pass's gains %s\nexpected decrease %s (backward_pass %s)"
+          % (J0.cpu().numpy(), J1.cpu().numpy(), J1r.cpu().numpy(), expected.cpu().numpy(), rexp.cpu().numpy()))
+    if (J1r < J0).all():
+        assert (J1 < J0).all()
+    else:
+        assert torch.equal(torch.sign(J1 - J0), torch.sign(J1r - J0))
     sim.close()
 
 
@@ -251,6 +418,165 @@ def test_a_rollout_that_is_not_positive_definite_takes_no_step_and_leaves_the_ot
     assert not kff[1].any() and not K[1].any() and expected[1] == 0
     for b in (0, 2):
         assert all(np.array_equal(g[b], r[b]) for g, r in zip((kff, K, expected), ref)), b
+
+
+FILL = 1234.5                      # what the output buffers hold before a device call
+FILL_WORD = 0x55555555             # and the status words
+
+
+class _Outputs:
+    """Device buffers for kff, K, expected and status, each with a guard row behind [B][N].. (one more row of the last axis; B more
+    words behind status), all of it pre-filled: what a call leaves untouched shows."""
+
+    def __init__(self, N, nr):
+        self.shapes = dict(kff=(B * N + 1, nr), K=(B * N + 1, 2 * nr * nr), exp=(B + 1,))
+        self.dev = {k: _DevArray(np.full(s, FILL)) for k, s in self.shapes.items()}
+        self.dev["st"] = _DevArray(np.full(2 * B, FILL_WORD, dtype=np.int32).view(np.float64))
+        self.N, self.nr = N, nr
+
+    def ptrs(self):
+        return tuple(self.dev[k].ptr.value for k in ("kff", "K", "exp", "st"))
+
+    def get(self):
+        """(kff, K, expected, notpd) as rollout_lqr returns them, after checking the guards."""
+        N, nr = self.N, self.nr
+        kff, K, ex, st = (self.dev[k].get() for k in ("kff", "K", "exp", "st"))
+        st = st.view(np.int32)
+        assert (kff[-1] == FILL).all() and (K[-1] == FILL).all() and ex[-1] == FILL and (st[B:] == FILL_WORD).all()
+        assert set(st[:B].tolist()) <= {0, 1}
+        return kff[:-1].reshape(B, N, nr), K[:-1].reshape(B, N, 2 * nr, nr), ex[:B], st[:B] != 0
+
+    def free(self):
+        for a in self.dev.values():
+            a.free()
+
+
+def _device_call(sim, N, nr, lx, lu, Q, R, mu=MU, mu_b=None):
+    """rollout_lqr_device into pre-filled, guarded output buffers: (kff, K, expected, notpd)."""
+    ins = [_DevArray(a) for a in (lx, lu, Q, R)] + ([] if mu_b is None else [_DevArray(mu_b)])
+    out = _Outputs(N, nr)
+    sim.rollout_lqr_device(N, *([a.ptr.value for a in ins[:4]] + list(out.ptrs())), per_rollout=Q.ndim == 4, mu=mu,
+                           mu_b_ptr=None if mu_b is None else ins[4].ptr.value)
+    got = out.get()
+    for a in ins:
+        a.free()
+    out.free()
+    return got
+
+
+def _interior(size):
+    """Per-rollout dense tables at a size and rollout 1's made indefinite at the interior step N // 2 (proto_lqr_backward.indefinite_at),
+    with the mu that rescues it: computed once."""
+    key = ("interior", size)
+    if key not in _CACHE:
+        sc, cs, N = _setup(size)
+        nom = _nominal(size)
+        lx, lu, Qb, R = _dense(size, None, True)
+        s = N // 2
+        Q1, c = P.indefinite_at(nom["A"][1], nom["Bm"][1], lx[1], lu[1], Qb[1], R, MU, s)
+        Qi = Qb.copy()
+        Qi[1] = Q1
+        where = P.backward_pass_ext(nom["A"][1], nom["Bm"][1], lx[1], lu[1], Q1, R, MU, flag=True)[5]
+        mu, rounds = P.rescue_mu(nom["A"][1], nom["Bm"][1], lx[1], lu[1], Q1, R, MU)
+        print("size %s: indefinite at step row %d of %d, c = %g, stopped at (step, pivot) %s; rescued by mu = %.6g after %d quadruplings"
+              % (size, s, N, c, where, mu, rounds))
+        _CACHE[key] = dict(Qi=Qi, s=s, c=c, where=where, mu=mu)
+    return _CACHE[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [5, 11])
+def test_indefinite_at_an_interior_step_zeroes_the_rows_already_written(size):
+    """Rollout 1 stops at step row N // 2 behind one or more good pivots: the gains of the steps after it are in memory by then and
+    must be zeroed with the rest.  Device form, output buffers pre-filled: the zeros are written, not left over."""
+    from redmax_amd import BatchSim
+    sc, cs, N = _setup(size)
+    lx, lu, Qb, R = _dense(size, None, True)
+    it = _interior(size)
+    assert it["where"][0] == it["s"] == N // 2 and it["where"][1] >= 1 and 0 < it["s"] < N - 1
+    sim = BatchSim(sc, batch=B)
+    _tape(sim, sc, cs)
+    ref = sim.rollout_lqr(N, lx, lu, Qb, R, mu=MU)
+    assert not ref[3].any() and all(np.abs(ref[0][1, k]).max() > 0 for k in range(N))      # (every row of rollout 1 is non-zero before)
+    kff, K, expected, notpd = _device_call(sim, N, sc.nr, lx, lu, it["Qi"], R)
+    sim.close()
+    assert notpd.tolist() == [False, True, False]
+    assert all(not kff[1, k].any() and not K[1, k].any() for k in range(N)) and expected[1] == 0
+    for b in (0, 2):
+        assert all(np.array_equal(g[b], r[b]) for g, r in zip((kff, K, expected), ref)), b
+        assert (kff[b] != FILL).all() and (K[b] != FILL).all() and expected[b] != FILL
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [5, 11])
+def test_a_larger_mu_for_that_rollout_alone_rescues_it(size):
+    """The regularise-and-retry step of an iLQR: the same tables, mu_b = [MU, rescue_mu, MU] - mu of the size of Quu0 decides rollout
+    1's answer, where Quu0 and Quu0 + mu I must each keep their place."""
+    from redmax_amd import BatchSim
+    sc, cs, N = _setup(size)
+    nom = _nominal(size)
+    lx, lu, Qb, R = _dense(size, None, True)
+    it = _interior(size)
+    mub = np.array([MU, it["mu"], MU])
+    sim = BatchSim(sc, batch=B)
+    _tape(sim, sc, cs)
+    ref = sim.rollout_lqr(N, lx, lu, Qb, R, mu=MU)
+    kff, K, expected, notpd = sim.rollout_lqr(N, lx, lu, it["Qi"], R, mu=123.0, mu_b=mub)
+    dev = _device_call(sim, N, sc.nr, lx, lu, it["Qi"], R, mu=123.0, mu_b=mub)
+    sim.close()
+    assert not notpd.any() and _same((kff, K, expected, notpd), dev)
+    for b in (0, 2):
+        assert all(np.array_equal(g[b], r[b]) for g, r in zip((kff, K, expected), ref)), b
+    ext = P.backward_pass_ext(nom["A"][1], nom["Bm"][1], lx[1], lu[1], it["Qi"][1], R, it["mu"])
+    assert not ext[3] and np.abs(ext[0]).max() > 0
+    assert _judge("size %s N %d rescued, mu %.6g" % (size, N, it["mu"]), 1, _backward_pass(nom, lx, lu, it["Qi"], R, it["mu"], 1),
+                  (kff[1], K[1].transpose(0, 2, 1), expected[1]), ext[:3], ext[4])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [3, 5])
+def test_the_device_form_reads_both_triangles_of_R(size):
+    """R as the kernel reads it is 0.5 (R(i, j) + R(j, i)): a table with an antisymmetric part of the size of its entries, which no
+    host wrapper would pass on as it is, gives the gains of its symmetric part - judged by the file's rule against the longdouble
+    recursion on (R + R')/2."""
+    from redmax_amd import BatchSim
+    sc, cs, N = _setup(size)
+    nom = _nominal(size)
+    lx, lu, Q, R = _dense(size, None, False)
+    skew = np.triu(np.random.default_rng(13).uniform(0.25, 0.5, R.shape), 1) * np.abs(R).max()
+    Rns = R + skew - skew.T
+    assert np.abs(Rns - Rns.T).max() > np.abs(R).max() / 4
+    Rs = (Rns.astype(P.LD) + Rns.T.astype(P.LD)) / 2
+    sim = BatchSim(sc, batch=B)
+    _tape(sim, sc, cs)
+    kff, K, expected, notpd = _device_call(sim, N, sc.nr, lx, lu, Q, Rns)
+    sim.close()
+    assert not notpd.any()
+    ok = True
+    for b in range(B):
+        ext = P.backward_pass_ext(nom["A"][b], nom["Bm"][b], lx[b], lu[b], Q, Rs, MU)
+        assert not ext[3]
+        ok = _judge("size %s N %d R with an antisymmetric part" % (size, N), b, _backward_pass(nom, lx, lu, Q, Rs.astype(np.float64), MU, b),
+                    (kff[b], K[b].transpose(0, 2, 1), expected[b]), ext[:3], ext[4]) and ok
+    assert ok
+
+
+@pytest.mark.gpu
+def test_lqr_backward_returns_the_bits_of_rollout_lqr_on_dense_per_rollout_tables():
+    import torch
+    from redmax_amd import BatchSim, diff
+    sc, cs, N = _setup(5)
+    lx, lu, Qb, R = _dense(5, None, True)
+    sim = BatchSim(sc, batch=B)
+    _tape(sim, sc, cs)
+    ref = sim.rollout_lqr(N, lx, lu, Qb, R, mu=MU)
+    t = lambda a: torch.tensor(a, dtype=torch.float64, device=torch.device("cuda", sim.device))      # noqa: E731
+    for Q, want in ((Qb, ref), (Qb[2], sim.rollout_lqr(N, lx, lu, Qb[2], R, mu=MU))):
+        kff, K, expected, notpd = diff.lqr_backward(sim, t(lx), t(lu), t(Q), t(R), MU)
+        assert K.shape == (B, N, 2 * sc.nr, sc.nr) and K.is_contiguous()                  # rollout_feedback's layout, as it takes it
+        assert _same(want, (kff.cpu().numpy(), K.cpu().numpy(), expected.cpu().numpy(), notpd.cpu().numpy()))
+    assert not np.array_equal(want[1], ref[1])
+    sim.close()
 
 
 # ---------------------------------------------------------------- 5. refusals
