@@ -681,6 +681,66 @@ typedef struct rmx_lqr_gains {          /* kff and K required */
 int rmx_rollout_lqr(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out);
 int rmx_rollout_lqr_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out);
 
+/* Torque limits ulo <= u <= uhi in the device iLQR: control-limited DDP (Tassa, Mansard, Todorov 2014) - a box-constrained QP for
+ * the feed-forward term at every step of the Riccati sweep, zero feedback rows for the torques on a bound, and the applied torque
+ * clamped in the forward pass.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.  No existing struct
+ * grows.  One box for all steps and rollouts.
+ *
+ * rmx_rollout_tape_feedback_box is rmx_rollout_tape_feedback with one change to the torque of step k:
+ *     uapp = min(max(uff + K (x - xref), ulo), uhi)      per DOF
+ * - the clamp comes behind the feedback sum, and applies with fb->K NULL too (actuator saturation of an open-loop torque); both
+ * integrators; under BDF2 the clamped torque of step 1 holds for both SDIRK2 solves.  Everything else is that entry's, in its words:
+ * the record and uapp, the tape (the open-loop tape under uapp: rmx_rollout_vjp, _linearize, _jvp, _vjp_params and _lqr read it
+ * unchanged), the state the batch is left in, the refusals.  New refusals (RMX_E_INVALID), which leave an existing tape alone: a null
+ * box ("null argument"); an entry with ulo > uhi, or a NaN bound (the message names the DOF).  With both pointers NULL, or every bound
+ * infinite, the call returns rmx_rollout_tape_feedback's bits.  The _device form: ulo and uhi are DEVICE pointers too (the struct is
+ * a host object); it reads them back once for the check.
+ *
+ * rmx_rollout_lqr_box is rmx_rollout_lqr with one change: the solve [k, K] = -(Quu0 + mu I)^-1 [Qu, Qux] of every step becomes the
+ * box QP   min Qu'x + 1/2 x'Hq x,  lo_k <= x <= hi_k,   Hq = Quu0 + mu I,  lo_k = ulo - ubar_k,  hi_k = uhi - ubar_k
+ * with ubar [batch][nsteps][nr] the nominal applied torques (the uapp of the launch that left the tape; required).  Per step, with
+ * val(x) = Qu'x + 1/2 x'Hq x (a bound at +-inf never counts as reached):
+ *     x = clamp(0, lo, hi); full = false; prev = none
+ *     for it = 1 .. max_iter:
+ *         grad = Qu + Hq x
+ *         c_i  = (x_i == lo_i and grad_i > 0) or (x_i == hi_i and grad_i < 0);   f = not c
+ *         if prev is set and c == prev and full: converged
+ *         if every DOF is in c: converged
+ *         factorise Hq_ff (LDL' without pivoting); a pivot not > 0: status 1
+ *         xn_f = -Hq_ff^-1 (Qu_f + Hq_fc x_c);  xn_c = x_c;  s = xn - x;  sg = s'grad
+ *         if not (sg < 0): converged
+ *         step = 1;  while (val(clamp(x + step s)) - val(x)) / (step sg) < 0.1:  step *= 0.6;  if step < 1e-20: status 2
+ *         full = (step == 1 and the clamp moved nothing);  x = clamp(x + step s);  prev = c
+ *     cap reached: status 2
+ * The outputs depend on the final set c alone: k_c = x_c (exactly lo_i or hi_i), K_c = 0, [k_f, K_f] = -Hq_ff^-1 [Qu_f + Hq_fc k_c,
+ * Qux_f] by one final solve, k_f then clamped into the box.  The value recursion and expected keep rmx_rollout_lqr's formulas, with
+ * the constrained k, K.  max_iter: the cap on the QP iterations of a step; 0 selects the default of 64, a negative value is refused.
+ * clamped [batch][nsteps] or NULL: bit i of row k-1 is set where DOF i of step k ended on a bound (the final set; nr <= 32 holds here).
+ * out->status: 0, 1 = some factorised free block of Quu0 + mu I had a pivot that is not > 0, 2 = the QP of some step did not terminate
+ * within max_iter or its line search ran out.  A rollout with status 1 or 2 gets what rmx_rollout_lqr gives a flagged rollout - every
+ * kff, K and clamped row zero, expected 0 -, the other rollouts are untouched and the call returns RMX_OK.
+ * Every refusal of rmx_rollout_lqr holds in its words, and: a null box or ubar ("null argument"), ulo > uhi or a NaN bound (as above),
+ * max_iter < 0.  The tape and state are not touched, the call can be repeated with the same bits, and a rollout's rows do not depend
+ * on its place in the batch, the batch size, shared against per-rollout Q, mu against mu_b, or which optional outputs are NULL.  With
+ * every bound infinite or NULL, kff, K, expected and status are THE BITS of rmx_rollout_lqr, and clamped is zero.
+ *
+ * Out of scope: rmx_rollout_vjp_feedback does not know about the clamp (gradients through a saturated feedback law); BDF2 tapes in
+ * the Riccati sweep; per-step or per-rollout limits. */
+typedef struct rmx_box {
+    const double* ulo;   /* [nr] reduced DOF order, or NULL: no lower bound; entries may be -inf */
+    const double* uhi;   /* [nr], or NULL: no upper bound; entries may be +inf                    */
+} rmx_box;
+int rmx_rollout_tape_feedback_box(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
+                                  const rmx_feedback* fb, const rmx_box* box, double* qtraj, double* qdtraj, double* uapp,
+                                  rmx_stats* stats);
+int rmx_rollout_tape_feedback_box_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
+                                         const rmx_feedback* fb, const rmx_box* box, double* d_qtraj, double* d_qdtraj, double* d_uapp,
+                                         rmx_stats* stats);
+int rmx_rollout_lqr_box(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_box* box, const double* ubar, int max_iter,
+                        const rmx_lqr_gains* out, unsigned* clamped);
+int rmx_rollout_lqr_box_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_box* box, const double* d_ubar,
+                               int max_iter, const rmx_lqr_gains* out, unsigned* d_clamped);
+
 /* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
  * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of
  * RMX_VERSION (it stays 111): probe for the symbols.

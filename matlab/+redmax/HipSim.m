@@ -265,5 +265,30 @@ classdef HipSim < handle
 			end
 			[kff, K, expected, notpd] = redmax_hip_mex('rollout_lqr', this.h, nsteps, lx, lu, Q, R, mu);
 		end
+
+		function [qtraj, qdtraj, uapp, stats] = rolloutFeedbackBox(this, hstep, nsteps, pscale, uff, K, xref, ulo, uhi, integrator)
+			% rolloutFeedback with torque limits: uapp = min(max(uff + K*(x - xref), ulo), uhi) per DOF, clamped on the device
+			% behind the feedback sum (with K = [] too: actuator saturation of an open-loop torque).  ulo, uhi: nr elements, or
+			% []: that side is unbounded.  Everything else is rolloutFeedback's; rolloutVjpFeedback does not know about the clamp.
+			if nargin < 10
+				integrator = 1;
+			end
+			[qtraj, qdtraj, uapp, stats] = redmax_hip_mex('rollout_feedback_box', this.h, hstep, nsteps, pscale, uff, K, xref, ulo, uhi, integrator);
+		end
+
+		function [kff, K, expected, status, clamped] = rolloutLqrBox(this, nsteps, lx, lu, Q, R, ubar, ulo, uhi, mu, maxIter)
+			% rolloutLqr under the torque limits ulo <= u <= uhi (control-limited DDP): at every step the box QP over
+			% ulo - ubar_k <= k <= uhi - ubar_k in the place of the solve; ubar (nr x nsteps x B) are the nominal applied torques,
+			% the uapp of the rolloutFeedbackBox call that left the tape.  A torque on a bound has kff = bound - ubar exactly and
+			% a zero row of K.  status (1 x B): 0, 1 (a pivot not > 0), 2 (a QP did not terminate within maxIter, default 64) - the
+			% gains of such a rollout are zero; clamped (nsteps x B): bit i-1 set where DOF i of the step ended on a bound.
+			if nargin < 10
+				mu = 0;
+			end
+			if nargin < 11
+				maxIter = 0;
+			end
+			[kff, K, expected, status, clamped] = redmax_hip_mex('rollout_lqr_box', this.h, nsteps, lx, lu, Q, R, ubar, ulo, uhi, mu, maxIter);
+		end
 	end
 end

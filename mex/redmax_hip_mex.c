@@ -87,6 +87,13 @@
  *                  the cost's gradients at the nominal; Q: 2nr x 2nr x nsteps (shared) or 2nr x 2nr x nsteps x B, R: nr x nr, both
  *                  symmetric; mu (default 0) regularises Quu.  kff: nr x nsteps x B; K: nr x 2nr x nsteps x B, K(i,j,k,b) = du_i/dx_j -
  *                  what 'rollout_feedback' takes; expected, notpd: 1 x B (notpd 1: Quu + mu I was not positive definite, zero gains).
+ *   [qtraj,qdtraj,uapp,st] = redmax_hip_mex('rollout_feedback_box', h, hstep, nsteps, pscale, uff, K, xref, ulo, uhi [, integrator])
+ *                  rmx_rollout_tape_feedback_box: 'rollout_feedback' with uapp clamped into ulo <= u <= uhi behind the feedback sum
+ *                  (with K = [] too).  ulo, uhi: nr elements, or []: that side is unbounded.
+ *   [kff,K,expected,status,clamped] = redmax_hip_mex('rollout_lqr_box', h, nsteps, lx, lu, Q, R, ubar, ulo, uhi [, mu [, max_iter]])
+ *                  rmx_rollout_lqr_box: 'rollout_lqr' with the box QP of control-limited DDP at every step.  ubar (nr x nsteps x B):
+ *                  the nominal applied torques; max_iter (default 0: 64) caps the QP iterations of a step.  status 1 x B: 0, 1 (a
+ *                  pivot not > 0), 2 (a QP did not terminate); clamped nsteps x B: bit i set where DOF i ended on a bound.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -682,6 +689,69 @@ static void cmd_rollout_feedback(int nlhs, mxArray* plhs[], int nrhs, const mxAr
     else mxDestroyArray(st);
 }
 
+/* a limit argument of 'rollout_feedback_box' / 'rollout_lqr_box': [] (NULL: that side is unbounded) or nr doubles */
+static const double* bound_arg(const mxArray* a, const handle_t* h, const char* cmd, const char* what) {
+    if (mxIsEmpty(a)) return NULL;
+    if (!mxIsDouble(a) || mxIsComplex(a) || mxGetNumberOfElements(a) != (size_t)h->nr)
+        mexErrMsgIdAndTxt("redmax:hip", "%s: %s must be [] or a real double array of nr = %d elements", cmd, what, h->nr);
+    return mxGetPr(a);
+}
+
+/* 'rollout_feedback_box': 'rollout_feedback' with the applied torque clamped into ulo <= u <= uhi (rmx_rollout_tape_feedback_box) */
+static void cmd_rollout_feedback_box(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 10)
+        die("usage: [qtraj,qdtraj,uapp,stats] = redmax_hip_mex('rollout_feedback_box', h, hstep, nsteps, pscale, uff, K, xref, ulo, uhi [, integrator])");
+    const double integ_arg = nrhs > 10 ? mxGetScalar(prhs[10]) : 1.0;
+    if (integ_arg != 1.0 && integ_arg != 2.0) die("rollout_feedback_box: integrator must be 1 (BDF1) or 2 (BDF2)");
+    const int integ = integ_arg == 2.0 ? 2 : 1;
+    rmx_opts o;
+    rmx_opts_default(&o);
+    o.h = mxGetScalar(prhs[2]);
+    o.iterMaxPerDof = 5;                               /* as 'rollout_tape' */
+    const int nsteps = (int)mxGetScalar(prhs[3]);
+    if (nsteps < 1) die("rollout_feedback_box: nsteps must be at least 1");
+    const double pscale = mxGetScalar(prhs[4]);
+    const double* uff = traj_arg(prhs[5], h, nsteps, "uff");
+    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps;
+    int per_rollout = -1;
+    const double* K = feedback_arg(prhs[6], h, 2 * nr * nr, nsteps, &per_rollout, "K");
+    const double* xref = feedback_arg(prhs[7], h, 2 * nr, nsteps, &per_rollout, "xref");
+    if (per_rollout < 0) per_rollout = 0;
+    rmx_box box;
+    box.ulo = bound_arg(prhs[8], h, "rollout_feedback_box", "ulo");
+    box.uhi = bound_arg(prhs[9], h, "rollout_feedback_box", "uhi");
+    const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B};
+    mxArray* out[3];
+    for (int i = 0; i < 3; ++i) out[i] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* st = new_i32((size_t)h->B, 2);
+    int* sp = (int*)mxGetData(st);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'rollout_tape' */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_stats st_s;
+        st_s.newton_iters = sp + f;
+        st_s.ls_halvings = NULL;
+        st_s.status = sp + h->B + f;
+        rmx_feedback fb;
+        fb.uff = uff + f * per;
+        fb.K = K ? K + (per_rollout ? f * (size_t)nsteps * 2 * nr * nr : 0) : NULL;
+        fb.xref = xref ? xref + (per_rollout ? f * (size_t)nsteps * 2 * nr : 0) : NULL;
+        fb.per_rollout = per_rollout;
+        if (rmx_rollout_tape_feedback_box(b, &o, nsteps, integ, pscale, &fb, &box, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * per,
+                                          mxGetPr(out[2]) + f * per, &st_s))
+            die_rmx("rmx_rollout_tape_feedback_box");
+    }
+    h->tape_integ = integ;
+    plhs[0] = out[0];
+    for (int i = 1; i < 3; ++i) {
+        if (nlhs > i) plhs[i] = out[i];
+        else mxDestroyArray(out[i]);
+    }
+    if (nlhs > 3) plhs[3] = st;
+    else mxDestroyArray(st);
+}
+
 static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
     if (nrhs < 5) die("usage: [du,dq0,dqd0] = redmax_hip_mex('rollout_vjp', h, nsteps, gq, gqd)");
@@ -864,6 +934,64 @@ static void cmd_rollout_lqr(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     }
 }
 
+/* 'rollout_lqr_box': 'rollout_lqr' under the torque limits ulo <= u <= uhi (rmx_rollout_lqr_box).  status 1 x B (0, 1: a pivot not
+ * > 0, 2: a QP did not terminate), clamped nsteps x B (the bit masks as doubles: nr <= 32, exact) */
+static void cmd_rollout_lqr_box(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 10)
+        die("usage: [kff,K,expected,status,clamped] = redmax_hip_mex('rollout_lqr_box', h, nsteps, lx, lu, Q, R, ubar, ulo, uhi [, mu [, max_iter]])");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_lqr_box: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
+    const size_t perq = 4 * nr * nr * N;
+    const double* lx = lqr_arg(prhs[3], 2 * nr * N * B, 0, "lx", "2nr x nsteps x batch");
+    const double* lu = lqr_arg(prhs[4], nr * N * B, 0, "lu", "nr x nsteps x batch");
+    const double* Q = lqr_arg(prhs[5], perq, perq * B, "Q", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
+    const double* R = lqr_arg(prhs[6], nr * nr, 0, "R", "nr x nr");
+    const double* ubar = lqr_arg(prhs[7], nr * N * B, 0, "ubar", "nr x nsteps x batch");
+    rmx_box box;
+    box.ulo = bound_arg(prhs[8], h, "rollout_lqr_box", "ulo");
+    box.uhi = bound_arg(prhs[9], h, "rollout_lqr_box", "uhi");
+    const int per_rollout = mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
+    const int max_iter = nrhs > 11 ? (int)mxGetScalar(prhs[11]) : 0;
+    const size_t dk[3] = {nr, N, B}, dK[4] = {nr, 2 * nr, N, B};
+    mxArray* kff = mxCreateNumericArray(3, dk, mxDOUBLE_CLASS, mxREAL);
+    mxArray* K = mxCreateNumericArray(4, dK, mxDOUBLE_CLASS, mxREAL);
+    mxArray* ex = mxCreateDoubleMatrix(1, B, mxREAL);
+    mxArray* stat = mxCreateDoubleMatrix(1, B, mxREAL);
+    mxArray* cl = mxCreateDoubleMatrix(N, B, mxREAL);
+    int* status = (int*)mxCalloc(B, sizeof *status);
+    unsigned* mask = (unsigned*)mxCalloc(N * B, sizeof *mask);
+    rmx_lqr_cost cost;
+    memset(&cost, 0, sizeof cost);
+    cost.R = R;
+    cost.per_rollout = per_rollout;
+    cost.mu = nrhs > 10 ? mxGetScalar(prhs[10]) : 0.0;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_lqr_gains out;
+        cost.lx = lx + f * 2 * nr * N;
+        cost.lu = lu + f * nr * N;
+        cost.Q = per_rollout ? Q + f * perq : Q;
+        out.kff = mxGetPr(kff) + f * nr * N;
+        out.K = mxGetPr(K) + f * 2 * nr * nr * N;
+        out.expected = mxGetPr(ex) + f;
+        out.status = status + f;
+        if (rmx_rollout_lqr_box(b, nsteps, &cost, &box, ubar + f * nr * N, max_iter, &out, mask + f * N)) die_rmx("rmx_rollout_lqr_box");
+    }
+    for (size_t i = 0; i < B; ++i) mxGetPr(stat)[i] = (double)status[i];
+    for (size_t i = 0; i < N * B; ++i) mxGetPr(cl)[i] = (double)mask[i];
+    mxFree(status);
+    mxFree(mask);
+    mxArray* outs[5] = {kff, K, ex, stat, cl};
+    plhs[0] = kff;
+    for (int i = 1; i < 5; ++i) {
+        if (nlhs > i) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
 /* one tangent argument of 'rollout_jvp': [] (NULL: zero) or a double array of `per` * ntan * B elements; *ntan is set by the first
  * array given and the others must agree */
 static const double* tangent_arg(const mxArray* a, const handle_t* h, size_t per, size_t* ntan, const char* what) {
@@ -1002,7 +1130,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr",
+                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
                                              NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
@@ -1124,6 +1252,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_jvp(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_lqr")) {
         cmd_rollout_lqr(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_feedback_box")) {
+        cmd_rollout_feedback_box(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_lqr_box")) {
+        cmd_rollout_lqr_box(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

@@ -32,6 +32,7 @@ SYMBOLS = (
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
     "rmx_rollout_lqr", "rmx_rollout_lqr_device",
+    "rmx_rollout_tape_feedback_box", "rmx_rollout_tape_feedback_box_device", "rmx_rollout_lqr_box", "rmx_rollout_lqr_box_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -107,6 +108,10 @@ class LqrCost(C.Structure):      # rmx_lqr_cost: host pointers in the host form,
 
 class LqrGains(C.Structure):      # rmx_lqr_gains
     _fields_ = [("kff", C.c_void_p), ("K", C.c_void_p), ("expected", C.c_void_p), ("status", C.c_void_p)]
+
+
+class Box(C.Structure):      # rmx_box: host pointers in the host form, device pointers in the _device form
+    _fields_ = [("ulo", C.c_void_p), ("uhi", C.c_void_p)]
 
 
 FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
@@ -187,6 +192,12 @@ def lib():
     L.rmx_rollout_jvp_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.rmx_rollout_lqr.argtypes = [vp, C.c_int, C.POINTER(LqrCost), C.POINTER(LqrGains)]
     L.rmx_rollout_lqr_device.argtypes = L.rmx_rollout_lqr.argtypes
+    L.rmx_rollout_tape_feedback_box.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), C.POINTER(Box), _dp, _dp, _dp,
+                                                C.POINTER(Stats)]
+    L.rmx_rollout_tape_feedback_box_device.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), C.POINTER(Box), vp, vp,
+                                                       vp, C.POINTER(Stats)]
+    L.rmx_rollout_lqr_box.argtypes = [vp, C.c_int, C.POINTER(LqrCost), C.POINTER(Box), vp, C.c_int, C.POINTER(LqrGains), vp]
+    L.rmx_rollout_lqr_box_device.argtypes = L.rmx_rollout_lqr_box.argtypes
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

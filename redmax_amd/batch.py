@@ -473,7 +473,20 @@ class BatchSim:
             raise ValueError("%s: K and xref must both be shared by the batch or both hold one table per rollout" % who)
         return K, xref, int(bool(per and per[0]))
 
-    def rollout_feedback(self, nsteps, h, uff, K=None, xref=None, pscale=1.0, stats=False, integrator=1):
+    def _ulim(self, ulim, who):
+        """(ulo, uhi) of a ``ulim`` keyword as contiguous float64 [nr] arrays or None each: the torque limits of rmx_box."""
+        if not isinstance(ulim, (tuple, list)) or len(ulim) != 2:
+            raise ValueError("%s: ulim must be a pair (ulo, uhi), either may be None" % who)
+        out = []
+        for name, a in zip(("ulo", "uhi"), ulim):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (self.nr,):
+                    raise ValueError("%s: %s must have shape %r, got %r" % (who, name, (self.nr,), a.shape))
+            out.append(a)
+        return out
+
+    def rollout_feedback(self, nsteps, h, uff, K=None, xref=None, pscale=1.0, stats=False, integrator=1, ulim=None):
         """rmx_rollout_tape_feedback: rollout_tape in closed loop - at step k the joint torque is tau + pscale*uapp[:, k-1] with
             uapp[b, k-1] = uff[b, k-1] + K[k-1].T @ (x - xref[k-1]),    x = (q, qdot) at the START of step k,
         formed on the device from the state the rollout has reached (one launch for all steps).  uff: [B][nsteps][nr] (or
@@ -481,7 +494,9 @@ class BatchSim:
         du_i/dx_j (the row index is the STATE entry, q block first: the memory is the ABI's column-major table); None: no feedback,
         uapp is uff bit for bit.  xref: [nsteps][2nr] or [B][nsteps][2nr], None: zero.  Returns (qtraj, qdtraj, uapp[, info]) - info
         with stats=True.  The tape it leaves is the open-loop tape under uapp: rollout_vjp, rollout_linearize, rollout_jvp and
-        rollout_vjp_params differentiate that open-loop rollout, not the feedback law; rollout_vjp_feedback differentiates the closed loop."""
+        rollout_vjp_params differentiate that open-loop rollout, not the feedback law; rollout_vjp_feedback differentiates the closed loop.
+        ulim=(ulo, uhi), each [nr] or None: rmx_rollout_tape_feedback_box - uapp is clamped into the limits behind the feedback sum
+        (with K None too: actuator saturation).  rollout_vjp_feedback does not know about the clamp."""
         if integrator not in (1, 2):
             raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
         nsteps = int(nsteps)
@@ -501,19 +516,27 @@ class BatchSim:
         info, st = self._tape_stats(stats)
         self.tape_count += 1
         self._tape_integrator = integrator
-        _abi.check(self._L.rmx_rollout_tape_feedback(self._batch, C.byref(opts), nsteps, int(integrator), float(pscale), C.byref(fb),
-                                                     _abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp),
-                                                     C.byref(st) if st is not None else None), "rmx_rollout_tape_feedback")
+        if ulim is not None:
+            ulo, uhi = self._ulim(ulim, "rollout_feedback")
+            box = _abi.Box(None if ulo is None else ulo.ctypes.data, None if uhi is None else uhi.ctypes.data)
+            _abi.check(self._L.rmx_rollout_tape_feedback_box(self._batch, C.byref(opts), nsteps, int(integrator), float(pscale), C.byref(fb),
+                                                             C.byref(box), _abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp),
+                                                             C.byref(st) if st is not None else None), "rmx_rollout_tape_feedback_box")
+        else:
+            _abi.check(self._L.rmx_rollout_tape_feedback(self._batch, C.byref(opts), nsteps, int(integrator), float(pscale), C.byref(fb),
+                                                         _abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp),
+                                                         C.byref(st) if st is not None else None), "rmx_rollout_tape_feedback")
         if not stats:
             return qtraj, qdtraj, uapp
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return qtraj, qdtraj, uapp, info
 
     def rollout_feedback_device(self, nsteps, h, uff_ptr, K_ptr, xref_ptr, qtraj_ptr, qdtraj_ptr, uapp_ptr, per_rollout=False, pscale=1.0,
-                                stats=False, integrator=1):
+                                stats=False, integrator=1, ulim=None):
         """rollout_feedback with DEVICE pointers (integers): uff, qtraj, qdtraj, uapp [B][nsteps][nr]; K [nsteps][2nr][nr] and xref
         [nsteps][2nr], or one table per rollout with per_rollout=True.  K_ptr 0 / None: no feedback; xref_ptr 0 / None: zero;
-        qtraj_ptr and qdtraj_ptr 0 / None together: no record; uapp_ptr 0 / None: not stored.  Returns info."""
+        qtraj_ptr and qdtraj_ptr 0 / None together: no record; uapp_ptr 0 / None: not stored.  ulim=(ulo_ptr, uhi_ptr), DEVICE
+        pointers to [nr] doubles, either 0 / None: rmx_rollout_tape_feedback_box_device.  Returns info."""
         if integrator not in (1, 2):
             raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
         fb = _abi.Feedback(uff_ptr or None, K_ptr or None, xref_ptr or None, int(bool(per_rollout)))
@@ -521,10 +544,18 @@ class BatchSim:
         info, st = self._tape_stats(stats)
         self.tape_count += 1
         self._tape_integrator = integrator
-        _abi.check(self._L.rmx_rollout_tape_feedback_device(self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale),
-                                                            C.byref(fb), C.c_void_p(qtraj_ptr or None), C.c_void_p(qdtraj_ptr or None),
-                                                            C.c_void_p(uapp_ptr or None), C.byref(st) if st is not None else None),
-                   "rmx_rollout_tape_feedback_device")
+        if ulim is not None:
+            box = _abi.Box(ulim[0] or None, ulim[1] or None)
+            _abi.check(self._L.rmx_rollout_tape_feedback_box_device(self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale),
+                                                                    C.byref(fb), C.byref(box), C.c_void_p(qtraj_ptr or None),
+                                                                    C.c_void_p(qdtraj_ptr or None), C.c_void_p(uapp_ptr or None),
+                                                                    C.byref(st) if st is not None else None),
+                       "rmx_rollout_tape_feedback_box_device")
+        else:
+            _abi.check(self._L.rmx_rollout_tape_feedback_device(self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale),
+                                                                C.byref(fb), C.c_void_p(qtraj_ptr or None), C.c_void_p(qdtraj_ptr or None),
+                                                                C.c_void_p(uapp_ptr or None), C.byref(st) if st is not None else None),
+                       "rmx_rollout_tape_feedback_device")
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
@@ -731,6 +762,57 @@ class BatchSim:
         gains = _abi.LqrGains(kff.ctypes.data, K.ctypes.data, expected.ctypes.data, status.ctypes.data)
         _abi.check(self._L.rmx_rollout_lqr(self._batch, nsteps, C.byref(cost), C.byref(gains)), "rmx_rollout_lqr")
         return kff, K, expected, status != 0
+
+    def rollout_lqr_box(self, nsteps, lx, lu, Q, R, ubar, ulim, mu=0.0, mu_b=None, max_iter=0):
+        """rmx_rollout_lqr_box: rollout_lqr under the torque limits ulim=(ulo, uhi) ([nr] each or None) - at every step the box QP of
+        control-limited DDP over ulo - ubar_k <= k <= uhi - ubar_k in the place of the solve, ubar [B][nsteps][nr] the nominal
+        applied torques (the uapp of the launch that left the tape).  max_iter caps the QP iterations of a step (0: 64).  Returns
+        (kff, K, expected, status [B] int32, clamped [B][nsteps] uint32): a DOF on a bound has kff = bound - ubar exactly, a zero
+        row of K and its bit set in clamped; status 0, 1 (a pivot not > 0) or 2 (a QP did not terminate) - a rollout with status != 0
+        has zero kff, K, clamped and expected 0.  With no finite bound: rollout_lqr's bits."""
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        lx = np.ascontiguousarray(lx, dtype=np.float64)
+        lu = np.ascontiguousarray(lu, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        ubar = np.ascontiguousarray(ubar, dtype=np.float64)
+        if lx.shape != (B, nsteps, 2 * nr) or lu.shape != (B, nsteps, nr) or ubar.shape != (B, nsteps, nr):
+            raise ValueError("rollout_lqr_box: lx, lu and ubar must have shapes %r, %r and %r, got %r, %r and %r"
+                             % ((B, nsteps, 2 * nr), (B, nsteps, nr), (B, nsteps, nr), lx.shape, lu.shape, ubar.shape))
+        tail = (nsteps, 2 * nr, 2 * nr)
+        if Q.shape not in (tail, (B,) + tail):
+            raise ValueError("rollout_lqr_box: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, Q.shape))
+        if R.shape != (nr, nr):
+            raise ValueError("rollout_lqr_box: R must have shape %r, got %r" % ((nr, nr), R.shape))
+        if mu_b is not None:
+            mu_b = np.ascontiguousarray(mu_b, dtype=np.float64)
+            if mu_b.shape != (B,):
+                raise ValueError("rollout_lqr_box: mu_b must have shape %r, got %r" % ((B,), mu_b.shape))
+        ulo, uhi = self._ulim(ulim, "rollout_lqr_box")
+        kff = np.empty((B, nsteps, nr))
+        K = np.empty((B, nsteps, 2 * nr, nr))
+        expected = np.empty(B)
+        status = np.zeros(B, dtype=np.int32)
+        clamped = np.zeros((B, nsteps), dtype=np.uint32)
+        cost = _abi.LqrCost(lx.ctypes.data, lu.ctypes.data, Q.ctypes.data, R.ctypes.data, int(Q.ndim == 4), float(mu),
+                            None if mu_b is None else mu_b.ctypes.data)
+        box = _abi.Box(None if ulo is None else ulo.ctypes.data, None if uhi is None else uhi.ctypes.data)
+        gains = _abi.LqrGains(kff.ctypes.data, K.ctypes.data, expected.ctypes.data, status.ctypes.data)
+        _abi.check(self._L.rmx_rollout_lqr_box(self._batch, nsteps, C.byref(cost), C.byref(box), ubar.ctypes.data, int(max_iter), C.byref(gains),
+                                               clamped.ctypes.data), "rmx_rollout_lqr_box")
+        return kff, K, expected, status, clamped
+
+    def rollout_lqr_box_device(self, nsteps, lx_ptr, lu_ptr, Q_ptr, R_ptr, ubar_ptr, ulo_ptr, uhi_ptr, kff_ptr, K_ptr, expected_ptr=None,
+                               status_ptr=None, clamped_ptr=None, per_rollout=False, mu=0.0, mu_b_ptr=None, max_iter=0):
+        """rollout_lqr_box with DEVICE pointers (integers): as rollout_lqr_device, and ubar [B][nsteps][nr], ulo, uhi [nr] (0 / None:
+        that side is unbounded), clamped [B][nsteps] uint32 (0 / None: not stored)."""
+        cost = _abi.LqrCost(lx_ptr or None, lu_ptr or None, Q_ptr or None, R_ptr or None, int(bool(per_rollout)), float(mu), mu_b_ptr or None)
+        box = _abi.Box(ulo_ptr or None, uhi_ptr or None)
+        gains = _abi.LqrGains(kff_ptr or None, K_ptr or None, expected_ptr or None, status_ptr or None)
+        _abi.check(self._L.rmx_rollout_lqr_box_device(self._batch, int(nsteps), C.byref(cost), C.byref(box), C.c_void_p(ubar_ptr or None),
+                                                      int(max_iter), C.byref(gains), C.c_void_p(clamped_ptr or None)),
+                   "rmx_rollout_lqr_box_device")
 
     def rollout_lqr_device(self, nsteps, lx_ptr, lu_ptr, Q_ptr, R_ptr, kff_ptr, K_ptr, expected_ptr=None, status_ptr=None, per_rollout=False,
                            mu=0.0, mu_b_ptr=None):

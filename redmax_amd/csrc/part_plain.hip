@@ -105,6 +105,11 @@ void RMX_CAT(launch_lqr_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const 
     const dim3 grid(b->B), block(LQR_THREADS);
     RMX_LAUNCH((k_rollout_lqr<RMX_NP>), grid, block, lds_bytes, b->stream, m->dm, a);
 }
+// rmx_rollout_lqr_box: the same sweep with the box QP in the place of the solve (select_rollout_lqr_box: its LDS)
+void RMX_CAT(launch_lqr_box_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes) {
+    const dim3 grid(b->B), block(LQR_THREADS);
+    RMX_LAUNCH((k_rollout_lqr<RMX_NP, true>), grid, block, lds_bytes, b->stream, m->dm, a);
+}
 #endif
 
 // rmx_rollout_jvp: one wavefront per rollout and chunk of tangent directions

@@ -1629,11 +1629,35 @@ static hipError_t generic_only(const rmx_select::AdjPlan& plan) {
     return plan.kernel == AdjKernel::Generic ? hipSuccess : hipErrorInvalidDeviceFunction;
 }
 
+// The torque limits of rmx_rollout_tape_feedback_box / rmx_rollout_lqr_box: an entry with ulo > uhi or a NaN bound is refused, by the
+// name of its DOF.  The device forms read the 2 nr doubles back for the check; nothing of the batch is touched.
+static int box_refusal(const rmx_batch* b, const rmx_box* box, const bool on_device, const std::string& who) {
+    const int nr = b->m->nr;
+    std::vector<double> lo(nr, -HUGE_VAL), hi(nr, HUGE_VAL);
+    for (int side = 0; side < 2; ++side) {
+        const double* p = side ? box->uhi : box->ulo;
+        double* dst = side ? hi.data() : lo.data();
+        if (!p || !nr) continue;
+        if (on_device) {
+            HIPCHK(hipSetDevice(b->m->device));
+            HIPCHK(hipMemcpy(dst, p, sizeof(double) * nr, hipMemcpyDeviceToHost));
+        } else {
+            std::copy(p, p + nr, dst);
+        }
+    }
+    for (int i = 0; i < nr; ++i) {
+        if (std::isnan(lo[i]) || std::isnan(hi[i])) return fail(RMX_E_INVALID, who + ": a bound of DOF " + std::to_string(i) + " is NaN");
+        if (lo[i] > hi[i]) return fail(RMX_E_INVALID, who + ": ulo > uhi at DOF " + std::to_string(i));
+    }
+    return RMX_OK;
+}
+
 // fb (rmx_rollout_tape_feedback): u is fb->uff, the sweep is the ADJ_FB kernel and uapp (or null) takes the applied torques.  The host
 // form stages K, xref and uapp through a device allocation of its own, freed before the return; the tape's workspace is the same.
+// box (rmx_rollout_tape_feedback_box, with fb): the same kernel clamps the torque into the limits, staged with the gain tables.
 static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                              double* qdtraj, rmx_stats* stats, const bool on_device, const int integ = INTEG_BDF1,
-                             const rmx_feedback* fb = nullptr, double* uapp = nullptr) {
+                             const rmx_feedback* fb = nullptr, double* uapp = nullptr, const rmx_box* box = nullptr) {
     if (!b || !u) return fail(RMX_E_INVALID, "rmx_rollout_tape: null argument");
     if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
     rmx_model* m = b->m;
@@ -1647,13 +1671,16 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
     if (rc) return rc;
     const rmx_tape::Layout t = tape_layout(b, nsteps, integ);
     if (3 * t.bytes_hist > ((size_t)200 << 30)) return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
-    enum { F_K, F_X, F_UAPP };
+    if (box && (rc = box_refusal(b, box, on_device, "rmx_rollout_tape_feedback_box"))) return rc;
+    enum { F_K, F_X, F_UAPP, F_ULO, F_UHI };
     Staging fbst(on_device);
     if (fb) {
         const size_t row = (fb->per_rollout ? (size_t)b->B : 1) * nsteps * 2 * m->nr * sizeof(double);
         fbst.add(row * m->nr, fb->K, nullptr);
         fbst.add(row, fb->xref, nullptr);
         fbst.add(t.bytes_traj, nullptr, uapp);
+        fbst.add(m->nr * sizeof(double), box ? box->ulo : nullptr, nullptr);
+        fbst.add(m->nr * sizeof(double), box ? box->uhi : nullptr, nullptr);
         if (fbst.plan.total > 0)      // (ahead of everything that ends the present tape)
             if ((rc = fbst.allocate("rmx_rollout_tape_feedback", "the gain tables"))) return rc;
     }
@@ -1673,6 +1700,8 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
             a.fbx = fbst.dev(F_X);
             a.fb_stride = fb->per_rollout ? (size_t)nsteps : 0;
             a.uapp = fbst.dev(F_UAPP);
+            a.ulo = fbst.dev(F_ULO);
+            a.uhi = fbst.dev(F_UHI);
         }
         a.B = b->B; a.nsteps = nsteps; a.pscale = pscale;
         a.q = b->q; a.qd = b->qd; a.qp = b->qp; a.qdp = b->qdp;
@@ -1691,7 +1720,7 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
             if (fb) {
                 const rmx_select::AdjPlan plan = rmx_select::select_rollout_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
                 if (generic_only(plan) == hipSuccess) DISPATCH_NP(m->NP, launch_rollout_feedback, m, b, integ, o, a)
-                b->last_kernel = rmx_select::label_rollout_feedback(integ);
+                b->last_kernel = box ? rmx_select::label_rollout_feedback_box(integ) : rmx_select::label_rollout_feedback(integ);
                 return generic_only(plan);
             }
             const rmx_select::AdjPlan plan = tape_plan(b, integ);
@@ -1928,10 +1957,15 @@ static int rollout_jvp_impl(rmx_batch* b, int nsteps, int ntan, const double* tu
 // rmx_rollout_lqr: the Riccati sweep of iLQR over the BDF1 tape, one workgroup per rollout (rmx_lqr.h); the per-slot sensitivities
 // are formed inside the sweep, nothing proportional to B N nr^2 is allocated.  The host form stages through an allocation of its
 // own, as rmx_rollout_linearize does.
-static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out, const bool on_device) {
-    const std::string who = "rmx_rollout_lqr";
-    if (!b || !cost || !out || !cost->lx || !cost->lu || !cost->Q || !cost->R || !out->kff || !out->K)
+// boxed (rmx_rollout_lqr_box): the BOX instantiation of the same kernel; the limits, ubar and clamped join the same staging.
+static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out, const bool on_device,
+                            const bool boxed = false, const rmx_box* box = nullptr, const double* ubar = nullptr, int max_iter = 0,
+                            unsigned* clamped = nullptr) {
+    const std::string who = boxed ? "rmx_rollout_lqr_box" : "rmx_rollout_lqr";
+    if (!b || !cost || !out || !cost->lx || !cost->lu || !cost->Q || !cost->R || !out->kff || !out->K || (boxed && (!box || !ubar)))
         return fail(RMX_E_INVALID, who + ": null argument");
+    if (boxed && max_iter < 0) return fail(RMX_E_INVALID, who + ": max_iter must be >= 0 (0: the default of " +
+                                                              std::to_string(rmx_select::LQR_BOX_MAX_ITER) + ")");
     if (cost->per_rollout != 0 && cost->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
     if (!(cost->mu >= 0.0) || !std::isfinite(cost->mu)) return fail(RMX_E_INVALID, who + ": mu must be finite and >= 0");
     TapeView v;
@@ -1939,7 +1973,7 @@ static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, 
     if (v.integ != INTEG_BDF1)
         return fail(RMX_E_INVALID, who + ": needs a BDF1 tape (the tape on this batch is BDF2: its augmented state is not built)");
     rmx_model* m = b->m;
-    const rmx_select::LqrPlan plan = rmx_select::select_rollout_lqr(step_traits(m), m->nr);
+    const rmx_select::LqrPlan plan = boxed ? rmx_select::select_rollout_lqr_box(step_traits(m), m->nr) : rmx_select::select_rollout_lqr(step_traits(m), m->nr);
     if (plan.kernel == rmx_select::LqrKernel::RefusedNr)
         return fail(RMX_E_INVALID, who + ": nr > " + std::to_string(rmx_select::LQR_MAX_NR) + " (the model has nr = " + std::to_string(m->nr) +
                                        "; the LDS-resident sweep stops at " + std::to_string(rmx_select::LQR_MAX_NR) + " reduced DOFs)");
@@ -1948,7 +1982,9 @@ static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, 
                                        " for nr = " + std::to_string(m->nr) + "; the LDS-resident sweep stops there)");
     const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
     const size_t bytes_q = (cost->per_rollout ? B : 1) * N * 4 * nr * nr * dbl;
-    enum { S_KFF, S_K, S_EXP, S_ST, S_LX, S_LU, S_Q, S_R, S_MUB };      // the outputs first
+    if (boxed)
+        if (int rc = box_refusal(b, box, on_device, who)) return rc;
+    enum { S_KFF, S_K, S_EXP, S_ST, S_LX, S_LU, S_Q, S_R, S_MUB, S_CL, S_ULO, S_UHI, S_UBAR };      // the outputs first (clamped: with the box)
     Staging st(on_device);
     st.add(B * N * nr * dbl, nullptr, out->kff);
     st.add(B * N * 2 * nr * nr * dbl, nullptr, out->K);
@@ -1959,6 +1995,10 @@ static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, 
     st.add(bytes_q, cost->Q, nullptr);
     st.add(nr * nr * dbl, cost->R, nullptr);
     st.add(B * dbl, cost->mu_b, nullptr);
+    st.add(B * N * sizeof(unsigned), nullptr, clamped);
+    st.add(nr * dbl, boxed ? box->ulo : nullptr, nullptr);
+    st.add(nr * dbl, boxed ? box->uhi : nullptr, nullptr);
+    st.add(B * N * nr * dbl, ubar, nullptr);
     if (int rc = st.allocate(who, "the staging of the cost and the gains")) return rc;
     LqrArgs a{};
     a.nsteps = nsteps; a.h = v.h; a.pscale = v.pscale; a.mu = cost->mu;
@@ -1966,14 +2006,28 @@ static int rollout_lqr_impl(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, 
     a.lx = st.dev(S_LX); a.lu = st.dev(S_LU); a.Q = st.dev(S_Q); a.R = st.dev(S_R); a.mu_b = st.dev(S_MUB);
     a.q_stride = cost->per_rollout ? N * 4 * nr * nr : 0;
     a.kff = st.dev(S_KFF); a.K = st.dev(S_K); a.expected = st.dev(S_EXP); a.status = (int*)st.at[S_ST];
+    a.ulo = st.dev(S_ULO); a.uhi = st.dev(S_UHI); a.ubar = st.dev(S_UBAR); a.clamped = (unsigned*)st.at[S_CL];
+    a.max_iter = max_iter > 0 ? max_iter : rmx_select::LQR_BOX_MAX_ITER;
     if (!nr) {      // (no reduced DOF: no gains to compute, and no kernel time to take)
         hipError_t e = hipSuccess;
         if (a.expected) e = hipMemsetAsync(a.expected, 0, B * dbl, b->stream);
         if (e == hipSuccess && a.status) e = hipMemsetAsync(a.status, 0, B * sizeof(int), b->stream);
+        if (e == hipSuccess && a.clamped) e = hipMemsetAsync(a.clamped, 0, B * N * sizeof(unsigned), b->stream);
         return tape_call_end(b, st.copy_out(b, e), st, who);
     }
     hipError_t e = st.copy_in(b, hipSuccess);
     e = timed_launch(b, e, [&] {
+        if (boxed) {
+            b->last_kernel = rmx_select::label_rollout_lqr_box();
+            switch (m->NP) {
+                case 4: launch_lqr_box_4(m, b, a, plan.lds_bytes); break;
+                case 8: launch_lqr_box_8(m, b, a, plan.lds_bytes); break;
+                case 16: launch_lqr_box_16(m, b, a, plan.lds_bytes); break;
+                case 32: launch_lqr_box_32(m, b, a, plan.lds_bytes); break;
+                default: return hipErrorInvalidDeviceFunction;
+            }
+            return hipSuccess;
+        }
         switch (m->NP) {
             case 4: launch_lqr_4(m, b, a, plan.lds_bytes); break;
             case 8: launch_lqr_8(m, b, a, plan.lds_bytes); break;
@@ -1991,6 +2045,14 @@ extern "C" int rmx_rollout_lqr(rmx_batch* b, int nsteps, const rmx_lqr_cost* cos
 extern "C" int rmx_rollout_lqr_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_lqr_gains* out) {
     return rollout_lqr_impl(b, nsteps, cost, out, true);
 }
+extern "C" int rmx_rollout_lqr_box(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_box* box, const double* ubar, int max_iter,
+                                   const rmx_lqr_gains* out, unsigned* clamped) {
+    return rollout_lqr_impl(b, nsteps, cost, out, false, true, box, ubar, max_iter, clamped);
+}
+extern "C" int rmx_rollout_lqr_box_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_box* box, const double* d_ubar,
+                                          int max_iter, const rmx_lqr_gains* out, unsigned* d_clamped) {
+    return rollout_lqr_impl(b, nsteps, cost, out, true, true, box, d_ubar, max_iter, d_clamped);
+}
 
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                 double* qdtraj, rmx_stats* stats) {
@@ -2001,11 +2063,23 @@ extern "C" int rmx_rollout_tape_device(rmx_batch* b, const rmx_opts* opts, int n
     return rollout_tape_impl(b, opts, nsteps, pscale, d_u, d_qtraj, d_qdtraj, stats, true);
 }
 static int rollout_feedback_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale, const rmx_feedback* fb,
-                                 double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats, const bool on_device) {
-    if (!b || !fb || !fb->uff) return fail(RMX_E_INVALID, "rmx_rollout_tape_feedback: null argument");
-    if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, "rmx_rollout_tape_feedback: integrator must be 1 (BDF1) or 2 (BDF2)");
-    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, "rmx_rollout_tape_feedback: per_rollout must be 0 or 1");
-    return rollout_tape_impl(b, opts, nsteps, pscale, fb->uff, qtraj, qdtraj, stats, on_device, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, fb, uapp);
+                                 double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats, const bool on_device,
+                                 const rmx_box* box = nullptr, const bool boxed = false) {
+    const std::string who = boxed ? "rmx_rollout_tape_feedback_box" : "rmx_rollout_tape_feedback";
+    if (!b || !fb || !fb->uff || (boxed && !box)) return fail(RMX_E_INVALID, who + ": null argument");
+    if (integrator != 1 && integrator != 2) return fail(RMX_E_INVALID, who + ": integrator must be 1 (BDF1) or 2 (BDF2)");
+    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    return rollout_tape_impl(b, opts, nsteps, pscale, fb->uff, qtraj, qdtraj, stats, on_device, integrator == 1 ? INTEG_BDF1 : INTEG_BDF2, fb, uapp,
+                             box);
+}
+extern "C" int rmx_rollout_tape_feedback_box(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale, const rmx_feedback* fb,
+                                             const rmx_box* box, double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats) {
+    return rollout_feedback_impl(b, opts, nsteps, integrator, pscale, fb, qtraj, qdtraj, uapp, stats, false, box, true);
+}
+extern "C" int rmx_rollout_tape_feedback_box_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
+                                                    const rmx_feedback* fb, const rmx_box* box, double* d_qtraj, double* d_qdtraj,
+                                                    double* d_uapp, rmx_stats* stats) {
+    return rollout_feedback_impl(b, opts, nsteps, integrator, pscale, fb, d_qtraj, d_qdtraj, d_uapp, stats, true, box, true);
 }
 extern "C" int rmx_rollout_tape_feedback(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale, const rmx_feedback* fb,
                                          double* qtraj, double* qdtraj, double* uapp, rmx_stats* stats) {

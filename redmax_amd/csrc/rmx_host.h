@@ -89,6 +89,8 @@ struct AdjArgs {
     double* dxref;            // [B][nsteps][2 nr] one row per rollout (out), or null
     const double *fq0, *fqd0; // [B][nr] the state the tape started from (its parts Q0, QD0 of rmx_tape.h): read for dK alone
     const double *fqt, *fqdt; // [B][nsteps][nr] the tape's trajectory (parts QT, QDT): read for dK alone
+    // rmx_rollout_tape_feedback_box (the ADJ_FB instantiations of the forward kernel alone read these)
+    const double *ulo, *uhi;  // [nr] the torque limits the applied torque is clamped into, or null: that side is skipped
 };
 
 // rmx_rollout_vjp_params (rmx_params.h): one wavefront per rollout walks the slots of its tape
@@ -142,6 +144,11 @@ struct LqrArgs {
     double *kff, *K;          // [B][nsteps][nr], [B][nsteps][2 nr nr] (entry j*nr + i of a row: du_i/dx_j)
     double* expected;         // [B] or null
     int* status;              // [B] or null
+    // rmx_rollout_lqr_box (the BOX instantiations alone read these)
+    const double *ulo, *uhi;  // [nr] the torque limits, or null: that side is unbounded
+    const double* ubar;       // [B][nsteps][nr] the nominal applied torques: the QP of step k is over ulo - ubar_k <= x <= uhi - ubar_k
+    int max_iter;             // >= 1: the cap on the QP iterations of a step
+    unsigned* clamped;        // [B][nsteps] or null: bit i of row k-1 is set where DOF i of step k ended on a bound
 };
 
 struct rmx_model {
@@ -268,6 +275,11 @@ void launch_lqr_4(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size
 void launch_lqr_8(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
 void launch_lqr_16(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
 void launch_lqr_32(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+// ... and its box-constrained form (k_rollout_lqr<NP, true>; select_rollout_lqr_box)
+void launch_lqr_box_4(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+void launch_lqr_box_8(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+void launch_lqr_box_16(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+void launch_lqr_box_32(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
 RMX_DECLARE_LAUNCHERS(4)
 RMX_DECLARE_LAUNCHERS(8)
 RMX_DECLARE_LAUNCHERS(16)

@@ -892,6 +892,16 @@ __global__ void __launch_bounds__(HELP ? 128 : 64) k_adjoint_fwd(const DevModel 
                     us = feedback_torque<NP>(us, a.fbK + row * ((size_t)2 * M.nr * M.nr), a.fbx ? a.fbx + row * ((size_t)2 * M.nr) : nullptr,
                                              M.nr, n, id, q, qd);
                 }
+                // rmx_rollout_tape_feedback_box: the actuator saturates - behind the feedback sum, and with a null K too.  The tests
+                // on the pointers are wave-uniform; two selects on the lane's own value (a NaN torque stays one)
+                if (a.ulo && id >= 0) {
+                    const double lo = a.ulo[id];
+                    us = us < lo ? lo : us;
+                }
+                if (a.uhi && id >= 0) {
+                    const double hi = a.uhi[id];
+                    us = us > hi ? hi : us;
+                }
                 if (a.uapp && id >= 0) a.uapp[((size_t)traj * a.nsteps + (s - 1)) * M.nr + id] = us;
             }
             fs.tau_add = a.pscale * us;

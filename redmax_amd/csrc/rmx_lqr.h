@@ -32,6 +32,15 @@
 //      13,14  Kq, Kv             the right-hand sides, solved in place
 //      15,16  Quu0, LDL'(Quu0 + mu I)
 // and 8 vectors of NP doubles behind them (p, r, the next p, r, Qu, k, Quu0 k, g).  Nothing is reused across steps but Vxx, Vx.
+//
+// BOX (k_rollout_lqr<NP, true>, rmx_rollout_lqr_box): the solve of a step becomes the box QP of control-limited DDP (Tassa, Mansard,
+// Todorov 2014) over lo_k = ulo - ubar_k <= x <= hi_k = uhi - ubar_k - projected Newton steps, each one LDL' of Hq = Quu0 + mu I in
+// which the rows and columns of the clamped set are the identity's (selects, no compaction), with an Armijo search along the projected
+// arc - and the final solve for [k, K] is the unconstrained kernel's code on the matrix masked by the final set: k_c = x_c, K_c = 0.
+// With an empty set every select is the identity, so infinite bounds return rmx_rollout_lqr's bits by construction.  The set is a
+// 32-bit word every thread computes from the same LDS values (nr <= 32), so the loop's control flow is uniform without a broadcast.
+// 8 more vectors of NP doubles (lo, hi, x, grad, the trial point, the direction, Hq y, the right-hand column): 16 in all, 147 712
+// bytes at NP = 32 with the 17 blocks.  BOX = false compiles to the kernel as it was: every addition sits under if constexpr.
 #pragma once
 #include "rmx_linearize.h"      /* lin_load_*, lin_eliminate; rmx_host.h: LqrArgs */
 
@@ -101,7 +110,47 @@ __device__ __forceinline__ void lqr_store(double* __restrict__ blk, const double
     }
 }
 
-template <int NP>
+// ---- BOX (rmx_rollout_lqr_box): the pieces of the box QP of a step.  Hq = Quu0 + mu I is read off Quu0, never stored.
+template <int LD>
+__device__ __forceinline__ double lqr_hq(const double* Quu, const double mu, const int i, const int j) {
+    const double v = Quu[j * LD + i];
+    return i == j ? v + mu : v;
+}
+// val(y) = Qu'y + 1/2 y'Hq y, the same bits in every thread: Hq y row by row into hx, then one sum each
+template <int LD>
+__device__ __forceinline__ double lqr_box_val(const double* Quu, const double mu, const double* Qu, const double* y, double* hx, const int d,
+                                              const int tid) {
+    __syncthreads();      // (y is written; the last sum over hx is over)
+    if (tid < d) {
+        double t = 0.0;
+        for (int j = 0; j < d; ++j) t = fma(lqr_hq<LD>(Quu, mu, tid, j), y[j], t);
+        hx[tid] = t;
+    }
+    __syncthreads();
+    double v = 0.0;
+    for (int i = 0; i < d; ++i) v = fma(y[i], Qu[i] + 0.5 * hx[i], v);
+    return v;
+}
+// Hq_fc x_c of row i: the columns of the set alone (a free row has no diagonal term in it)
+template <int LD>
+__device__ __forceinline__ double lqr_box_fc(const double* Quu, const double* x, const unsigned cset, const int i, const int d) {
+    double t = 0.0;
+    for (int j = 0; j < d; ++j)
+        if ((cset >> j) & 1u) t = fma(Quu[j * LD + i], x[j], t);
+    return t;
+}
+// Lc = Hq with every row and column of the set replaced by the identity's - selects, so that an empty set writes Hq's bits
+template <int LD>
+__device__ __forceinline__ void lqr_box_mask(double* Lc, const double* Quu, const double mu, const unsigned cset, const int d, const int tid) {
+    for (int e = tid; e < d * d; e += LQR_THREADS) {
+        const int j = e / d, i = e - j * d, o = j * LD + i;
+        const bool m = (((cset >> i) | (cset >> j)) & 1u) != 0;
+        const double v = Quu[o];
+        Lc[o] = m ? (i == j ? 1.0 : 0.0) : (i == j ? v + mu : v);
+    }
+}
+
+template <int NP, bool BOX = false>
 __global__ void __launch_bounds__(LQR_THREADS) k_rollout_lqr(const DevModel M, const LqrArgs a) {
     constexpr int LD = NP + 1, BLK = LD * NP;
     extern __shared__ double lqr_lds[];
@@ -130,6 +179,15 @@ __global__ void __launch_bounds__(LQR_THREADS) k_rollout_lqr(const DevModel M, c
     double* const vk = vQu + NP;
     double* const vqk = vk + NP;
     double* const vg = vqk + NP;
+    // BOX: the vectors of the QP (lo_k, hi_k, the iterate, its gradient, the trial point, the direction, Hq y, the right-hand column)
+    double* const blo = vg + NP;
+    double* const bhi = blo + NP;
+    double* const bx = bhi + NP;
+    double* const bgrad = bx + NP;
+    double* const bxt = bgrad + NP;
+    double* const bs = bxt + NP;
+    double* const bhx = bs + NP;
+    double* const brhs = bhx + NP;
 
     const int tid = threadIdx.x, n = M.n, d = M.nr, traj = blockIdx.x, N = a.nsteps;
     const int d2 = 2 * d, dd = d * d;
@@ -158,6 +216,7 @@ __global__ void __launch_bounds__(LQR_THREADS) k_rollout_lqr(const DevModel M, c
     }
     double expected = 0.0;      // (thread 0's)
     bool bad = false;           // (uniform over the workgroup)
+    bool slow = false;          // BOX: bad because a QP ran out of iterations or of line search (status 2), not because of a pivot
 
 #pragma unroll 1
     for (int s = N - 1; s >= 0; --s) {
@@ -243,6 +302,122 @@ __global__ void __launch_bounds__(LQR_THREADS) k_rollout_lqr(const DevModel M, c
             Kv[o] = -Quv[o];
         }
         if (tid < d) vk[tid] = -vQu[tid];
+        unsigned cset = 0;      // BOX: the DOFs of this step that end on a bound (uniform over the workgroup)
+        if constexpr (BOX) {
+            // ---- the box QP  min Qu'x + 1/2 x'Hq x,  lo <= x <= hi,  Hq = Quu0 + mu I  (projected Newton; the header's algorithm).
+            // Every decision is taken by every thread from the same LDS values: the control flow is uniform without a broadcast.
+            const double inf = __builtin_huge_val();
+            if (tid < d) {
+                const double ub = a.ubar[((size_t)traj * N + s) * d + tid];
+                const double lo = a.ulo ? a.ulo[tid] - ub : -inf, hi = a.uhi ? a.uhi[tid] - ub : inf;
+                blo[tid] = lo;
+                bhi[tid] = hi;
+                bx[tid] = 0.0 < lo ? lo : (0.0 > hi ? hi : 0.0);
+            }
+            const unsigned all = d >= 32 ? 0xffffffffu : ((1u << d) - 1u);
+            unsigned prev = 0;
+            bool have_prev = false, full = false, done = false;
+            for (int it = 0; it < a.max_iter; ++it) {
+                __syncthreads();      // (x of the iteration before; the first time vQu, Quu, lo, hi, x)
+                if (tid < d) {
+                    double t = 0.0;
+                    for (int j = 0; j < d; ++j) t = fma(lqr_hq<LD>(Quu, mu, tid, j), bx[j], t);
+                    bgrad[tid] = vQu[tid] + t;
+                }
+                __syncthreads();
+                cset = 0;
+                for (int i = 0; i < d; ++i) {
+                    const double xi = bx[i], gi = bgrad[i];
+                    if ((xi == blo[i] && gi > 0.0) || (xi == bhi[i] && gi < 0.0)) cset |= 1u << i;
+                }
+                if ((have_prev && cset == prev && full) || cset == all) {
+                    done = true;
+                    break;
+                }
+                // Hq with the rows and columns of the set replaced by the identity's, and -(Qu_f + Hq_fc x_c) over zeros
+                lqr_box_mask<LD>(Lc, Quu, mu, cset, d, tid);
+                if (tid < d) brhs[tid] = ((cset >> tid) & 1u) ? 0.0 : -(vQu[tid] + lqr_box_fc<LD>(Quu, bx, cset, tid, d));
+                // LDL' as below, one right-hand column: lane i of wavefront 0 holds its row of the forward substitution
+                for (int k = 0; k < d; ++k) {
+                    __syncthreads();
+                    const double piv = Lc[k * LD + k];
+                    if (!(piv > 0.0)) {
+                        bad = true;
+                        break;
+                    }
+                    const double rp = 1.0 / piv;
+                    if (tid < 64) {
+                        if (tid > k && tid < d) brhs[tid] = fma(-Lc[k * LD + tid], brhs[k] * rp, brhs[tid]);
+                    } else if (tid >= 128) {
+                        const int u = tid - 128, i = u & 31;
+                        if (i > k && i < d) {
+                            const double cik = Lc[k * LD + i];
+                            for (int j = k + 1 + (u >> 5); j <= i; j += 4) Lc[j * LD + i] = fma(-cik, Lc[k * LD + j] * rp, Lc[j * LD + i]);
+                        }
+                    }
+                }
+                if (bad) break;
+                __syncthreads();
+                // z = y / d and x = L'^-1 z in the registers of wavefront 0 (lane r its row), then the direction s = xn - x
+                if (tid < 64) {
+                    const int r = tid < d ? tid : 0;
+                    const double pr = Lc[r * LD + r];
+                    double y = brhs[r] / pr;
+                    for (int i = d - 1; i > 0; --i) {
+                        const double xi = __shfl(y, i);
+                        if (tid < i) y = fma(-(Lc[r * LD + i] / pr), xi, y);
+                    }
+                    if (tid < d) bs[tid] = ((cset >> tid) & 1u) ? 0.0 : y - bx[tid];
+                }
+                __syncthreads();
+                double sg = 0.0;
+                for (int i = 0; i < d; ++i) sg = fma(bs[i], bgrad[i], sg);
+                if (!(sg < 0.0)) {      // (x already minimises on this face)
+                    done = true;
+                    break;
+                }
+                const double vold = lqr_box_val<LD>(Quu, mu, vQu, bx, bhx, d, tid);
+                double step = 1.0;
+                for (;;) {      // Armijo on the projected arc
+                    __syncthreads();      // (the trial point of the round before has been read)
+                    if (tid < d) {
+                        const double t = fma(step, bs[tid], bx[tid]);
+                        bxt[tid] = t < blo[tid] ? blo[tid] : (t > bhi[tid] ? bhi[tid] : t);
+                    }
+                    const double vnew = lqr_box_val<LD>(Quu, mu, vQu, bxt, bhx, d, tid);
+                    if (!((vnew - vold) / (step * sg) < 0.1)) break;
+                    step *= 0.6;
+                    if (step < 1e-20) {
+                        bad = slow = true;
+                        break;
+                    }
+                }
+                if (bad) break;
+                bool moved = false;
+                for (int i = 0; i < d; ++i) moved = moved || bxt[i] != fma(step, bs[i], bx[i]);
+                full = step == 1.0 && !moved;
+                __syncthreads();
+                if (tid < d) bx[tid] = bxt[tid];
+                prev = cset;
+                have_prev = true;
+            }
+            if (!done && !bad) bad = slow = true;      // (the cap on the iterations)
+            if (bad) break;
+            // the final solve is the code below on the masked matrix: k_c = x_c and K_c = 0 are written behind it, and with an empty
+            // set every select here is the identity - rmx_rollout_lqr's bits
+            __syncthreads();
+            lqr_box_mask<LD>(Lc, Quu, mu, cset, d, tid);
+            if (cset) {
+                for (int e = tid; e < dd; e += LQR_THREADS) {
+                    const int j = e / d, i = e - j * d, o = j * LD + i;
+                    if ((cset >> i) & 1u) {
+                        Kq[o] = 0.0;
+                        Kv[o] = 0.0;
+                    }
+                }
+                if (tid < d) vk[tid] = ((cset >> tid) & 1u) ? 0.0 : -(vQu[tid] + lqr_box_fc<LD>(Quu, bx, cset, tid, d));
+            }
+        }
         // ---- LDL' of Quu0 + mu I without pivoting, in the lower triangle of Lc: column k keeps L(i, k) d_k below its pivot d_k.
         // The forward substitution rides along: wavefronts 0 and 1 hold one right-hand column per thread (2d + 1 of them, the same
         // thread from here to the end of the solve, so the columns need no barrier of their own), wavefronts 2 and 3 update the
@@ -286,6 +461,23 @@ __global__ void __launch_bounds__(LQR_THREADS) k_rollout_lqr(const DevModel M, c
             }
         }
         __syncthreads();
+        if constexpr (BOX) {      // k_c = x_c (lo or hi exactly), K_c = 0, k_f into the box; the mask of the step leaves
+            if (cset) {
+                for (int e = tid; e < dd; e += LQR_THREADS) {
+                    const int j = e / d, i = e - j * d, o = j * LD + i;
+                    if ((cset >> i) & 1u) {
+                        Kq[o] = 0.0;
+                        Kv[o] = 0.0;
+                    }
+                }
+            }
+            if (tid < d) {
+                const double v = vk[tid];
+                vk[tid] = ((cset >> tid) & 1u) ? bx[tid] : (v < blo[tid] ? blo[tid] : (v > bhi[tid] ? bhi[tid] : v));
+            }
+            if (tid == 0 && a.clamped) a.clamped[(size_t)traj * N + s] = cset;
+            __syncthreads();
+        }
         // G = Quu0 K + Qux (over T11, T12), Quu0 k and g = Quu0 k + Qu; the gains leave
         lqr_mm2<LD, false, false>(T11, Quq, Quu, Kq, 1.0, nullptr, nullptr, 0.0, d, tid);
         lqr_mm2<LD, false, false>(T12, Quv, Quu, Kv, 1.0, nullptr, nullptr, 0.0, d, tid);
@@ -348,9 +540,17 @@ __global__ void __launch_bounds__(LQR_THREADS) k_rollout_lqr(const DevModel M, c
     if (bad) {      // not positive definite: the rollout takes no step - every row zero, the rows of later steps included
         for (size_t e = tid; e < (size_t)N * d; e += LQR_THREADS) kffo[e] = 0.0;
         for (size_t e = tid; e < (size_t)N * d2 * d; e += LQR_THREADS) Ko[e] = 0.0;
+        if constexpr (BOX) {
+            if (a.clamped)
+                for (int e = tid; e < N; e += LQR_THREADS) a.clamped[(size_t)traj * N + e] = 0u;
+        }
     }
     if (tid == 0) {
         if (a.expected) a.expected[traj] = bad ? 0.0 : expected;
-        if (a.status) a.status[traj] = bad ? 1 : 0;
+        if constexpr (BOX) {
+            if (a.status) a.status[traj] = bad ? (slow ? 2 : 1) : 0;
+        } else {
+            if (a.status) a.status[traj] = bad ? 1 : 0;
+        }
     }
 }

@@ -214,4 +214,19 @@ inline LqrPlan select_rollout_lqr(const StepTraits& t, const int nr) {
     return p;
 }
 
+// The box-constrained sweep (rmx_rollout_lqr_box): k_rollout_lqr<NP, true>, the same workgroup and blocks with the vectors of the QP
+// behind them (lo, hi, x, grad, the trial point, the direction, Hq y, the right-hand column): 17 blocks and 16 vectors, 147 712 bytes
+// at NP = 32 of the CU's 163 840.  The sizes it exists for, and so its refusals, are select_rollout_lqr's.
+constexpr int LQR_BOX_VECTORS = LQR_VECTORS + 8, LQR_BOX_MAX_ITER = 64;      // (the default cap on the QP iterations of a step)
+inline size_t lqr_box_lds_bytes(const int NP) { return sizeof(double) * ((size_t)LQR_BLOCKS * (NP + 1) * NP + (size_t)LQR_BOX_VECTORS * NP); }
+inline LqrPlan select_rollout_lqr_box(const StepTraits& t, const int nr) {
+    LqrPlan p = select_rollout_lqr(t, nr);
+    if (p.kernel == LqrKernel::Lds) p.lds_bytes = lqr_box_lds_bytes(t.NP);
+    return p;
+}
+inline const char* label_rollout_lqr_box() { return "k_rollout_lqr<box>"; }      // what rmx_last_step_kernel reports after rmx_rollout_lqr_box
+inline const char* label_rollout_feedback_box(const int integ) {      // ... after rmx_rollout_tape_feedback_box
+    return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback,box>" : "k_adjoint_fwd<bdf1,tape,feedback,box>";
+}
+
 }      // namespace rmx_select

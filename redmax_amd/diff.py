@@ -273,7 +273,7 @@ def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     return qtraj, qdtraj, A, Bm
 
 
-def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0, check=True, integrator=1, status=False):
+def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0, check=True, integrator=1, status=False, ulim=None):
     """The controlled rollout of ``rollout`` in CLOSED LOOP: (qtraj, qdtraj, uapp), with the torque of step k
 
         uapp[b, k-1] = uff[b, k-1] + K[.., k-1].T @ (x - xref[.., k-1]),      x = (q, qdot) at the START of step k
@@ -288,7 +288,10 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     (dL/dK, dL/dxref, the closed-loop dL/duff) come from ``rollout_closed_loop``, the same rollout as an autograd function.  Arguments, checks and words are rollout's (uff in the place of u).  The call replaces the sim's tape, as
     rollout does, and leaves the sim at the end of the rollout.  status=True appends the rollouts' status words (a bool tensor [B] on
     the sim's device: did a Newton solve diverge, hit its iteration limit or meet a NaN) - for a caller that passes check=False and
-    sorts the rollouts itself, as a line search does."""
+    sorts the rollouts itself, as a line search does.
+    ulim=(ulo, uhi), float64 tensors [nr] on the sim's device or None each: the applied torque is clamped into the limits behind the
+    feedback sum, uapp = min(max(uff + K'(x - xref), ulo), uhi), with K None too (rmx_rollout_tape_feedback_box_device).
+    ``rollout_closed_loop`` does not know about the clamp: gradients through a saturated feedback law are not formed."""
     import torch
     if integrator not in (1, 2):
         raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
@@ -311,6 +314,7 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     if len(set(per)) > 1:
         raise ValueError("rollout: K and xref must both be shared by the batch or both hold one table per rollout")
     h = float(sim.opts.h if h is None else h)
+    lim = None if ulim is None else _check_ulim("rollout", ulim, nr, dev)
     q0c, qd0c, uc = q0.detach().contiguous(), qdot0.detach().contiguous(), uff.detach().contiguous()
     Kc = None if K is None else K.detach().contiguous()
     xc = None if xref is None else xref.detach().contiguous()
@@ -321,13 +325,73 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
     info = sim.rollout_feedback_device(nsteps, h, uc.data_ptr(), 0 if Kc is None else Kc.data_ptr(), 0 if xc is None else xc.data_ptr(),
                                        qtraj.data_ptr(), qdtraj.data_ptr(), uapp.data_ptr(), per_rollout=bool(per and per[0]),
-                                       pscale=float(pscale), stats=bool(check or status), integrator=integrator)
+                                       pscale=float(pscale), stats=bool(check or status), integrator=integrator,
+                                       ulim=None if lim is None else tuple(0 if t is None else t.data_ptr() for t in lim))
     if check and (info["status"] & _BAD_STATUS).any():
         bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
         raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
     if status:
         return qtraj, qdtraj, uapp, torch.as_tensor((info["status"] & _BAD_STATUS) != 0, device=dev)
     return qtraj, qdtraj, uapp
+
+
+def _check_ulim(who, ulim, nr, dev):
+    """(ulo, uhi) of a ``ulim`` argument as contiguous tensors or None each."""
+    import torch
+    if not isinstance(ulim, (tuple, list)) or len(ulim) != 2:
+        raise ValueError("%s: ulim must be a pair (ulo, uhi), either may be None" % who)
+    out = []
+    for name, t in zip(("ulo", "uhi"), ulim):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != (nr,):
+                raise ValueError("%s: %s must be a float64 tensor of shape (%d,) on %s" % (who, name, nr, dev))
+            t = t.detach().contiguous()
+        out.append(t)
+    return out
+
+
+def lqr_backward_box(sim, lx, lu, Q, R, ubar, ulim, mu=0.0, max_iter=0):
+    """``lqr_backward`` under the torque limits ulim=(ulo, uhi) (rmx_rollout_lqr_box_device, include/redmax_hip.h): control-limited
+    DDP - at every step the box QP over ulo - ubar_k <= k <= uhi - ubar_k in the place of the solve, the feedback rows of the
+    torques on a bound zero.  ubar [B][N][nr]: the nominal applied torques (the uapp of the launch that left the tape); ulo, uhi:
+    float64 tensors [nr] on the sim's device or None; max_iter: the cap on the QP iterations of a step (0: 64); the rest is
+    lqr_backward's.  Returns (kff, K, expected, status [B] int32, clamped [B][N] int32 holding the bit masks): status 0, 1 (a pivot
+    not > 0) or 2 (a QP did not terminate); a rollout with status != 0 has zero gains and expected 0.  One box for all steps and
+    rollouts; BDF1 tapes only."""
+    import torch
+    dev = torch.device("cuda", sim.device)
+    for name, t in (("lx", lx), ("lu", lu), ("Q", Q), ("R", R), ("ubar", ubar)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("lqr_backward_box: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("lqr_backward_box: %s must be float64, got %s" % (name, t.dtype))
+        if t.device != dev:
+            raise ValueError("lqr_backward_box: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+    B, nr = sim.B, sim.nr
+    if lu.dim() != 3 or lu.shape[0] != B or lu.shape[2] != nr or lu.shape[1] < 1:
+        raise ValueError("lqr_backward_box: lu must have shape (%d, nsteps, %d), got %r" % (B, nr, tuple(lu.shape)))
+    N = lu.shape[1]
+    if tuple(lx.shape) != (B, N, 2 * nr) or tuple(ubar.shape) != (B, N, nr):
+        raise ValueError("lqr_backward_box: lx and ubar must have shapes %r and %r, got %r and %r"
+                         % ((B, N, 2 * nr), (B, N, nr), tuple(lx.shape), tuple(ubar.shape)))
+    tail = (N, 2 * nr, 2 * nr)
+    if tuple(Q.shape) not in (tail, (B,) + tail):
+        raise ValueError("lqr_backward_box: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, tuple(Q.shape)))
+    if tuple(R.shape) != (nr, nr):
+        raise ValueError("lqr_backward_box: R must have shape %r, got %r" % ((nr, nr), tuple(R.shape)))
+    ulo, uhi = _check_ulim("lqr_backward_box", ulim, nr, dev)
+    lxc, luc, Qc, Rc, ubc = (t.detach().contiguous() for t in (lx, lu, Q, R, ubar))
+    kff = torch.empty((B, N, nr), dtype=torch.float64, device=dev)
+    K = torch.empty((B, N, 2 * nr, nr), dtype=torch.float64, device=dev)
+    expected = torch.empty(B, dtype=torch.float64, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    clamped = torch.zeros((B, N), dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    sim.rollout_lqr_box_device(N, lxc.data_ptr(), luc.data_ptr(), Qc.data_ptr(), Rc.data_ptr(), ubc.data_ptr(),
+                               0 if ulo is None else ulo.data_ptr(), 0 if uhi is None else uhi.data_ptr(), kff.data_ptr(), K.data_ptr(),
+                               expected.data_ptr(), status.data_ptr(), clamped.data_ptr(), per_rollout=Q.dim() == 4, mu=float(mu),
+                               max_iter=int(max_iter))
+    return kff, K, expected, status, clamped
 
 
 def lqr_backward(sim, lx, lu, Q, R, mu=0.0):

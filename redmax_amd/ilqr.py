@@ -94,7 +94,7 @@ def backward_pass(A, Bm, lx, lu, Q, R, mu=0.0):
 Result = namedtuple("Result", "u qtraj qdtraj cost alpha")
 
 
-def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0, backward="torch"):
+def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0, backward="torch", ulim=None):
     """Batched iLQR: one problem per rollout of ``sim`` (a BatchSim), BDF1.  Returns (result, history).
 
     q0, qdot0 [B][nr], u0 [B][N][nr]: float64 tensors on the sim's device; cost: a QuadraticCost on that device.  Each iteration
@@ -114,17 +114,26 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
     previous launch left (``diff.lqr_backward``, rmx_rollout_lqr_device): no ``diff.linearize``, no extra forward launch per
     iteration and no A_k, B_k in memory; needs nr <= 32.  A rollout whose Quu + mu I is not positive definite there gets zero gains
     and keeps alpha = 0 in that iteration.  The two paths evaluate one recursion in different summation orders: their results agree
-    to rounding, not bit for bit."""
+    to rounding, not bit for bit.
+    ulim=(ulo, uhi), float64 tensors [nr] on the sim's device or None each: torque limits ulo <= u <= uhi, control-limited DDP
+    (Tassa, Mansard, Todorov 2014).  Every launch is then the clamped feedback rollout (u0 is clamped by the first launch itself),
+    and the backward pass is ``diff.lqr_backward_box`` at ubar = the applied torques of the accepted launch; it exists on the device
+    alone, so backward must be "device".  A rollout whose backward pass reports a status != 0 keeps alpha = 0 in that iteration.
+    ``backward_pass`` knows no limits."""
     import torch
     from . import diff
     if backward not in ("torch", "device"):
         raise ValueError("solve: backward must be 'torch' or 'device', got %r" % (backward,))
+    if ulim is not None and backward != "device":
+        raise ValueError("solve: torque limits (ulim) need backward='device': the box-constrained backward pass exists on the device alone")
     diff._check_inputs(sim, q0, qdot0, u0)
     B, N, nr = u0.shape
     if tuple(cost.Q.shape) != (N, 2 * nr, 2 * nr):
         raise ValueError("solve: the cost is for %d steps of %d states, the rollout has %d steps of %d" % (cost.Q.shape[0], cost.Q.shape[1], N, 2 * nr))
     x0 = torch.cat([q0, qdot0], dim=-1).unsqueeze(1)
     kw = dict(h=h, pscale=pscale, integrator=1)
+    if ulim is not None:
+        kw["ulim"] = ulim
 
     tape = [None]                                                      # sim.tape_count after the last launch
 
@@ -146,9 +155,13 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
             if sim.tape_count != tape[0]:
                 raise RuntimeError("the tape of this rollout has been replaced")
             lx, lu = cost.gradients(xbar, ubar)
-            kff, Kabi, _, notpd = diff.lqr_backward(sim, lx, lu, cost.Q, cost.R, mu)
+            if ulim is not None:
+                kff, Kabi, _, st, _ = diff.lqr_backward_box(sim, lx, lu, cost.Q, cost.R, ubar, ulim, mu)
+                notpd = st != 0
+            else:
+                kff, Kabi, _, notpd = diff.lqr_backward(sim, lx, lu, cost.Q, cost.R, mu)
         else:
-            _, _, A, Bm = diff.linearize(sim, q0, qdot0, ubar, **{k: v for k, v in kw.items() if k != "integrator"})
+            _, _, A, Bm = diff.linearize(sim, q0, qdot0, ubar, **{k: v for k, v in kw.items() if k not in ("integrator", "ulim")})
             lx, lu = cost.gradients(xbar, ubar)
             kff, K, _ = backward_pass(A, Bm, lx, lu, cost.Q, cost.R, mu)
             Kabi = K.transpose(-1, -2).contiguous()

@@ -50,9 +50,12 @@ ROWS = (  # (name fragment, what it runs)
     ("k_rollout_jvp<16>", "rmx_rollout_jvp: 9..16 nodes"),
     ("k_rollout_jvp<32>", "rmx_rollout_jvp: 17..32 nodes"),
     ("k_rollout_jvp<64>", "rmx_rollout_jvp: 33..64 nodes, H, 8 columns and the carried tangents in registers"),
-    ("k_rollout_lqr<8>", "rmx_rollout_lqr (Riccati sweep of iLQR over a BDF1 tape; one workgroup of 256 threads per rollout, Vxx in LDS): 5..8 nodes"),
-    ("k_rollout_lqr<16>", "rmx_rollout_lqr: 9..16 nodes"),
-    ("k_rollout_lqr<32>", "rmx_rollout_lqr: 17..32 nodes (145 664 bytes of LDS)"),
+    ("k_rollout_lqr<8, false>", "rmx_rollout_lqr (Riccati sweep of iLQR over a BDF1 tape; one workgroup of 256 threads per rollout, Vxx in LDS): 5..8 nodes"),
+    ("k_rollout_lqr<16, false>", "rmx_rollout_lqr: 9..16 nodes"),
+    ("k_rollout_lqr<32, false>", "rmx_rollout_lqr: 17..32 nodes (145 664 bytes of LDS)"),
+    ("k_rollout_lqr<8, true>", "rmx_rollout_lqr_box (the same sweep with the box QP of control-limited DDP in the place of the solve): 5..8 nodes"),
+    ("k_rollout_lqr<16, true>", "rmx_rollout_lqr_box: 9..16 nodes"),
+    ("k_rollout_lqr<32, true>", "rmx_rollout_lqr_box: 17..32 nodes (147 712 bytes of LDS)"),
     ("k_rollout_param_grad<4>", "rmx_rollout_vjp_params (the contraction over the slots of a tape; one wavefront per rollout): <= 4 nodes"),
     ("k_rollout_param_grad<8>", "rmx_rollout_vjp_params: 5..8 nodes"),
     ("k_rollout_param_grad<16>", "rmx_rollout_vjp_params: 9..16 nodes"),
