@@ -741,6 +741,72 @@ int rmx_rollout_lqr_box(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, cons
 int rmx_rollout_lqr_box_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_box* box, const double* d_ubar,
                                int max_iter, const rmx_lqr_gains* out, unsigned* d_clamped);
 
+/* Task-space costs for the device iLQR: world positions of body points along a state record, the pull-back of cotangents through
+ * them, and the second-order model of "a joint-space quadratic plus point targets" in the tables rmx_rollout_lqr takes.  Added
+ * WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.  No existing struct grows.
+ *
+ * A term is rmx_adjoint_track's: a point xlocal of a body, the step k (1 .. nsteps) at which it is read, a weight.  Arrays over the
+ * steps hold step k in row k-1; q [batch][nsteps][nr] is ANY state record in reduced DOF order, typically the qtraj of the last
+ * rollout.  For a term t with step_t == k, p_t(q_k) is the world position of its point at the posture q_k and Jp_t = dp_t/dq_k its
+ * 3 x nr Jacobian AT THAT STATE (columns of joints off the path from the root to the body are exact zeros) - not at a Newton
+ * iterate of the step that produced q_k, which is what rmx_adjoint_track reproduces from the reference.
+ *
+ * rmx_rollout_points:   x[b][t] = p_t          gq[b][k-1] = sum over the terms of step k of Jp_t' gx[b][t]   (zero rows elsewhere)
+ * x and gx are indexed by the term's position in `terms`.  It reads neither xtarget nor wpos.  x or gq may be NULL, not both; gq
+ * needs gx.
+ *
+ * rmx_rollout_cost, with x_k = (q_k, qdot_k), dx = x_k - xgoal_k and r_t = p_t(q_k) - xtarget_t:
+ *     Jk[b][k-1] = 1/2 dx' Q_k dx + sum_t 1/2 w_t |r_t|^2                 (the caller sums over k: one fixed order)
+ *     lx[b][k-1] = Q_k dx + ( sum_t w_t Jp_t' r_t ; 0 )                   the exact gradient of Jk: rmx_lqr_cost.lx
+ *     Q [b][k-1] = Q_k + [ sum_t w_t Jp_t' Jp_t, 0 ; 0, 0 ]               rmx_lqr_cost.Q with per_rollout = 1
+ * The last is the GAUSS-NEWTON model: the term sum_t w_t r_t . d2p_t/dq2 of the Hessian is dropped, so the block stays positive
+ * semi-definite whatever the residuals.  Every sum runs in one order - the joint-space part, then the terms of the step in the
+ * caller's order - and entry (i, j) is formed by the products of entry (j, i) in the same order: the Q written is symmetric bit for
+ * bit whenever Q_k is.  The rows and columns of the qdot block, and the rows of steps without a term, are Q_k's bits.
+ * sc may be NULL (no joint-space part), and so may sc->Q and sc->xgoal (zero: the bits a table of zeros gives); pts may be NULL (no
+ * terms); not sc and pts both.  Any of out's members may be NULL, not all.
+ *
+ * Both calls read the model and their arguments only: they need no tape, change neither the batch's state nor its tape
+ * (rmx_rollout_vjp and the others return the same bits before and after), and can be repeated with the same bits.  A rollout's
+ * rows do not depend on its place in the batch, on the batch size, on shared against per-rollout tables, or on which optional
+ * outputs are NULL.
+ * Refusals (RMX_E_INVALID): the kinematic ones of rmx_rollout_tape, in its words - spherical joints, more than 64 nodes (ground
+ * contact and point forces do not enter kinematics: such models are taken); a null batch, q, qdot, out or both of sc and pts, a
+ * null pts in rmx_rollout_points, a null xtarget in rmx_rollout_cost ("null argument"); "all outputs are null"; gq without gx;
+ * rmx_adjoint_track's messages about the terms; a per-rollout flag other than 0 or 1; nsteps < 1; in rmx_rollout_cost a wpos that is
+ * negative or not finite (the message names the term).
+ * The host forms stage through one device allocation of their own, made first and freed before they return.  The _device forms:
+ * every array a DEVICE pointer (the structs are host objects, `terms` stays a host array), nothing staged but the term table, which
+ * goes to a small area of the batch's own; they return when the kernel has finished.
+ * Out of scope: orientation and velocity targets; a table of the q block alone for rmx_rollout_lqr (the full 2nr x 2nr table per
+ * rollout and step is written here and read there). */
+typedef struct rmx_point_terms {
+    int nterms;                    /* >= 1 */
+    const rmx_track_term* terms;   /* host; body, xlocal, step (1..nsteps), wpos - rmx_adjoint_track's term */
+    const double* xtarget;         /* [nterms][3] or [batch][nterms][3], row = the term's position in `terms` */
+    int per_rollout;
+} rmx_point_terms;
+int rmx_rollout_points(rmx_batch* b, int nsteps, const double* q /*[batch][nsteps][nr]*/, const rmx_point_terms* pts,
+                       double* x /*[batch][nterms][3] or NULL*/, const double* gx /*[batch][nterms][3] or NULL*/,
+                       double* gq /*[batch][nsteps][nr] or NULL; needs gx*/);
+int rmx_rollout_points_device(rmx_batch* b, int nsteps, const double* d_q, const rmx_point_terms* pts, double* d_x, const double* d_gx,
+                              double* d_gq);
+typedef struct rmx_state_cost {    /* the joint-space quadratic of ilqr.QuadraticCost; may be passed as NULL */
+    const double* Q;       /* [nsteps][2nr*2nr] or [batch][..], symmetric, column-major; NULL: zero */
+    const double* xgoal;   /* [nsteps][2nr] or [batch][..]; NULL: zero */
+    int Q_per_rollout, goal_per_rollout;
+} rmx_state_cost;
+typedef struct rmx_cost_model {    /* any may be NULL, not all */
+    double* Jk;   /* [batch][nsteps]            state cost of step k (the caller sums over k: one fixed order) */
+    double* lx;   /* [batch][nsteps][2nr]       rmx_lqr_cost.lx */
+    double* Q;    /* [batch][nsteps][2nr*2nr]   rmx_lqr_cost.Q with per_rollout = 1 */
+} rmx_cost_model;
+int rmx_rollout_cost(rmx_batch* b, int nsteps, const double* q, const double* qdot /*[batch][nsteps][nr] each*/,
+                     const rmx_state_cost* sc, const rmx_point_terms* pts /* either may be NULL, not both */,
+                     const rmx_cost_model* out);
+int rmx_rollout_cost_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
+                            const rmx_point_terms* pts, const rmx_cost_model* out);
+
 /* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
  * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of
  * RMX_VERSION (it stays 111): probe for the symbols.

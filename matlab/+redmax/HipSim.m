@@ -290,5 +290,35 @@ classdef HipSim < handle
 			end
 			[kff, K, expected, status, clamped] = redmax_hip_mex('rollout_lqr_box', this.h, nsteps, lx, lu, Q, R, ubar, ulo, uhi, mu, maxIter);
 		end
+
+		function [x, gq] = rolloutPoints(this, nsteps, q, terms, gx)
+			% World positions of body points along a state record q (nr x nsteps x batch; any record, typically a qtraj):
+			% x is 3 x nterms x batch.  terms: struct array with the fields body (1-based listing index), xlocal, step - the
+			% point of term t is read at the posture q(:, step_t, b).  With gx (3 x nterms x batch), gq (nr x nsteps x batch) is the
+			% pull-back sum_t Jp_t' * gx_t over the terms of each step, Jp_t the Jacobian of the point AT THAT STATE.  Needs no
+			% tape and leaves the tape alone.
+			if nargin < 5
+				x = redmax_hip_mex('rollout_points', this.h, nsteps, q, terms);
+				gq = [];
+			else
+				[x, gq] = redmax_hip_mex('rollout_points', this.h, nsteps, q, terms, gx);
+			end
+		end
+
+		function [Jk, lx, Q] = rolloutCost(this, nsteps, q, qdot, Qin, xgoal, terms, xtarget)
+			% The cost of a state record and its second-order model for rolloutLqr: the joint-space quadratic Qin (2nr x 2nr x
+			% nsteps [x batch], symmetric) about xgoal (2nr x nsteps [x batch]) plus point targets - terms (struct array body,
+			% xlocal, step, wpos >= 0) and xtarget (3 x nterms [x batch]).  [] for Qin, xgoal: zero; [] for terms: no targets.
+			% Jk (nsteps x batch) = 1/2 dx'*Qin*dx + sum_t w_t/2 |p_t - xtarget_t|^2; lx (2nr x nsteps x batch) its exact gradient;
+			% Q (2nr x 2nr x nsteps x batch) = Qin + sum_t w_t Jp_t'*Jp_t in the q block - the Gauss-Newton model (the curvature of
+			% the points is dropped), the per-rollout table rolloutLqr takes.  Needs no tape and leaves the tape alone.
+			if nargin < 8
+				xtarget = [];
+			end
+			if nargin < 7
+				terms = [];
+			end
+			[Jk, lx, Q] = redmax_hip_mex('rollout_cost', this.h, nsteps, q, qdot, Qin, xgoal, terms, xtarget);
+		end
 	end
 end

@@ -94,6 +94,16 @@
  *                  rmx_rollout_lqr_box: 'rollout_lqr' with the box QP of control-limited DDP at every step.  ubar (nr x nsteps x B):
  *                  the nominal applied torques; max_iter (default 0: 64) caps the QP iterations of a step.  status 1 x B: 0, 1 (a
  *                  pivot not > 0), 2 (a QP did not terminate); clamped nsteps x B: bit i set where DOF i ended on a bound.
+ *   [x,gq] = redmax_hip_mex('rollout_points', h, nsteps, q, terms [, gx])  rmx_rollout_points: the world positions of body points
+ *                  along a state record q (nr x nsteps x B, any record - typically a qtraj), x 3 x nterms x B, and with gx (3 x
+ *                  nterms x B) the pull-back gq (nr x nsteps x B) = sum over the terms of a step of Jp'*gx.  terms: struct array
+ *                  body (1-based), xlocal, step, as task.terms of 'adjoint_track' (a wpos is not read).  Needs no tape.
+ *   [Jk,lx,Q] = redmax_hip_mex('rollout_cost', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget)  rmx_rollout_cost: the cost of a
+ *                  state record and its second-order model for 'rollout_lqr' - the joint-space quadratic Qin (2nr x 2nr x nsteps
+ *                  [x B], symmetric) about xgoal (2nr x nsteps [x B]) plus point targets: terms (struct array body, xlocal, step,
+ *                  wpos >= 0) and xtarget (3 x nterms [x B]).  [] for Qin, xgoal: zero; [] for terms: no targets.  Jk: nsteps x B;
+ *                  lx: 2nr x nsteps x B, the exact gradient; Q: 2nr x 2nr x nsteps x B, Qin + sum w Jp'*Jp in the q block
+ *                  (Gauss-Newton).  Outputs that are not asked for are not computed.  Needs no tape.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -1107,6 +1117,115 @@ static void cmd_adjoint_track(int nlhs, mxArray* plhs[], int nrhs, const mxArray
     else mxDestroyArray(st);
 }
 
+/* the struct array `ta` (body 1-based, xlocal, step[, wpos]) as rmx_track_term's; the caller frees the result */
+static rmx_track_term* point_terms(const mxArray* ta, const char* who, int need_wpos, size_t* nterms) {
+    if (!mxIsStruct(ta)) mexErrMsgIdAndTxt("redmax:hip", "%s: terms must be a struct array with the fields body, xlocal, step%s", who, need_wpos ? ", wpos" : "");
+    *nterms = mxGetNumberOfElements(ta);
+    rmx_track_term* terms = (rmx_track_term*)mxCalloc(*nterms ? *nterms : 1, sizeof *terms);
+    for (size_t i = 0; i < *nterms; ++i) {
+        terms[i].body = (int)mxGetScalar(term_field(ta, i, "body")) - 1;   /* MATLAB listing index -> 0-based */
+        const mxArray* xl = term_field(ta, i, "xlocal");
+        if (!mxIsDouble(xl) || mxGetNumberOfElements(xl) != 3) mexErrMsgIdAndTxt("redmax:hip", "%s: terms(%d).xlocal must have 3 elements", who, (int)i + 1);
+        memcpy(terms[i].xlocal, mxGetPr(xl), 3 * sizeof(double));
+        terms[i].step = (int)mxGetScalar(term_field(ta, i, "step"));
+        terms[i].wpos = need_wpos ? mxGetScalar(term_field(ta, i, "wpos")) : 0.0;
+    }
+    return terms;
+}
+/* a real double argument with `want` elements (or `alt`, where alt != 0), or - where empty_ok - []: NULL */
+static const double* cost_arg(const mxArray* a, size_t want, size_t alt, int empty_ok, const char* who, const char* what, const char* shape) {
+    if (empty_ok && mxIsEmpty(a)) return NULL;
+    const size_t n = mxGetNumberOfElements(a);
+    if (!mxIsDouble(a) || mxIsComplex(a) || (n != want && !(alt && n == alt)))
+        mexErrMsgIdAndTxt("redmax:hip", "%s: %s must be a real double %s array", who, what, shape);
+    return mxGetPr(a);
+}
+
+static void cmd_rollout_points(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 5) die("usage: [x,gq] = redmax_hip_mex('rollout_points', h, nsteps, q, terms [, gx])");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_points: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
+    const double* q = cost_arg(prhs[3], nr * N * B, 0, 0, "rollout_points", "q", "nr x nsteps x batch");
+    size_t nterms;
+    rmx_track_term* terms = point_terms(prhs[4], "rollout_points", 0, &nterms);
+    const double* gx = nrhs > 5 ? cost_arg(prhs[5], 3 * nterms * B, 0, 1, "rollout_points", "gx", "3 x nterms x batch") : NULL;
+    if (nlhs > 1 && !gx) die("rollout_points: gq needs gx");
+    const size_t dx[3] = {3, nterms, B}, dg[3] = {nr, N, B};
+    mxArray* x = mxCreateNumericArray(3, dx, mxDOUBLE_CLASS, mxREAL);
+    mxArray* gq = nlhs > 1 ? mxCreateNumericArray(3, dg, mxDOUBLE_CLASS, mxREAL) : NULL;
+    rmx_point_terms pts;
+    memset(&pts, 0, sizeof pts);
+    pts.nterms = (int)nterms;
+    pts.terms = terms;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: the record, the points and the cotangents advance */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        if (rmx_rollout_points(b, nsteps, q + f * nr * N, &pts, mxGetPr(x) + f * 3 * nterms, gq ? gx + f * 3 * nterms : NULL,
+                               gq ? mxGetPr(gq) + f * nr * N : NULL)) {
+            mxFree(terms);
+            die_rmx("rmx_rollout_points");
+        }
+    }
+    mxFree(terms);
+    plhs[0] = x;
+    if (nlhs > 1) plhs[1] = gq;
+}
+
+static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 9) die("usage: [Jk,lx,Q] = redmax_hip_mex('rollout_cost', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_cost: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
+    const size_t perq = 4 * nr * nr * N, perg = 2 * nr * N;
+    const char* who = "rollout_cost";
+    const double* q = cost_arg(prhs[3], nr * N * B, 0, 0, who, "q", "nr x nsteps x batch");
+    const double* qd = cost_arg(prhs[4], nr * N * B, 0, 0, who, "qdot", "nr x nsteps x batch");
+    const double* Qin = cost_arg(prhs[5], perq, perq * B, 1, who, "Qin", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
+    const double* xg = cost_arg(prhs[6], perg, perg * B, 1, who, "xgoal", "2nr x nsteps or 2nr x nsteps x batch");
+    /* (a batch of one: a table is one table either way) */
+    const int Q_per = Qin && mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
+    const int g_per = xg && mxGetNumberOfElements(prhs[6]) == perg * B && B > 1;
+    size_t nterms = 0;
+    rmx_track_term* terms = mxIsEmpty(prhs[7]) ? NULL : point_terms(prhs[7], who, 1, &nterms);
+    const double* xt = terms ? cost_arg(prhs[8], 3 * nterms, 3 * nterms * B, 0, who, "xtarget", "3 x nterms or 3 x nterms x batch") : NULL;
+    const int t_per = terms && mxGetNumberOfElements(prhs[8]) == 3 * nterms * B && B > 1;
+    const size_t dJ[2] = {N, B}, dl[3] = {2 * nr, N, B}, dQ[4] = {2 * nr, 2 * nr, N, B};
+    mxArray* Jk = mxCreateNumericArray(2, dJ, mxDOUBLE_CLASS, mxREAL);
+    mxArray* lx = nlhs > 1 ? mxCreateNumericArray(3, dl, mxDOUBLE_CLASS, mxREAL) : NULL;
+    mxArray* Qo = nlhs > 2 ? mxCreateNumericArray(4, dQ, mxDOUBLE_CLASS, mxREAL) : NULL;
+    rmx_state_cost sc;
+    rmx_point_terms pts;
+    memset(&sc, 0, sizeof sc);
+    memset(&pts, 0, sizeof pts);
+    sc.Q_per_rollout = Q_per;
+    sc.goal_per_rollout = g_per;
+    pts.nterms = (int)nterms;
+    pts.terms = terms;
+    pts.per_rollout = t_per;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: the record, the per-rollout tables and the outputs advance */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_cost_model out;
+        sc.Q = Qin ? Qin + (Q_per ? f * perq : 0) : NULL;
+        sc.xgoal = xg ? xg + (g_per ? f * perg : 0) : NULL;
+        pts.xtarget = xt ? xt + (t_per ? f * 3 * nterms : 0) : NULL;
+        out.Jk = mxGetPr(Jk) + f * N;
+        out.lx = lx ? mxGetPr(lx) + f * perg : NULL;
+        out.Q = Qo ? mxGetPr(Qo) + f * perq : NULL;
+        if (rmx_rollout_cost(b, nsteps, q + f * nr * N, qd + f * nr * N, (Qin || xg) ? &sc : NULL, terms ? &pts : NULL, &out)) {
+            if (terms) mxFree(terms);
+            die_rmx("rmx_rollout_cost");
+        }
+    }
+    if (terms) mxFree(terms);
+    plhs[0] = Jk;
+    if (nlhs > 1) plhs[1] = lx;
+    if (nlhs > 2) plhs[2] = Qo;
+}
+
 /* `clear mex` / MATLAB exit: free what is still alive on the device */
 static void at_exit(void) {
     for (int i = 0; i < MAX_LIVE; ++i)
@@ -1131,7 +1250,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
                                              "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
-                                             NULL};
+                                             "rollout_points", "rollout_cost", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -1256,6 +1375,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_feedback_box(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_lqr_box")) {
         cmd_rollout_lqr_box(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_points")) {
+        cmd_rollout_points(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_cost")) {
+        cmd_rollout_cost(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

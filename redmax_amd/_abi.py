@@ -33,6 +33,7 @@ SYMBOLS = (
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
     "rmx_rollout_lqr", "rmx_rollout_lqr_device",
     "rmx_rollout_tape_feedback_box", "rmx_rollout_tape_feedback_box_device", "rmx_rollout_lqr_box", "rmx_rollout_lqr_box_device",
+    "rmx_rollout_points", "rmx_rollout_points_device", "rmx_rollout_cost", "rmx_rollout_cost_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -112,6 +113,18 @@ class LqrGains(C.Structure):      # rmx_lqr_gains
 
 class Box(C.Structure):      # rmx_box: host pointers in the host form, device pointers in the _device form
     _fields_ = [("ulo", C.c_void_p), ("uhi", C.c_void_p)]
+
+
+class PointTerms(C.Structure):      # rmx_point_terms: terms is a host array in both forms, xtarget a device pointer in the _device form
+    _fields_ = [("nterms", C.c_int), ("terms", C.POINTER(TrackTerm)), ("xtarget", C.c_void_p), ("per_rollout", C.c_int)]
+
+
+class StateCost(C.Structure):      # rmx_state_cost: host pointers in the host form, device pointers in the _device form
+    _fields_ = [("Q", C.c_void_p), ("xgoal", C.c_void_p), ("Q_per_rollout", C.c_int), ("goal_per_rollout", C.c_int)]
+
+
+class CostModel(C.Structure):      # rmx_cost_model
+    _fields_ = [("Jk", C.c_void_p), ("lx", C.c_void_p), ("Q", C.c_void_p)]
 
 
 FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
@@ -198,6 +211,10 @@ def lib():
                                                        vp, C.POINTER(Stats)]
     L.rmx_rollout_lqr_box.argtypes = [vp, C.c_int, C.POINTER(LqrCost), C.POINTER(Box), vp, C.c_int, C.POINTER(LqrGains), vp]
     L.rmx_rollout_lqr_box_device.argtypes = L.rmx_rollout_lqr_box.argtypes
+    L.rmx_rollout_points.argtypes = [vp, C.c_int, vp, C.POINTER(PointTerms), vp, vp, vp]
+    L.rmx_rollout_points_device.argtypes = L.rmx_rollout_points.argtypes
+    L.rmx_rollout_cost.argtypes = [vp, C.c_int, vp, vp, C.POINTER(StateCost), C.POINTER(PointTerms), C.POINTER(CostModel)]
+    L.rmx_rollout_cost_device.argtypes = L.rmx_rollout_cost.argtypes
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

@@ -823,6 +823,117 @@ class BatchSim:
         gains = _abi.LqrGains(kff_ptr or None, K_ptr or None, expected_ptr or None, status_ptr or None)
         _abi.check(self._L.rmx_rollout_lqr_device(self._batch, int(nsteps), C.byref(cost), C.byref(gains)), "rmx_rollout_lqr_device")
 
+    @staticmethod
+    def _point_terms(terms, who, need_wpos):
+        """terms (a list of dict(body, xlocal, step[, wpos]), adjoint_track's) -> (array of TrackTerm, count)."""
+        terms = list(terms)
+        arr = (_abi.TrackTerm * max(len(terms), 1))()
+        for a, t in zip(arr, terms):
+            xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
+            if xl.shape != (3,):
+                raise ValueError("%s: a term's xlocal must have shape (3,), got %r" % (who, xl.shape))
+            a.body, a.step = int(t["body"]), int(t["step"])
+            a.wpos = float(t["wpos"]) if need_wpos else float(t.get("wpos", 0.0))
+            for i in range(3):
+                a.xlocal[i] = float(xl[i])
+        return arr, len(terms)
+
+    def rollout_points(self, nsteps, q, terms, gx=None, points=True):
+        """rmx_rollout_points: the world positions of body points along a state record q [B][nsteps][nr] (any record, typically a
+        qtraj), and the pull-back of cotangents through them.  terms: a list of dict(body, xlocal, step) - adjoint_track's term, a
+        wpos is not read; the point of term t is taken at the posture q[:, step_t - 1].  Returns (x [B][nterms][3] or None with
+        points=False, gq [B][nsteps][nr] or None without gx): gq[b][k-1] = sum over the terms of step k of Jp_t' gx[b][t], with Jp_t
+        the Jacobian of the point at that posture.  Needs no tape and changes neither the state nor the tape."""
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.shape != (B, nsteps, nr):
+            raise ValueError("rollout_points: q must have shape %r, got %r" % ((B, nsteps, nr), q.shape))
+        arr, nterms = self._point_terms(terms, "rollout_points", False)
+        if gx is not None:
+            gx = np.ascontiguousarray(gx, dtype=np.float64)
+            if gx.shape != (B, nterms, 3):
+                raise ValueError("rollout_points: gx must have shape %r, got %r" % ((B, nterms, 3), gx.shape))
+        x = np.empty((B, nterms, 3)) if points else None
+        gq = np.empty((B, nsteps, nr)) if gx is not None else None
+        pts = _abi.PointTerms(nterms, arr, None, 0)
+        _abi.check(self._L.rmx_rollout_points(self._batch, nsteps, q.ctypes.data, C.byref(pts), None if x is None else x.ctypes.data,
+                                              None if gx is None else gx.ctypes.data, None if gq is None else gq.ctypes.data),
+                   "rmx_rollout_points")
+        return x, gq
+
+    def rollout_points_device(self, nsteps, q_ptr, terms, x_ptr=None, gx_ptr=None, gq_ptr=None):
+        """rollout_points with DEVICE pointers (integers): q, gq [B][nsteps][nr]; x, gx [B][nterms][3]; 0 / None: x not stored, gq
+        not formed (not both; gq needs gx).  terms stays the host list."""
+        arr, nterms = self._point_terms(terms, "rollout_points_device", False)
+        pts = _abi.PointTerms(nterms, arr, None, 0)
+        _abi.check(self._L.rmx_rollout_points_device(self._batch, int(nsteps), C.c_void_p(q_ptr or None), C.byref(pts), C.c_void_p(x_ptr or None),
+                                                     C.c_void_p(gx_ptr or None), C.c_void_p(gq_ptr or None)), "rmx_rollout_points_device")
+
+    def rollout_cost(self, nsteps, q, qdot, Q=None, xgoal=None, terms=None, xtarget=None, want=("Jk", "lx", "Q")):
+        """rmx_rollout_cost: the cost of a state record q, qdot [B][nsteps][nr] and its second-order model for rollout_lqr -
+        a joint-space quadratic (Q [nsteps][2nr][2nr] or [B][..], symmetric; xgoal [nsteps][2nr] or [B][..]; None: zero) plus point
+        targets (terms: a list of dict(body, xlocal, step, wpos), wpos >= 0; xtarget [nterms][3] or [B][nterms][3]).  With
+        x = (q, qdot), dx = x - xgoal, r_t = p_t(q_k) - xtarget_t, returns a dict with the names in `want`:
+        "Jk" [B][nsteps] = 1/2 dx'Q dx + sum_t w_t/2 |r_t|^2, "lx" [B][nsteps][2nr] its exact gradient, "Q" [B][nsteps][2nr][2nr] =
+        Q + sum_t w_t Jp_t'Jp_t in the q block (Gauss-Newton: the curvature of the points is dropped), symmetric bit for bit.  Needs
+        no tape and changes neither the state nor the tape."""
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("Jk", "lx", "Q") for w in want) or len(set(want)) != len(want):
+            raise ValueError("rollout_cost: want must name distinct outputs among 'Jk', 'lx', 'Q', got %r" % (want,))
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        qdot = np.ascontiguousarray(qdot, dtype=np.float64)
+        if q.shape != (B, nsteps, nr) or qdot.shape != (B, nsteps, nr):
+            raise ValueError("rollout_cost: q and qdot must have shape %r, got %r and %r" % ((B, nsteps, nr), q.shape, qdot.shape))
+        sc = None
+        if Q is not None or xgoal is not None:
+            sc = _abi.StateCost(None, None, 0, 0)
+            if Q is not None:
+                Q = np.ascontiguousarray(Q, dtype=np.float64)
+                tail = (nsteps, 2 * nr, 2 * nr)
+                if Q.shape not in (tail, (B,) + tail):
+                    raise ValueError("rollout_cost: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, Q.shape))
+                sc.Q, sc.Q_per_rollout = Q.ctypes.data, int(Q.ndim == 4)      # (symmetric: row-major memory is the column-major table)
+            if xgoal is not None:
+                xgoal = np.ascontiguousarray(xgoal, dtype=np.float64)
+                tail = (nsteps, 2 * nr)
+                if xgoal.shape not in (tail, (B,) + tail):
+                    raise ValueError("rollout_cost: xgoal must have shape %r or %r, got %r" % (tail, (B,) + tail, xgoal.shape))
+                sc.xgoal, sc.goal_per_rollout = xgoal.ctypes.data, int(xgoal.ndim == 3)
+        pts = None
+        if terms is not None:
+            arr, nterms = self._point_terms(terms, "rollout_cost", True)
+            if xtarget is None:
+                raise ValueError("rollout_cost: xtarget is None")
+            xtarget = np.ascontiguousarray(xtarget, dtype=np.float64)
+            if xtarget.shape not in ((nterms, 3), (B, nterms, 3)):
+                raise ValueError("rollout_cost: xtarget must have shape (%d, 3) or (%d, %d, 3), got %r" % (nterms, B, nterms, xtarget.shape))
+            pts = _abi.PointTerms(nterms, arr, xtarget.ctypes.data, int(xtarget.ndim == 3))
+        shapes = {"Jk": (B, nsteps), "lx": (B, nsteps, 2 * nr), "Q": (B, nsteps, 2 * nr, 2 * nr)}
+        out = {w: np.empty(shapes[w]) for w in want}
+        cm = _abi.CostModel(*[out[n].ctypes.data if n in out else None for n in ("Jk", "lx", "Q")])
+        _abi.check(self._L.rmx_rollout_cost(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, None if sc is None else C.byref(sc),
+                                            None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost")
+        return out
+
+    def rollout_cost_device(self, nsteps, q_ptr, qdot_ptr, Q_ptr=None, xgoal_ptr=None, Q_per_rollout=False, goal_per_rollout=False, terms=None,
+                            xtarget_ptr=None, target_per_rollout=False, Jk_ptr=None, lx_ptr=None, Qout_ptr=None):
+        """rollout_cost with DEVICE pointers (integers): q, qdot [B][nsteps][nr]; Q [nsteps][2nr*2nr] and xgoal [nsteps][2nr], or one
+        table per rollout with the flag set, 0 / None: zero; xtarget [nterms][3] or [B][nterms][3]; Jk [B][nsteps], lx
+        [B][nsteps][2nr], Qout [B][nsteps][2nr*2nr], 0 / None: not formed (not all three).  terms stays the host list (None: no
+        point targets)."""
+        sc = _abi.StateCost(Q_ptr or None, xgoal_ptr or None, int(bool(Q_per_rollout)), int(bool(goal_per_rollout)))
+        pts = None
+        if terms is not None:
+            arr, nterms = self._point_terms(terms, "rollout_cost_device", True)
+            pts = _abi.PointTerms(nterms, arr, xtarget_ptr or None, int(bool(target_per_rollout)))
+        cm = _abi.CostModel(Jk_ptr or None, lx_ptr or None, Qout_ptr or None)
+        _abi.check(self._L.rmx_rollout_cost_device(self._batch, int(nsteps), C.c_void_p(q_ptr or None), C.c_void_p(qdot_ptr or None),
+                                                   C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
+                                                   None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost_device")
+
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent
         variant the library chose."""

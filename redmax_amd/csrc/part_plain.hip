@@ -4,6 +4,7 @@
 #include "rmx_linearize.h"
 #include "rmx_jvp.h"
 #include "rmx_params.h"
+#include "rmx_cost.h"
 #if RMX_NP <= 32
 #include "rmx_lqr.h"
 #endif
@@ -116,6 +117,12 @@ void RMX_CAT(launch_lqr_box_, RMX_NP)(const rmx_model* m, const rmx_batch* b, co
 void RMX_CAT(launch_jvp_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nchunks)), block(64);
     k_rollout_jvp<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+}
+
+// rmx_rollout_points / rmx_rollout_cost: one wavefront per (rollout, step) of the record (rmx_select.h select_rollout_cost)
+void RMX_CAT(launch_cost_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const CostArgs& a) {
+    const dim3 grid((unsigned)((size_t)b->B * a.nsteps)), block(64);
+    k_rollout_cost<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
 
 // rmx_rollout_vjp_params: the backward sweep of the tape's integrator in its ADJ_ZS instantiation (du, dq0, dqd0 as rmx_rollout_vjp's

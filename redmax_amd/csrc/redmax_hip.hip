@@ -772,7 +772,7 @@ extern "C" void rmx_batch_destroy(rmx_batch* b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     hist_free(b);
     for (void* p : {(void*)b->q, (void*)b->qd, (void*)b->qp, (void*)b->qdp, (void*)b->tmpA, (void*)b->tmpB, (void*)b->tmpC,
-                    (void*)b->started, (void*)b->it, (void*)b->ls, (void*)b->status, (void*)b->resume, (void*)b->park, (void*)b->xch, (void*)b->xrec, b->gargs, (void*)b->chart, (void*)b->ticks, (void*)b->bigws, b->adjws})
+                    (void*)b->started, (void*)b->it, (void*)b->ls, (void*)b->status, (void*)b->resume, (void*)b->park, (void*)b->xch, (void*)b->xrec, b->gargs, (void*)b->chart, (void*)b->ticks, (void*)b->bigws, b->adjws, b->costws})
         if (p) (void)hipFree(p);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
@@ -2052,6 +2052,113 @@ extern "C" int rmx_rollout_lqr_box(rmx_batch* b, int nsteps, const rmx_lqr_cost*
 extern "C" int rmx_rollout_lqr_box_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cost, const rmx_box* box, const double* d_ubar,
                                           int max_iter, const rmx_lqr_gains* out, unsigned* d_clamped) {
     return rollout_lqr_impl(b, nsteps, cost, out, true, true, box, d_ubar, max_iter, d_clamped);
+}
+
+// rmx_rollout_points / rmx_rollout_cost: point kinematics along a state record and the cost model the Riccati sweep takes, one
+// wavefront per (rollout, step) (rmx_cost.h; rmx_select.h select_rollout_cost).  They read the model and their arguments alone: no
+// tape is needed and none is touched.  The term table (rmx_track::plan_terms, a host array in both forms) goes to a small device
+// area of the batch's own that only grows; the host form stages every other array through an allocation of its own, as
+// rmx_rollout_lqr does.
+static hipError_t costws_reserve(rmx_batch* b, const size_t total) {
+    if (total <= b->costws_bytes) return hipSuccess;
+    void* fresh = nullptr;
+    const hipError_t e = hipMalloc(&fresh, total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e;
+    }
+    if (b->costws) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->costws); }
+    b->costws = fresh;
+    b->costws_bytes = total;
+    return hipSuccess;
+}
+static int rollout_cost_impl(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_point_terms* pts,
+                             const rmx_cost_model* out, double* x, const double* gx, double* gq, const bool on_device, const bool points) {
+    const std::string who = points ? "rmx_rollout_points" : "rmx_rollout_cost";
+    if (!b || !q || (points ? !pts : (!qdot || !out || (!sc && !pts)))) return fail(RMX_E_INVALID, who + ": null argument");
+    if (!points && pts && !pts->xtarget) return fail(RMX_E_INVALID, who + ": null argument");
+    if (points ? (!x && !gq) : (!out->Jk && !out->lx && !out->Q)) return fail(RMX_E_INVALID, who + ": all outputs are null");
+    if (gq && !gx) return fail(RMX_E_INVALID, who + ": gq needs gx (the cotangents of the points)");
+    if (pts && pts->per_rollout != 0 && pts->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    if (sc && ((sc->Q_per_rollout != 0 && sc->Q_per_rollout != 1) || (sc->goal_per_rollout != 0 && sc->goal_per_rollout != 1)))
+        return fail(RMX_E_INVALID, who + ": Q_per_rollout and goal_per_rollout must be 0 or 1");
+    if (nsteps < 1) return fail(RMX_E_INVALID, who + ": nsteps < 1");
+    rmx_model* m = b->m;
+    const rmx_select::CostPlan plan = rmx_select::select_rollout_cost(step_traits(m), b->B, nsteps);
+    if (plan.kernel == rmx_select::CostKernel::RefusedSpherical)
+        return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
+    if (plan.kernel == rmx_select::CostKernel::RefusedNodes)
+        return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
+    if (plan.kernel != rmx_select::CostKernel::Wave) return fail(RMX_E_INVALID, who + ": batch * nsteps exceeds the grid");
+    rmx_track::Plan tplan;
+    if (pts) {
+        tplan = rmx_track::plan_terms(pts->terms, pts->nterms, nsteps, m->nlist, m->node_of_listing.data());
+        if (!tplan.error.empty()) return fail(RMX_E_INVALID, who + ": " + tplan.error);
+        for (int i = 0; i < pts->nterms && !points; ++i)
+            if (!(pts->terms[i].wpos >= 0.0) || !std::isfinite(pts->terms[i].wpos))
+                return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": wpos must be finite and >= 0 (the Gauss-Newton block must stay positive semi-definite)");
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (int rc = pending_error_check(b, who.c_str())) return rc;
+    const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
+    const size_t nterms = pts ? (size_t)pts->nterms : 0;
+    const size_t bytes_traj = B * N * nr * dbl, bytes_pts = B * nterms * 3 * dbl, bytes_Q = N * 4 * nr * nr * dbl;
+    enum { S_Q, S_QD, S_XT, S_QIN, S_XG, S_JK, S_LX, S_QOUT, S_X, S_GX, S_GQ };
+    Staging st(on_device);
+    st.add(bytes_traj, q, nullptr);
+    st.add(bytes_traj, points ? nullptr : qdot, nullptr);
+    st.add((pts && pts->per_rollout ? B : 1) * nterms * 3 * dbl, (pts && !points) ? pts->xtarget : nullptr, nullptr);
+    st.add((sc && sc->Q_per_rollout ? B : 1) * bytes_Q, (sc && !points) ? sc->Q : nullptr, nullptr);
+    st.add((sc && sc->goal_per_rollout ? B : 1) * N * 2 * nr * dbl, (sc && !points) ? sc->xgoal : nullptr, nullptr);
+    st.add(B * N * dbl, nullptr, points ? nullptr : out->Jk);
+    st.add(B * N * 2 * nr * dbl, nullptr, points ? nullptr : out->lx);
+    st.add(B * bytes_Q, nullptr, points ? nullptr : out->Q);
+    st.add(bytes_pts, nullptr, x);
+    st.add(bytes_pts, gq ? gx : nullptr, nullptr);
+    st.add(bytes_traj, nullptr, gq);
+    if (int rc = st.allocate(who, "the staging")) return rc;
+    const size_t trk_bytes = rmx_tape::round256(nterms * sizeof(rmx_track::DevTerm)), begin_bytes = (N + 1) * sizeof(int);
+    hipError_t e = pts ? costws_reserve(b, trk_bytes + begin_bytes) : hipSuccess;
+    if (e == hipErrorOutOfMemory) {
+        st.release(b, hipSuccess);
+        return fail(RMX_E_NOMEM, who + ": no device memory for the term table");
+    }
+    CostArgs a{};
+    a.nsteps = nsteps; a.nterms = (int)nterms;
+    a.q = st.dev(S_Q); a.qd = st.dev(S_QD);
+    if (pts && e == hipSuccess) {
+        a.trk = (const rmx_track::DevTerm*)b->costws;
+        a.trk_begin = (const int*)((const char*)b->costws + trk_bytes);
+        e = hipMemcpyAsync(b->costws, tplan.terms.data(), nterms * sizeof(rmx_track::DevTerm), hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)b->costws + trk_bytes, tplan.begin.data(), begin_bytes, hipMemcpyHostToDevice, b->stream);
+    }
+    a.xt = st.dev(S_XT); a.xt_stride = (pts && pts->per_rollout) ? nterms * 3 : 0;
+    a.Qin = st.dev(S_QIN); a.q_stride = (sc && sc->Q_per_rollout) ? N * 4 * nr * nr : 0;
+    a.xgoal = st.dev(S_XG); a.goal_stride = (sc && sc->goal_per_rollout) ? N * 2 * nr : 0;
+    a.Jk = st.dev(S_JK); a.lx = st.dev(S_LX); a.Qout = st.dev(S_QOUT);
+    a.x = st.dev(S_X); a.gx = st.dev(S_GX); a.gq = st.dev(S_GQ);
+    e = st.copy_in(b, e);
+    e = timed_launch(b, e, [&] {
+        DISPATCH_NP(plan.np, launch_cost, m, b, a)
+        b->last_kernel = rmx_select::label_rollout_cost();
+        return hipSuccess;
+    });
+    return tape_call_end(b, st.copy_out(b, e), st, who);      // (the wait keeps the plan's arrays alive for their copies)
+}
+extern "C" int rmx_rollout_points(rmx_batch* b, int nsteps, const double* q, const rmx_point_terms* pts, double* x, const double* gx, double* gq) {
+    return rollout_cost_impl(b, nsteps, q, nullptr, nullptr, pts, nullptr, x, gx, gq, false, true);
+}
+extern "C" int rmx_rollout_points_device(rmx_batch* b, int nsteps, const double* d_q, const rmx_point_terms* pts, double* d_x, const double* d_gx,
+                                         double* d_gq) {
+    return rollout_cost_impl(b, nsteps, d_q, nullptr, nullptr, pts, nullptr, d_x, d_gx, d_gq, true, true);
+}
+extern "C" int rmx_rollout_cost(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_point_terms* pts,
+                                const rmx_cost_model* out) {
+    return rollout_cost_impl(b, nsteps, q, qdot, sc, pts, out, nullptr, nullptr, nullptr, false, false);
+}
+extern "C" int rmx_rollout_cost_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
+                                       const rmx_point_terms* pts, const rmx_cost_model* out) {
+    return rollout_cost_impl(b, nsteps, d_q, d_qdot, sc, pts, out, nullptr, nullptr, nullptr, true, false);
 }
 
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,

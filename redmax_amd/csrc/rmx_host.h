@@ -151,6 +151,24 @@ struct LqrArgs {
     unsigned* clamped;        // [B][nsteps] or null: bit i of row k-1 is set where DOF i of step k ended on a bound
 };
 
+// rmx_rollout_points / rmx_rollout_cost (rmx_cost.h): one wavefront per (rollout, step) of a state record
+struct CostArgs {
+    int nsteps, nterms;
+    const double *q, *qd;     // [B][nsteps][nr] the record (qd: rmx_rollout_cost alone)
+    const rmx_track::DevTerm* trk;   // [nterms] the terms sorted by step (rmx_track.h), or null: no terms
+    const int* trk_begin;     // [nsteps + 1] step k owns terms trk_begin[k-1] .. trk_begin[k]-1, or null
+    const double* xt;         // targets, [nterms][3] or [B][nterms][3], indexed by the term's position in the caller's array
+    size_t xt_stride;         // doubles from one rollout's target table to the next (0: one table for the batch)
+    const double* Qin;        // [nsteps][2nr * 2nr] or [B][..], column-major, or null: zero
+    size_t q_stride;          // doubles from one rollout's Q table to the next (0: one table for the batch)
+    const double* xgoal;      // [nsteps][2nr] or [B][..], or null: zero
+    size_t goal_stride;
+    double *Jk, *lx, *Qout;   // [B][nsteps], [B][nsteps][2nr], [B][nsteps][2nr * 2nr]; null: not wanted
+    double* x;                // [B][nterms][3] the points (rmx_rollout_points), or null
+    const double* gx;         // [B][nterms][3] their cotangents (with gq)
+    double* gq;               // [B][nsteps][nr], or null
+};
+
 struct rmx_model {
     int device = 0;
     int n = 0, nr = 0, nm = 0, NP = 0;   // n: 1-DOF nodes on the device (after lowering multi-DOF joints)
@@ -197,7 +215,7 @@ struct rmx_batch {
     size_t bigws_stride = 0;        // doubles per rollout
     void* adjws = nullptr;          // rmx_adjoint_*: H, M, D of every step and rollout, dP/dq, P, dP/dp - one allocation that is kept
     size_t adjws_bytes = 0;         // between calls and only ever grows (hipMalloc + hipFree of 3 x 20 MB cost more than the kernels)
-    int tape_nsteps = 0;            // rmx_rollout_tape: steps of the tape H, M, D in adjws hold (0: none - every rmx_adjoint_* call rewrites them)
+    int tape_nsteps = 0;           // rmx_rollout_tape: steps of the tape H, M, D in adjws hold (0: none - every rmx_adjoint_* call rewrites them)
     int tape_integ = 0;             // ... the integrator that recorded it (INTEG_BDF2: nsteps + 1 slots per rollout, rmx_rollout_tape_bdf2)
     double tape_h = 0.0, tape_pscale = 0.0;   // ... and the step size and torque scale it was recorded with
     double last_ms = 0.0;
@@ -218,6 +236,10 @@ struct rmx_batch {
         int* C = nullptr;
         size_t capH = 0, capQ = 0, capC = 0;    // elements
     } hpool;
+    // rmx_rollout_points / rmx_rollout_cost: the term table and its step offsets on the device - an allocation of its own that only
+    // grows (the adjoint workspace holds the tape, which these calls must leave alone)
+    void* costws = nullptr;
+    size_t costws_bytes = 0;
 };
 
 // launchers defined by the multi-size parts (part_plain / part_ct / part_fullchain / part_pf .hip) for one RMX_NP each
@@ -233,6 +255,7 @@ struct rmx_batch {
     void RMX_CAT(launch_vjp_feedback_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
+    void RMX_CAT(launch_cost_, NPV)(const rmx_model* m, const rmx_batch* b, const CostArgs& a); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \
     void RMX_CAT(launch_param_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a); \
     void RMX_CAT(launch_phase_, NPV)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d); \

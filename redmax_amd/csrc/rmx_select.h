@@ -229,4 +229,34 @@ inline const char* label_rollout_feedback_box(const int integ) {      // ... aft
     return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback,box>" : "k_adjoint_fwd<bdf1,tape,feedback,box>";
 }
 
+// Point kinematics and the cost model along a state record (rmx_rollout_points, rmx_rollout_cost; rmx_cost.h): one wavefront per
+// (rollout, step), lane = node, in part_plain's object of the model's padded size - every size has one, 64 included, and the kernel
+// holds nothing in LDS.  Kinematics alone decides: spherical joints (their Euler charts are not a function of q alone) and trees of
+// more than 64 nodes are refused; ground contact and point forces do not enter kinematics and are taken.
+enum class CostKernel {
+    Wave,                // part_plain: k_rollout_cost<NP>
+    RefusedSpherical,
+    RefusedNodes,        // more than 64 nodes
+    RefusedGrid,         // batch * nsteps wavefronts exceed the grid
+};
+struct CostPlan {
+    CostKernel kernel = CostKernel::Wave;
+    int np = 0;                         // the padded size that runs
+    int block = 64;                     // threads per workgroup
+    size_t grid = 0;                    // workgroups: batch * nsteps
+};
+constexpr size_t COST_MAX_GRID = 0x7fffffff;
+inline CostPlan select_rollout_cost(const StepTraits& t, const int B, const int nsteps) {
+    CostPlan p;
+    if (t.spherical) p.kernel = CostKernel::RefusedSpherical;
+    else if (t.big || t.NP > 64) p.kernel = CostKernel::RefusedNodes;
+    else if (B < 1 || nsteps < 1 || (size_t)B * (size_t)nsteps > COST_MAX_GRID) p.kernel = CostKernel::RefusedGrid;
+    else {
+        p.np = t.NP;
+        p.grid = (size_t)B * (size_t)nsteps;
+    }
+    return p;
+}
+inline const char* label_rollout_cost() { return "k_rollout_cost"; }      // what rmx_last_step_kernel reports after the two entries
+
 }      // namespace rmx_select

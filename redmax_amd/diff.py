@@ -434,6 +434,126 @@ def lqr_backward(sim, lx, lu, Q, R, mu=0.0):
     return kff, K, expected, status != 0
 
 
+def _check_tensors(who, sim, named):
+    """float64 tensors on the sim's device, in the words of lqr_backward."""
+    import torch
+    dev = torch.device("cuda", sim.device)
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a torch.Tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise ValueError("%s: %s must be float64, got %s" % (who, name, t.dtype))
+        if t.device != dev:
+            raise ValueError("%s: %s must be on %s (the sim's device), got %s" % (who, name, dev, t.device))
+    return dev
+
+
+_Points = None
+
+
+def _points_function():
+    """The torch.autograd.Function of points, made on first use."""
+    global _Points
+    if _Points is not None:
+        return _Points
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _PointsFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, q, sim, terms):
+            B, N, _ = q.shape
+            qc = q.detach().contiguous()
+            x = torch.empty((B, len(terms), 3), dtype=torch.float64, device=q.device)
+            torch.cuda.current_stream(q.device).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+            sim.rollout_points_device(N, qc.data_ptr(), terms, x_ptr=x.data_ptr())
+            ctx.sim, ctx.terms = sim, terms
+            ctx.save_for_backward(qc)
+            return x
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gx):
+            (qc,) = ctx.saved_tensors
+            gxc = gx.contiguous()
+            gq = torch.empty_like(qc)
+            torch.cuda.current_stream(qc.device).synchronize()
+            ctx.sim.rollout_points_device(qc.shape[1], qc.data_ptr(), ctx.terms, gx_ptr=gxc.data_ptr(), gq_ptr=gq.data_ptr())
+            return gq, None, None
+
+    _Points = _PointsFn
+    return _Points
+
+
+def points(sim, q, terms):
+    """World positions of body points along a state record, differentiable: q [B][N][nr] -> x [B][nterms][3]
+    (rmx_rollout_points_device forward and, with the cotangents gx, backward).  terms: a list of dict(body, xlocal, step) -
+    ``BatchSim.adjoint_track``'s term without its weight; the point of term t is read at the posture q[:, step_t - 1].  It composes
+    with ``rollout``: any task-space loss on ``points(sim, rollout(...)[0], terms)`` backpropagates to u, q0 and qdot0.  The Jacobian
+    is taken at the given state.  Needs no tape and leaves the sim's tape alone."""
+    _check_tensors("points", sim, (("q", q),))
+    if q.dim() != 3 or q.shape[0] != sim.B or q.shape[2] != sim.nr or q.shape[1] < 1:
+        raise ValueError("points: q must have shape (%d, nsteps, %d), got %r" % (sim.B, sim.nr, tuple(q.shape)))
+    terms = [dict(t) for t in terms]
+    if not terms:
+        raise ValueError("points: terms is empty")
+    return _points_function().apply(q, sim, terms)
+
+
+def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None, want=("J", "lx", "Q")):
+    """The cost of a trajectory and its second-order model for ``lqr_backward`` (rmx_rollout_cost_device, include/redmax_hip.h): a
+    joint-space quadratic - Q [N][2nr][2nr] or [B][N][2nr][2nr], symmetric; xgoal [N][2nr] or [B][N][2nr]; None: zero - plus point
+    targets - terms: a list of dict(body, xlocal, step, wpos), wpos >= 0; xtarget [nterms][3] or [B][nterms][3].  qtraj, qdtraj
+    [B][N][nr]: float64 tensors on the sim's device, as every table.  Returns a dict with the names in `want`: "J" [B], the cost
+    summed over the steps (Jk.sum(1)); "lx" [B][N][2nr], its exact gradient by the states; "Q" [B][N][2nr][2nr], the Gauss-Newton
+    model Q + sum_t w_t Jp_t'Jp_t (the curvature of the points is dropped), symmetric bit for bit - the per-rollout table
+    ``lqr_backward`` takes.  No rollout is run and the sim's tape is left alone."""
+    import torch
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("J", "lx", "Q") for w in want) or len(set(want)) != len(want):
+        raise ValueError("cost_model: want must name distinct outputs among 'J', 'lx', 'Q', got %r" % (want,))
+    named = [("qtraj", qtraj), ("qdtraj", qdtraj)] + [(n, t) for n, t in (("Q", Q), ("xgoal", xgoal), ("xtarget", xtarget)) if t is not None]
+    dev = _check_tensors("cost_model", sim, named)
+    B, nr = sim.B, sim.nr
+    if qtraj.dim() != 3 or qtraj.shape[0] != B or qtraj.shape[2] != nr or qtraj.shape[1] < 1:
+        raise ValueError("cost_model: qtraj must have shape (%d, nsteps, %d), got %r" % (B, nr, tuple(qtraj.shape)))
+    N = qtraj.shape[1]
+    if tuple(qdtraj.shape) != (B, N, nr):
+        raise ValueError("cost_model: qdtraj must have shape %r, got %r" % ((B, N, nr), tuple(qdtraj.shape)))
+    if Q is not None and tuple(Q.shape) not in ((N, 2 * nr, 2 * nr), (B, N, 2 * nr, 2 * nr)):
+        raise ValueError("cost_model: Q must have shape %r or %r, got %r" % ((N, 2 * nr, 2 * nr), (B, N, 2 * nr, 2 * nr), tuple(Q.shape)))
+    if xgoal is not None and tuple(xgoal.shape) not in ((N, 2 * nr), (B, N, 2 * nr)):
+        raise ValueError("cost_model: xgoal must have shape %r or %r, got %r" % ((N, 2 * nr), (B, N, 2 * nr), tuple(xgoal.shape)))
+    if Q is None and xgoal is None and terms is None:
+        raise ValueError("cost_model: neither a joint-space cost (Q, xgoal) nor terms")
+    nterms = 0
+    if terms is not None:
+        terms = [dict(t) for t in terms]
+        nterms = len(terms)
+        if xtarget is None:
+            raise ValueError("cost_model: xtarget is None")
+        if tuple(xtarget.shape) not in ((nterms, 3), (B, nterms, 3)):
+            raise ValueError("cost_model: xtarget must have shape (%d, 3) or (%d, %d, 3), got %r" % (nterms, B, nterms, tuple(xtarget.shape)))
+    qc, qdc = qtraj.detach().contiguous(), qdtraj.detach().contiguous()
+    Qc, xgc, xtc = (None if t is None else t.detach().contiguous() for t in (Q, xgoal, xtarget if terms is not None else None))
+    Jk = torch.empty((B, N), dtype=torch.float64, device=dev) if "J" in want else None
+    lx = torch.empty((B, N, 2 * nr), dtype=torch.float64, device=dev) if "lx" in want else None
+    Qo = torch.empty((B, N, 2 * nr, 2 * nr), dtype=torch.float64, device=dev) if "Q" in want else None
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
+    sim.rollout_cost_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q is not None and Q.dim() == 4,
+                            goal_per_rollout=xgoal is not None and xgoal.dim() == 3, terms=terms, xtarget_ptr=ptr(xtc),
+                            target_per_rollout=xtc is not None and xtc.dim() == 3, Jk_ptr=ptr(Jk), lx_ptr=ptr(lx), Qout_ptr=ptr(Qo))
+    out = {}
+    if Jk is not None:
+        out["J"] = Jk.sum(1)
+    if lx is not None:
+        out["lx"] = lx
+    if Qo is not None:
+        out["Q"] = Qo
+    return out
+
+
 _ClosedLoop = None
 
 

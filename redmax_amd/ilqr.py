@@ -45,11 +45,55 @@ class QuadraticCost:
         return torch.einsum("kij,bkj->bki", self.Q, x - self.xgoal), torch.einsum("ij,bkj->bki", self.R, u)
 
 
+class TrackingCost:
+    """J_b = sum_{k=1..N} 1/2 (x_k - xg_k)' Q_k (x_k - xg_k) + 1/2 u_k' R u_k + sum_t 1/2 w_t |p_t(q_{step_t}) - xtarget_t|^2:
+    QuadraticCost plus point targets in task space - a point of a body brought to a world target at a step.
+
+    sim: the BatchSim the rollouts run on; Q, R, xgoal: as QuadraticCost (Q, xgoal may be None: no joint-space state cost); terms: a
+    list of dict(body, xlocal, step, wpos), wpos >= 0 (``BatchSim.adjoint_track``'s term); xtarget: [nterms][3] or [B][nterms][3] -
+    float64 tensors on the sim's device.  The state part is evaluated on the device (``diff.cost_model``, rmx_rollout_cost_device):
+    the value and the gradient are exact, ``model`` returns the Gauss-Newton Hessian Q_k + sum_t w_t Jp_t'Jp_t per rollout - the
+    curvature of the points is dropped, so the table stays positive semi-definite.  The control part stays torch."""
+
+    def __init__(self, sim, Q, R, xgoal, terms, xtarget):
+        if R.dim() != 2 or R.shape[0] != R.shape[1] or R.shape[0] != sim.nr:
+            raise ValueError("TrackingCost: R must have shape (%d, %d), got %r" % (sim.nr, sim.nr, tuple(R.shape)))
+        self.sim, self.Q, self.R, self.xgoal = sim, Q, R, xgoal
+        self.terms, self.xtarget = [dict(t) for t in terms], xtarget
+
+    def _state(self, x, want):
+        from . import diff
+        nr = self.sim.nr
+        xg = self.xgoal
+        if xg is not None and xg.dim() == 3 and xg.shape[0] == 1:
+            xg = xg[0]
+        return diff.cost_model(self.sim, x[..., :nr], x[..., nr:], Q=self.Q, xgoal=xg, terms=self.terms, xtarget=self.xtarget, want=want)
+
+    def _lu(self, u):
+        import torch
+        return torch.einsum("ij,bkj->bki", self.R, u)
+
+    def value(self, x, u):
+        """J [B] of the states x [B][N][2nr] (after every step) and torques u [B][N][nr]."""
+        import torch
+        return self._state(x, ("J",))["J"] + 0.5 * torch.einsum("bki,ij,bkj->b", u, self.R, u)
+
+    def gradients(self, x, u):
+        """(lx [B][N][2nr], lu [B][N][nr]) = dJ/dx_k, dJ/du_k (exact)."""
+        return self._state(x, ("lx",))["lx"], self._lu(u)
+
+    def model(self, x, u):
+        """(lx, lu, Qfull [B][N][2nr][2nr]): the gradients and the Gauss-Newton Hessian of the state cost, one table per rollout."""
+        m = self._state(x, ("lx", "Q"))
+        return m["lx"], self._lu(u), m["Q"]
+
+
 def backward_pass(A, Bm, lx, lu, Q, R, mu=0.0):
     """The Riccati recursion of iLQR for a quadratic cost, batched: (k, K, expected).
 
     A [B][N][2nr][2nr], Bm [B][N][2nr][nr]: dx_k/dx_{k-1}, dx_k/du_k (``diff.linearize``); lx [B][N][2nr], lu [B][N][nr]: the cost's
-    gradients at the nominal; Q [N][2nr][2nr], R [nr][nr]: its Hessians; mu >= 0: the regulariser of Quu.  With V the cost-to-go at x_k
+    gradients at the nominal; Q [N][2nr][2nr], shared by the batch, or [B][N][2nr][2nr], one table per rollout (``TrackingCost.model``),
+    R [nr][nr]: its Hessians; mu >= 0: the regulariser of Quu.  With V the cost-to-go at x_k
     (state cost of step k included; Vx_N = lx_N, Vxx_N = Q_N), for k = N .. 1:
         Qx = A' Vx        Qu = lu + B' Vx        Qxx = A' Vxx A        Qux = B' Vxx A        Quu = R + B' Vxx B + mu I
         k = -Quu^-1 Qu    K = -Quu^-1 Qux
@@ -65,7 +109,8 @@ def backward_pass(A, Bm, lx, lu, Q, R, mu=0.0):
     expected = torch.zeros(B, dtype=A.dtype, device=A.device)
     eye = torch.eye(nu, dtype=A.dtype, device=A.device)
     Vx = lx[:, N - 1]
-    Vxx = Q[N - 1].expand(B, nx, nx)
+    per = Q.dim() == 4                                                 # one table per rollout
+    Vxx = Q[:, N - 1] if per else Q[N - 1].expand(B, nx, nx)
     for s in range(N - 1, -1, -1):
         Ak, Bk = A[:, s], Bm[:, s]
         BtV = Bk.transpose(1, 2) @ Vxx
@@ -87,7 +132,7 @@ def backward_pass(A, Bm, lx, lu, Q, R, mu=0.0):
         Vxx = 0.5 * (Vxx + Vxx.transpose(1, 2))
         if s > 0:
             Vx = Vx + lx[:, s - 1]
-            Vxx = Vxx + Q[s - 1]
+            Vxx = Vxx + (Q[:, s - 1] if per else Q[s - 1])
     return kff, K, expected
 
 
@@ -97,7 +142,9 @@ Result = namedtuple("Result", "u qtraj qdtraj cost alpha")
 def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0, backward="torch", ulim=None):
     """Batched iLQR: one problem per rollout of ``sim`` (a BatchSim), BDF1.  Returns (result, history).
 
-    q0, qdot0 [B][nr], u0 [B][N][nr]: float64 tensors on the sim's device; cost: a QuadraticCost on that device.  Each iteration
+    q0, qdot0 [B][nr], u0 [B][N][nr]: float64 tensors on the sim's device; cost: a QuadraticCost on that device, or a cost with
+    ``value``, ``R`` and ``model(x, u) -> (lx, lu, Q [B][N][2nr][2nr])`` - a TrackingCost, whose Q is a Gauss-Newton table per
+    rollout.  Each iteration
       1. linearises the nominal (``diff.linearize`` at the nominal torques) and runs ``backward_pass``;
       2. for each alpha in turn launches ``diff.rollout_feedback`` on the whole batch with uff = ubar + alpha_b k, the gains K per
          rollout and xref = xbar; a rollout keeps the FIRST alpha that lowers its own cost and is launched with that alpha again
@@ -128,7 +175,8 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
         raise ValueError("solve: torque limits (ulim) need backward='device': the box-constrained backward pass exists on the device alone")
     diff._check_inputs(sim, q0, qdot0, u0)
     B, N, nr = u0.shape
-    if tuple(cost.Q.shape) != (N, 2 * nr, 2 * nr):
+    has_model = hasattr(cost, "model")                                 # a cost with a Hessian of its own per rollout (TrackingCost)
+    if not has_model and tuple(cost.Q.shape) != (N, 2 * nr, 2 * nr):
         raise ValueError("solve: the cost is for %d steps of %d states, the rollout has %d steps of %d" % (cost.Q.shape[0], cost.Q.shape[1], N, 2 * nr))
     x0 = torch.cat([q0, qdot0], dim=-1).unsqueeze(1)
     kw = dict(h=h, pscale=pscale, integrator=1)
@@ -149,21 +197,27 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
         raise RuntimeError("solve: the rollout under u0 failed")
     history = [Jbar]
     alpha = torch.zeros(B, dtype=torch.float64, device=u0.device)
+
+    def quadratic_model():                                             # (lx, lu, Q) of the cost at the nominal
+        if has_model:
+            return cost.model(xbar, ubar)
+        return cost.gradients(xbar, ubar) + (cost.Q,)
+
     for _ in range(int(iters)):
         if backward == "device":
             # the last launch held the accepted trajectories only (points 2 and 4): its open-loop tape under ubar IS the nominal's
             if sim.tape_count != tape[0]:
                 raise RuntimeError("the tape of this rollout has been replaced")
-            lx, lu = cost.gradients(xbar, ubar)
+            lx, lu, Qk = quadratic_model()
             if ulim is not None:
-                kff, Kabi, _, st, _ = diff.lqr_backward_box(sim, lx, lu, cost.Q, cost.R, ubar, ulim, mu)
+                kff, Kabi, _, st, _ = diff.lqr_backward_box(sim, lx, lu, Qk, cost.R, ubar, ulim, mu)
                 notpd = st != 0
             else:
-                kff, Kabi, _, notpd = diff.lqr_backward(sim, lx, lu, cost.Q, cost.R, mu)
+                kff, Kabi, _, notpd = diff.lqr_backward(sim, lx, lu, Qk, cost.R, mu)
         else:
             _, _, A, Bm = diff.linearize(sim, q0, qdot0, ubar, **{k: v for k, v in kw.items() if k not in ("integrator", "ulim")})
-            lx, lu = cost.gradients(xbar, ubar)
-            kff, K, _ = backward_pass(A, Bm, lx, lu, cost.Q, cost.R, mu)
+            lx, lu, Qk = quadratic_model()
+            kff, K, _ = backward_pass(A, Bm, lx, lu, Qk, cost.R, mu)
             Kabi = K.transpose(-1, -2).contiguous()
             notpd = None
         xref = torch.cat([x0, xbar[:, :-1]], dim=1).contiguous()      # the nominal state at the START of every step
