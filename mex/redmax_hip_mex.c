@@ -183,6 +183,25 @@ static rmx_batch* shard(const handle_t* h, int s, size_t* first) {
     *first = (size_t)f;
     return rmx_group_shard_batch(h->g, s);
 }
+/* the rmx_stats of the shard that begins at rollout f: its rows of the B x 2 int32 output st = [newton iterations, status] */
+static rmx_stats shard_stats(mxArray* st, const handle_t* h, size_t f) {
+    int* sp = (int*)mxGetData(st);
+    rmx_stats s;
+    s.newton_iters = sp + f;
+    s.ls_halvings = NULL;
+    s.status = sp + h->B + f;
+    return s;
+}
+/* the part of the shard that begins at rollout f of a table that is NULL, shared by the batch, or holds `per` doubles per rollout */
+static const double* table_at(const double* t, int per_rollout, size_t f, size_t per) { return (t && per_rollout) ? t + f * per : t; }
+/* the tail of a command: out[0] is returned always, out[i] where the caller asked for it, else destroyed (NULL: never made) */
+static void give(int nlhs, mxArray* plhs[], mxArray* const out[], int n) {
+    plhs[0] = out[0];
+    for (int i = 1; i < n; ++i) {
+        if (nlhs > i) plhs[i] = out[i];
+        else if (out[i]) mxDestroyArray(out[i]);
+    }
+}
 
 /* Scene.init() (Scene.m:59-119) -> rmx_model_create.  desc fields, joints in the scene's listing order (N = njoints):
  *   njoints; parent int32 1xN (0-based, -1 root); type int32 1xN (RMX_JOINT_*); axis 3xN; E0_pj, E0_ji 4x4xN; I_i 6xN;
@@ -439,8 +458,8 @@ static void cmd_euler(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]
             mxFree(tmp);
         }
     }
-    plhs[0] = T;
-    if (nlhs > 1) plhs[1] = V;
+    mxArray* const out[2] = {T, V};
+    give(nlhs, plhs, out, 2);
 }
 
 static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -461,8 +480,8 @@ static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
         const size_t o = f * (size_t)h->nr;
         if (rmx_eval(b, q + o, qA + o, qB + o, mxGetScalar(prhs[5]), mxGetPr(g) + o, H ? mxGetPr(H) + o * (size_t)h->nr : NULL)) die_rmx("rmx_eval");
     }
-    plhs[0] = g;
-    if (nlhs > 1) plhs[1] = H;
+    mxArray* const out[2] = {g, H};
+    give(nlhs, plhs, out, 2);
 }
 
 /* [M,f,K,D,dMv] = redmax_hip_mex('values', h, q, qdot [, v]) - computeValues' full output (driverRedMaxBDF1.m:188-243: [M,f,dMdq,K,D])
@@ -494,6 +513,15 @@ static void cmd_values(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
     for (int i = 0; i < 5 && (i == 0 || i < nlhs); ++i) plhs[i] = out[i];
 }
 
+/* the options of an 'adjoint*' or tape-recording command: the defaults under the step size of the call */
+static rmx_opts tape_opts(double hstep) {
+    rmx_opts o;
+    rmx_opts_default(&o);
+    o.h = hstep;
+    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    return o;
+}
+
 /* the task struct of 'adjoint' / 'adjoint_controls' (TaskBDF1PointPos) */
 static void read_task(const mxArray* t, rmx_task_pointpos* task) {
     if (!mxIsStruct(t)) die("task must be a struct");
@@ -515,37 +543,25 @@ static void cmd_adjoint(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     if (nrhs < 6) die("usage: [P,dPdp,stats] = redmax_hip_mex('adjoint', h, hstep, nsteps, task, p [, integrator])");
     rmx_task_pointpos task;
     read_task(prhs[4], &task);
-    rmx_opts o;
-    rmx_opts_default(&o);
-    o.h = mxGetScalar(prhs[2]);
-    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    const rmx_opts o = tape_opts(mxGetScalar(prhs[2]));
     const int nsteps = (int)mxGetScalar(prhs[3]);
     const double* p = state_arg(prhs[5], h, "p");
     mxArray* P = mxCreateDoubleMatrix(1, (size_t)h->B, mxREAL);
     mxArray* dPdp = mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL);
     mxArray* st = new_i32((size_t)h->B, 2);
-    int* sp = (int*)mxGetData(st);
-    rmx_stats stats;
-    stats.newton_iters = sp;
-    stats.ls_halvings = NULL;
-    stats.status = sp + h->B;
     /* optional 7th argument: the integrator, 1 = BDF1 (driverRedMaxAdjointBDF1.m, default), 2 = BDF2 (driverRedMaxAdjointBDF2.m) */
     const int integ = nrhs > 6 ? (int)mxGetScalar(prhs[6]) : 1;
     if (integ != 1 && integ != 2) die("adjoint: the integrator must be 1 (BDF1) or 2 (BDF2)");
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard (the adjoint has no asynchronous entry: its outputs are per-call host buffers) */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        rmx_stats st_s;
-        st_s.newton_iters = stats.newton_iters + f;
-        st_s.ls_halvings = NULL;
-        st_s.status = stats.status + f;
+        rmx_stats st_s = shard_stats(st, h, f);
         if ((integ == 1 ? rmx_adjoint_bdf1 : rmx_adjoint_bdf2)(b, &o, nsteps, &task, p + f * (size_t)h->nr, mxGetPr(P) + f,
                                                                 mxGetPr(dPdp) + f * (size_t)h->nr, &st_s))
             die_rmx(integ == 1 ? "rmx_adjoint_bdf1" : "rmx_adjoint_bdf2");
     }
-    plhs[0] = P;
-    if (nlhs > 1) plhs[1] = dPdp;
-    if (nlhs > 2) plhs[2] = st;
+    mxArray* const out[3] = {P, dPdp, st};
+    give(nlhs, plhs, out, 3);
 }
 
 static void cmd_adjoint_controls(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -553,10 +569,7 @@ static void cmd_adjoint_controls(int nlhs, mxArray* plhs[], int nrhs, const mxAr
     if (nrhs < 6) die("usage: [P,dPdu,stats] = redmax_hip_mex('adjoint_controls', h, hstep, nsteps, task, u [, integrator])");
     rmx_task_pointpos task;
     read_task(prhs[4], &task);
-    rmx_opts o;
-    rmx_opts_default(&o);
-    o.h = mxGetScalar(prhs[2]);
-    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    const rmx_opts o = tape_opts(mxGetScalar(prhs[2]));
     const int nsteps = (int)mxGetScalar(prhs[3]);
     if (nsteps < 1) die("adjoint_controls: nsteps must be at least 1");
     const int integ = nrhs > 6 ? (int)mxGetScalar(prhs[6]) : 1;
@@ -573,21 +586,15 @@ static void cmd_adjoint_controls(int nlhs, mxArray* plhs[], int nrhs, const mxAr
         dPdu = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
     }
     mxArray* st = new_i32((size_t)h->B, 2);
-    int* sp = (int*)mxGetData(st);
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'adjoint' */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        rmx_stats st_s;
-        st_s.newton_iters = sp + f;
-        st_s.ls_halvings = NULL;
-        st_s.status = sp + h->B + f;
+        rmx_stats st_s = shard_stats(st, h, f);
         if (rmx_adjoint_controls(b, &o, nsteps, integ, &task, u + f * per, mxGetPr(P) + f, dPdu ? mxGetPr(dPdu) + f * per : NULL, &st_s))
             die_rmx("rmx_adjoint_controls");
     }
-    plhs[0] = P;
-    if (nlhs > 1) plhs[1] = dPdu;
-    if (nlhs > 2) plhs[2] = st;
-    else mxDestroyArray(st);
+    mxArray* const out[3] = {P, dPdu, st};
+    give(nlhs, plhs, out, 3);
 }
 
 /* an nr x nsteps x B argument of 'rollout_tape' / 'rollout_vjp' (the ABI's [B][nsteps][nr]) */
@@ -597,43 +604,42 @@ static const double* traj_arg(const mxArray* a, const handle_t* h, int nsteps, c
     return mxGetPr(a);
 }
 
+/* the head of a tape-recording command `cmd` ('rollout_tape', 'rollout_feedback', 'rollout_feedback_box'): hstep, nsteps, pscale in
+ * prhs[2..4], the required arguments up to prhs[nreq - 1] and the optional integrator behind them */
+typedef struct { rmx_opts o; int nsteps, integ; double pscale; } tape_head_t;
+static tape_head_t tape_head(int nrhs, const mxArray* prhs[], int nreq, const char* cmd, const char* usage) {
+    tape_head_t t;
+    if (nrhs < nreq) die(usage);
+    const double integ_arg = nrhs > nreq ? mxGetScalar(prhs[nreq]) : 1.0;
+    if (integ_arg != 1.0 && integ_arg != 2.0) mexErrMsgIdAndTxt("redmax:hip", "%s: integrator must be 1 (BDF1) or 2 (BDF2)", cmd);
+    t.integ = integ_arg == 2.0 ? 2 : 1;
+    t.o = tape_opts(mxGetScalar(prhs[2]));
+    t.nsteps = (int)mxGetScalar(prhs[3]);
+    if (t.nsteps < 1) mexErrMsgIdAndTxt("redmax:hip", "%s: nsteps must be at least 1", cmd);
+    t.pscale = mxGetScalar(prhs[4]);
+    return t;
+}
+
 static void cmd_rollout_tape(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 6) die("usage: [qtraj,qdtraj,stats] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u [, integrator])");
-    const double integ_arg = nrhs > 6 ? mxGetScalar(prhs[6]) : 1.0;
-    if (integ_arg != 1.0 && integ_arg != 2.0) die("rollout_tape: integrator must be 1 (BDF1) or 2 (BDF2)");
-    const int integ = integ_arg == 2.0 ? 2 : 1;
-    rmx_opts o;
-    rmx_opts_default(&o);
-    o.h = mxGetScalar(prhs[2]);
-    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
-    const int nsteps = (int)mxGetScalar(prhs[3]);
-    if (nsteps < 1) die("rollout_tape: nsteps must be at least 1");
-    const double pscale = mxGetScalar(prhs[4]);
+    const tape_head_t t = tape_head(nrhs, prhs, 6, "rollout_tape",
+                                    "usage: [qtraj,qdtraj,stats] = redmax_hip_mex('rollout_tape', h, hstep, nsteps, pscale, u [, integrator])");
+    const int nsteps = t.nsteps;
     const double* u = traj_arg(prhs[5], h, nsteps, "u");
     const size_t per = (size_t)h->nr * (size_t)nsteps;
     const size_t dims[3] = {(size_t)h->nr, (size_t)nsteps, (size_t)h->B};
-    mxArray* qt = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
-    mxArray* qdt = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
-    mxArray* st = new_i32((size_t)h->B, 2);
-    int* sp = (int*)mxGetData(st);
+    mxArray* const out[3] = {mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL), mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL),
+                             new_i32((size_t)h->B, 2)};
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'adjoint_controls' */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        rmx_stats st_s;
-        st_s.newton_iters = sp + f;
-        st_s.ls_halvings = NULL;
-        st_s.status = sp + h->B + f;
-        if ((integ == 2 ? rmx_rollout_tape_bdf2 : rmx_rollout_tape)(b, &o, nsteps, pscale, u + f * per, mxGetPr(qt) + f * per,
-                                                                    mxGetPr(qdt) + f * per, &st_s))
-            die_rmx(integ == 2 ? "rmx_rollout_tape_bdf2" : "rmx_rollout_tape");
+        rmx_stats st_s = shard_stats(out[2], h, f);
+        if ((t.integ == 2 ? rmx_rollout_tape_bdf2 : rmx_rollout_tape)(b, &t.o, nsteps, t.pscale, u + f * per, mxGetPr(out[0]) + f * per,
+                                                                      mxGetPr(out[1]) + f * per, &st_s))
+            die_rmx(t.integ == 2 ? "rmx_rollout_tape_bdf2" : "rmx_rollout_tape");
     }
-    h->tape_integ = integ;
-    plhs[0] = qt;
-    if (nlhs > 1) plhs[1] = qdt;
-    else mxDestroyArray(qdt);
-    if (nlhs > 2) plhs[2] = st;
-    else mxDestroyArray(st);
+    h->tape_integ = t.integ;
+    give(nlhs, plhs, out, 3);
 }
 
 /* a table argument of 'rollout_feedback': [] (NULL), `per` elements per step shared by the batch, or as many for every rollout;
@@ -649,56 +655,6 @@ static const double* feedback_arg(const mxArray* a, const handle_t* h, size_t pe
     return mxGetPr(a);
 }
 
-static void cmd_rollout_feedback(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 8) die("usage: [qtraj,qdtraj,uapp,stats] = redmax_hip_mex('rollout_feedback', h, hstep, nsteps, pscale, uff, K, xref [, integrator])");
-    const double integ_arg = nrhs > 8 ? mxGetScalar(prhs[8]) : 1.0;
-    if (integ_arg != 1.0 && integ_arg != 2.0) die("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2)");
-    const int integ = integ_arg == 2.0 ? 2 : 1;
-    rmx_opts o;
-    rmx_opts_default(&o);
-    o.h = mxGetScalar(prhs[2]);
-    o.iterMaxPerDof = 5;                               /* as 'rollout_tape' */
-    const int nsteps = (int)mxGetScalar(prhs[3]);
-    if (nsteps < 1) die("rollout_feedback: nsteps must be at least 1");
-    const double pscale = mxGetScalar(prhs[4]);
-    const double* uff = traj_arg(prhs[5], h, nsteps, "uff");
-    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps;
-    int per_rollout = -1;
-    const double* K = feedback_arg(prhs[6], h, 2 * nr * nr, nsteps, &per_rollout, "K");            /* nr x 2nr x nsteps [x B] */
-    const double* xref = feedback_arg(prhs[7], h, 2 * nr, nsteps, &per_rollout, "xref");           /* 2nr x nsteps [x B] */
-    if (per_rollout < 0) per_rollout = 0;
-    const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B};
-    mxArray* out[3];
-    for (int i = 0; i < 3; ++i) out[i] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
-    mxArray* st = new_i32((size_t)h->B, 2);
-    int* sp = (int*)mxGetData(st);
-    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'rollout_tape' */
-        size_t f;
-        rmx_batch* b = shard(h, s, &f);
-        rmx_stats st_s;
-        st_s.newton_iters = sp + f;
-        st_s.ls_halvings = NULL;
-        st_s.status = sp + h->B + f;
-        rmx_feedback fb;
-        fb.uff = uff + f * per;
-        fb.K = K ? K + (per_rollout ? f * (size_t)nsteps * 2 * nr * nr : 0) : NULL;
-        fb.xref = xref ? xref + (per_rollout ? f * (size_t)nsteps * 2 * nr : 0) : NULL;
-        fb.per_rollout = per_rollout;
-        if (rmx_rollout_tape_feedback(b, &o, nsteps, integ, pscale, &fb, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * per,
-                                      mxGetPr(out[2]) + f * per, &st_s))
-            die_rmx("rmx_rollout_tape_feedback");
-    }
-    h->tape_integ = integ;
-    plhs[0] = out[0];
-    for (int i = 1; i < 3; ++i) {
-        if (nlhs > i) plhs[i] = out[i];
-        else mxDestroyArray(out[i]);
-    }
-    if (nlhs > 3) plhs[3] = st;
-    else mxDestroyArray(st);
-}
-
 /* a limit argument of 'rollout_feedback_box' / 'rollout_lqr_box': [] (NULL: that side is unbounded) or nr doubles */
 static const double* bound_arg(const mxArray* a, const handle_t* h, const char* cmd, const char* what) {
     if (mxIsEmpty(a)) return NULL;
@@ -707,59 +663,46 @@ static const double* bound_arg(const mxArray* a, const handle_t* h, const char* 
     return mxGetPr(a);
 }
 
-/* 'rollout_feedback_box': 'rollout_feedback' with the applied torque clamped into ulo <= u <= uhi (rmx_rollout_tape_feedback_box) */
-static void cmd_rollout_feedback_box(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+/* 'rollout_feedback' and, with box, 'rollout_feedback_box': the same with the applied torque clamped into ulo <= u <= uhi
+ * (rmx_rollout_tape_feedback_box); the limits push the optional integrator two arguments back */
+static void cmd_rollout_feedback(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int box) {
     handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 10)
-        die("usage: [qtraj,qdtraj,uapp,stats] = redmax_hip_mex('rollout_feedback_box', h, hstep, nsteps, pscale, uff, K, xref, ulo, uhi [, integrator])");
-    const double integ_arg = nrhs > 10 ? mxGetScalar(prhs[10]) : 1.0;
-    if (integ_arg != 1.0 && integ_arg != 2.0) die("rollout_feedback_box: integrator must be 1 (BDF1) or 2 (BDF2)");
-    const int integ = integ_arg == 2.0 ? 2 : 1;
-    rmx_opts o;
-    rmx_opts_default(&o);
-    o.h = mxGetScalar(prhs[2]);
-    o.iterMaxPerDof = 5;                               /* as 'rollout_tape' */
-    const int nsteps = (int)mxGetScalar(prhs[3]);
-    if (nsteps < 1) die("rollout_feedback_box: nsteps must be at least 1");
-    const double pscale = mxGetScalar(prhs[4]);
+    const char* cmd = box ? "rollout_feedback_box" : "rollout_feedback";
+    const tape_head_t t = tape_head(nrhs, prhs, box ? 10 : 8, cmd, box
+        ? "usage: [qtraj,qdtraj,uapp,stats] = redmax_hip_mex('rollout_feedback_box', h, hstep, nsteps, pscale, uff, K, xref, ulo, uhi [, integrator])"
+        : "usage: [qtraj,qdtraj,uapp,stats] = redmax_hip_mex('rollout_feedback', h, hstep, nsteps, pscale, uff, K, xref [, integrator])");
+    const int nsteps = t.nsteps;
     const double* uff = traj_arg(prhs[5], h, nsteps, "uff");
     const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps;
     int per_rollout = -1;
-    const double* K = feedback_arg(prhs[6], h, 2 * nr * nr, nsteps, &per_rollout, "K");
-    const double* xref = feedback_arg(prhs[7], h, 2 * nr, nsteps, &per_rollout, "xref");
+    const double* K = feedback_arg(prhs[6], h, 2 * nr * nr, nsteps, &per_rollout, "K");            /* nr x 2nr x nsteps [x B] */
+    const double* xref = feedback_arg(prhs[7], h, 2 * nr, nsteps, &per_rollout, "xref");           /* 2nr x nsteps [x B] */
     if (per_rollout < 0) per_rollout = 0;
-    rmx_box box;
-    box.ulo = bound_arg(prhs[8], h, "rollout_feedback_box", "ulo");
-    box.uhi = bound_arg(prhs[9], h, "rollout_feedback_box", "uhi");
+    rmx_box lim = {NULL, NULL};
+    if (box) {
+        lim.ulo = bound_arg(prhs[8], h, cmd, "ulo");
+        lim.uhi = bound_arg(prhs[9], h, cmd, "uhi");
+    }
     const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B};
-    mxArray* out[3];
+    mxArray* out[4];
     for (int i = 0; i < 3; ++i) out[i] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
-    mxArray* st = new_i32((size_t)h->B, 2);
-    int* sp = (int*)mxGetData(st);
+    out[3] = new_i32((size_t)h->B, 2);
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'rollout_tape' */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        rmx_stats st_s;
-        st_s.newton_iters = sp + f;
-        st_s.ls_halvings = NULL;
-        st_s.status = sp + h->B + f;
+        rmx_stats st_s = shard_stats(out[3], h, f);
         rmx_feedback fb;
         fb.uff = uff + f * per;
-        fb.K = K ? K + (per_rollout ? f * (size_t)nsteps * 2 * nr * nr : 0) : NULL;
-        fb.xref = xref ? xref + (per_rollout ? f * (size_t)nsteps * 2 * nr : 0) : NULL;
+        fb.K = table_at(K, per_rollout, f, per * 2 * nr);
+        fb.xref = table_at(xref, per_rollout, f, per * 2);
         fb.per_rollout = per_rollout;
-        if (rmx_rollout_tape_feedback_box(b, &o, nsteps, integ, pscale, &fb, &box, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * per,
-                                          mxGetPr(out[2]) + f * per, &st_s))
-            die_rmx("rmx_rollout_tape_feedback_box");
+        double *qt = mxGetPr(out[0]) + f * per, *qdt = mxGetPr(out[1]) + f * per, *uapp = mxGetPr(out[2]) + f * per;
+        if (box ? rmx_rollout_tape_feedback_box(b, &t.o, nsteps, t.integ, t.pscale, &fb, &lim, qt, qdt, uapp, &st_s)
+                : rmx_rollout_tape_feedback(b, &t.o, nsteps, t.integ, t.pscale, &fb, qt, qdt, uapp, &st_s))
+            die_rmx(box ? "rmx_rollout_tape_feedback_box" : "rmx_rollout_tape_feedback");
     }
-    h->tape_integ = integ;
-    plhs[0] = out[0];
-    for (int i = 1; i < 3; ++i) {
-        if (nlhs > i) plhs[i] = out[i];
-        else mxDestroyArray(out[i]);
-    }
-    if (nlhs > 3) plhs[3] = st;
-    else mxDestroyArray(st);
+    h->tape_integ = t.integ;
+    give(nlhs, plhs, out, 4);
 }
 
 static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -771,21 +714,16 @@ static void cmd_rollout_vjp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     const double* gqd = traj_arg(prhs[4], h, nsteps, "gqd");
     const size_t per = (size_t)h->nr * (size_t)nsteps;
     const size_t dims[3] = {(size_t)h->nr, (size_t)nsteps, (size_t)h->B};
-    mxArray* du = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
-    mxArray* dq0 = mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL);
-    mxArray* dqd0 = mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL);
+    mxArray* const out[3] = {mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL), mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL),
+                             mxCreateDoubleMatrix((size_t)h->nr, (size_t)h->B, mxREAL)};      /* du, dq0, dqd0 */
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        if (rmx_rollout_vjp(b, nsteps, gq + f * per, gqd + f * per, mxGetPr(du) + f * per, mxGetPr(dq0) + f * (size_t)h->nr,
-                            mxGetPr(dqd0) + f * (size_t)h->nr))
+        if (rmx_rollout_vjp(b, nsteps, gq + f * per, gqd + f * per, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * (size_t)h->nr,
+                            mxGetPr(out[2]) + f * (size_t)h->nr))
             die_rmx("rmx_rollout_vjp");
     }
-    plhs[0] = du;
-    if (nlhs > 1) plhs[1] = dq0;
-    else mxDestroyArray(dq0);
-    if (nlhs > 2) plhs[2] = dqd0;
-    else mxDestroyArray(dqd0);
+    give(nlhs, plhs, out, 3);
 }
 
 /* 'rollout_vjp_feedback': the closed-loop adjoint on the tape 'rollout_feedback' left.  K, xref as there ([]: none); gu [] or as gq.
@@ -816,8 +754,8 @@ static void cmd_rollout_vjp_feedback(int nlhs, mxArray* plhs[], int nrhs, const 
         rmx_batch* b = shard(h, s, &f);
         rmx_feedback fb;
         fb.uff = NULL;
-        fb.K = K ? K + (per_rollout ? f * (size_t)nsteps * 2 * nr * nr : 0) : NULL;
-        fb.xref = xref ? xref + (per_rollout ? f * (size_t)nsteps * 2 * nr : 0) : NULL;
+        fb.K = table_at(K, per_rollout, f, per * 2 * nr);
+        fb.xref = table_at(xref, per_rollout, f, per * 2);
         fb.per_rollout = per_rollout;
         rmx_feedback_grads g;
         g.duff = mxGetPr(out[0]) + f * per;
@@ -827,11 +765,7 @@ static void cmd_rollout_vjp_feedback(int nlhs, mxArray* plhs[], int nrhs, const 
         g.dqd0 = mxGetPr(out[4]) + f * nr;
         if (rmx_rollout_vjp_feedback(b, nsteps, &fb, gq + f * per, gqd + f * per, gu ? gu + f * per : NULL, &g)) die_rmx("rmx_rollout_vjp_feedback");
     }
-    plhs[0] = out[0];
-    for (int i = 1; i < 5; ++i) {
-        if (nlhs > i) plhs[i] = out[i];
-        else mxDestroyArray(out[i]);
-    }
+    give(nlhs, plhs, out, 5);
 }
 
 static void cmd_rollout_vjp_params(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -861,11 +795,7 @@ static void cmd_rollout_vjp_params(int nlhs, mxArray* plhs[], int nrhs, const mx
                                    mxGetPr(out[2]) + f * nr, &pg))
             die_rmx("rmx_rollout_vjp_params");
     }
-    plhs[0] = out[0];
-    for (int i = 1; i < 8; ++i) {
-        if (nlhs > i) plhs[i] = out[i];
-        else mxDestroyArray(out[i]);
-    }
+    give(nlhs, plhs, out, 8);
 }
 
 static void cmd_rollout_linearize(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -897,109 +827,61 @@ static const double* lqr_arg(const mxArray* a, size_t want, size_t alt, const ch
     return mxGetPr(a);
 }
 
-static void cmd_rollout_lqr(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+/* 'rollout_lqr' (fourth output notpd, 1 x B: 0 or 1) and, with box, 'rollout_lqr_box': the same under the torque limits ulo <= u <= uhi
+ * (rmx_rollout_lqr_box) - the fourth output is status 1 x B (0, 1: a pivot not > 0, 2: a QP did not terminate), the fifth clamped
+ * nsteps x B (the bit masks as doubles: nr <= 32, exact); ubar and the limits push the optional mu three arguments back */
+static void cmd_rollout_lqr(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int box) {
     handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 7) die("usage: [kff,K,expected,notpd] = redmax_hip_mex('rollout_lqr', h, nsteps, lx, lu, Q, R [, mu])");
+    if (nrhs < (box ? 10 : 7))
+        die(box ? "usage: [kff,K,expected,status,clamped] = redmax_hip_mex('rollout_lqr_box', h, nsteps, lx, lu, Q, R, ubar, ulo, uhi [, mu [, max_iter]])"
+                : "usage: [kff,K,expected,notpd] = redmax_hip_mex('rollout_lqr', h, nsteps, lx, lu, Q, R [, mu])");
     const int nsteps = (int)mxGetScalar(prhs[2]);
-    if (nsteps < 1) die("rollout_lqr: nsteps must be at least 1");
+    if (nsteps < 1) die(box ? "rollout_lqr_box: nsteps must be at least 1" : "rollout_lqr: nsteps must be at least 1");
     const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
     const size_t perq = 4 * nr * nr * N;
     const double* lx = lqr_arg(prhs[3], 2 * nr * N * B, 0, "lx", "2nr x nsteps x batch");
     const double* lu = lqr_arg(prhs[4], nr * N * B, 0, "lu", "nr x nsteps x batch");
     const double* Q = lqr_arg(prhs[5], perq, perq * B, "Q", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
     const double* R = lqr_arg(prhs[6], nr * nr, 0, "R", "nr x nr");
+    const double* ubar = box ? lqr_arg(prhs[7], nr * N * B, 0, "ubar", "nr x nsteps x batch") : NULL;
+    rmx_box lim = {NULL, NULL};
+    if (box) {
+        lim.ulo = bound_arg(prhs[8], h, "rollout_lqr_box", "ulo");
+        lim.uhi = bound_arg(prhs[9], h, "rollout_lqr_box", "uhi");
+    }
+    const int imu = box ? 10 : 7;      /* where the optional mu stands */
+    const int max_iter = (box && nrhs > 11) ? (int)mxGetScalar(prhs[11]) : 0;
+    const size_t dk[3] = {nr, N, B}, dK[4] = {nr, 2 * nr, N, B};
+    mxArray* const out[5] = {mxCreateNumericArray(3, dk, mxDOUBLE_CLASS, mxREAL), mxCreateNumericArray(4, dK, mxDOUBLE_CLASS, mxREAL),
+                             mxCreateDoubleMatrix(1, B, mxREAL), mxCreateDoubleMatrix(1, B, mxREAL),
+                             box ? mxCreateDoubleMatrix(N, B, mxREAL) : NULL};      /* kff, K, expected, notpd | status, clamped */
+    int* status = (int*)mxCalloc(B, sizeof *status);
+    unsigned* mask = box ? (unsigned*)mxCalloc(N * B, sizeof *mask) : NULL;
+    rmx_lqr_cost cost;
+    memset(&cost, 0, sizeof cost);
+    cost.R = R;
     /* (a batch of one: Q is one table either way) */
-    const int per_rollout = mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
-    const size_t dk[3] = {nr, N, B}, dK[4] = {nr, 2 * nr, N, B};
-    mxArray* kff = mxCreateNumericArray(3, dk, mxDOUBLE_CLASS, mxREAL);
-    mxArray* K = mxCreateNumericArray(4, dK, mxDOUBLE_CLASS, mxREAL);
-    mxArray* ex = mxCreateDoubleMatrix(1, B, mxREAL);
-    mxArray* bad = mxCreateDoubleMatrix(1, B, mxREAL);
-    int* status = (int*)mxCalloc(B, sizeof *status);
-    rmx_lqr_cost cost;
-    memset(&cost, 0, sizeof cost);
-    cost.R = R;
-    cost.per_rollout = per_rollout;
-    cost.mu = nrhs > 7 ? mxGetScalar(prhs[7]) : 0.0;
+    cost.per_rollout = mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
+    cost.mu = nrhs > imu ? mxGetScalar(prhs[imu]) : 0.0;
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        rmx_lqr_gains out;
+        rmx_lqr_gains g;
         cost.lx = lx + f * 2 * nr * N;
         cost.lu = lu + f * nr * N;
-        cost.Q = per_rollout ? Q + f * perq : Q;
-        out.kff = mxGetPr(kff) + f * nr * N;
-        out.K = mxGetPr(K) + f * 2 * nr * nr * N;
-        out.expected = mxGetPr(ex) + f;
-        out.status = status + f;
-        if (rmx_rollout_lqr(b, nsteps, &cost, &out)) die_rmx("rmx_rollout_lqr");
+        cost.Q = table_at(Q, cost.per_rollout, f, perq);
+        g.kff = mxGetPr(out[0]) + f * nr * N;
+        g.K = mxGetPr(out[1]) + f * 2 * nr * nr * N;
+        g.expected = mxGetPr(out[2]) + f;
+        g.status = status + f;
+        if (box ? rmx_rollout_lqr_box(b, nsteps, &cost, &lim, ubar + f * nr * N, max_iter, &g, mask + f * N) : rmx_rollout_lqr(b, nsteps, &cost, &g))
+            die_rmx(box ? "rmx_rollout_lqr_box" : "rmx_rollout_lqr");
     }
-    for (size_t i = 0; i < B; ++i) mxGetPr(bad)[i] = status[i] ? 1.0 : 0.0;
+    for (size_t i = 0; i < B; ++i) mxGetPr(out[3])[i] = box ? (double)status[i] : (status[i] ? 1.0 : 0.0);
+    for (size_t i = 0; box && i < N * B; ++i) mxGetPr(out[4])[i] = (double)mask[i];
     mxFree(status);
-    mxArray* outs[4] = {kff, K, ex, bad};
-    plhs[0] = kff;
-    for (int i = 1; i < 4; ++i) {
-        if (nlhs > i) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
-}
-
-/* 'rollout_lqr_box': 'rollout_lqr' under the torque limits ulo <= u <= uhi (rmx_rollout_lqr_box).  status 1 x B (0, 1: a pivot not
- * > 0, 2: a QP did not terminate), clamped nsteps x B (the bit masks as doubles: nr <= 32, exact) */
-static void cmd_rollout_lqr_box(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 10)
-        die("usage: [kff,K,expected,status,clamped] = redmax_hip_mex('rollout_lqr_box', h, nsteps, lx, lu, Q, R, ubar, ulo, uhi [, mu [, max_iter]])");
-    const int nsteps = (int)mxGetScalar(prhs[2]);
-    if (nsteps < 1) die("rollout_lqr_box: nsteps must be at least 1");
-    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
-    const size_t perq = 4 * nr * nr * N;
-    const double* lx = lqr_arg(prhs[3], 2 * nr * N * B, 0, "lx", "2nr x nsteps x batch");
-    const double* lu = lqr_arg(prhs[4], nr * N * B, 0, "lu", "nr x nsteps x batch");
-    const double* Q = lqr_arg(prhs[5], perq, perq * B, "Q", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
-    const double* R = lqr_arg(prhs[6], nr * nr, 0, "R", "nr x nr");
-    const double* ubar = lqr_arg(prhs[7], nr * N * B, 0, "ubar", "nr x nsteps x batch");
-    rmx_box box;
-    box.ulo = bound_arg(prhs[8], h, "rollout_lqr_box", "ulo");
-    box.uhi = bound_arg(prhs[9], h, "rollout_lqr_box", "uhi");
-    const int per_rollout = mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
-    const int max_iter = nrhs > 11 ? (int)mxGetScalar(prhs[11]) : 0;
-    const size_t dk[3] = {nr, N, B}, dK[4] = {nr, 2 * nr, N, B};
-    mxArray* kff = mxCreateNumericArray(3, dk, mxDOUBLE_CLASS, mxREAL);
-    mxArray* K = mxCreateNumericArray(4, dK, mxDOUBLE_CLASS, mxREAL);
-    mxArray* ex = mxCreateDoubleMatrix(1, B, mxREAL);
-    mxArray* stat = mxCreateDoubleMatrix(1, B, mxREAL);
-    mxArray* cl = mxCreateDoubleMatrix(N, B, mxREAL);
-    int* status = (int*)mxCalloc(B, sizeof *status);
-    unsigned* mask = (unsigned*)mxCalloc(N * B, sizeof *mask);
-    rmx_lqr_cost cost;
-    memset(&cost, 0, sizeof cost);
-    cost.R = R;
-    cost.per_rollout = per_rollout;
-    cost.mu = nrhs > 10 ? mxGetScalar(prhs[10]) : 0.0;
-    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
-        size_t f;
-        rmx_batch* b = shard(h, s, &f);
-        rmx_lqr_gains out;
-        cost.lx = lx + f * 2 * nr * N;
-        cost.lu = lu + f * nr * N;
-        cost.Q = per_rollout ? Q + f * perq : Q;
-        out.kff = mxGetPr(kff) + f * nr * N;
-        out.K = mxGetPr(K) + f * 2 * nr * nr * N;
-        out.expected = mxGetPr(ex) + f;
-        out.status = status + f;
-        if (rmx_rollout_lqr_box(b, nsteps, &cost, &box, ubar + f * nr * N, max_iter, &out, mask + f * N)) die_rmx("rmx_rollout_lqr_box");
-    }
-    for (size_t i = 0; i < B; ++i) mxGetPr(stat)[i] = (double)status[i];
-    for (size_t i = 0; i < N * B; ++i) mxGetPr(cl)[i] = (double)mask[i];
-    mxFree(status);
-    mxFree(mask);
-    mxArray* outs[5] = {kff, K, ex, stat, cl};
-    plhs[0] = kff;
-    for (int i = 1; i < 5; ++i) {
-        if (nlhs > i) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    if (mask) mxFree(mask);
+    give(nlhs, plhs, out, box ? 5 : 4);
 }
 
 /* one tangent argument of 'rollout_jvp': [] (NULL: zero) or a double array of `per` * ntan * B elements; *ntan is set by the first
@@ -1026,18 +908,15 @@ static void cmd_rollout_jvp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     const double* tqd0 = tangent_arg(prhs[5], h, nr, &ntan, "tqd0");
     if (!ntan) ntan = 1;      /* (every tangent empty: the library refuses it in its own words) */
     const size_t dims[4] = {nr, (size_t)nsteps, ntan, (size_t)h->B};
-    mxArray* tq = mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL);
-    mxArray* tqd = mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* const out[2] = {mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL), mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL)};
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        if (rmx_rollout_jvp(b, nsteps, (int)ntan, tu ? tu + f * ntan * per : NULL, tq0 ? tq0 + f * ntan * nr : NULL,
-                            tqd0 ? tqd0 + f * ntan * nr : NULL, mxGetPr(tq) + f * ntan * per, mxGetPr(tqd) + f * ntan * per))
+        if (rmx_rollout_jvp(b, nsteps, (int)ntan, table_at(tu, 1, f, ntan * per), table_at(tq0, 1, f, ntan * nr), table_at(tqd0, 1, f, ntan * nr),
+                            mxGetPr(out[0]) + f * ntan * per, mxGetPr(out[1]) + f * ntan * per))
             die_rmx("rmx_rollout_jvp");
     }
-    plhs[0] = tq;
-    if (nlhs > 1) plhs[1] = tqd;
-    else mxDestroyArray(tqd);
+    give(nlhs, plhs, out, 2);
 }
 
 /* field k of element i of the struct array task.terms */
@@ -1055,10 +934,7 @@ static void cmd_adjoint_track(int nlhs, mxArray* plhs[], int nrhs, const mxArray
     const mxArray* ta = field(t, "terms", 1);
     if (!mxIsStruct(ta)) die("task.terms must be a struct array with the fields body, xlocal, step, wpos");
     const size_t nterms = mxGetNumberOfElements(ta);
-    rmx_opts o;
-    rmx_opts_default(&o);
-    o.h = mxGetScalar(prhs[2]);
-    o.iterMaxPerDof = 5;                               /* driverRedMaxAdjointBDF1.m:108 */
+    const rmx_opts o = tape_opts(mxGetScalar(prhs[2]));
     const int nsteps = (int)mxGetScalar(prhs[3]);
     if (nsteps < 1) die("adjoint_track: nsteps must be at least 1");
     const int integ = nrhs > 6 ? (int)mxGetScalar(prhs[6]) : 1;
@@ -1096,25 +972,19 @@ static void cmd_adjoint_track(int nlhs, mxArray* plhs[], int nrhs, const mxArray
         dPdu = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
     }
     mxArray* st = new_i32((size_t)h->B, 2);
-    int* sp = (int*)mxGetData(st);
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'adjoint_controls': u, the per-rollout targets and the outputs advance */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
-        rmx_stats st_s;
-        st_s.newton_iters = sp + f;
-        st_s.ls_halvings = NULL;
-        st_s.status = sp + h->B + f;
-        task.xtarget = mxGetPr(xa) + (task.per_rollout ? f * 3 * nterms : 0);
+        rmx_stats st_s = shard_stats(st, h, f);
+        task.xtarget = table_at(mxGetPr(xa), task.per_rollout, f, 3 * nterms);
         if (rmx_adjoint_track(b, &o, nsteps, integ, &task, mxGetPr(ua) + f * per, mxGetPr(P) + f, dPdu ? mxGetPr(dPdu) + f * per : NULL, &st_s)) {
             mxFree(terms);
             die_rmx("rmx_adjoint_track");
         }
     }
     mxFree(terms);
-    plhs[0] = P;
-    if (nlhs > 1) plhs[1] = dPdu;
-    if (nlhs > 2) plhs[2] = st;
-    else mxDestroyArray(st);
+    mxArray* const out[3] = {P, dPdu, st};
+    give(nlhs, plhs, out, 3);
 }
 
 /* the struct array `ta` (body 1-based, xlocal, step[, wpos]) as rmx_track_term's; the caller frees the result */
@@ -1169,8 +1039,8 @@ static void cmd_rollout_points(int nlhs, mxArray* plhs[], int nrhs, const mxArra
         }
     }
     mxFree(terms);
-    plhs[0] = x;
-    if (nlhs > 1) plhs[1] = gq;
+    mxArray* const out[2] = {x, gq};
+    give(nlhs, plhs, out, 2);
 }
 
 static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -1209,9 +1079,9 @@ static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
         size_t f;
         rmx_batch* b = shard(h, s, &f);
         rmx_cost_model out;
-        sc.Q = Qin ? Qin + (Q_per ? f * perq : 0) : NULL;
-        sc.xgoal = xg ? xg + (g_per ? f * perg : 0) : NULL;
-        pts.xtarget = xt ? xt + (t_per ? f * 3 * nterms : 0) : NULL;
+        sc.Q = table_at(Qin, Q_per, f, perq);
+        sc.xgoal = table_at(xg, g_per, f, perg);
+        pts.xtarget = table_at(xt, t_per, f, 3 * nterms);
         out.Jk = mxGetPr(Jk) + f * N;
         out.lx = lx ? mxGetPr(lx) + f * perg : NULL;
         out.Q = Qo ? mxGetPr(Qo) + f * perq : NULL;
@@ -1221,9 +1091,8 @@ static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
         }
     }
     if (terms) mxFree(terms);
-    plhs[0] = Jk;
-    if (nlhs > 1) plhs[1] = lx;
-    if (nlhs > 2) plhs[2] = Qo;
+    mxArray* const res[3] = {Jk, lx, Qo};
+    give(nlhs, plhs, res, 3);
 }
 
 /* `clear mex` / MATLAB exit: free what is still alive on the device */
@@ -1358,7 +1227,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(cmd, "rollout_tape")) {
         cmd_rollout_tape(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_feedback")) {
-        cmd_rollout_feedback(nlhs, plhs, nrhs, prhs);
+        cmd_rollout_feedback(nlhs, plhs, nrhs, prhs, 0);
     } else if (!strcmp(cmd, "rollout_vjp")) {
         cmd_rollout_vjp(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp_feedback")) {
@@ -1370,11 +1239,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(cmd, "rollout_jvp")) {
         cmd_rollout_jvp(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_lqr")) {
-        cmd_rollout_lqr(nlhs, plhs, nrhs, prhs);
+        cmd_rollout_lqr(nlhs, plhs, nrhs, prhs, 0);
     } else if (!strcmp(cmd, "rollout_feedback_box")) {
-        cmd_rollout_feedback_box(nlhs, plhs, nrhs, prhs);
+        cmd_rollout_feedback(nlhs, plhs, nrhs, prhs, 1);
     } else if (!strcmp(cmd, "rollout_lqr_box")) {
-        cmd_rollout_lqr_box(nlhs, plhs, nrhs, prhs);
+        cmd_rollout_lqr(nlhs, plhs, nrhs, prhs, 1);
     } else if (!strcmp(cmd, "rollout_points")) {
         cmd_rollout_points(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_cost")) {

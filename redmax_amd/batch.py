@@ -13,6 +13,76 @@ import numpy as np
 from . import _abi
 
 
+# ---- argument checks and marshalling of the entries below: every check, and its words, is written here once ----
+def _and(items):
+    items = list(items)
+    return ", ".join(items[:-1]) + " and " + items[-1]
+
+
+def _f64(who, name, a, *shapes):
+    """`a` as a contiguous float64 array whose shape is one of `shapes` (one or two)."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape not in shapes:
+        raise ValueError("%s: %s must have shape %s, got %r" % (who, name, " or ".join("%r" % (s,) for s in shapes), a.shape))
+    return a
+
+
+def _f64_joint(who, names, arrays, shapes):
+    """Arrays that are refused together ("gq and gqd must have shape .., got .. and ..").  shapes: one shape for all of them (a
+    tuple), or a list with one shape each."""
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+    each = shapes if isinstance(shapes, list) else [shapes] * len(arrays)
+    if any(a.shape != s for a, s in zip(arrays, each)):
+        want = "shapes " + _and("%r" % (s,) for s in each) if isinstance(shapes, list) else "shape %r" % (shapes,)
+        raise ValueError("%s: %s must have %s, got %s" % (who, _and(names), want, _and("%r" % (a.shape,) for a in arrays)))
+    return arrays
+
+
+def _table(who, name, a, tail, B):
+    """A table the batch shares, shape `tail`, or one per rollout, (B,) + tail: (the array, 1 if per rollout else 0)."""
+    a = _f64(who, name, a, tail, (B,) + tail)
+    return a, int(a.ndim > len(tail))
+
+
+def _names(who, arg, given, allowed, empty_ok):
+    """A `want` / `which` list as a tuple of distinct names among `allowed`."""
+    given = (given,) if isinstance(given, str) else tuple(given)
+    if (not given and not empty_ok) or any(w not in allowed for w in given) or len(set(given)) != len(given):
+        raise ValueError("%s: %s must name distinct outputs among %s, got %r" % (who, arg, ", ".join(repr(n) for n in allowed), given))
+    return given
+
+
+def _vp(ptr):
+    """A device pointer (an integer; 0 / None: null) as the c_void_p of a call."""
+    return C.c_void_p(ptr or None)
+
+
+def _addr(a):
+    """The address of an array for a c_void_p struct member (None: null).  The struct does not hold the array: its caller does."""
+    return None if a is None else a.ctypes.data
+
+
+def _stats_arrays(B):
+    """The three per-rollout counters of a step call and the Stats that points into them."""
+    out = {k: np.zeros(B, dtype=np.int32) for k in ("newton_iters", "ls_halvings", "status")}
+    return out, _abi.Stats(_abi.iptr(out["newton_iters"]), _abi.iptr(out["ls_halvings"]), _abi.iptr(out["status"]))
+
+
+def _history_arrays(B, nr, nsph, nsteps, record):
+    """The per-step arrays `record` (REC_ENERGY | REC_STATE | REC_CHARTS) asks for and the History that points into them."""
+    out, hist = {}, _abi.History()
+    if record & _abi.REC_ENERGY:
+        out["T"], out["V"] = np.empty((nsteps, B)), np.empty((nsteps, B))
+        hist.T, hist.V = _abi.dptr(out["T"]), _abi.dptr(out["V"])
+    if record & _abi.REC_STATE:
+        out["q"], out["qdot"] = np.empty((nsteps, B, nr)), np.empty((nsteps, B, nr))
+        hist.q, hist.qdot = _abi.dptr(out["q"]), _abi.dptr(out["qdot"])
+    if record & _abi.REC_CHARTS and nsph:
+        out["charts"] = np.full((nsteps, B, nsph), 7, dtype=np.int32)
+        hist.charts = _abi.iptr(out["charts"])
+    return out, hist
+
+
 class BatchSim:
     def __init__(self, scene_or_desc, batch=1, device=0):
         d = scene_or_desc.desc() if hasattr(scene_or_desc, "desc") else scene_or_desc
@@ -154,30 +224,19 @@ class BatchSim:
         if h is not None:
             self.opts.h = float(h)
         self._async = None                                 # any step call replaces the record of an earlier step_history_async
-        st = None
-        out = {}
-        if stats:
-            out["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            out["ls_halvings"] = np.zeros(self.B, dtype=np.int32)
-            out["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(out["newton_iters"]), _abi.iptr(out["ls_halvings"]), _abi.iptr(out["status"]))
-        T = V = None
-        if history:
-            T = np.empty((nsteps, self.B))
-            V = np.empty((nsteps, self.B))
-            out["T"], out["V"] = T, V
+        out, st = _stats_arrays(self.B) if stats else ({}, None)
         stp = C.byref(st) if st is not None else None
-        if history == "full":                     # Scene.saveHistory: q, qdot of every step as well (Scene.m:134-161)
-            out["q"] = np.empty((nsteps, self.B, self.nr))
-            out["qdot"] = np.empty((nsteps, self.B, self.nr))
-            out["charts"] = np.full((nsteps, self.B, self.nsph), 7, dtype=np.int32)     # JointSpherical.chart after every step
-            hist = _abi.History(_abi.dptr(T), _abi.dptr(V), _abi.dptr(out["q"]), _abi.dptr(out["qdot"]),
-                                _abi.iptr(out["charts"]) if self.nsph else None)
+        # history "full" is Scene.saveHistory: q, qdot and JointSpherical.chart of every step as well (Scene.m:134-161)
+        record = 0 if not history else _abi.REC_ENERGY | (_abi.REC_STATE | _abi.REC_CHARTS if history == "full" else 0)
+        rec, hist = _history_arrays(self.B, self.nr, self.nsph, nsteps, record)
+        out.update(rec)
+        if history == "full":
+            out.setdefault("charts", np.full((nsteps, self.B, 0), 7, dtype=np.int32))     # (a model without spherical joints)
             _abi.check(self._L.rmx_step_history(self._batch, C.byref(self.opts), int(nsteps), 1 if fn == "bdf1" else 2, stp,
                                                 C.byref(hist)), "rmx_step_history")
         else:
             f = self._L.rmx_step_bdf1 if fn == "bdf1" else self._L.rmx_step_bdf2
-            _abi.check(f(self._batch, C.byref(self.opts), int(nsteps), stp, _abi.dptr(T), _abi.dptr(V)), "rmx_step")
+            _abi.check(f(self._batch, C.byref(self.opts), int(nsteps), stp, _abi.dptr(out.get("T")), _abi.dptr(out.get("V"))), "rmx_step")
         out["ms"] = self._L.rmx_last_step_ms(self._batch)
         return out
 
@@ -213,14 +272,9 @@ class BatchSim:
         p = self._arr(p)
         P = np.empty(self.B)
         dPdp = np.empty((self.B, self.nr))
-        info = {}
-        st = None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        info, st = self._tape_stats(stats)
         _abi.check(getattr(self._L, _fn)(self._batch, C.byref(opts), int(nsteps), C.byref(tk), _abi.dptr(p), _abi.dptr(P),
-                                         _abi.dptr(dPdp), C.byref(st) if st is not None else None), _fn)
+                                         _abi.dptr(dPdp), st), _fn)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return P, dPdp, info
 
@@ -228,14 +282,9 @@ class BatchSim:
         """adjoint_bdf1 with DEVICE pointers (integers, e.g. torch.Tensor.data_ptr()) for p [B][nr], P [B] and dPdp [B][nr]: nothing
         crosses the host boundary but the optional counters.  Returns info."""
         tk, opts = self._task_and_opts(task, h)
-        info = {}
-        st = None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        info, st = self._tape_stats(stats)
         _abi.check(getattr(self._L, _fn)(self._batch, C.byref(opts), int(nsteps), C.byref(tk), C.c_void_p(p_ptr), C.c_void_p(P_ptr),
-                                         C.c_void_p(dPdp_ptr), C.byref(st) if st is not None else None), _fn)
+                                         C.c_void_p(dPdp_ptr), st), _fn)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
@@ -250,12 +299,17 @@ class BatchSim:
             tk.xtarget[i] = float(task["xtarget"][i])
         tk.step = int(task["step"]) if "step" in task else int(round(float(task["t"]) / float(h)))
         tk.pscale, tk.wreg, tk.wpos = float(task["pscale"]), float(task["wreg"]), float(task["wpos"])
-        opts = _abi.Opts()
-        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
-        opts.h = float(h)
-        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        opts = self._tape_opts(float(h))
         self.tape_count += 1                        # (every adjoint_* call comes through here or _track_task: it ends a rollout_tape's tape)
         return tk, opts
+
+    def _controls(self, who, name, u, nsteps):
+        """u / uff of an entry with one torque per joint and step: [B][nsteps][nr], or [nsteps][nr] for every rollout alike."""
+        if u is None:
+            raise ValueError("%s: %s is None" % (who, name))
+        full = (self.B, nsteps, self.nr)
+        u = _f64(who, name, u, full, full[1:])
+        return u if u.shape == full else np.ascontiguousarray(np.broadcast_to(u, full))
 
     def adjoint_controls(self, nsteps, h, task, u, integrator=1, stats=False, gradient=True):
         """rmx_adjoint_controls: the adjoint with one torque per joint and STEP.  u: [B][nsteps][nr] (a [nsteps][nr] array holds for
@@ -263,27 +317,13 @@ class BatchSim:
         adjoint_bdf1.  Returns (P[B], dPdu[B][nsteps][nr], info); gradient=False runs the forward rollout alone and returns None for
         dPdu.  Under BDF2 the k = 1 rows of dPdu carry the reference's start-step approximation (include/redmax_hip.h)."""
         nsteps = int(nsteps)
-        if u is None:
-            raise ValueError("adjoint_controls: u is None")
-        u = np.asarray(u, dtype=np.float64)
-        if u.shape == (nsteps, self.nr):
-            u = np.broadcast_to(u, (self.B, nsteps, self.nr))
-        if u.shape != (self.B, nsteps, self.nr):
-            raise ValueError("adjoint_controls: u must have shape (%d, %d, %d) or (%d, %d), got %r"
-                             % (self.B, nsteps, self.nr, nsteps, self.nr, u.shape))
-        u = np.ascontiguousarray(u)
+        u = self._controls("adjoint_controls", "u", u, nsteps)
         tk, opts = self._task_and_opts(task, h)
         P = np.empty(self.B)
         dPdu = np.empty((self.B, nsteps, self.nr)) if gradient else None
-        info = {}
-        st = None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        info, st = self._tape_stats(stats)
         _abi.check(self._L.rmx_adjoint_controls(self._batch, C.byref(opts), nsteps, int(integrator), C.byref(tk), _abi.dptr(u),
-                                                _abi.dptr(P), _abi.dptr(dPdu), C.byref(st) if st is not None else None),
-                   "rmx_adjoint_controls")
+                                                _abi.dptr(P), _abi.dptr(dPdu), st), "rmx_adjoint_controls")
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return P, dPdu, info
 
@@ -291,32 +331,21 @@ class BatchSim:
         """adjoint_controls with DEVICE pointers (integers) for u [B][nsteps][nr], P [B] and dPdu [B][nsteps][nr]; dPdu_ptr 0 / None:
         the forward rollout alone.  Returns info."""
         tk, opts = self._task_and_opts(task, h)
-        info = {}
-        st = None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        info, st = self._tape_stats(stats)
         _abi.check(self._L.rmx_adjoint_controls_device(self._batch, C.byref(opts), int(nsteps), int(integrator), C.byref(tk),
-                                                       C.c_void_p(u_ptr), C.c_void_p(P_ptr), C.c_void_p(dPdu_ptr or None),
-                                                       C.byref(st) if st is not None else None), "rmx_adjoint_controls_device")
+                                                       _vp(u_ptr), _vp(P_ptr), _vp(dPdu_ptr), st), "rmx_adjoint_controls_device")
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
+    def _targets(self, who, xtarget, nterms):
+        """The point targets of `nterms` terms, [nterms][3] or [B][nterms][3]: (the array, 1 if per rollout else 0)."""
+        if xtarget is None:
+            raise ValueError("%s: xtarget is None" % who)
+        return _table(who, "xtarget", xtarget, (nterms, 3), self.B)
+
     def _track_task(self, task, h, nsteps, device_targets=False):
         """task dict of adjoint_track -> (TaskTrack, Opts, keepalive).  Shapes are checked here, before any call into the library."""
-        terms = list(task["terms"])
-        nterms = len(terms)
-        arr = (_abi.TrackTerm * max(nterms, 1))()
-        for a, t in zip(arr, terms):
-            xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
-            if xl.shape != (3,):
-                raise ValueError("adjoint_track: a term's xlocal must have shape (3,), got %r" % (xl.shape,))
-            a.body = int(t["body"])
-            a.step = int(t["step"]) if "step" in t else int(round(float(t["t"]) / float(h)))
-            a.wpos = float(t["wpos"])
-            for i in range(3):
-                a.xlocal[i] = float(xl[i])
+        arr, nterms = self._point_terms(task["terms"], "adjoint_track", True, h)
         tk = _abi.TaskTrack()
         tk.nterms, tk.terms = nterms, arr
         tk.pscale, tk.wreg = float(task["pscale"]), float(task["wreg"])
@@ -324,17 +353,9 @@ class BatchSim:
         if device_targets:
             tk.per_rollout = 1 if task.get("per_rollout") else 0
         else:
-            if task.get("xtarget") is None:
-                raise ValueError("adjoint_track: xtarget is None")
-            xt = np.ascontiguousarray(task["xtarget"], dtype=np.float64)
-            if xt.shape not in ((nterms, 3), (self.B, nterms, 3)):
-                raise ValueError("adjoint_track: xtarget must have shape (%d, 3) or (%d, %d, 3), got %r" % (nterms, self.B, nterms, xt.shape))
-            tk.per_rollout = 1 if xt.ndim == 3 else 0
+            xt, tk.per_rollout = self._targets("adjoint_track", task.get("xtarget"), nterms)
             tk.xtarget = _abi.dptr(xt)
-        opts = _abi.Opts()
-        C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
-        opts.h = float(h)
-        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
+        opts = self._tape_opts(float(h))
         self.tape_count += 1
         return tk, opts, (arr, xt)
 
@@ -345,27 +366,13 @@ class BatchSim:
         P[b] = sum_i wpos_i/2 |x_i(step_i) - xtarget[b][i]|^2 + wreg/2 sum u[b]^2.  u, integrator, stats, gradient and the result
         (P[B], dPdu[B][nsteps][nr] or None, info) as adjoint_controls."""
         nsteps = int(nsteps)
-        if u is None:
-            raise ValueError("adjoint_track: u is None")
-        u = np.asarray(u, dtype=np.float64)
-        if u.shape == (nsteps, self.nr):
-            u = np.broadcast_to(u, (self.B, nsteps, self.nr))
-        if u.shape != (self.B, nsteps, self.nr):
-            raise ValueError("adjoint_track: u must have shape (%d, %d, %d) or (%d, %d), got %r"
-                             % (self.B, nsteps, self.nr, nsteps, self.nr, u.shape))
-        u = np.ascontiguousarray(u)
+        u = self._controls("adjoint_track", "u", u, nsteps)
         tk, opts, keep = self._track_task(task, h, nsteps)
         P = np.empty(self.B)
         dPdu = np.empty((self.B, nsteps, self.nr)) if gradient else None
-        info = {}
-        st = None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        info, st = self._tape_stats(stats)
         _abi.check(self._L.rmx_adjoint_track(self._batch, C.byref(opts), nsteps, int(integrator), C.byref(tk), _abi.dptr(u),
-                                             _abi.dptr(P), _abi.dptr(dPdu), C.byref(st) if st is not None else None),
-                   "rmx_adjoint_track")
+                                             _abi.dptr(P), _abi.dptr(dPdu), st), "rmx_adjoint_track")
         del keep
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return P, dPdu, info
@@ -375,35 +382,28 @@ class BatchSim:
         task["xtarget"] is not read), u [B][nsteps][nr], P [B] and dPdu [B][nsteps][nr]; dPdu_ptr 0 / None: the forward rollout alone.
         Returns info."""
         tk, opts, keep = self._track_task(task, h, int(nsteps), device_targets=True)
-        info = {}
-        st = None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
+        info, st = self._tape_stats(stats)
         _abi.check(self._L.rmx_adjoint_track_device(self._batch, C.byref(opts), int(nsteps), int(integrator), C.byref(tk),
-                                                    C.c_void_p(xtarget_ptr or None), C.c_void_p(u_ptr or None), C.c_void_p(P_ptr or None),
-                                                    C.c_void_p(dPdu_ptr or None), C.byref(st) if st is not None else None),
-                   "rmx_adjoint_track_device")
+                                                    _vp(xtarget_ptr), _vp(u_ptr), _vp(P_ptr), _vp(dPdu_ptr), st), "rmx_adjoint_track_device")
         del keep
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
     def _tape_opts(self, h):
+        """The options of one taped-rollout or adjoint_* call: a copy of self.opts under the step size h (None: self.opts.h)."""
         opts = _abi.Opts()
         C.memmove(C.byref(opts), C.byref(self.opts), C.sizeof(opts))
         if h is not None:
             opts.h = float(h)
-        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108, as the adjoint_* calls
+        opts.iterMaxPerDof = 5                      # driverRedMaxAdjointBDF1.m:108
         return opts
 
     def _tape_stats(self, stats):
-        info, st = {}, None
-        if stats:
-            info["newton_iters"] = np.zeros(self.B, dtype=np.int32)
-            info["status"] = np.zeros(self.B, dtype=np.int32)
-            st = _abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"]))
-        return info, st
+        """(info, the rmx_stats argument of the call or None): with stats, info holds the counters the call fills."""
+        if not stats:
+            return {}, None
+        info = {"newton_iters": np.zeros(self.B, dtype=np.int32), "status": np.zeros(self.B, dtype=np.int32)}
+        return info, C.byref(_abi.Stats(_abi.iptr(info["newton_iters"]), None, _abi.iptr(info["status"])))
 
     def _tape_entry(self, integrator, device):
         """(function, name) of the rollout_tape entry of an integrator: 1 BDF1, 2 BDF2 (rmx_rollout_tape_bdf2)."""
@@ -411,6 +411,14 @@ class BatchSim:
             raise ValueError("rollout_tape: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
         name = ("rmx_rollout_tape" if integrator == 1 else "rmx_rollout_tape_bdf2") + ("_device" if device else "")
         return getattr(self._L, name), name
+
+    def _begin_tape(self, h, stats, integrator):
+        """What every call that records a tape does once its arguments stand: (opts, info, stats argument), and the tape is claimed."""
+        opts = self._tape_opts(h)
+        info, st = self._tape_stats(stats)
+        self.tape_count += 1
+        self._tape_integrator = integrator
+        return opts, info, st
 
     def rollout_tape(self, nsteps, h, u, pscale=1.0, stats=False, trajectory=True, integrator=1):
         """rmx_rollout_tape: a controlled BDF1 rollout from the current state that records its trajectory and keeps H, M, D of every
@@ -421,23 +429,11 @@ class BatchSim:
         rollout_vjp follows the integrator of the tape."""
         fn, fname = self._tape_entry(integrator, False)
         nsteps = int(nsteps)
-        if u is None:
-            raise ValueError("rollout_tape: u is None")
-        u = np.asarray(u, dtype=np.float64)
-        if u.shape == (nsteps, self.nr):
-            u = np.broadcast_to(u, (self.B, nsteps, self.nr))
-        if u.shape != (self.B, nsteps, self.nr):
-            raise ValueError("rollout_tape: u must have shape (%d, %d, %d) or (%d, %d), got %r"
-                             % (self.B, nsteps, self.nr, nsteps, self.nr, u.shape))
-        u = np.ascontiguousarray(u)
-        opts = self._tape_opts(h)
+        u = self._controls("rollout_tape", "u", u, nsteps)
         qtraj = np.empty((self.B, nsteps, self.nr)) if trajectory else None
         qdtraj = np.empty((self.B, nsteps, self.nr)) if trajectory else None
-        info, st = self._tape_stats(stats)
-        self.tape_count += 1
-        self._tape_integrator = integrator
-        _abi.check(fn(self._batch, C.byref(opts), nsteps, float(pscale), _abi.dptr(u), _abi.dptr(qtraj), _abi.dptr(qdtraj),
-                      C.byref(st) if st is not None else None), fname)
+        opts, info, st = self._begin_tape(h, stats, integrator)
+        _abi.check(fn(self._batch, C.byref(opts), nsteps, float(pscale), _abi.dptr(u), _abi.dptr(qtraj), _abi.dptr(qdtraj), st), fname)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return qtraj, qdtraj, info
 
@@ -445,12 +441,8 @@ class BatchSim:
         """rollout_tape with DEVICE pointers (integers) for u, qtraj and qdtraj, all [B][nsteps][nr]; qtraj_ptr and qdtraj_ptr 0 /
         None together: no record.  Returns info."""
         fn, fname = self._tape_entry(integrator, True)
-        opts = self._tape_opts(h)
-        info, st = self._tape_stats(stats)
-        self.tape_count += 1
-        self._tape_integrator = integrator
-        _abi.check(fn(self._batch, C.byref(opts), int(nsteps), float(pscale), C.c_void_p(u_ptr or None), C.c_void_p(qtraj_ptr or None),
-                      C.c_void_p(qdtraj_ptr or None), C.byref(st) if st is not None else None), fname)
+        opts, info, st = self._begin_tape(h, stats, integrator)
+        _abi.check(fn(self._batch, C.byref(opts), int(nsteps), float(pscale), _vp(u_ptr), _vp(qtraj_ptr), _vp(qdtraj_ptr), st), fname)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
@@ -458,33 +450,30 @@ class BatchSim:
         """K and xref of rollout_feedback as contiguous float64 arrays, and whether they hold one table per rollout.  K:
         [nsteps][2nr][nr] or [B][nsteps][2nr][nr], K[.., k-1, j, i] = du_i/dx_j of step k with x = (q, qdot) - the ABI's column-major
         table as a C array -; xref: [nsteps][2nr] or [B][nsteps][2nr].  Both shared or both per rollout."""
-        nr, B = self.nr, self.B
-        shapes = {}
-        for name, a, tail in (("K", K, (nsteps, 2 * nr, nr)), ("xref", xref, (nsteps, 2 * nr))):
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.shape not in (tail, (B,) + tail):
-                raise ValueError("%s: %s must have shape %r or %r, got %r" % (who, name, tail, (B,) + tail, a.shape))
-            shapes[name] = a
-        K, xref = shapes.get("K"), shapes.get("xref")
-        per = [a.ndim == len(t) + 1 for a, t in ((K, (0, 0, 0)), (xref, (0, 0))) if a is not None]
+        nr, per = self.nr, []
+        if K is not None:
+            K, p = _table(who, "K", K, (nsteps, 2 * nr, nr), self.B)
+            per.append(p)
+        if xref is not None:
+            xref, p = _table(who, "xref", xref, (nsteps, 2 * nr), self.B)
+            per.append(p)
         if len(set(per)) > 1:
             raise ValueError("%s: K and xref must both be shared by the batch or both hold one table per rollout" % who)
         return K, xref, int(bool(per and per[0]))
 
     def _ulim(self, ulim, who):
-        """(ulo, uhi) of a ``ulim`` keyword as contiguous float64 [nr] arrays or None each: the torque limits of rmx_box."""
+        """The torque limits of a ``ulim`` keyword, (ulo, uhi) with [nr] or None each -> (rmx_box, the arrays it points into)."""
         if not isinstance(ulim, (tuple, list)) or len(ulim) != 2:
             raise ValueError("%s: ulim must be a pair (ulo, uhi), either may be None" % who)
-        out = []
-        for name, a in zip(("ulo", "uhi"), ulim):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (self.nr,):
-                    raise ValueError("%s: %s must have shape %r, got %r" % (who, name, (self.nr,), a.shape))
-            out.append(a)
-        return out
+        keep = [None if a is None else _f64(who, name, a, (self.nr,)) for name, a in zip(("ulo", "uhi"), ulim)]
+        return _abi.Box(_addr(keep[0]), _addr(keep[1])), keep
+
+    def _feedback_call(self, device, opts, nsteps, integrator, pscale, fb, box, outs, st):
+        """THE call of rmx_rollout_tape_feedback[_box][_device]: box None selects the plain entry, the argument list is formed once."""
+        name = "rmx_rollout_tape_feedback" + ("" if box is None else "_box") + ("_device" if device else "")
+        args = (self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale), C.byref(fb))
+        args += (() if box is None else (C.byref(box),)) + tuple(outs) + (st,)
+        _abi.check(getattr(self._L, name)(*args), name)
 
     def rollout_feedback(self, nsteps, h, uff, K=None, xref=None, pscale=1.0, stats=False, integrator=1, ulim=None):
         """rmx_rollout_tape_feedback: rollout_tape in closed loop - at step k the joint torque is tau + pscale*uapp[:, k-1] with
@@ -500,32 +489,14 @@ class BatchSim:
         if integrator not in (1, 2):
             raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
         nsteps = int(nsteps)
-        if uff is None:
-            raise ValueError("rollout_feedback: uff is None")
-        uff = np.asarray(uff, dtype=np.float64)
-        if uff.shape == (nsteps, self.nr):
-            uff = np.broadcast_to(uff, (self.B, nsteps, self.nr))
-        if uff.shape != (self.B, nsteps, self.nr):
-            raise ValueError("rollout_feedback: uff must have shape (%d, %d, %d) or (%d, %d), got %r"
-                             % (self.B, nsteps, self.nr, nsteps, self.nr, uff.shape))
-        uff = np.ascontiguousarray(uff)
+        uff = self._controls("rollout_feedback", "uff", uff, nsteps)
         K, xref, per = self._feedback_tables(nsteps, K, xref)
-        fb = _abi.Feedback(uff.ctypes.data, K.ctypes.data if K is not None else None, xref.ctypes.data if xref is not None else None, per)
-        opts = self._tape_opts(h)
+        fb = _abi.Feedback(_addr(uff), _addr(K), _addr(xref), per)
         qtraj, qdtraj, uapp = (np.empty((self.B, nsteps, self.nr)) for _ in range(3))
-        info, st = self._tape_stats(stats)
-        self.tape_count += 1
-        self._tape_integrator = integrator
-        if ulim is not None:
-            ulo, uhi = self._ulim(ulim, "rollout_feedback")
-            box = _abi.Box(None if ulo is None else ulo.ctypes.data, None if uhi is None else uhi.ctypes.data)
-            _abi.check(self._L.rmx_rollout_tape_feedback_box(self._batch, C.byref(opts), nsteps, int(integrator), float(pscale), C.byref(fb),
-                                                             C.byref(box), _abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp),
-                                                             C.byref(st) if st is not None else None), "rmx_rollout_tape_feedback_box")
-        else:
-            _abi.check(self._L.rmx_rollout_tape_feedback(self._batch, C.byref(opts), nsteps, int(integrator), float(pscale), C.byref(fb),
-                                                         _abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp),
-                                                         C.byref(st) if st is not None else None), "rmx_rollout_tape_feedback")
+        opts, info, st = self._begin_tape(h, stats, integrator)
+        box, keep = self._ulim(ulim, "rollout_feedback") if ulim is not None else (None, None)
+        self._feedback_call(False, opts, nsteps, integrator, pscale, fb, box, (_abi.dptr(qtraj), _abi.dptr(qdtraj), _abi.dptr(uapp)), st)
+        del keep      # (the limits box points into: held until the call has returned)
         if not stats:
             return qtraj, qdtraj, uapp
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
@@ -540,22 +511,9 @@ class BatchSim:
         if integrator not in (1, 2):
             raise ValueError("rollout_feedback: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
         fb = _abi.Feedback(uff_ptr or None, K_ptr or None, xref_ptr or None, int(bool(per_rollout)))
-        opts = self._tape_opts(h)
-        info, st = self._tape_stats(stats)
-        self.tape_count += 1
-        self._tape_integrator = integrator
-        if ulim is not None:
-            box = _abi.Box(ulim[0] or None, ulim[1] or None)
-            _abi.check(self._L.rmx_rollout_tape_feedback_box_device(self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale),
-                                                                    C.byref(fb), C.byref(box), C.c_void_p(qtraj_ptr or None),
-                                                                    C.c_void_p(qdtraj_ptr or None), C.c_void_p(uapp_ptr or None),
-                                                                    C.byref(st) if st is not None else None),
-                       "rmx_rollout_tape_feedback_box_device")
-        else:
-            _abi.check(self._L.rmx_rollout_tape_feedback_device(self._batch, C.byref(opts), int(nsteps), int(integrator), float(pscale),
-                                                                C.byref(fb), C.c_void_p(qtraj_ptr or None), C.c_void_p(qdtraj_ptr or None),
-                                                                C.c_void_p(uapp_ptr or None), C.byref(st) if st is not None else None),
-                       "rmx_rollout_tape_feedback_device")
+        opts, info, st = self._begin_tape(h, stats, integrator)
+        box = None if ulim is None else _abi.Box(ulim[0] or None, ulim[1] or None)
+        self._feedback_call(True, opts, nsteps, integrator, pscale, fb, box, (_vp(qtraj_ptr), _vp(qdtraj_ptr), _vp(uapp_ptr)), st)
         info["ms"] = self._L.rmx_last_step_ms(self._batch)
         return info
 
@@ -564,23 +522,21 @@ class BatchSim:
         (du[B][nsteps][nr], dq0[B][nr], dqd0[B][nr]) = dL/du, dL/dq0, dL/dqdot0; initial_state=False returns None for the last two.
         Neither the state nor the tape changes: the call may be repeated with other cotangents."""
         nsteps = int(nsteps)
-        sh = (self.B, nsteps, self.nr)
-        gq = np.ascontiguousarray(gq, dtype=np.float64)
-        gqd = np.ascontiguousarray(gqd, dtype=np.float64)
-        if gq.shape != sh or gqd.shape != sh:
-            raise ValueError("rollout_vjp: gq and gqd must have shape %r, got %r and %r" % (sh, gq.shape, gqd.shape))
-        du = np.empty(sh)
-        dq0 = np.empty((self.B, self.nr)) if initial_state else None
-        dqd0 = np.empty((self.B, self.nr)) if initial_state else None
+        gq, gqd = _f64_joint("rollout_vjp", ("gq", "gqd"), (gq, gqd), (self.B, nsteps, self.nr))
+        du, dq0, dqd0 = self._vjp_outputs(nsteps, initial_state)
         _abi.check(self._L.rmx_rollout_vjp(self._batch, nsteps, _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(du), _abi.dptr(dq0),
                                            _abi.dptr(dqd0)), "rmx_rollout_vjp")
         return du, dq0, dqd0
 
+    def _vjp_outputs(self, nsteps, initial_state):
+        """du [B][nsteps][nr] and dq0, dqd0 [B][nr] (None each without initial_state) of rollout_vjp and rollout_vjp_params."""
+        dq0, dqd0 = (np.empty((self.B, self.nr)), np.empty((self.B, self.nr))) if initial_state else (None, None)
+        return np.empty((self.B, nsteps, self.nr)), dq0, dqd0
+
     def rollout_vjp_device(self, nsteps, gq_ptr, gqd_ptr, du_ptr, dq0_ptr=None, dqd0_ptr=None):
         """rollout_vjp with DEVICE pointers (integers): gq, gqd, du [B][nsteps][nr]; dq0, dqd0 [B][nr], 0 / None together: not formed."""
-        _abi.check(self._L.rmx_rollout_vjp_device(self._batch, int(nsteps), C.c_void_p(gq_ptr or None), C.c_void_p(gqd_ptr or None),
-                                                  C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None)),
-                   "rmx_rollout_vjp_device")
+        _abi.check(self._L.rmx_rollout_vjp_device(self._batch, int(nsteps), _vp(gq_ptr), _vp(gqd_ptr), _vp(du_ptr), _vp(dq0_ptr),
+                                                  _vp(dqd0_ptr)), "rmx_rollout_vjp_device")
 
     def rollout_vjp_feedback(self, nsteps, gq, gqd, K=None, xref=None, gu=None, want=None):
         """rmx_rollout_vjp_feedback on the tape of the last rollout_feedback: the closed-loop adjoint.  gq, gqd [B][nsteps][nr] are
@@ -592,27 +548,20 @@ class BatchSim:
         nsteps = int(nsteps)
         if want is None:
             want = ("duff", "dq0") if K is None else ("duff", "dK", "dxref", "dq0")
-        want = (want,) if isinstance(want, str) else tuple(want)
         names = _abi.FEEDBACK_GRAD_NAMES
-        if any(w not in names for w in want) or len(set(want)) != len(want):
-            raise ValueError("rollout_vjp_feedback: want must name distinct outputs among %s, got %r" % (", ".join(repr(n) for n in names), want))
+        want = _names("rollout_vjp_feedback", "want", want, names, True)
         if "dq0" in want or "dqd0" in want:
             want = tuple(w for w in want if w not in ("dq0", "dqd0")) + ("dq0", "dqd0")
         sh = (self.B, nsteps, self.nr)
-        gq = np.ascontiguousarray(gq, dtype=np.float64)
-        gqd = np.ascontiguousarray(gqd, dtype=np.float64)
-        if gq.shape != sh or gqd.shape != sh:
-            raise ValueError("rollout_vjp_feedback: gq and gqd must have shape %r, got %r and %r" % (sh, gq.shape, gqd.shape))
+        gq, gqd = _f64_joint("rollout_vjp_feedback", ("gq", "gqd"), (gq, gqd), sh)
         if gu is not None:
-            gu = np.ascontiguousarray(gu, dtype=np.float64)
-            if gu.shape != sh:
-                raise ValueError("rollout_vjp_feedback: gu must have shape %r, got %r" % (sh, gu.shape))
+            gu = _f64("rollout_vjp_feedback", "gu", gu, sh)
         K, xref, per = self._feedback_tables(nsteps, K, xref, who="rollout_vjp_feedback")
-        fb = _abi.Feedback(None, K.ctypes.data if K is not None else None, xref.ctypes.data if xref is not None else None, per)
+        fb = _abi.Feedback(None, _addr(K), _addr(xref), per)
         shapes = {"duff": sh, "dK": (self.B, nsteps, 2 * self.nr, self.nr), "dxref": (self.B, nsteps, 2 * self.nr),
                   "dq0": (self.B, self.nr), "dqd0": (self.B, self.nr)}
         out = {w: np.zeros(shapes[w]) for w in want}
-        fg = _abi.FeedbackGrads(*[out[n].ctypes.data if n in out else None for n in names])
+        fg = _abi.FeedbackGrads(*[_addr(out.get(n)) for n in names])
         _abi.check(self._L.rmx_rollout_vjp_feedback(self._batch, nsteps, C.byref(fb), _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(gu),
                                                     C.byref(fg)), "rmx_rollout_vjp_feedback")
         return out
@@ -624,20 +573,12 @@ class BatchSim:
         [B][nr].  0 / None: gu zero, no gains, a zero reference, that output not formed (dq0 and dqd0 together; not all outputs)."""
         fb = _abi.Feedback(None, K_ptr or None, xref_ptr or None, int(bool(per_rollout)))
         fg = _abi.FeedbackGrads(duff_ptr or None, dK_ptr or None, dxref_ptr or None, dq0_ptr or None, dqd0_ptr or None)
-        _abi.check(self._L.rmx_rollout_vjp_feedback_device(self._batch, int(nsteps), C.byref(fb), C.c_void_p(gq_ptr or None),
-                                                           C.c_void_p(gqd_ptr or None), C.c_void_p(gu_ptr or None), C.byref(fg)),
-                   "rmx_rollout_vjp_feedback_device")
+        _abi.check(self._L.rmx_rollout_vjp_feedback_device(self._batch, int(nsteps), C.byref(fb), _vp(gq_ptr), _vp(gqd_ptr), _vp(gu_ptr),
+                                                           C.byref(fg)), "rmx_rollout_vjp_feedback_device")
 
     def _param_shapes(self):
         """The shape of one rollout's row of every rmx_param_grads member."""
         return {"stiffness": (self.nr,), "damping": (self.nr,), "qrest": (self.nr,), "inertia": (int(self._desc.njoints), 6), "grav": (3,)}
-
-    @staticmethod
-    def _param_names(want, who):
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(w not in _abi.PARAM_NAMES for w in want) or len(set(want)) != len(want):
-            raise ValueError("%s: want must name distinct outputs among %s, got %r" % (who, ", ".join(repr(n) for n in _abi.PARAM_NAMES), want))
-        return want
 
     def rollout_vjp_params(self, nsteps, gq, gqd, want=_abi.PARAM_NAMES, initial_state=True):
         """rmx_rollout_vjp_params on the tape of the last rollout_tape: rollout_vjp's sweep for the cotangents gq, gqd [B][nsteps][nr],
@@ -647,18 +588,12 @@ class BatchSim:
         grav [B][3].  The gradient of a parameter the rollouts share is the sum over the batch; of a stiffness or damping set per
         joint the sum over that joint's DOFs.  Neither the state nor the tape changes."""
         nsteps = int(nsteps)
-        want = self._param_names(want, "rollout_vjp_params")
-        sh = (self.B, nsteps, self.nr)
-        gq = np.ascontiguousarray(gq, dtype=np.float64)
-        gqd = np.ascontiguousarray(gqd, dtype=np.float64)
-        if gq.shape != sh or gqd.shape != sh:
-            raise ValueError("rollout_vjp_params: gq and gqd must have shape %r, got %r and %r" % (sh, gq.shape, gqd.shape))
-        du = np.empty(sh)
-        dq0 = np.empty((self.B, self.nr)) if initial_state else None
-        dqd0 = np.empty((self.B, self.nr)) if initial_state else None
+        want = _names("rollout_vjp_params", "want", want, _abi.PARAM_NAMES, False)
+        gq, gqd = _f64_joint("rollout_vjp_params", ("gq", "gqd"), (gq, gqd), (self.B, nsteps, self.nr))
+        du, dq0, dqd0 = self._vjp_outputs(nsteps, initial_state)
         shapes = self._param_shapes()
         grads = {w: np.zeros((self.B,) + shapes[w]) for w in want}
-        pg = _abi.ParamGrads(*[grads[n].ctypes.data if n in grads else None for n in _abi.PARAM_NAMES])
+        pg = _abi.ParamGrads(*[_addr(grads.get(n)) for n in _abi.PARAM_NAMES])
         _abi.check(self._L.rmx_rollout_vjp_params(self._batch, nsteps, _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(du), _abi.dptr(dq0),
                                                   _abi.dptr(dqd0), C.byref(pg)), "rmx_rollout_vjp_params")
         return du, dq0, dqd0, grads
@@ -669,9 +604,8 @@ class BatchSim:
         formed; stiffness, damping, qrest [B][nr], inertia [B][njoints][6], grav [B][3], 0 / None: that output is neither computed
         nor stored (not all five)."""
         pg = _abi.ParamGrads(stiffness_ptr or None, damping_ptr or None, qrest_ptr or None, inertia_ptr or None, grav_ptr or None)
-        _abi.check(self._L.rmx_rollout_vjp_params_device(self._batch, int(nsteps), C.c_void_p(gq_ptr or None), C.c_void_p(gqd_ptr or None),
-                                                         C.c_void_p(du_ptr or None), C.c_void_p(dq0_ptr or None), C.c_void_p(dqd0_ptr or None),
-                                                         C.byref(pg)), "rmx_rollout_vjp_params_device")
+        _abi.check(self._L.rmx_rollout_vjp_params_device(self._batch, int(nsteps), _vp(gq_ptr), _vp(gqd_ptr), _vp(du_ptr), _vp(dq0_ptr),
+                                                         _vp(dqd0_ptr), C.byref(pg)), "rmx_rollout_vjp_params_device")
 
     def rollout_linearize(self, nsteps, which=("XA", "XB", "XU")):
         """rmx_rollout_linearize on the tape of the last rollout_tape: the forward sensitivities of every taped solve x(qA, qB, u),
@@ -679,9 +613,7 @@ class BatchSim:
         name in `which`, in that order, each [B][nslots][nr][nr] with [.., i, j] = dx_i/d(.)_j; nslots = nsteps for a BDF1 tape,
         nsteps + 1 for a BDF2 tape (slot nsteps: the SDIRK2a solve).  Neither the state nor the tape changes."""
         nsteps = int(nsteps)
-        which = (which,) if isinstance(which, str) else tuple(which)
-        if any(w not in ("XA", "XB", "XU") for w in which) or len(set(which)) != len(which):
-            raise ValueError("rollout_linearize: which must name distinct outputs among 'XA', 'XB', 'XU', got %r" % (which,))
+        which = _names("rollout_linearize", "which", which, ("XA", "XB", "XU"), True)
         nslots = max(nsteps, 0) + (1 if self._tape_integrator == 2 else 0)
         out = {w: np.empty((self.B, nslots, self.nr, self.nr)) for w in which}
         _abi.check(self._L.rmx_rollout_linearize(self._batch, nsteps, _abi.dptr(out.get("XA")), _abi.dptr(out.get("XB")),
@@ -692,8 +624,8 @@ class BatchSim:
     def rollout_linearize_device(self, nsteps, XA_ptr, XB_ptr, XU_ptr):
         """rollout_linearize with DEVICE pointers (integers), each [B][nslots][nr*nr] with entry j*nr + i = dx_i/d(.)_j (column-major
         in the last index); 0 / None: that output is neither computed nor stored (not all three)."""
-        _abi.check(self._L.rmx_rollout_linearize_device(self._batch, int(nsteps), C.c_void_p(XA_ptr or None), C.c_void_p(XB_ptr or None),
-                                                        C.c_void_p(XU_ptr or None)), "rmx_rollout_linearize_device")
+        _abi.check(self._L.rmx_rollout_linearize_device(self._batch, int(nsteps), _vp(XA_ptr), _vp(XB_ptr), _vp(XU_ptr)),
+                   "rmx_rollout_linearize_device")
 
     def rollout_jvp(self, nsteps, tu=None, tq0=None, tqd0=None):
         """rmx_rollout_jvp on the tape of the last rollout_tape: the tangents of the whole trajectory for tangents of the controls,
@@ -723,9 +655,8 @@ class BatchSim:
     def rollout_jvp_device(self, nsteps, ntan, tu_ptr, tq0_ptr, tqd0_ptr, tq_ptr, tqd_ptr):
         """rollout_jvp with DEVICE pointers (integers): tu [B][ntan][nsteps][nr], tq0, tqd0 [B][ntan][nr], 0 / None: zero (not all
         three); tq, tqd [B][ntan][nsteps][nr]."""
-        _abi.check(self._L.rmx_rollout_jvp_device(self._batch, int(nsteps), int(ntan), C.c_void_p(tu_ptr or None), C.c_void_p(tq0_ptr or None),
-                                                  C.c_void_p(tqd0_ptr or None), C.c_void_p(tq_ptr or None), C.c_void_p(tqd_ptr or None)),
-                   "rmx_rollout_jvp_device")
+        _abi.check(self._L.rmx_rollout_jvp_device(self._batch, int(nsteps), int(ntan), _vp(tu_ptr), _vp(tq0_ptr), _vp(tqd0_ptr), _vp(tq_ptr),
+                                                  _vp(tqd_ptr)), "rmx_rollout_jvp_device")
 
     def rollout_lqr(self, nsteps, lx, lu, Q, R, mu=0.0, mu_b=None):
         """rmx_rollout_lqr on the BDF1 tape of the last rollout_tape / rollout_feedback: the Riccati sweep of iLQR (the recursion of
@@ -735,33 +666,30 @@ class BatchSim:
         K[b, k-1, j, i] = du_i/dx_j, the table rollout_feedback takes per rollout; a rollout whose Quu + mu I was not positive
         definite has notpd set and zero gains.  Neither the state nor the tape changes."""
         nsteps = int(nsteps)
-        B, nr = self.B, self.nr
-        lx = np.ascontiguousarray(lx, dtype=np.float64)
-        lu = np.ascontiguousarray(lu, dtype=np.float64)
-        Q = np.ascontiguousarray(Q, dtype=np.float64)
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        if lx.shape != (B, nsteps, 2 * nr) or lu.shape != (B, nsteps, nr):
-            raise ValueError("rollout_lqr: lx and lu must have shapes %r and %r, got %r and %r"
-                             % ((B, nsteps, 2 * nr), (B, nsteps, nr), lx.shape, lu.shape))
-        tail = (nsteps, 2 * nr, 2 * nr)
-        if Q.shape not in (tail, (B,) + tail):
-            raise ValueError("rollout_lqr: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, Q.shape))
-        if R.shape != (nr, nr):
-            raise ValueError("rollout_lqr: R must have shape %r, got %r" % ((nr, nr), R.shape))
-        if mu_b is not None:
-            mu_b = np.ascontiguousarray(mu_b, dtype=np.float64)
-            if mu_b.shape != (B,):
-                raise ValueError("rollout_lqr: mu_b must have shape %r, got %r" % ((B,), mu_b.shape))
-        kff = np.empty((B, nsteps, nr))
-        K = np.empty((B, nsteps, 2 * nr, nr))
-        expected = np.empty(B)
-        status = np.zeros(B, dtype=np.int32)
-        # (Q and R are symmetric: their row-major memory is the ABI's column-major table)
-        cost = _abi.LqrCost(lx.ctypes.data, lu.ctypes.data, Q.ctypes.data, R.ctypes.data, int(Q.ndim == 4), float(mu),
-                            None if mu_b is None else mu_b.ctypes.data)
-        gains = _abi.LqrGains(kff.ctypes.data, K.ctypes.data, expected.ctypes.data, status.ctypes.data)
+        cost, keep = self._lqr_cost("rollout_lqr", nsteps, [("lx", lx), ("lu", lu)], Q, R, mu, mu_b)
+        gains, (kff, K, expected, status) = self._lqr_gains(nsteps)
         _abi.check(self._L.rmx_rollout_lqr(self._batch, nsteps, C.byref(cost), C.byref(gains)), "rmx_rollout_lqr")
+        del keep
         return kff, K, expected, status != 0
+
+    def _lqr_cost(self, who, nsteps, named, Q, R, mu, mu_b):
+        """The checked cost of rollout_lqr / rollout_lqr_box -> (LqrCost, the arrays it points into).  named: ("lx", lx), ("lu", lu)
+        and, for the box form, ("ubar", ubar) - refused together; the arrays come back in that order at the head of the second item."""
+        B, nr = self.B, self.nr
+        shapes = [(B, nsteps, 2 * nr)] + [(B, nsteps, nr)] * (len(named) - 1)
+        keep = _f64_joint(who, [n for n, _ in named], [a for _, a in named], shapes)
+        Q, per = _table(who, "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
+        R = _f64(who, "R", R, (nr, nr))
+        if mu_b is not None:
+            mu_b = _f64(who, "mu_b", mu_b, (B,))
+        # (Q and R are symmetric: their row-major memory is the ABI's column-major table)
+        return _abi.LqrCost(_addr(keep[0]), _addr(keep[1]), _addr(Q), _addr(R), per, float(mu), _addr(mu_b)), keep + [Q, R, mu_b]
+
+    def _lqr_gains(self, nsteps):
+        """The outputs of a Riccati sweep -> (LqrGains, (kff, K, expected, status))."""
+        B, nr = self.B, self.nr
+        out = (np.empty((B, nsteps, nr)), np.empty((B, nsteps, 2 * nr, nr)), np.empty(B), np.zeros(B, dtype=np.int32))
+        return _abi.LqrGains(*[a.ctypes.data for a in out]), out
 
     def rollout_lqr_box(self, nsteps, lx, lu, Q, R, ubar, ulim, mu=0.0, mu_b=None, max_iter=0):
         """rmx_rollout_lqr_box: rollout_lqr under the torque limits ulim=(ulo, uhi) ([nr] each or None) - at every step the box QP of
@@ -771,68 +699,50 @@ class BatchSim:
         row of K and its bit set in clamped; status 0, 1 (a pivot not > 0) or 2 (a QP did not terminate) - a rollout with status != 0
         has zero kff, K, clamped and expected 0.  With no finite bound: rollout_lqr's bits."""
         nsteps = int(nsteps)
-        B, nr = self.B, self.nr
-        lx = np.ascontiguousarray(lx, dtype=np.float64)
-        lu = np.ascontiguousarray(lu, dtype=np.float64)
-        Q = np.ascontiguousarray(Q, dtype=np.float64)
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        ubar = np.ascontiguousarray(ubar, dtype=np.float64)
-        if lx.shape != (B, nsteps, 2 * nr) or lu.shape != (B, nsteps, nr) or ubar.shape != (B, nsteps, nr):
-            raise ValueError("rollout_lqr_box: lx, lu and ubar must have shapes %r, %r and %r, got %r, %r and %r"
-                             % ((B, nsteps, 2 * nr), (B, nsteps, nr), (B, nsteps, nr), lx.shape, lu.shape, ubar.shape))
-        tail = (nsteps, 2 * nr, 2 * nr)
-        if Q.shape not in (tail, (B,) + tail):
-            raise ValueError("rollout_lqr_box: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, Q.shape))
-        if R.shape != (nr, nr):
-            raise ValueError("rollout_lqr_box: R must have shape %r, got %r" % ((nr, nr), R.shape))
-        if mu_b is not None:
-            mu_b = np.ascontiguousarray(mu_b, dtype=np.float64)
-            if mu_b.shape != (B,):
-                raise ValueError("rollout_lqr_box: mu_b must have shape %r, got %r" % ((B,), mu_b.shape))
-        ulo, uhi = self._ulim(ulim, "rollout_lqr_box")
-        kff = np.empty((B, nsteps, nr))
-        K = np.empty((B, nsteps, 2 * nr, nr))
-        expected = np.empty(B)
-        status = np.zeros(B, dtype=np.int32)
-        clamped = np.zeros((B, nsteps), dtype=np.uint32)
-        cost = _abi.LqrCost(lx.ctypes.data, lu.ctypes.data, Q.ctypes.data, R.ctypes.data, int(Q.ndim == 4), float(mu),
-                            None if mu_b is None else mu_b.ctypes.data)
-        box = _abi.Box(None if ulo is None else ulo.ctypes.data, None if uhi is None else uhi.ctypes.data)
-        gains = _abi.LqrGains(kff.ctypes.data, K.ctypes.data, expected.ctypes.data, status.ctypes.data)
-        _abi.check(self._L.rmx_rollout_lqr_box(self._batch, nsteps, C.byref(cost), C.byref(box), ubar.ctypes.data, int(max_iter), C.byref(gains),
-                                               clamped.ctypes.data), "rmx_rollout_lqr_box")
+        cost, keep = self._lqr_cost("rollout_lqr_box", nsteps, [("lx", lx), ("lu", lu), ("ubar", ubar)], Q, R, mu, mu_b)
+        box, lim = self._ulim(ulim, "rollout_lqr_box")
+        gains, (kff, K, expected, status) = self._lqr_gains(nsteps)
+        clamped = np.zeros((self.B, nsteps), dtype=np.uint32)
+        _abi.check(self._L.rmx_rollout_lqr_box(self._batch, nsteps, C.byref(cost), C.byref(box), keep[2].ctypes.data, int(max_iter),
+                                               C.byref(gains), clamped.ctypes.data), "rmx_rollout_lqr_box")
+        del keep, lim
         return kff, K, expected, status, clamped
+
+    @staticmethod
+    def _lqr_device(lx_ptr, lu_ptr, Q_ptr, R_ptr, per_rollout, mu, mu_b_ptr, kff_ptr, K_ptr, expected_ptr, status_ptr):
+        """(LqrCost, LqrGains) of the _device forms of the two Riccati sweeps, from DEVICE pointers."""
+        return (_abi.LqrCost(lx_ptr or None, lu_ptr or None, Q_ptr or None, R_ptr or None, int(bool(per_rollout)), float(mu), mu_b_ptr or None),
+                _abi.LqrGains(kff_ptr or None, K_ptr or None, expected_ptr or None, status_ptr or None))
 
     def rollout_lqr_box_device(self, nsteps, lx_ptr, lu_ptr, Q_ptr, R_ptr, ubar_ptr, ulo_ptr, uhi_ptr, kff_ptr, K_ptr, expected_ptr=None,
                                status_ptr=None, clamped_ptr=None, per_rollout=False, mu=0.0, mu_b_ptr=None, max_iter=0):
         """rollout_lqr_box with DEVICE pointers (integers): as rollout_lqr_device, and ubar [B][nsteps][nr], ulo, uhi [nr] (0 / None:
         that side is unbounded), clamped [B][nsteps] uint32 (0 / None: not stored)."""
-        cost = _abi.LqrCost(lx_ptr or None, lu_ptr or None, Q_ptr or None, R_ptr or None, int(bool(per_rollout)), float(mu), mu_b_ptr or None)
+        cost, gains = self._lqr_device(lx_ptr, lu_ptr, Q_ptr, R_ptr, per_rollout, mu, mu_b_ptr, kff_ptr, K_ptr, expected_ptr, status_ptr)
         box = _abi.Box(ulo_ptr or None, uhi_ptr or None)
-        gains = _abi.LqrGains(kff_ptr or None, K_ptr or None, expected_ptr or None, status_ptr or None)
-        _abi.check(self._L.rmx_rollout_lqr_box_device(self._batch, int(nsteps), C.byref(cost), C.byref(box), C.c_void_p(ubar_ptr or None),
-                                                      int(max_iter), C.byref(gains), C.c_void_p(clamped_ptr or None)),
-                   "rmx_rollout_lqr_box_device")
+        _abi.check(self._L.rmx_rollout_lqr_box_device(self._batch, int(nsteps), C.byref(cost), C.byref(box), _vp(ubar_ptr), int(max_iter),
+                                                      C.byref(gains), _vp(clamped_ptr)), "rmx_rollout_lqr_box_device")
 
     def rollout_lqr_device(self, nsteps, lx_ptr, lu_ptr, Q_ptr, R_ptr, kff_ptr, K_ptr, expected_ptr=None, status_ptr=None, per_rollout=False,
                            mu=0.0, mu_b_ptr=None):
         """rollout_lqr with DEVICE pointers (integers): lx [B][nsteps][2nr], lu, kff [B][nsteps][nr], Q [nsteps][2nr*2nr] or, with
         per_rollout=True, one table per rollout, R [nr*nr], K [B][nsteps][2nr*nr]; expected [B] doubles, status [B] int32 and mu_b
         [B] doubles may be 0 / None."""
-        cost = _abi.LqrCost(lx_ptr or None, lu_ptr or None, Q_ptr or None, R_ptr or None, int(bool(per_rollout)), float(mu), mu_b_ptr or None)
-        gains = _abi.LqrGains(kff_ptr or None, K_ptr or None, expected_ptr or None, status_ptr or None)
+        cost, gains = self._lqr_device(lx_ptr, lu_ptr, Q_ptr, R_ptr, per_rollout, mu, mu_b_ptr, kff_ptr, K_ptr, expected_ptr, status_ptr)
         _abi.check(self._L.rmx_rollout_lqr_device(self._batch, int(nsteps), C.byref(cost), C.byref(gains)), "rmx_rollout_lqr_device")
 
     @staticmethod
-    def _point_terms(terms, who, need_wpos):
-        """terms (a list of dict(body, xlocal, step[, wpos]), adjoint_track's) -> (array of TrackTerm, count)."""
+    def _point_terms(terms, who, need_wpos, h=None):
+        """terms (a list of dict(body, xlocal, step[, wpos]), adjoint_track's) -> (array of TrackTerm, count).  With the step size h a
+        term may give its time `t` in the place of `step`."""
         terms = list(terms)
         arr = (_abi.TrackTerm * max(len(terms), 1))()
         for a, t in zip(arr, terms):
             xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
             if xl.shape != (3,):
                 raise ValueError("%s: a term's xlocal must have shape (3,), got %r" % (who, xl.shape))
-            a.body, a.step = int(t["body"]), int(t["step"])
+            a.body = int(t["body"])
+            a.step = int(t["step"]) if "step" in t or h is None else int(round(float(t["t"]) / float(h)))
             a.wpos = float(t["wpos"]) if need_wpos else float(t.get("wpos", 0.0))
             for i in range(3):
                 a.xlocal[i] = float(xl[i])
@@ -846,19 +756,14 @@ class BatchSim:
         the Jacobian of the point at that posture.  Needs no tape and changes neither the state nor the tape."""
         nsteps = int(nsteps)
         B, nr = self.B, self.nr
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        if q.shape != (B, nsteps, nr):
-            raise ValueError("rollout_points: q must have shape %r, got %r" % ((B, nsteps, nr), q.shape))
+        q = _f64("rollout_points", "q", q, (B, nsteps, nr))
         arr, nterms = self._point_terms(terms, "rollout_points", False)
         if gx is not None:
-            gx = np.ascontiguousarray(gx, dtype=np.float64)
-            if gx.shape != (B, nterms, 3):
-                raise ValueError("rollout_points: gx must have shape %r, got %r" % ((B, nterms, 3), gx.shape))
+            gx = _f64("rollout_points", "gx", gx, (B, nterms, 3))
         x = np.empty((B, nterms, 3)) if points else None
         gq = np.empty((B, nsteps, nr)) if gx is not None else None
         pts = _abi.PointTerms(nterms, arr, None, 0)
-        _abi.check(self._L.rmx_rollout_points(self._batch, nsteps, q.ctypes.data, C.byref(pts), None if x is None else x.ctypes.data,
-                                              None if gx is None else gx.ctypes.data, None if gq is None else gq.ctypes.data),
+        _abi.check(self._L.rmx_rollout_points(self._batch, nsteps, q.ctypes.data, C.byref(pts), _addr(x), _addr(gx), _addr(gq)),
                    "rmx_rollout_points")
         return x, gq
 
@@ -867,8 +772,8 @@ class BatchSim:
         not formed (not both; gq needs gx).  terms stays the host list."""
         arr, nterms = self._point_terms(terms, "rollout_points_device", False)
         pts = _abi.PointTerms(nterms, arr, None, 0)
-        _abi.check(self._L.rmx_rollout_points_device(self._batch, int(nsteps), C.c_void_p(q_ptr or None), C.byref(pts), C.c_void_p(x_ptr or None),
-                                                     C.c_void_p(gx_ptr or None), C.c_void_p(gq_ptr or None)), "rmx_rollout_points_device")
+        _abi.check(self._L.rmx_rollout_points_device(self._batch, int(nsteps), _vp(q_ptr), C.byref(pts), _vp(x_ptr), _vp(gx_ptr), _vp(gq_ptr)),
+                   "rmx_rollout_points_device")
 
     def rollout_cost(self, nsteps, q, qdot, Q=None, xgoal=None, terms=None, xtarget=None, want=("Jk", "lx", "Q")):
         """rmx_rollout_cost: the cost of a state record q, qdot [B][nsteps][nr] and its second-order model for rollout_lqr -
@@ -880,40 +785,25 @@ class BatchSim:
         no tape and changes neither the state nor the tape."""
         nsteps = int(nsteps)
         B, nr = self.B, self.nr
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(w not in ("Jk", "lx", "Q") for w in want) or len(set(want)) != len(want):
-            raise ValueError("rollout_cost: want must name distinct outputs among 'Jk', 'lx', 'Q', got %r" % (want,))
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        qdot = np.ascontiguousarray(qdot, dtype=np.float64)
-        if q.shape != (B, nsteps, nr) or qdot.shape != (B, nsteps, nr):
-            raise ValueError("rollout_cost: q and qdot must have shape %r, got %r and %r" % ((B, nsteps, nr), q.shape, qdot.shape))
+        want = _names("rollout_cost", "want", want, ("Jk", "lx", "Q"), False)
+        q, qdot = _f64_joint("rollout_cost", ("q", "qdot"), (q, qdot), (B, nsteps, nr))
         sc = None
         if Q is not None or xgoal is not None:
             sc = _abi.StateCost(None, None, 0, 0)
-            if Q is not None:
-                Q = np.ascontiguousarray(Q, dtype=np.float64)
-                tail = (nsteps, 2 * nr, 2 * nr)
-                if Q.shape not in (tail, (B,) + tail):
-                    raise ValueError("rollout_cost: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, Q.shape))
-                sc.Q, sc.Q_per_rollout = Q.ctypes.data, int(Q.ndim == 4)      # (symmetric: row-major memory is the column-major table)
+            if Q is not None:      # (symmetric: row-major memory is the column-major table)
+                Q, sc.Q_per_rollout = _table("rollout_cost", "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
+                sc.Q = Q.ctypes.data
             if xgoal is not None:
-                xgoal = np.ascontiguousarray(xgoal, dtype=np.float64)
-                tail = (nsteps, 2 * nr)
-                if xgoal.shape not in (tail, (B,) + tail):
-                    raise ValueError("rollout_cost: xgoal must have shape %r or %r, got %r" % (tail, (B,) + tail, xgoal.shape))
-                sc.xgoal, sc.goal_per_rollout = xgoal.ctypes.data, int(xgoal.ndim == 3)
+                xgoal, sc.goal_per_rollout = _table("rollout_cost", "xgoal", xgoal, (nsteps, 2 * nr), B)
+                sc.xgoal = xgoal.ctypes.data
         pts = None
         if terms is not None:
             arr, nterms = self._point_terms(terms, "rollout_cost", True)
-            if xtarget is None:
-                raise ValueError("rollout_cost: xtarget is None")
-            xtarget = np.ascontiguousarray(xtarget, dtype=np.float64)
-            if xtarget.shape not in ((nterms, 3), (B, nterms, 3)):
-                raise ValueError("rollout_cost: xtarget must have shape (%d, 3) or (%d, %d, 3), got %r" % (nterms, B, nterms, xtarget.shape))
-            pts = _abi.PointTerms(nterms, arr, xtarget.ctypes.data, int(xtarget.ndim == 3))
+            xtarget, per = self._targets("rollout_cost", xtarget, nterms)
+            pts = _abi.PointTerms(nterms, arr, xtarget.ctypes.data, per)
         shapes = {"Jk": (B, nsteps), "lx": (B, nsteps, 2 * nr), "Q": (B, nsteps, 2 * nr, 2 * nr)}
         out = {w: np.empty(shapes[w]) for w in want}
-        cm = _abi.CostModel(*[out[n].ctypes.data if n in out else None for n in ("Jk", "lx", "Q")])
+        cm = _abi.CostModel(*[_addr(out.get(n)) for n in ("Jk", "lx", "Q")])
         _abi.check(self._L.rmx_rollout_cost(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, None if sc is None else C.byref(sc),
                                             None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost")
         return out
@@ -930,7 +820,7 @@ class BatchSim:
             arr, nterms = self._point_terms(terms, "rollout_cost_device", True)
             pts = _abi.PointTerms(nterms, arr, xtarget_ptr or None, int(bool(target_per_rollout)))
         cm = _abi.CostModel(Jk_ptr or None, lx_ptr or None, Qout_ptr or None)
-        _abi.check(self._L.rmx_rollout_cost_device(self._batch, int(nsteps), C.c_void_p(q_ptr or None), C.c_void_p(qdot_ptr or None),
+        _abi.check(self._L.rmx_rollout_cost_device(self._batch, int(nsteps), _vp(q_ptr), _vp(qdot_ptr),
                                                    C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
                                                    None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost_device")
 
@@ -970,17 +860,7 @@ class BatchSim:
             raise _abi.RedMaxHipError("history_read: no step_history_async record is outstanding on this batch "
                                       "(the last step call was synchronous, unrecorded, or has replaced it)")
         nsteps, record = self._async
-        out = {}
-        hist = _abi.History()
-        if record & _abi.REC_ENERGY:
-            out["T"], out["V"] = np.empty((nsteps, self.B)), np.empty((nsteps, self.B))
-            hist.T, hist.V = _abi.dptr(out["T"]), _abi.dptr(out["V"])
-        if record & _abi.REC_STATE:
-            out["q"], out["qdot"] = np.empty((nsteps, self.B, self.nr)), np.empty((nsteps, self.B, self.nr))
-            hist.q, hist.qdot = _abi.dptr(out["q"]), _abi.dptr(out["qdot"])
-        if record & _abi.REC_CHARTS and self.nsph:
-            out["charts"] = np.full((nsteps, self.B, self.nsph), 7, dtype=np.int32)
-            hist.charts = _abi.iptr(out["charts"])
+        out, hist = _history_arrays(self.B, self.nr, self.nsph, nsteps, record)
         _abi.check(self._L.rmx_history_read(self._batch, C.byref(hist)), "rmx_history_read")
         return out
 
@@ -1001,8 +881,7 @@ class BatchSim:
         _abi.check(self._L.rmx_stats_reset(self._batch), "rmx_stats_reset")
 
     def stats_read(self):
-        out = {k: np.zeros(self.B, dtype=np.int32) for k in ("newton_iters", "ls_halvings", "status")}
-        st = _abi.Stats(_abi.iptr(out["newton_iters"]), _abi.iptr(out["ls_halvings"]), _abi.iptr(out["status"]))
+        out, st = _stats_arrays(self.B)
         _abi.check(self._L.rmx_stats_read(self._batch, C.byref(st)), "rmx_stats_read")
         return out
 
@@ -1096,18 +975,9 @@ class GroupSim:
         return a.value, b.value
 
     def _outputs(self, nsteps, record):
-        out = {k: np.zeros(self.B, dtype=np.int32) for k in ("newton_iters", "ls_halvings", "status")}
-        st = _abi.Stats(_abi.iptr(out["newton_iters"]), _abi.iptr(out["ls_halvings"]), _abi.iptr(out["status"]))
-        hist = _abi.History()
-        if record & _abi.REC_ENERGY:
-            out["T"], out["V"] = np.empty((nsteps, self.B)), np.empty((nsteps, self.B))
-            hist.T, hist.V = _abi.dptr(out["T"]), _abi.dptr(out["V"])
-        if record & _abi.REC_STATE:
-            out["q"], out["qdot"] = np.empty((nsteps, self.B, self.nr)), np.empty((nsteps, self.B, self.nr))
-            hist.q, hist.qdot = _abi.dptr(out["q"]), _abi.dptr(out["qdot"])
-        if record & _abi.REC_CHARTS and self.nsph:
-            out["charts"] = np.full((nsteps, self.B, self.nsph), 7, dtype=np.int32)
-            hist.charts = _abi.iptr(out["charts"])
+        out, st = _stats_arrays(self.B)
+        rec, hist = _history_arrays(self.B, self.nr, self.nsph, nsteps, record)
+        out.update(rec)
         return out, st, hist
 
     def step(self, nsteps, integrator=1, h=None, record=0):

@@ -27,20 +27,7 @@ def _function():
         @staticmethod
         def forward(q0, qdot0, u, sim, h, pscale, check, integrator, names=(), *ptensors):
             # (names, ptensors: the model parameters of rollout(params=...); the forward does not read their values)
-            B, nsteps, nr = u.shape
-            q0c, qd0c, uc = q0.contiguous(), qdot0.contiguous(), u.contiguous()
-            qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
-            qdtraj = torch.empty_like(qtraj)
-            # the library works on a stream of its own and returns when its kernels have finished: what torch has queued for the
-            # inputs must be done before it starts
-            torch.cuda.current_stream(u.device).synchronize()
-            sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
-            info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=pscale, stats=check,
-                                           integrator=integrator)
-            if check and (info["status"] & _BAD_STATUS).any():
-                bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
-                raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
-            return qtraj, qdtraj
+            return _tape_forward(sim, q0.contiguous(), qdot0.contiguous(), u.contiguous(), h, pscale, check, integrator)
 
         @staticmethod
         def setup_context(ctx, inputs, output):
@@ -128,17 +115,68 @@ def _function():
     return _Function
 
 
-def _check_inputs(sim, q0, qdot0, u):
-    """The argument checks rollout, linearize, jvp and rollout_feedback share (and their words)."""
+def _check_tensors(who, sim, named):
+    """float64 tensors on the sim's device: THE place that says so.  named: (name, tensor) pairs.  Returns the device."""
     import torch
     dev = torch.device("cuda", sim.device)
-    for name, t in (("q0", q0), ("qdot0", qdot0), ("u", u)):
+    for name, t in named:
         if not isinstance(t, torch.Tensor):
-            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+            raise ValueError("%s: %s must be a torch.Tensor, got %s" % (who, name, type(t).__name__))
         if t.dtype != torch.float64:
-            raise ValueError("rollout: %s must be float64, got %s" % (name, t.dtype))
+            raise ValueError("%s: %s must be float64, got %s" % (who, name, t.dtype))
         if t.device != dev:
-            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+            raise ValueError("%s: %s must be on %s (the sim's device), got %s" % (who, name, dev, t.device))
+    return dev
+
+
+def _check_integrator(integrator):
+    if integrator not in (1, 2):
+        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+
+
+def _check_ulim(who, ulim, nr, dev):
+    """(ulo, uhi) of a ``ulim`` argument as contiguous tensors or None each."""
+    import torch
+    if not isinstance(ulim, (tuple, list)) or len(ulim) != 2:
+        raise ValueError("%s: ulim must be a pair (ulo, uhi), either may be None" % who)
+    out = []
+    for name, t in zip(("ulo", "uhi"), ulim):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != (nr,):
+                raise ValueError("%s: %s must be a float64 tensor of shape (%d,) on %s" % (who, name, nr, dev))
+            t = t.detach().contiguous()
+        out.append(t)
+    return out
+
+
+def _raise_newton_failed(info):
+    """RuntimeError when the status words of a taped rollout's info say that a Newton solve failed."""
+    if (info["status"] & _BAD_STATUS).any():
+        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
+        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+
+
+def _tape_forward(sim, q0c, qd0c, uc, h, pscale, check, integrator):
+    """The open-loop taped rollout of contiguous device tensors: (qtraj, qdtraj), the tape left in the sim.  The forward of rollout,
+    linearize and jvp; whatever else the caller allocates, it allocates before."""
+    import torch
+    B, nsteps, nr = uc.shape
+    qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=uc.device)
+    qdtraj = torch.empty_like(qtraj)
+    # the library works on a stream of its own and returns when its kernels have finished: what torch has queued for the
+    # inputs must be done before it starts
+    torch.cuda.current_stream(uc.device).synchronize()
+    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
+    info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=pscale, stats=check,
+                                   integrator=integrator)
+    if check:
+        _raise_newton_failed(info)
+    return qtraj, qdtraj
+
+
+def _check_inputs(sim, q0, qdot0, u):
+    """The argument checks rollout, linearize, jvp and rollout_feedback share (and their words)."""
+    _check_tensors("rollout", sim, (("q0", q0), ("qdot0", qdot0), ("u", u)))
     if u.dim() != 3 or u.shape[0] != sim.B or u.shape[2] != sim.nr or u.shape[1] < 1:
         raise ValueError("rollout: u must have shape (%d, nsteps, %d), got %r" % (sim.B, sim.nr, tuple(u.shape)))
     for name, t in (("q0", q0), ("qdot0", qdot0)):
@@ -177,7 +215,6 @@ def model_params(sim):
 
 def _check_params(sim, params):
     """params of rollout -> (names, tensors) in the order of rmx_param_grads; ValueError for anything the library cannot fill."""
-    import torch
     from . import _abi
     if not isinstance(params, dict):
         raise ValueError("rollout: params must be a dict of tensors (model_params(sim) or part of it), got %s" % type(params).__name__)
@@ -186,19 +223,12 @@ def _check_params(sim, params):
         raise ValueError("rollout: unknown model parameter %r (known: %s)" % (unknown[0], ", ".join(_abi.PARAM_NAMES)))
     if not params:
         raise ValueError("rollout: params names no parameter (pass None for a rollout without parameter gradients)")
-    dev = torch.device("cuda", sim.device)
     shapes = sim._param_shapes()
     names = tuple(n for n in _abi.PARAM_NAMES if n in params)
-    for n in names:
-        t = params[n]
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("rollout: params[%r] must be a torch.Tensor, got %s" % (n, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("rollout: params[%r] must be float64, got %s" % (n, t.dtype))
-        if t.device != dev:
-            raise ValueError("rollout: params[%r] must be on %s (the sim's device), got %s" % (n, dev, t.device))
-        if tuple(t.shape) != shapes[n]:
-            raise ValueError("rollout: params[%r] must have shape %r, got %r" % (n, shapes[n], tuple(t.shape)))
+    for n in names:      # (tensor by tensor: the first tensor that is wrong in any way is the one named)
+        _check_tensors("rollout", sim, [("params[%r]" % n, params[n])])
+        if tuple(params[n].shape) != shapes[n]:
+            raise ValueError("rollout: params[%r] must have shape %r, got %r" % (n, shapes[n], tuple(params[n].shape)))
     return names, tuple(params[n] for n in names)
 
 
@@ -221,9 +251,7 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, par
     that parameter, summed over the batch (one rmx_rollout_vjp_params call).  The forward does NOT read the tensors' values: the sim
     simulates the model it was built from, so the tensors must describe that model, and a parameter update means building a new
     BatchSim from the updated scene.  Unknown names and tensors of another shape, dtype or device raise ValueError."""
-    import torch
-    if integrator not in (1, 2):
-        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    _check_integrator(integrator)
     _check_inputs(sim, q0, qdot0, u)
     args = (q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check), integrator)
     if params is None:
@@ -254,16 +282,9 @@ def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):
     _check_inputs(sim, q0, qdot0, u)
     h = float(sim.opts.h if h is None else h)
     B, nsteps, nr = u.shape
-    q0c, qd0c, uc = q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous()
-    qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=u.device)
-    qdtraj = torch.empty_like(qtraj)
     X = torch.empty((3, B, nsteps, nr, nr), dtype=torch.float64, device=u.device)
-    torch.cuda.current_stream(u.device).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
-    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
-    info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=float(pscale), stats=bool(check))
-    if check and (info["status"] & _BAD_STATUS).any():
-        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
-        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+    qtraj, qdtraj = _tape_forward(sim, q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous(), h, float(pscale),
+                                  bool(check), 1)
     sim.rollout_linearize_device(nsteps, X[0].data_ptr(), X[1].data_ptr(), X[2].data_ptr())
     XA, XB, XU = (X[i].transpose(-1, -2) for i in range(3))      # the ABI's last index is column-major: [.., i, j] = dx_i/d(.)_j
     S = XA + XB
@@ -293,8 +314,7 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     feedback sum, uapp = min(max(uff + K'(x - xref), ulo), uhi), with K None too (rmx_rollout_tape_feedback_box_device).
     ``rollout_closed_loop`` does not know about the clamp: gradients through a saturated feedback law are not formed."""
     import torch
-    if integrator not in (1, 2):
-        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    _check_integrator(integrator)
     _check_inputs(sim, q0, qdot0, uff)
     B, nsteps, nr = uff.shape
     dev = torch.device("cuda", sim.device)
@@ -302,12 +322,7 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     for name, t, tail in (("K", K, (nsteps, 2 * nr, nr)), ("xref", xref, (nsteps, 2 * nr))):
         if t is None:
             continue
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("rollout: %s must be float64, got %s" % (name, t.dtype))
-        if t.device != dev:
-            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
+        _check_tensors("rollout", sim, [(name, t)])
         if tuple(t.shape) not in (tail, (B,) + tail):
             raise ValueError("rollout: %s must have shape %r or %r, got %r" % (name, tail, (B,) + tail, tuple(t.shape)))
         per.append(t.dim() == len(tail) + 1)
@@ -321,33 +336,45 @@ def rollout_feedback(sim, q0, qdot0, uff, K=None, xref=None, h=None, pscale=1.0,
     qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=dev)
     qdtraj = torch.empty_like(qtraj)
     uapp = torch.empty_like(qtraj)
-    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
     sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
     info = sim.rollout_feedback_device(nsteps, h, uc.data_ptr(), 0 if Kc is None else Kc.data_ptr(), 0 if xc is None else xc.data_ptr(),
                                        qtraj.data_ptr(), qdtraj.data_ptr(), uapp.data_ptr(), per_rollout=bool(per and per[0]),
                                        pscale=float(pscale), stats=bool(check or status), integrator=integrator,
                                        ulim=None if lim is None else tuple(0 if t is None else t.data_ptr() for t in lim))
-    if check and (info["status"] & _BAD_STATUS).any():
-        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
-        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+    if check:
+        _raise_newton_failed(info)
     if status:
         return qtraj, qdtraj, uapp, torch.as_tensor((info["status"] & _BAD_STATUS) != 0, device=dev)
     return qtraj, qdtraj, uapp
 
 
-def _check_ulim(who, ulim, nr, dev):
-    """(ulo, uhi) of a ``ulim`` argument as contiguous tensors or None each."""
+def _lqr_arguments(who, sim, lx, lu, Q, R, ubar=None, box=False):
+    """The checks lqr_backward and lqr_backward_box share (ubar: the box form's) -> (the sim's device, the tape's steps N)."""
+    dev = _check_tensors(who, sim, [("lx", lx), ("lu", lu), ("Q", Q), ("R", R)] + ([("ubar", ubar)] if box else []))
+    B, nr = sim.B, sim.nr
+    if lu.dim() != 3 or lu.shape[0] != B or lu.shape[2] != nr or lu.shape[1] < 1:
+        raise ValueError("%s: lu must have shape (%d, nsteps, %d), got %r" % (who, B, nr, tuple(lu.shape)))
+    N = lu.shape[1]
+    if box and (tuple(lx.shape) != (B, N, 2 * nr) or tuple(ubar.shape) != (B, N, nr)):
+        raise ValueError("%s: lx and ubar must have shapes %r and %r, got %r and %r"
+                         % (who, (B, N, 2 * nr), (B, N, nr), tuple(lx.shape), tuple(ubar.shape)))
+    if tuple(lx.shape) != (B, N, 2 * nr):
+        raise ValueError("%s: lx must have shape %r, got %r" % (who, (B, N, 2 * nr), tuple(lx.shape)))
+    tail = (N, 2 * nr, 2 * nr)
+    if tuple(Q.shape) not in (tail, (B,) + tail):
+        raise ValueError("%s: Q must have shape %r or %r, got %r" % (who, tail, (B,) + tail, tuple(Q.shape)))
+    if tuple(R.shape) != (nr, nr):
+        raise ValueError("%s: R must have shape %r, got %r" % (who, (nr, nr), tuple(R.shape)))
+    return dev, N
+
+
+def _lqr_outputs(sim, N, dev):
+    """kff [B][N][nr], K [B][N][2nr][nr], expected [B] and the int32 status [B] of a Riccati sweep, on the device."""
     import torch
-    if not isinstance(ulim, (tuple, list)) or len(ulim) != 2:
-        raise ValueError("%s: ulim must be a pair (ulo, uhi), either may be None" % who)
-    out = []
-    for name, t in zip(("ulo", "uhi"), ulim):
-        if t is not None:
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != (nr,):
-                raise ValueError("%s: %s must be a float64 tensor of shape (%d,) on %s" % (who, name, nr, dev))
-            t = t.detach().contiguous()
-        out.append(t)
-    return out
+    B, nr = sim.B, sim.nr
+    return (torch.empty((B, N, nr), dtype=torch.float64, device=dev), torch.empty((B, N, 2 * nr, nr), dtype=torch.float64, device=dev),
+            torch.empty(B, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
 
 
 def lqr_backward_box(sim, lx, lu, Q, R, ubar, ulim, mu=0.0, max_iter=0):
@@ -359,34 +386,12 @@ def lqr_backward_box(sim, lx, lu, Q, R, ubar, ulim, mu=0.0, max_iter=0):
     not > 0) or 2 (a QP did not terminate); a rollout with status != 0 has zero gains and expected 0.  One box for all steps and
     rollouts; BDF1 tapes only."""
     import torch
-    dev = torch.device("cuda", sim.device)
-    for name, t in (("lx", lx), ("lu", lu), ("Q", Q), ("R", R), ("ubar", ubar)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("lqr_backward_box: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("lqr_backward_box: %s must be float64, got %s" % (name, t.dtype))
-        if t.device != dev:
-            raise ValueError("lqr_backward_box: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
-    B, nr = sim.B, sim.nr
-    if lu.dim() != 3 or lu.shape[0] != B or lu.shape[2] != nr or lu.shape[1] < 1:
-        raise ValueError("lqr_backward_box: lu must have shape (%d, nsteps, %d), got %r" % (B, nr, tuple(lu.shape)))
-    N = lu.shape[1]
-    if tuple(lx.shape) != (B, N, 2 * nr) or tuple(ubar.shape) != (B, N, nr):
-        raise ValueError("lqr_backward_box: lx and ubar must have shapes %r and %r, got %r and %r"
-                         % ((B, N, 2 * nr), (B, N, nr), tuple(lx.shape), tuple(ubar.shape)))
-    tail = (N, 2 * nr, 2 * nr)
-    if tuple(Q.shape) not in (tail, (B,) + tail):
-        raise ValueError("lqr_backward_box: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, tuple(Q.shape)))
-    if tuple(R.shape) != (nr, nr):
-        raise ValueError("lqr_backward_box: R must have shape %r, got %r" % ((nr, nr), tuple(R.shape)))
-    ulo, uhi = _check_ulim("lqr_backward_box", ulim, nr, dev)
+    dev, N = _lqr_arguments("lqr_backward_box", sim, lx, lu, Q, R, ubar, box=True)
+    ulo, uhi = _check_ulim("lqr_backward_box", ulim, sim.nr, dev)
     lxc, luc, Qc, Rc, ubc = (t.detach().contiguous() for t in (lx, lu, Q, R, ubar))
-    kff = torch.empty((B, N, nr), dtype=torch.float64, device=dev)
-    K = torch.empty((B, N, 2 * nr, nr), dtype=torch.float64, device=dev)
-    expected = torch.empty(B, dtype=torch.float64, device=dev)
-    status = torch.zeros(B, dtype=torch.int32, device=dev)
-    clamped = torch.zeros((B, N), dtype=torch.int32, device=dev)
-    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    kff, K, expected, status = _lqr_outputs(sim, N, dev)
+    clamped = torch.zeros((sim.B, N), dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
     sim.rollout_lqr_box_device(N, lxc.data_ptr(), luc.data_ptr(), Qc.data_ptr(), Rc.data_ptr(), ubc.data_ptr(),
                                0 if ulo is None else ulo.data_ptr(), 0 if uhi is None else uhi.data_ptr(), kff.data_ptr(), K.data_ptr(),
                                expected.data_ptr(), status.data_ptr(), clamped.data_ptr(), per_rollout=Q.dim() == 4, mu=float(mu),
@@ -404,48 +409,13 @@ def lqr_backward(sim, lx, lu, Q, R, mu=0.0):
     expected [B], notpd [B] bool): K is what ``rollout_feedback`` takes as is (K[b, k-1, j, i] = du_i/dx_j, the transpose of
     backward_pass's), and a rollout whose Quu + mu I was not positive definite has notpd set, zero gains and expected 0."""
     import torch
-    dev = torch.device("cuda", sim.device)
-    for name, t in (("lx", lx), ("lu", lu), ("Q", Q), ("R", R)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("lqr_backward: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("lqr_backward: %s must be float64, got %s" % (name, t.dtype))
-        if t.device != dev:
-            raise ValueError("lqr_backward: %s must be on %s (the sim's device), got %s" % (name, dev, t.device))
-    B, nr = sim.B, sim.nr
-    if lu.dim() != 3 or lu.shape[0] != B or lu.shape[2] != nr or lu.shape[1] < 1:
-        raise ValueError("lqr_backward: lu must have shape (%d, nsteps, %d), got %r" % (B, nr, tuple(lu.shape)))
-    N = lu.shape[1]
-    if tuple(lx.shape) != (B, N, 2 * nr):
-        raise ValueError("lqr_backward: lx must have shape %r, got %r" % ((B, N, 2 * nr), tuple(lx.shape)))
-    tail = (N, 2 * nr, 2 * nr)
-    if tuple(Q.shape) not in (tail, (B,) + tail):
-        raise ValueError("lqr_backward: Q must have shape %r or %r, got %r" % (tail, (B,) + tail, tuple(Q.shape)))
-    if tuple(R.shape) != (nr, nr):
-        raise ValueError("lqr_backward: R must have shape %r, got %r" % ((nr, nr), tuple(R.shape)))
+    dev, N = _lqr_arguments("lqr_backward", sim, lx, lu, Q, R)
     lxc, luc, Qc, Rc = (t.detach().contiguous() for t in (lx, lu, Q, R))
-    kff = torch.empty((B, N, nr), dtype=torch.float64, device=dev)
-    K = torch.empty((B, N, 2 * nr, nr), dtype=torch.float64, device=dev)
-    expected = torch.empty(B, dtype=torch.float64, device=dev)
-    status = torch.zeros(B, dtype=torch.int32, device=dev)
-    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    kff, K, expected, status = _lqr_outputs(sim, N, dev)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
     sim.rollout_lqr_device(N, lxc.data_ptr(), luc.data_ptr(), Qc.data_ptr(), Rc.data_ptr(), kff.data_ptr(), K.data_ptr(),
                            expected.data_ptr(), status.data_ptr(), per_rollout=Q.dim() == 4, mu=float(mu))
     return kff, K, expected, status != 0
-
-
-def _check_tensors(who, sim, named):
-    """float64 tensors on the sim's device, in the words of lqr_backward."""
-    import torch
-    dev = torch.device("cuda", sim.device)
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a torch.Tensor, got %s" % (who, name, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("%s: %s must be float64, got %s" % (who, name, t.dtype))
-        if t.device != dev:
-            raise ValueError("%s: %s must be on %s (the sim's device), got %s" % (who, name, dev, t.device))
-    return dev
 
 
 _Points = None
@@ -465,7 +435,7 @@ def _points_function():
             B, N, _ = q.shape
             qc = q.detach().contiguous()
             x = torch.empty((B, len(terms), 3), dtype=torch.float64, device=q.device)
-            torch.cuda.current_stream(q.device).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+            torch.cuda.current_stream(q.device).synchronize()      # (the library works on a stream of its own: see _tape_forward)
             sim.rollout_points_device(N, qc.data_ptr(), terms, x_ptr=x.data_ptr())
             ctx.sim, ctx.terms = sim, terms
             ctx.save_for_backward(qc)
@@ -539,7 +509,7 @@ def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None,
     Jk = torch.empty((B, N), dtype=torch.float64, device=dev) if "J" in want else None
     lx = torch.empty((B, N, 2 * nr), dtype=torch.float64, device=dev) if "lx" in want else None
     Qo = torch.empty((B, N, 2 * nr, 2 * nr), dtype=torch.float64, device=dev) if "Q" in want else None
-    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
     ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
     sim.rollout_cost_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q is not None and Q.dim() == 4,
                             goal_per_rollout=xgoal is not None and xgoal.dim() == 3, terms=terms, xtarget_ptr=ptr(xtc),
@@ -634,8 +604,7 @@ def rollout_closed_loop(sim, q0, qdot0, uff, K, xref=None, h=None, pscale=1.0, c
     states the steps started from (no [B][nsteps][2nr][nr] tensor is made).  Arguments, checks and words are rollout_feedback's.
     backward() must run before the next rollout or adjoint_* call on the same sim: those replace the tape, and backward raises
     RuntimeError("the tape of this rollout has been replaced") then.  First derivatives only."""
-    if integrator not in (1, 2):
-        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    _check_integrator(integrator)
     return _closed_loop_function().apply(q0, qdot0, uff, K, xref, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check),
                                          integrator)
 
@@ -650,22 +619,14 @@ def jvp(sim, q0, qdot0, u, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, c
     one elimination per step whatever T is; no autograd graph is made.  Arguments, checks and words are rollout's.  The call
     replaces the sim's tape, as rollout does, and leaves the sim at the end of the rollout."""
     import torch
-    if integrator not in (1, 2):
-        raise ValueError("rollout: integrator must be 1 (BDF1) or 2 (BDF2), got %r" % (integrator,))
+    _check_integrator(integrator)
     _check_inputs(sim, q0, qdot0, u)
     B, nsteps, nr = u.shape
-    dev = torch.device("cuda", sim.device)
     tans = {n: t for n, t in (("tu", tu), ("tq0", tq0), ("tqdot0", tqdot0)) if t is not None}
     if not tans:
         raise ValueError("rollout: all tangents are None")
     tail = {"tu": (nsteps, nr), "tq0": (nr,), "tqdot0": (nr,)}
-    for n, t in tans.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("rollout: %s must be a torch.Tensor, got %s" % (n, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise ValueError("rollout: %s must be float64, got %s" % (n, t.dtype))
-        if t.device != dev:
-            raise ValueError("rollout: %s must be on %s (the sim's device), got %s" % (n, dev, t.device))
+    dev = _check_tensors("rollout", sim, tans.items())
     single = all(t.dim() == 1 + len(tail[n]) for n, t in tans.items())
     if single:
         tans = {n: t.unsqueeze(1) for n, t in tans.items()}
@@ -676,18 +637,10 @@ def jvp(sim, q0, qdot0, u, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, c
                              % (n, (B, T) + tail[n], tuple(t.shape[:1] + t.shape[2:]) if single else tuple(t.shape)))
     tans = {n: t.detach().contiguous() for n, t in tans.items()}
     h = float(sim.opts.h if h is None else h)
-    q0c, qd0c, uc = q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous()
-    qtraj = torch.empty((B, nsteps, nr), dtype=torch.float64, device=dev)
-    qdtraj = torch.empty_like(qtraj)
     tq = torch.empty((B, T, nsteps, nr), dtype=torch.float64, device=dev)
     tqd = torch.empty_like(tq)
-    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _Rollout.forward)
-    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
-    info = sim.rollout_tape_device(nsteps, h, uc.data_ptr(), qtraj.data_ptr(), qdtraj.data_ptr(), pscale=float(pscale), stats=bool(check),
-                                   integrator=integrator)
-    if check and (info["status"] & _BAD_STATUS).any():
-        bad = [(int(b), int(s)) for b, s in enumerate(info["status"]) if s & _BAD_STATUS]
-        raise RuntimeError("rollout: Newton failed (rollout, status bits; 1 diverged, 2 iteration limit, 4 NaN): %r" % (bad[:8],))
+    qtraj, qdtraj = _tape_forward(sim, q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous(), h, float(pscale),
+                                  bool(check), integrator)
     sim.rollout_jvp_device(nsteps, T, *(tans[n].data_ptr() if n in tans else 0 for n in ("tu", "tq0", "tqdot0")), tq.data_ptr(),
                            tqd.data_ptr())
     return (qtraj, qdtraj, tq[:, 0], tqd[:, 0]) if single else (qtraj, qdtraj, tq, tqd)
