@@ -778,8 +778,8 @@ int rmx_rollout_lqr_box_device(rmx_batch* b, int nsteps, const rmx_lqr_cost* cos
  * The host forms stage through one device allocation of their own, made first and freed before they return.  The _device forms:
  * every array a DEVICE pointer (the structs are host objects, `terms` stays a host array), nothing staged but the term table, which
  * goes to a small area of the batch's own; they return when the kernel has finished.
- * Out of scope: orientation and velocity targets; a table of the q block alone for rmx_rollout_lqr (the full 2nr x 2nr table per
- * rollout and step is written here and read there). */
+ * Out of scope: a table of the q block alone for rmx_rollout_lqr (the full 2nr x 2nr table per rollout and step is written here and
+ * read there).  Orientation and velocity targets: rmx_rollout_frames / rmx_rollout_cost_frames below. */
 typedef struct rmx_point_terms {
     int nterms;                    /* >= 1 */
     const rmx_track_term* terms;   /* host; body, xlocal, step (1..nsteps), wpos - rmx_adjoint_track's term */
@@ -806,6 +806,66 @@ int rmx_rollout_cost(rmx_batch* b, int nsteps, const double* q, const double* qd
                      const rmx_cost_model* out);
 int rmx_rollout_cost_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
                             const rmx_point_terms* pts, const rmx_cost_model* out);
+
+/* Frame targets in the task-space cost: position, point velocity and orientation of a body frame along a state record, the pull-back
+ * of cotangents through them, and the second-order model of "a joint-space quadratic plus frame targets" in the tables
+ * rmx_rollout_lqr takes.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.  No existing struct grows and
+ * no existing entry changes.
+ *
+ * A frame term is a point xlocal of body n, read at step k (1-based), with three weights wpos, wvel, wrot >= 0.  At the state
+ * (q_k, qdot_k) of row k-1 of the record, with Rw[i], pw[i] the world frame of node i, (sw_j, sv_j) the world screw of joint j and
+ * path = n and its strict ancestors (every Jacobian column of a DOF off the path is an exact zero):
+ *     position       p = Rw[n] xlocal + pw[n]                          Jp_j = sv_j + sw_j x p
+ *     orientation    R = Rw[n]                                          Jw_j = sw_j
+ *     node twists    om_i = sum_{j in anc*(i)} sw_j qdot_j             V_i = sum_{j in anc*(i)} sv_j qdot_j     (i itself included)
+ *     point velocity v = V_n + om_n x p  ( = Jp qdot )                 dv/dqdot_j = Jp_j
+ *                    dv/dq_i = G_i = sw_i x (v - (V_i + om_i x p)) + om_i x Jp_i       for i on the path
+ *     residuals      r = p - xtarget,  rv = v - vtarget,  e_w = 1/2 a(R Rtarget'),  a(M) = (M32 - M23, M13 - M31, M21 - M12)
+ *     cost           wpos/2 |r|^2 + wvel/2 |rv|^2 + wrot/4 |R - Rtarget|_F^2
+ * The last piece is wrot (1 - cos theta), theta the angle between the two frames: the chordal cost.  Its gradient VANISHES at
+ * theta = pi (a target exactly opposite gives no direction); keep targets away from it or pass through an intermediate one.
+ *     gradient       q rows: wpos Jp'r + wvel G'rv + wrot Jw'e_w        qdot rows: wvel Jp'rv                      (exact)
+ *     Gauss-Newton   qq: wpos Jp'Jp + wvel G'G + wrot Jw'Jw    q,qdot: wvel G'Jp    qdot,q: wvel Jp'G    qdot,qdot: wvel Jp'Jp
+ * The curvature of p, v and R is dropped, so the addition is positive semi-definite whatever the residuals; wrot Jw'Jw does not
+ * depend on R or Rtarget.  A 3x3 is column-major, as everywhere in this header.  A constant frame offset Rl on the body is not an
+ * argument: it folds into the target, R Rl against Rt being R against Rt Rl'.
+ *
+ * rmx_rollout_frames: x[b][t] = p_t, v[b][t] = v_t, R[b][t] = R_t (any may be NULL), and for cotangents gx, gv, gR (any may be NULL:
+ * zero)   gq[b][k-1] = sum_t Jp'gx + G'gv + Jw'a(gR R'),   gqd[b][k-1] = sum_t Jp'gv   over the terms of step k, zero rows at steps
+ * without a term.  gq needs one of the cotangents, gqd needs gv.  It reads neither the weights nor the targets.  With v, R, gv, gR and
+ * gqd all NULL, x and gq are the bits of rmx_rollout_points.
+ *
+ * rmx_rollout_cost_frames is rmx_rollout_cost with frame terms: Jk, lx and Q keep the layouts rmx_rollout_lqr reads.  Order of every
+ * sum: the joint-space part, then the terms in the caller's order, inside a term position, velocity, rotation.  Entries (i, j) and
+ * (j, i) of Q are formed from the same products in the same order: Q is symmetric bit for bit whenever the input is, the two cross
+ * blocks included.  A structural zero adds nothing: a step whose terms all have wvel = wrot = 0, and a step without terms, has the
+ * bits rmx_rollout_cost writes for the same position terms (Jk, lx and Q), whatever the other steps of the call carry.  A target
+ * table may be NULL only if every term's matching weight is zero; otherwise the call is refused and the message names the table.
+ *
+ * Everything else is rmx_rollout_cost's: no tape is needed, state and tape are left untouched, calls repeat with the same bits, a
+ * rollout's rows do not depend on its place in the batch, the batch size, shared against per-rollout tables or which outputs are
+ * NULL; models with ground contact and point forces are taken; the refusals in its words (spherical joints, more than 64 nodes,
+ * the terms, the per-rollout flags, nsteps; "null argument" for a null batch, q, qdot, out - ft in rmx_rollout_frames - or both of
+ * sc and ft; "all outputs are null"); a weight that is negative or not finite is refused by the term and the weight's name.  The host
+ * forms stage through one allocation of their own; the _device forms take DEVICE pointers for every array (`terms` stays host).
+ * Out of scope: angular-velocity targets; the logarithmic-map residual; a q-block-only table. */
+typedef struct rmx_frame_term { int body; double xlocal[3]; int step; double wpos, wvel, wrot; } rmx_frame_term;
+typedef struct rmx_frame_terms {
+    int nterms; const rmx_frame_term* terms;          /* host */
+    const double *xtarget, *vtarget, *Rtarget;        /* [nterms][3], [nterms][3], [nterms][9], or [batch][..] */
+    int per_rollout;
+} rmx_frame_terms;
+int rmx_rollout_frames(rmx_batch* b, int nsteps, const double* q, const double* qdot /*[batch][nsteps][nr] each*/, const rmx_frame_terms* ft,
+                       double* x /*[batch][nterms][3]*/, double* v /*[batch][nterms][3]*/, double* R /*[batch][nterms][9]*/,
+                       const double* gx, const double* gv, const double* gR /* the shapes of x, v, R */,
+                       double* gq, double* gqd /*[batch][nsteps][nr] each*/);
+int rmx_rollout_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_frame_terms* ft, double* d_x,
+                              double* d_v, double* d_R, const double* d_gx, const double* d_gv, const double* d_gR, double* d_gq,
+                              double* d_gqd);
+int rmx_rollout_cost_frames(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc,
+                            const rmx_frame_terms* ft /* either may be NULL, not both */, const rmx_cost_model* out);
+int rmx_rollout_cost_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
+                                   const rmx_frame_terms* ft, const rmx_cost_model* out);
 
 /* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
  * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of

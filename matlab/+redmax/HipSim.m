@@ -320,5 +320,46 @@ classdef HipSim < handle
 			end
 			[Jk, lx, Q] = redmax_hip_mex('rollout_cost', this.h, nsteps, q, qdot, Qin, xgoal, terms, xtarget);
 		end
+
+		function [x, v, R, gq, gqd] = rolloutFrames(this, nsteps, q, qdot, terms, gx, gv, gR)
+			% Position x and point velocity v (3 x nterms x batch) and orientation R (3 x 3 x nterms x batch) of body frames
+			% along a state record q, qdot (nr x nsteps x batch).  terms: struct array with the fields body (1-based listing
+			% index), xlocal, step - the frame of term t is read at the state of column step_t; weights are not read.  With
+			% cotangents gx, gv (3 x nterms x batch) and gR (3 x 3 x nterms x batch), [] for zero, gq and gqd (nr x nsteps x
+			% batch) are the pull-backs sum_t Jp'*gx + G'*gv + Jw'*a(gR*R') and sum_t Jp'*gv, with Jp = dp/dq = dv/dqdot,
+			% G = dv/dq and Jw the angular Jacobian AT THAT STATE.  Needs no tape and leaves the tape alone.
+			if nargin < 6
+				[x, v, R] = redmax_hip_mex('rollout_frames', this.h, nsteps, q, qdot, terms);
+				gq = [];
+				gqd = [];
+				return
+			end
+			if nargin < 7
+				gv = [];
+			end
+			if nargin < 8
+				gR = [];
+			end
+			[x, v, R, gq, gqd] = redmax_hip_mex('rollout_frames', this.h, nsteps, q, qdot, terms, gx, gv, gR);
+		end
+
+		function [Jk, lx, Q] = rolloutCostFrames(this, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget)
+			% rolloutCost with frame terms: terms is a struct array body, xlocal, step and the weights wpos, wvel, wrot >= 0 (a
+			% missing one is 0); xtarget, vtarget (3 x nterms [x batch]) and Rtarget (3 x 3 x nterms [x batch]) are the targets
+			% of the point's position, its velocity and the body's orientation, [] for a table no term weighs.  Per term
+			% wpos/2 |p - xtarget|^2 + wvel/2 |v - vtarget|^2 + wrot/4 |R - Rtarget|_F^2 (the last is wrot (1 - cos theta); its
+			% gradient vanishes at theta = pi).  lx is the exact gradient in (q, qdot); Q is the Gauss-Newton table with the
+			% velocity terms' q, qdot cross blocks, symmetric bit for bit.  Needs no tape and leaves the tape alone.
+			if nargin < 10
+				Rtarget = [];
+			end
+			if nargin < 9
+				vtarget = [];
+			end
+			if nargin < 8
+				xtarget = [];
+			end
+			[Jk, lx, Q] = redmax_hip_mex('rollout_cost_frames', this.h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget);
+		end
 	end
 end

@@ -104,6 +104,16 @@
  *                  wpos >= 0) and xtarget (3 x nterms [x B]).  [] for Qin, xgoal: zero; [] for terms: no targets.  Jk: nsteps x B;
  *                  lx: 2nr x nsteps x B, the exact gradient; Q: 2nr x 2nr x nsteps x B, Qin + sum w Jp'*Jp in the q block
  *                  (Gauss-Newton).  Outputs that are not asked for are not computed.  Needs no tape.
+ *   [x,v,R,gq,gqd] = redmax_hip_mex('rollout_frames', h, nsteps, q, qdot, terms [, gx, gv, gR])  rmx_rollout_frames: position x and
+ *                  point velocity v (3 x nterms x B) and orientation R (3 x 3 x nterms x B) of body frames along a state record
+ *                  q, qdot (nr x nsteps x B), and with cotangents gx, gv (3 x nterms x B), gR (3 x 3 x nterms x B), [] for zero, the
+ *                  pull-back gq = sum_t Jp'*gx + G'*gv + Jw'*a(gR*R'), gqd = sum_t Jp'*gv (nr x nsteps x B).  terms: struct array
+ *                  body (1-based), xlocal, step (weights are not read).  Needs no tape.
+ *   [Jk,lx,Q] = redmax_hip_mex('rollout_cost_frames', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget)
+ *                  rmx_rollout_cost_frames: 'rollout_cost' with frame terms - struct array body, xlocal, step and the weights wpos,
+ *                  wvel, wrot >= 0 (a missing one is 0) - and the targets xtarget, vtarget (3 x nterms [x B]) and Rtarget (3 x 3 x
+ *                  nterms [x B]); [] for a table no term weighs.  Per term wpos/2 |p - xtarget|^2 + wvel/2 |v - vtarget|^2 +
+ *                  wrot/4 |R - Rtarget|_F^2; lx is the exact gradient, Q the Gauss-Newton table with the velocity terms' cross blocks.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -1095,6 +1105,137 @@ static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
     give(nlhs, plhs, res, 3);
 }
 
+/* the struct array `ta` (body 1-based, xlocal, step[, wpos, wvel, wrot]: a missing weight is 0) as rmx_frame_term's; the caller frees */
+static rmx_frame_term* frame_terms(const mxArray* ta, const char* who, size_t* nterms) {
+    if (!mxIsStruct(ta)) mexErrMsgIdAndTxt("redmax:hip", "%s: terms must be a struct array with the fields body, xlocal, step[, wpos, wvel, wrot]", who);
+    *nterms = mxGetNumberOfElements(ta);
+    rmx_frame_term* terms = (rmx_frame_term*)mxCalloc(*nterms ? *nterms : 1, sizeof *terms);
+    for (size_t i = 0; i < *nterms; ++i) {
+        terms[i].body = (int)mxGetScalar(term_field(ta, i, "body")) - 1;   /* MATLAB listing index -> 0-based */
+        const mxArray* xl = term_field(ta, i, "xlocal");
+        if (!mxIsDouble(xl) || mxGetNumberOfElements(xl) != 3) mexErrMsgIdAndTxt("redmax:hip", "%s: terms(%d).xlocal must have 3 elements", who, (int)i + 1);
+        memcpy(terms[i].xlocal, mxGetPr(xl), 3 * sizeof(double));
+        terms[i].step = (int)mxGetScalar(term_field(ta, i, "step"));
+        const char* const names[3] = {"wpos", "wvel", "wrot"};
+        double* const w[3] = {&terms[i].wpos, &terms[i].wvel, &terms[i].wrot};
+        for (int k = 0; k < 3; ++k) {
+            const mxArray* f = mxGetField(ta, i, names[k]);
+            *w[k] = (f && !mxIsEmpty(f)) ? mxGetScalar(f) : 0.0;
+        }
+    }
+    return terms;
+}
+
+static void cmd_rollout_frames(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    const char* who = "rollout_frames";
+    if (nrhs < 6) die("usage: [x,v,R,gq,gqd] = redmax_hip_mex('rollout_frames', h, nsteps, q, qdot, terms [, gx, gv, gR])");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_frames: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
+    const double* q = cost_arg(prhs[3], nr * N * B, 0, 0, who, "q", "nr x nsteps x batch");
+    const double* qd = cost_arg(prhs[4], nr * N * B, 0, 0, who, "qdot", "nr x nsteps x batch");
+    size_t nterms;
+    rmx_frame_term* terms = frame_terms(prhs[5], who, &nterms);
+    const double* gx = nrhs > 6 ? cost_arg(prhs[6], 3 * nterms * B, 0, 1, who, "gx", "3 x nterms x batch") : NULL;
+    const double* gv = nrhs > 7 ? cost_arg(prhs[7], 3 * nterms * B, 0, 1, who, "gv", "3 x nterms x batch") : NULL;
+    const double* gR = nrhs > 8 ? cost_arg(prhs[8], 9 * nterms * B, 0, 1, who, "gR", "3 x 3 x nterms x batch") : NULL;
+    if (nlhs > 3 && !gx && !gv && !gR) die("rollout_frames: gq needs gx, gv or gR");
+    const size_t dx[3] = {3, nterms, B}, dR[4] = {3, 3, nterms, B}, dg[3] = {nr, N, B};
+    mxArray* x = mxCreateNumericArray(3, dx, mxDOUBLE_CLASS, mxREAL);
+    mxArray* v = nlhs > 1 ? mxCreateNumericArray(3, dx, mxDOUBLE_CLASS, mxREAL) : NULL;
+    mxArray* R = nlhs > 2 ? mxCreateNumericArray(4, dR, mxDOUBLE_CLASS, mxREAL) : NULL;
+    mxArray* gq = nlhs > 3 ? mxCreateNumericArray(3, dg, mxDOUBLE_CLASS, mxREAL) : NULL;
+    mxArray* gqd = nlhs > 4 ? mxCreateNumericArray(3, dg, mxDOUBLE_CLASS, mxREAL) : NULL;      /* (zeros without gv) */
+    rmx_frame_terms ft;
+    memset(&ft, 0, sizeof ft);
+    ft.nterms = (int)nterms;
+    ft.terms = terms;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: the record, the frames and the cotangents advance */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        if (rmx_rollout_frames(b, nsteps, q + f * nr * N, qd + f * nr * N, &ft, mxGetPr(x) + f * 3 * nterms, v ? mxGetPr(v) + f * 3 * nterms : NULL,
+                               R ? mxGetPr(R) + f * 9 * nterms : NULL, (gq && gx) ? gx + f * 3 * nterms : NULL,
+                               (gq && gv) ? gv + f * 3 * nterms : NULL, (gq && gR) ? gR + f * 9 * nterms : NULL,
+                               gq ? mxGetPr(gq) + f * nr * N : NULL, (gqd && gv) ? mxGetPr(gqd) + f * nr * N : NULL)) {
+            mxFree(terms);
+            die_rmx("rmx_rollout_frames");
+        }
+    }
+    mxFree(terms);
+    mxArray* const out[5] = {x, v, R, gq, gqd};
+    give(nlhs, plhs, out, 5);
+}
+
+static void cmd_rollout_cost_frames(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 11) die("usage: [Jk,lx,Q] = redmax_hip_mex('rollout_cost_frames', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_cost_frames: nsteps must be at least 1");
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
+    const size_t perq = 4 * nr * nr * N, perg = 2 * nr * N;
+    const char* who = "rollout_cost_frames";
+    const double* q = cost_arg(prhs[3], nr * N * B, 0, 0, who, "q", "nr x nsteps x batch");
+    const double* qd = cost_arg(prhs[4], nr * N * B, 0, 0, who, "qdot", "nr x nsteps x batch");
+    const double* Qin = cost_arg(prhs[5], perq, perq * B, 1, who, "Qin", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
+    const double* xg = cost_arg(prhs[6], perg, perg * B, 1, who, "xgoal", "2nr x nsteps or 2nr x nsteps x batch");
+    /* (a batch of one: a table is one table either way) */
+    const int Q_per = Qin && mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
+    const int g_per = xg && mxGetNumberOfElements(prhs[6]) == perg * B && B > 1;
+    size_t nterms = 0;
+    rmx_frame_term* terms = mxIsEmpty(prhs[7]) ? NULL : frame_terms(prhs[7], who, &nterms);
+    /* the three target tables ([]: no term weighs it - the library refuses otherwise) share one per-rollout flag */
+    const size_t width[3] = {3 * nterms, 3 * nterms, 9 * nterms};
+    const char* const tname[3] = {"xtarget", "vtarget", "Rtarget"};
+    const char* const tshape[3] = {"3 x nterms or 3 x nterms x batch", "3 x nterms or 3 x nterms x batch", "3 x 3 x nterms or 3 x 3 x nterms x batch"};
+    const double* tab[3] = {NULL, NULL, NULL};
+    int t_per = -1;
+    for (int k = 0; k < 3 && terms; ++k) {
+        tab[k] = cost_arg(prhs[8 + k], width[k], width[k] * B, 1, who, tname[k], tshape[k]);
+        if (!tab[k] || B == 1) continue;
+        const int per = mxGetNumberOfElements(prhs[8 + k]) == width[k] * B;
+        if (t_per >= 0 && per != t_per) {
+            mxFree(terms);
+            die("rollout_cost_frames: xtarget, vtarget and Rtarget must all be shared by the batch or all hold one table per rollout");
+        }
+        t_per = per;
+    }
+    if (t_per < 0) t_per = 0;
+    const size_t dJ[2] = {N, B}, dl[3] = {2 * nr, N, B}, dQ[4] = {2 * nr, 2 * nr, N, B};
+    mxArray* Jk = mxCreateNumericArray(2, dJ, mxDOUBLE_CLASS, mxREAL);
+    mxArray* lx = nlhs > 1 ? mxCreateNumericArray(3, dl, mxDOUBLE_CLASS, mxREAL) : NULL;
+    mxArray* Qo = nlhs > 2 ? mxCreateNumericArray(4, dQ, mxDOUBLE_CLASS, mxREAL) : NULL;
+    rmx_state_cost sc;
+    rmx_frame_terms ft;
+    memset(&sc, 0, sizeof sc);
+    memset(&ft, 0, sizeof ft);
+    sc.Q_per_rollout = Q_per;
+    sc.goal_per_rollout = g_per;
+    ft.nterms = (int)nterms;
+    ft.terms = terms;
+    ft.per_rollout = t_per;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: the record, the per-rollout tables and the outputs advance */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_cost_model out;
+        sc.Q = table_at(Qin, Q_per, f, perq);
+        sc.xgoal = table_at(xg, g_per, f, perg);
+        ft.xtarget = table_at(tab[0], t_per, f, width[0]);
+        ft.vtarget = table_at(tab[1], t_per, f, width[1]);
+        ft.Rtarget = table_at(tab[2], t_per, f, width[2]);
+        out.Jk = mxGetPr(Jk) + f * N;
+        out.lx = lx ? mxGetPr(lx) + f * perg : NULL;
+        out.Q = Qo ? mxGetPr(Qo) + f * perq : NULL;
+        if (rmx_rollout_cost_frames(b, nsteps, q + f * nr * N, qd + f * nr * N, (Qin || xg) ? &sc : NULL, terms ? &ft : NULL, &out)) {
+            if (terms) mxFree(terms);
+            die_rmx("rmx_rollout_cost_frames");
+        }
+    }
+    if (terms) mxFree(terms);
+    mxArray* const res[3] = {Jk, lx, Qo};
+    give(nlhs, plhs, res, 3);
+}
+
 /* `clear mex` / MATLAB exit: free what is still alive on the device */
 static void at_exit(void) {
     for (int i = 0; i < MAX_LIVE; ++i)
@@ -1119,7 +1260,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
                                              "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
-                                             "rollout_points", "rollout_cost", NULL};
+                                             "rollout_points", "rollout_cost", "rollout_frames", "rollout_cost_frames", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -1248,6 +1389,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_points(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_cost")) {
         cmd_rollout_cost(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_frames")) {
+        cmd_rollout_frames(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_cost_frames")) {
+        cmd_rollout_cost_frames(nlhs, plhs, nrhs, prhs);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

@@ -34,6 +34,7 @@ SYMBOLS = (
     "rmx_rollout_lqr", "rmx_rollout_lqr_device",
     "rmx_rollout_tape_feedback_box", "rmx_rollout_tape_feedback_box_device", "rmx_rollout_lqr_box", "rmx_rollout_lqr_box_device",
     "rmx_rollout_points", "rmx_rollout_points_device", "rmx_rollout_cost", "rmx_rollout_cost_device",
+    "rmx_rollout_frames", "rmx_rollout_frames_device", "rmx_rollout_cost_frames", "rmx_rollout_cost_frames_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -127,6 +128,15 @@ class CostModel(C.Structure):      # rmx_cost_model
     _fields_ = [("Jk", C.c_void_p), ("lx", C.c_void_p), ("Q", C.c_void_p)]
 
 
+class FrameTerm(C.Structure):      # rmx_frame_term
+    _fields_ = [("body", C.c_int), ("xlocal", C.c_double * 3), ("step", C.c_int), ("wpos", C.c_double), ("wvel", C.c_double), ("wrot", C.c_double)]
+
+
+class FrameTerms(C.Structure):      # rmx_frame_terms: terms is a host array in both forms, the targets device pointers in the _device form
+    _fields_ = [("nterms", C.c_int), ("terms", C.POINTER(FrameTerm)), ("xtarget", C.c_void_p), ("vtarget", C.c_void_p), ("Rtarget", C.c_void_p),
+                ("per_rollout", C.c_int)]
+
+
 FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
 PARAM_NAMES = ("stiffness", "damping", "qrest", "inertia", "grav")      # the members of rmx_param_grads, in their order
 
@@ -215,6 +225,10 @@ def lib():
     L.rmx_rollout_points_device.argtypes = L.rmx_rollout_points.argtypes
     L.rmx_rollout_cost.argtypes = [vp, C.c_int, vp, vp, C.POINTER(StateCost), C.POINTER(PointTerms), C.POINTER(CostModel)]
     L.rmx_rollout_cost_device.argtypes = L.rmx_rollout_cost.argtypes
+    L.rmx_rollout_frames.argtypes = [vp, C.c_int, vp, vp, C.POINTER(FrameTerms), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rmx_rollout_frames_device.argtypes = L.rmx_rollout_frames.argtypes
+    L.rmx_rollout_cost_frames.argtypes = [vp, C.c_int, vp, vp, C.POINTER(StateCost), C.POINTER(FrameTerms), C.POINTER(CostModel)]
+    L.rmx_rollout_cost_frames_device.argtypes = L.rmx_rollout_cost_frames.argtypes
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

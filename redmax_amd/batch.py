@@ -824,6 +824,122 @@ class BatchSim:
                                                    C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
                                                    None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost_device")
 
+    @staticmethod
+    def _frame_terms(terms, who, h=None):
+        """terms (a list of dict(body, xlocal, step | t, wpos, wvel, wrot); a missing weight is 0) -> (array of FrameTerm, count)."""
+        terms = list(terms)
+        arr = (_abi.FrameTerm * max(len(terms), 1))()
+        for a, t in zip(arr, terms):
+            xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
+            if xl.shape != (3,):
+                raise ValueError("%s: a term's xlocal must have shape (3,), got %r" % (who, xl.shape))
+            a.body = int(t["body"])
+            a.step = int(t["step"]) if "step" in t or h is None else int(round(float(t["t"]) / float(h)))
+            a.wpos, a.wvel, a.wrot = (float(t.get(k, 0.0)) for k in ("wpos", "wvel", "wrot"))
+            for i in range(3):
+                a.xlocal[i] = float(xl[i])
+        return arr, len(terms)
+
+    def _frame_targets(self, who, nterms, xtarget, vtarget, Rtarget):
+        """The target tables of frame terms, each None or shared or one per rollout: ([xtarget, vtarget, Rtarget] as the library reads
+        them - Rtarget column-major - and the one per-rollout flag; a shared table beside a per-rollout one is repeated)."""
+        B = self.B
+        tabs = [None if a is None else _table(who, name, a, (nterms,) + tail, B)
+                for name, a, tail in (("xtarget", xtarget, (3,)), ("vtarget", vtarget, (3,)), ("Rtarget", Rtarget, (3, 3)))]
+        per = int(any(t is not None and t[1] for t in tabs))
+        out = [None if t is None else (np.broadcast_to(t[0], (B,) + t[0].shape) if per and not t[1] else t[0]) for t in tabs]
+        if out[2] is not None:      # R[..., r, c] -> column-major
+            out[2] = np.swapaxes(out[2], -1, -2)
+        return [None if a is None else np.ascontiguousarray(a) for a in out], per
+
+    def rollout_frames(self, nsteps, q, qdot, terms, gx=None, gv=None, gR=None, want=("x", "v", "R")):
+        """rmx_rollout_frames: position x [B][nterms][3], point velocity v [B][nterms][3] and orientation R [B][nterms][3][3]
+        (R[..., r, c]) of body frames along a state record q, qdot [B][nsteps][nr], and the pull-back of cotangents gx, gv, gR (the
+        shapes of x, v, R; None: zero) through them.  terms: a list of dict(body, xlocal, step | t) - weights are not read; the frame
+        of term t is taken at the state of row step_t - 1.  Returns (a dict with the names in `want`, gq, gqd): gq, gqd
+        [B][nsteps][nr] = sum over the terms of a step of Jp'gx + G'gv + Jw'a(gR R') and Jp'gv, or None, None without a cotangent.
+        Needs no tape and changes neither the state nor the tape."""
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        want = _names("rollout_frames", "want", want, ("x", "v", "R"), any(g is not None for g in (gx, gv, gR)))
+        q, qdot = _f64_joint("rollout_frames", ("q", "qdot"), (q, qdot), (B, nsteps, nr))
+        arr, nterms = self._frame_terms(terms, "rollout_frames", self.opts.h)
+        if gx is not None:
+            gx = _f64("rollout_frames", "gx", gx, (B, nterms, 3))
+        if gv is not None:
+            gv = _f64("rollout_frames", "gv", gv, (B, nterms, 3))
+        if gR is not None:
+            gR = np.ascontiguousarray(np.swapaxes(_f64("rollout_frames", "gR", gR, (B, nterms, 3, 3)), -1, -2))
+        pull = any(g is not None for g in (gx, gv, gR))
+        shapes = {"x": (B, nterms, 3), "v": (B, nterms, 3), "R": (B, nterms, 3, 3)}
+        out = {w: np.empty(shapes[w]) for w in want}
+        gq = np.empty((B, nsteps, nr)) if pull else None
+        gqd = np.empty((B, nsteps, nr)) if gv is not None else (np.zeros((B, nsteps, nr)) if pull else None)
+        ft = _abi.FrameTerms(nterms, arr, None, None, None, 0)
+        _abi.check(self._L.rmx_rollout_frames(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, C.byref(ft), _addr(out.get("x")),
+                                              _addr(out.get("v")), _addr(out.get("R")), _addr(gx), _addr(gv), _addr(gR), _addr(gq),
+                                              _addr(gqd) if gv is not None else None), "rmx_rollout_frames")
+        if "R" in out:
+            out["R"] = np.ascontiguousarray(np.swapaxes(out["R"], -1, -2))
+        return out, gq, gqd
+
+    def rollout_frames_device(self, nsteps, q_ptr, qdot_ptr, terms, x_ptr=None, v_ptr=None, R_ptr=None, gx_ptr=None, gv_ptr=None, gR_ptr=None,
+                              gq_ptr=None, gqd_ptr=None):
+        """rollout_frames with DEVICE pointers (integers): q, qdot, gq, gqd [B][nsteps][nr]; x, v, gx, gv [B][nterms][3]; R, gR
+        [B][nterms][9], COLUMN-MAJOR as the library stores a 3x3; 0 / None: not stored / zero.  terms stays the host list."""
+        arr, nterms = self._frame_terms(terms, "rollout_frames_device", self.opts.h)
+        ft = _abi.FrameTerms(nterms, arr, None, None, None, 0)
+        _abi.check(self._L.rmx_rollout_frames_device(self._batch, int(nsteps), _vp(q_ptr), _vp(qdot_ptr), C.byref(ft), _vp(x_ptr), _vp(v_ptr),
+                                                     _vp(R_ptr), _vp(gx_ptr), _vp(gv_ptr), _vp(gR_ptr), _vp(gq_ptr), _vp(gqd_ptr)),
+                   "rmx_rollout_frames_device")
+
+    def rollout_cost_frames(self, nsteps, q, qdot, Q=None, xgoal=None, terms=None, xtarget=None, vtarget=None, Rtarget=None,
+                            want=("Jk", "lx", "Q")):
+        """rmx_rollout_cost_frames: rollout_cost with frame terms - dict(body, xlocal, step | t, wpos, wvel, wrot), a missing weight is
+        0 - and the targets xtarget, vtarget [nterms][3] and Rtarget [nterms][3][3] (R[..., r, c]), each shared or [B][..]; a table may
+        be None where no term weighs it.  Per term the cost is wpos/2 |p - xtarget|^2 + wvel/2 |v - vtarget|^2 + wrot/4 |R -
+        Rtarget|_F^2 (the last: wrot (1 - cos theta)); "lx" is its exact gradient in (q, qdot), "Q" the Gauss-Newton table with the
+        velocity terms' q, qdot cross blocks, symmetric bit for bit.  Needs no tape and changes neither the state nor the tape."""
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        want = _names("rollout_cost_frames", "want", want, ("Jk", "lx", "Q"), False)
+        q, qdot = _f64_joint("rollout_cost_frames", ("q", "qdot"), (q, qdot), (B, nsteps, nr))
+        sc = None
+        if Q is not None or xgoal is not None:
+            sc = _abi.StateCost(None, None, 0, 0)
+            if Q is not None:      # (symmetric: row-major memory is the column-major table)
+                Q, sc.Q_per_rollout = _table("rollout_cost_frames", "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
+                sc.Q = Q.ctypes.data
+            if xgoal is not None:
+                xgoal, sc.goal_per_rollout = _table("rollout_cost_frames", "xgoal", xgoal, (nsteps, 2 * nr), B)
+                sc.xgoal = xgoal.ctypes.data
+        ft = None
+        if terms is not None:
+            arr, nterms = self._frame_terms(terms, "rollout_cost_frames", self.opts.h)
+            tabs, per = self._frame_targets("rollout_cost_frames", nterms, xtarget, vtarget, Rtarget)
+            ft = _abi.FrameTerms(nterms, arr, _addr(tabs[0]), _addr(tabs[1]), _addr(tabs[2]), per)
+        shapes = {"Jk": (B, nsteps), "lx": (B, nsteps, 2 * nr), "Q": (B, nsteps, 2 * nr, 2 * nr)}
+        out = {w: np.empty(shapes[w]) for w in want}
+        cm = _abi.CostModel(*[_addr(out.get(n)) for n in ("Jk", "lx", "Q")])
+        _abi.check(self._L.rmx_rollout_cost_frames(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, None if sc is None else C.byref(sc),
+                                                   None if ft is None else C.byref(ft), C.byref(cm)), "rmx_rollout_cost_frames")
+        return out
+
+    def rollout_cost_frames_device(self, nsteps, q_ptr, qdot_ptr, Q_ptr=None, xgoal_ptr=None, Q_per_rollout=False, goal_per_rollout=False,
+                                   terms=None, xtarget_ptr=None, vtarget_ptr=None, Rtarget_ptr=None, target_per_rollout=False, Jk_ptr=None,
+                                   lx_ptr=None, Qout_ptr=None):
+        """rollout_cost_frames with DEVICE pointers (integers), as rollout_cost_device; vtarget [nterms][3] and Rtarget [nterms][9]
+        (COLUMN-MAJOR) or one table per rollout with the flag set - the three target tables share the flag."""
+        sc = _abi.StateCost(Q_ptr or None, xgoal_ptr or None, int(bool(Q_per_rollout)), int(bool(goal_per_rollout)))
+        ft = None
+        if terms is not None:
+            arr, nterms = self._frame_terms(terms, "rollout_cost_frames_device", self.opts.h)
+            ft = _abi.FrameTerms(nterms, arr, xtarget_ptr or None, vtarget_ptr or None, Rtarget_ptr or None, int(bool(target_per_rollout)))
+        cm = _abi.CostModel(Jk_ptr or None, lx_ptr or None, Qout_ptr or None)
+        _abi.check(self._L.rmx_rollout_cost_frames_device(self._batch, int(nsteps), _vp(q_ptr), _vp(qdot_ptr),
+                                                          C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
+                                                          None if ft is None else C.byref(ft), C.byref(cm)), "rmx_rollout_cost_frames_device")
+
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent
         variant the library chose."""

@@ -5,6 +5,7 @@
 #include "rmx_jvp.h"
 #include "rmx_params.h"
 #include "rmx_cost.h"
+#include "rmx_frames.h"
 #if RMX_NP <= 32
 #include "rmx_lqr.h"
 #endif
@@ -123,6 +124,12 @@ void RMX_CAT(launch_jvp_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const 
 void RMX_CAT(launch_cost_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const CostArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nsteps)), block(64);
     k_rollout_cost<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+}
+
+// rmx_rollout_frames / rmx_rollout_cost_frames: the same shape (rmx_select.h select_rollout_cost)
+void RMX_CAT(launch_frames_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const FrameArgs& a) {
+    const dim3 grid((unsigned)((size_t)b->B * a.nsteps)), block(64);
+    k_rollout_frames<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
 
 // rmx_rollout_vjp_params: the backward sweep of the tape's integrator in its ADJ_ZS instantiation (du, dq0, dqd0 as rmx_rollout_vjp's

@@ -2161,6 +2161,155 @@ extern "C" int rmx_rollout_cost_device(rmx_batch* b, int nsteps, const double* d
     return rollout_cost_impl(b, nsteps, d_q, d_qdot, sc, pts, out, nullptr, nullptr, nullptr, true, false);
 }
 
+// rmx_rollout_frames / rmx_rollout_cost_frames: rollout_cost_impl with frame terms (rmx_frames.h) - the same plan, the same term
+// planner (fed the position part of every term), the same device area for the term table and the same staging.
+struct FrameIO {      // rmx_rollout_frames' arrays
+    double *x, *v, *R;
+    const double *gx, *gv, *gR;
+    double *gq, *gqd;
+};
+static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_frame_terms* ft,
+                               const rmx_cost_model* out, const FrameIO* io, const bool on_device) {
+    const bool frames = io != nullptr;
+    const std::string who = frames ? "rmx_rollout_frames" : "rmx_rollout_cost_frames";
+    if (!b || !q || !qdot || (frames ? !ft : (!out || (!sc && !ft)))) return fail(RMX_E_INVALID, who + ": null argument");
+    if (frames ? (!io->x && !io->v && !io->R && !io->gq && !io->gqd) : (!out->Jk && !out->lx && !out->Q))
+        return fail(RMX_E_INVALID, who + ": all outputs are null");
+    if (frames && io->gq && !io->gx && !io->gv && !io->gR) return fail(RMX_E_INVALID, who + ": gq needs gx, gv or gR (the cotangents of the frames)");
+    if (frames && io->gqd && !io->gv) return fail(RMX_E_INVALID, who + ": gqd needs gv (the cotangents of the velocities)");
+    if (ft && ft->per_rollout != 0 && ft->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    if (sc && ((sc->Q_per_rollout != 0 && sc->Q_per_rollout != 1) || (sc->goal_per_rollout != 0 && sc->goal_per_rollout != 1)))
+        return fail(RMX_E_INVALID, who + ": Q_per_rollout and goal_per_rollout must be 0 or 1");
+    if (nsteps < 1) return fail(RMX_E_INVALID, who + ": nsteps < 1");
+    rmx_model* m = b->m;
+    const rmx_select::CostPlan plan = rmx_select::select_rollout_cost(step_traits(m), b->B, nsteps);
+    if (plan.kernel == rmx_select::CostKernel::RefusedSpherical)
+        return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
+    if (plan.kernel == rmx_select::CostKernel::RefusedNodes)
+        return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
+    if (plan.kernel != rmx_select::CostKernel::Wave) return fail(RMX_E_INVALID, who + ": batch * nsteps exceeds the grid");
+    std::vector<FrameDevTerm> dterms;
+    std::vector<int> begin;
+    if (ft) {
+        if (!ft->terms) return fail(RMX_E_INVALID, who + ": null terms");
+        if (ft->nterms < 1) return fail(RMX_E_INVALID, who + ": nterms < 1");
+        std::vector<rmx_track_term> pos((size_t)ft->nterms);
+        for (int i = 0; i < ft->nterms; ++i) {
+            const rmx_frame_term& t = ft->terms[i];
+            pos[(size_t)i].body = t.body;
+            for (int c = 0; c < 3; ++c) pos[(size_t)i].xlocal[c] = t.xlocal[c];
+            pos[(size_t)i].step = t.step;
+            pos[(size_t)i].wpos = t.wpos;
+        }
+        rmx_track::Plan tplan = rmx_track::plan_terms(pos.data(), ft->nterms, nsteps, m->nlist, m->node_of_listing.data());
+        if (!tplan.error.empty()) return fail(RMX_E_INVALID, who + ": " + tplan.error);
+        for (int i = 0; i < ft->nterms && !frames; ++i) {
+            const rmx_frame_term& t = ft->terms[i];
+            const struct { const char* name; double w; const void* table; const char* tname; } ws[3] = {
+                {"wpos", t.wpos, ft->xtarget, "xtarget"}, {"wvel", t.wvel, ft->vtarget, "vtarget"}, {"wrot", t.wrot, ft->Rtarget, "Rtarget"}};
+            for (const auto& e : ws) {
+                if (!(e.w >= 0.0) || !std::isfinite(e.w))
+                    return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": " + e.name +
+                                                   " must be finite and >= 0 (the Gauss-Newton block must stay positive semi-definite)");
+                if (e.w > 0.0 && !e.table)
+                    return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": " + e.name + " > 0 needs " + e.tname + ", which is null");
+            }
+        }
+        dterms.resize((size_t)ft->nterms);
+        for (int i = 0; i < ft->nterms; ++i) {
+            dterms[(size_t)i].t = tplan.terms[(size_t)i];
+            dterms[(size_t)i].wvel = ft->terms[tplan.terms[(size_t)i].orig].wvel;
+            dterms[(size_t)i].wrot = ft->terms[tplan.terms[(size_t)i].orig].wrot;
+        }
+        begin = std::move(tplan.begin);
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (int rc = pending_error_check(b, who.c_str())) return rc;
+    const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
+    const size_t nterms = ft ? (size_t)ft->nterms : 0, tabs = (ft && ft->per_rollout ? B : 1) * nterms;
+    const size_t bytes_traj = B * N * nr * dbl, bytes_Q = N * 4 * nr * nr * dbl;
+    // (each entry has eight arrays of its own after the record: the staging room holds rmx_tape::STAGE_MAX)
+    enum { S_Q, S_QD, S_XT, S_VT, S_RT, S_QIN, S_XG, S_JK, S_LX, S_QOUT };
+    enum { S_X = S_QD + 1, S_V, S_R, S_GX, S_GV, S_GR, S_GQ, S_GQD };
+    Staging st(on_device);
+    st.add(bytes_traj, q, nullptr);
+    st.add(bytes_traj, qdot, nullptr);
+    if (!frames) {
+        st.add(tabs * 3 * dbl, ft ? ft->xtarget : nullptr, nullptr);
+        st.add(tabs * 3 * dbl, ft ? ft->vtarget : nullptr, nullptr);
+        st.add(tabs * 9 * dbl, ft ? ft->Rtarget : nullptr, nullptr);
+        st.add((sc && sc->Q_per_rollout ? B : 1) * bytes_Q, sc ? sc->Q : nullptr, nullptr);
+        st.add((sc && sc->goal_per_rollout ? B : 1) * N * 2 * nr * dbl, sc ? sc->xgoal : nullptr, nullptr);
+        st.add(B * N * dbl, nullptr, out->Jk);
+        st.add(B * N * 2 * nr * dbl, nullptr, out->lx);
+        st.add(B * bytes_Q, nullptr, out->Q);
+    } else {
+        const bool pull = io->gq || io->gqd;
+        st.add(B * nterms * 3 * dbl, nullptr, io->x);
+        st.add(B * nterms * 3 * dbl, nullptr, io->v);
+        st.add(B * nterms * 9 * dbl, nullptr, io->R);
+        st.add(B * nterms * 3 * dbl, pull ? io->gx : nullptr, nullptr);
+        st.add(B * nterms * 3 * dbl, pull ? io->gv : nullptr, nullptr);
+        st.add(B * nterms * 9 * dbl, io->gq ? io->gR : nullptr, nullptr);
+        st.add(bytes_traj, nullptr, io->gq);
+        st.add(bytes_traj, nullptr, io->gqd);
+    }
+    if (int rc = st.allocate(who, "the staging")) return rc;
+    const size_t trk_bytes = rmx_tape::round256(nterms * sizeof(FrameDevTerm)), begin_bytes = (N + 1) * sizeof(int);
+    hipError_t e = ft ? costws_reserve(b, trk_bytes + begin_bytes) : hipSuccess;
+    if (e == hipErrorOutOfMemory) {
+        st.release(b, hipSuccess);
+        return fail(RMX_E_NOMEM, who + ": no device memory for the term table");
+    }
+    FrameArgs a{};
+    a.nsteps = nsteps; a.nterms = (int)nterms;
+    a.q = st.dev(S_Q); a.qd = st.dev(S_QD);
+    if (ft && e == hipSuccess) {
+        a.trk = (const FrameDevTerm*)b->costws;
+        a.trk_begin = (const int*)((const char*)b->costws + trk_bytes);
+        e = hipMemcpyAsync(b->costws, dterms.data(), nterms * sizeof(FrameDevTerm), hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)b->costws + trk_bytes, begin.data(), begin_bytes, hipMemcpyHostToDevice, b->stream);
+    }
+    a.t_stride = (ft && ft->per_rollout) ? nterms : 0;
+    a.q_stride = (sc && sc->Q_per_rollout) ? N * 4 * nr * nr : 0;
+    a.goal_stride = (sc && sc->goal_per_rollout) ? N * 2 * nr : 0;
+    if (!frames) {
+        a.xt = st.dev(S_XT); a.vt = st.dev(S_VT); a.Rt = st.dev(S_RT);
+        a.Qin = st.dev(S_QIN); a.xgoal = st.dev(S_XG);
+        a.Jk = st.dev(S_JK); a.lx = st.dev(S_LX); a.Qout = st.dev(S_QOUT);
+    } else {
+        a.x = st.dev(S_X); a.v = st.dev(S_V); a.R = st.dev(S_R);
+        a.gx = st.dev(S_GX); a.gv = st.dev(S_GV); a.gR = st.dev(S_GR);
+        a.gq = st.dev(S_GQ); a.gqd = st.dev(S_GQD);
+    }
+    e = st.copy_in(b, e);
+    e = timed_launch(b, e, [&] {
+        DISPATCH_NP(plan.np, launch_frames, m, b, a)
+        b->last_kernel = rmx_select::label_rollout_frames();
+        return hipSuccess;
+    });
+    return tape_call_end(b, st.copy_out(b, e), st, who);      // (the wait keeps the term arrays alive for their copies)
+}
+extern "C" int rmx_rollout_frames(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_frame_terms* ft, double* x, double* v,
+                                  double* R, const double* gx, const double* gv, const double* gR, double* gq, double* gqd) {
+    const FrameIO io{x, v, R, gx, gv, gR, gq, gqd};
+    return rollout_frames_impl(b, nsteps, q, qdot, nullptr, ft, nullptr, &io, false);
+}
+extern "C" int rmx_rollout_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_frame_terms* ft, double* d_x,
+                                         double* d_v, double* d_R, const double* d_gx, const double* d_gv, const double* d_gR, double* d_gq,
+                                         double* d_gqd) {
+    const FrameIO io{d_x, d_v, d_R, d_gx, d_gv, d_gR, d_gq, d_gqd};
+    return rollout_frames_impl(b, nsteps, d_q, d_qdot, nullptr, ft, nullptr, &io, true);
+}
+extern "C" int rmx_rollout_cost_frames(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc,
+                                       const rmx_frame_terms* ft, const rmx_cost_model* out) {
+    return rollout_frames_impl(b, nsteps, q, qdot, sc, ft, out, nullptr, false);
+}
+extern "C" int rmx_rollout_cost_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
+                                              const rmx_frame_terms* ft, const rmx_cost_model* out) {
+    return rollout_frames_impl(b, nsteps, d_q, d_qdot, sc, ft, out, nullptr, true);
+}
+
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                 double* qdtraj, rmx_stats* stats) {
     return rollout_tape_impl(b, opts, nsteps, pscale, u, qtraj, qdtraj, stats, false);

@@ -169,6 +169,29 @@ struct CostArgs {
     double* gq;               // [B][nsteps][nr], or null
 };
 
+// rmx_rollout_frames / rmx_rollout_cost_frames (rmx_frames.h): k_rollout_cost's launch shape, frame terms in the place of point terms
+struct FrameDevTerm {
+    rmx_track::DevTerm t;     // the point, its node, wpos and the term's position in the caller's array (what cost_term reads)
+    double wvel, wrot;
+};
+static_assert(sizeof(FrameDevTerm) == 56, "FrameDevTerm: a DevTerm and two doubles, no padding");
+struct FrameArgs {
+    int nsteps, nterms;
+    const double *q, *qd;     // [B][nsteps][nr] the record (qd may be null where no velocity is asked for)
+    const FrameDevTerm* trk;  // [nterms] the terms sorted by step, or null: no terms
+    const int* trk_begin;     // [nsteps + 1], as CostArgs
+    const double *xt, *vt, *Rt;   // targets [nterms][3], [nterms][3], [nterms][9] (column-major) or [B][..]; null: no term weighs it
+    size_t t_stride;          // TERMS from one rollout's target tables to the next (0: one table for the batch)
+    const double* Qin;        // as CostArgs
+    size_t q_stride;
+    const double* xgoal;
+    size_t goal_stride;
+    double *Jk, *lx, *Qout;   // as CostArgs
+    double *x, *v, *R;        // [B][nterms][3], [B][nterms][3], [B][nterms][9] (rmx_rollout_frames), or null
+    const double *gx, *gv, *gR;   // their cotangents, or null: zero
+    double *gq, *gqd;         // [B][nsteps][nr], or null
+};
+
 struct rmx_model {
     int device = 0;
     int n = 0, nr = 0, nm = 0, NP = 0;   // n: 1-DOF nodes on the device (after lowering multi-DOF joints)
@@ -256,6 +279,7 @@ struct rmx_batch {
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
     void RMX_CAT(launch_cost_, NPV)(const rmx_model* m, const rmx_batch* b, const CostArgs& a); \
+    void RMX_CAT(launch_frames_, NPV)(const rmx_model* m, const rmx_batch* b, const FrameArgs& a); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \
     void RMX_CAT(launch_param_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a); \
     void RMX_CAT(launch_phase_, NPV)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d); \

@@ -258,5 +258,6 @@ inline CostPlan select_rollout_cost(const StepTraits& t, const int B, const int 
     return p;
 }
 inline const char* label_rollout_cost() { return "k_rollout_cost"; }      // what rmx_last_step_kernel reports after the two entries
+inline const char* label_rollout_frames() { return "k_rollout_frames"; }  // ... after rmx_rollout_frames / rmx_rollout_cost_frames: the same plan
 
 }      // namespace rmx_select

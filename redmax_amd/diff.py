@@ -470,14 +470,116 @@ def points(sim, q, terms):
     return _points_function().apply(q, sim, terms)
 
 
-def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None, want=("J", "lx", "Q")):
+_Frames = None
+
+
+def _frames_function():
+    """The torch.autograd.Function of frames, made on first use."""
+    global _Frames
+    if _Frames is not None:
+        return _Frames
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _FramesFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, q, qdot, sim, terms):
+            B, N, _ = q.shape
+            qc, qdc = q.detach().contiguous(), qdot.detach().contiguous()
+            T = len(terms)
+            x, v = (torch.empty((B, T, 3), dtype=torch.float64, device=q.device) for _ in range(2))
+            Rcm = torch.empty((B, T, 3, 3), dtype=torch.float64, device=q.device)      # the library's 3x3 is column-major
+            torch.cuda.current_stream(q.device).synchronize()      # (the library works on a stream of its own: see _tape_forward)
+            sim.rollout_frames_device(N, qc.data_ptr(), qdc.data_ptr(), terms, x_ptr=x.data_ptr(), v_ptr=v.data_ptr(), R_ptr=Rcm.data_ptr())
+            ctx.sim, ctx.terms = sim, terms
+            ctx.save_for_backward(qc, qdc)
+            ctx.set_materialize_grads(False)
+            return x, v, Rcm.transpose(-1, -2).contiguous()
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gx, gv, gR):
+            qc, qdc = ctx.saved_tensors
+            gq, gqd = torch.zeros_like(qc), torch.zeros_like(qc)
+            if gx is None and gv is None and gR is None:
+                return gq, gqd, None, None
+            gxc, gvc = (None if g is None else g.contiguous() for g in (gx, gv))
+            gRc = None if gR is None else gR.transpose(-1, -2).contiguous()
+            ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
+            torch.cuda.current_stream(qc.device).synchronize()
+            ctx.sim.rollout_frames_device(qc.shape[1], qc.data_ptr(), qdc.data_ptr(), ctx.terms, gx_ptr=ptr(gxc), gv_ptr=ptr(gvc), gR_ptr=ptr(gRc),
+                                          gq_ptr=gq.data_ptr(), gqd_ptr=gqd.data_ptr() if gvc is not None else 0)
+            return gq, gqd, None, None
+
+    _Frames = _FramesFn
+    return _Frames
+
+
+def frames(sim, q, qdot, terms):
+    """Position, point velocity and orientation of body frames along a state record, differentiable: q, qdot [B][N][nr] ->
+    (x [B][nterms][3], v [B][nterms][3], R [B][nterms][3][3] with R[..., r, c]) (rmx_rollout_frames_device forward and, with the
+    cotangents, backward: gq = sum_t Jp'gx + G'gv + Jw'a(gR R'), gqd = sum_t Jp'gv).  terms: a list of dict(body, xlocal, step | t) -
+    weights are not read; the frame of term t is read at the state of row step_t - 1.  It composes with ``rollout``: a loss on
+    ``frames(sim, *rollout(...), terms)`` backpropagates to u, q0 and qdot0.  The Jacobians are taken at the given state.  Needs no
+    tape and leaves the sim's tape alone."""
+    _check_tensors("frames", sim, (("q", q), ("qdot", qdot)))
+    if q.dim() != 3 or q.shape[0] != sim.B or q.shape[2] != sim.nr or q.shape[1] < 1:
+        raise ValueError("frames: q must have shape (%d, nsteps, %d), got %r" % (sim.B, sim.nr, tuple(q.shape)))
+    if tuple(qdot.shape) != tuple(q.shape):
+        raise ValueError("frames: qdot must have shape %r, got %r" % (tuple(q.shape), tuple(qdot.shape)))
+    terms = [dict(t) for t in terms]
+    if not terms:
+        raise ValueError("frames: terms is empty")
+    return _frames_function().apply(q, qdot, sim, terms)
+
+
+def _frame_weighted(terms):
+    """Does a term carry a velocity or an orientation weight (then the cost goes through rmx_rollout_cost_frames)."""
+    return terms is not None and any(float(t.get("wvel", 0.0)) != 0.0 or float(t.get("wrot", 0.0)) != 0.0 for t in terms)
+
+
+def _check_frame_targets(sim, terms, vtarget, Rtarget):
+    """The checks of cost_model's two frame tables (xtarget has its own, older words)."""
+    B, T = sim.B, len(terms)
+    _check_tensors("cost_model", sim, [(n, t) for n, t in (("vtarget", vtarget), ("Rtarget", Rtarget)) if t is not None])
+    for name, t, tail in (("vtarget", vtarget, (3,)), ("Rtarget", Rtarget, (3, 3))):
+        if t is not None and tuple(t.shape) not in ((T,) + tail, (B, T) + tail):
+            raise ValueError("cost_model: %s must have shape %r or %r, got %r" % (name, (T,) + tail, (B, T) + tail, tuple(t.shape)))
+
+
+def _cost_model_frames(sim, dev, N, qc, qdc, Qc, xgc, Q_per, goal_per, terms, xtarget, vtarget, Rtarget, outs):
+    """cost_model's call where a term weighs velocity or orientation: the three target tables share one per-rollout flag, so a shared
+    table beside a per-rollout one is repeated; Rtarget [..][3][3] goes column-major."""
+    B = sim.B
+    per = any(t is not None and t.dim() == len(tail) + 2 for t, tail in ((xtarget, (3,)), (vtarget, (3,)), (Rtarget, (3, 3))))
+
+    def table(t, tail):
+        if t is None:
+            return None
+        t = t.detach()
+        if per and t.dim() == len(tail) + 1:
+            t = t.unsqueeze(0).expand((B,) + tuple(t.shape))
+        return (t.transpose(-1, -2) if len(tail) == 2 else t).contiguous()
+
+    xt, vt, Rt = table(xtarget, (3,)), table(vtarget, (3,)), table(Rtarget, (3, 3))
+    ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
+    sim.rollout_cost_frames_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q_per, goal_per_rollout=goal_per,
+                                   terms=terms, xtarget_ptr=ptr(xt), vtarget_ptr=ptr(vt), Rtarget_ptr=ptr(Rt), target_per_rollout=per,
+                                   Jk_ptr=ptr(outs[0]), lx_ptr=ptr(outs[1]), Qout_ptr=ptr(outs[2]))
+
+
+def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None, want=("J", "lx", "Q"), vtarget=None, Rtarget=None):
     """The cost of a trajectory and its second-order model for ``lqr_backward`` (rmx_rollout_cost_device, include/redmax_hip.h): a
     joint-space quadratic - Q [N][2nr][2nr] or [B][N][2nr][2nr], symmetric; xgoal [N][2nr] or [B][N][2nr]; None: zero - plus point
     targets - terms: a list of dict(body, xlocal, step, wpos), wpos >= 0; xtarget [nterms][3] or [B][nterms][3].  qtraj, qdtraj
     [B][N][nr]: float64 tensors on the sim's device, as every table.  Returns a dict with the names in `want`: "J" [B], the cost
     summed over the steps (Jk.sum(1)); "lx" [B][N][2nr], its exact gradient by the states; "Q" [B][N][2nr][2nr], the Gauss-Newton
     model Q + sum_t w_t Jp_t'Jp_t (the curvature of the points is dropped), symmetric bit for bit - the per-rollout table
-    ``lqr_backward`` takes.  No rollout is run and the sim's tape is left alone."""
+    ``lqr_backward`` takes.  No rollout is run and the sim's tape is left alone.
+    A term may also carry wvel and wrot (frame targets, rmx_rollout_cost_frames_device): wvel/2 |v - vtarget|^2 on the point's velocity
+    and wrot/4 |R - Rtarget|_F^2 = wrot (1 - cos theta) on the body's orientation, with vtarget [nterms][3] and Rtarget [nterms][3][3]
+    (R[..., r, c]), shared or [B][..]; a table may be None where no term weighs it.  Then "lx" has qdot rows and "Q" the velocity
+    terms' cross blocks.  Without such a term the call is the one above, bit for bit."""
     import torch
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in ("J", "lx", "Q") for w in want) or len(set(want)) != len(want):
@@ -500,10 +602,12 @@ def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None,
     if terms is not None:
         terms = [dict(t) for t in terms]
         nterms = len(terms)
-        if xtarget is None:
+        if xtarget is None and (not _frame_weighted(terms) or any(float(t.get("wpos", 0.0)) != 0.0 for t in terms)):
             raise ValueError("cost_model: xtarget is None")
-        if tuple(xtarget.shape) not in ((nterms, 3), (B, nterms, 3)):
+        if xtarget is not None and tuple(xtarget.shape) not in ((nterms, 3), (B, nterms, 3)):
             raise ValueError("cost_model: xtarget must have shape (%d, 3) or (%d, %d, 3), got %r" % (nterms, B, nterms, tuple(xtarget.shape)))
+        if _frame_weighted(terms):
+            _check_frame_targets(sim, terms, vtarget, Rtarget)
     qc, qdc = qtraj.detach().contiguous(), qdtraj.detach().contiguous()
     Qc, xgc, xtc = (None if t is None else t.detach().contiguous() for t in (Q, xgoal, xtarget if terms is not None else None))
     Jk = torch.empty((B, N), dtype=torch.float64, device=dev) if "J" in want else None
@@ -511,9 +615,13 @@ def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None,
     Qo = torch.empty((B, N, 2 * nr, 2 * nr), dtype=torch.float64, device=dev) if "Q" in want else None
     torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
     ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
-    sim.rollout_cost_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q is not None and Q.dim() == 4,
-                            goal_per_rollout=xgoal is not None and xgoal.dim() == 3, terms=terms, xtarget_ptr=ptr(xtc),
-                            target_per_rollout=xtc is not None and xtc.dim() == 3, Jk_ptr=ptr(Jk), lx_ptr=ptr(lx), Qout_ptr=ptr(Qo))
+    if _frame_weighted(terms):
+        _cost_model_frames(sim, dev, N, qc, qdc, Qc, xgc, Q is not None and Q.dim() == 4, xgoal is not None and xgoal.dim() == 3, terms,
+                           xtarget, vtarget, Rtarget, (Jk, lx, Qo))
+    else:
+        sim.rollout_cost_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q is not None and Q.dim() == 4,
+                                goal_per_rollout=xgoal is not None and xgoal.dim() == 3, terms=terms, xtarget_ptr=ptr(xtc),
+                                target_per_rollout=xtc is not None and xtc.dim() == 3, Jk_ptr=ptr(Jk), lx_ptr=ptr(lx), Qout_ptr=ptr(Qo))
     out = {}
     if Jk is not None:
         out["J"] = Jk.sum(1)

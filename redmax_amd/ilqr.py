@@ -53,13 +53,19 @@ class TrackingCost:
     list of dict(body, xlocal, step, wpos), wpos >= 0 (``BatchSim.adjoint_track``'s term); xtarget: [nterms][3] or [B][nterms][3] -
     float64 tensors on the sim's device.  The state part is evaluated on the device (``diff.cost_model``, rmx_rollout_cost_device):
     the value and the gradient are exact, ``model`` returns the Gauss-Newton Hessian Q_k + sum_t w_t Jp_t'Jp_t per rollout - the
-    curvature of the points is dropped, so the table stays positive semi-definite.  The control part stays torch."""
+    curvature of the points is dropped, so the table stays positive semi-definite.  The control part stays torch.
 
-    def __init__(self, sim, Q, R, xgoal, terms, xtarget):
+    Frame targets: a term may also carry wvel and wrot, adding wvel/2 |v_t - vtarget_t|^2 on the velocity of its point and
+    wrot/4 |R_t - Rtarget_t|_F^2 = wrot (1 - cos theta) on the orientation of its body (``diff.cost_model`` then goes through
+    rmx_rollout_cost_frames_device); vtarget: [nterms][3], Rtarget: [nterms][3][3] (R[..., r, c]), or one table per rollout; a table
+    may be None where no term weighs it.  Without such a term the cost is the one above, bit for bit."""
+
+    def __init__(self, sim, Q, R, xgoal, terms, xtarget, vtarget=None, Rtarget=None):
         if R.dim() != 2 or R.shape[0] != R.shape[1] or R.shape[0] != sim.nr:
             raise ValueError("TrackingCost: R must have shape (%d, %d), got %r" % (sim.nr, sim.nr, tuple(R.shape)))
         self.sim, self.Q, self.R, self.xgoal = sim, Q, R, xgoal
         self.terms, self.xtarget = [dict(t) for t in terms], xtarget
+        self.vtarget, self.Rtarget = vtarget, Rtarget
 
     def _state(self, x, want):
         from . import diff
@@ -67,7 +73,8 @@ class TrackingCost:
         xg = self.xgoal
         if xg is not None and xg.dim() == 3 and xg.shape[0] == 1:
             xg = xg[0]
-        return diff.cost_model(self.sim, x[..., :nr], x[..., nr:], Q=self.Q, xgoal=xg, terms=self.terms, xtarget=self.xtarget, want=want)
+        return diff.cost_model(self.sim, x[..., :nr], x[..., nr:], Q=self.Q, xgoal=xg, terms=self.terms, xtarget=self.xtarget, want=want,
+                               vtarget=self.vtarget, Rtarget=self.Rtarget)
 
     def _lu(self, u):
         import torch
