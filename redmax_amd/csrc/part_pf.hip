@@ -1,5 +1,10 @@
 // part_pf.hip (part 9 of the former rmx_kernels.hip) -- models with body-to-body forces (rmx_model_set_point_forces): the kernels around rmx_pf.h, for ONE
 // padded tree size RMX_NP (every size).
+// 64 lanes: the step kernels spill (H lives in 128 registers per lane beside the point stage), and a spill reload directly in
+// front of a row-broadcast FMA is a DPP read of a register that the preceding VALU instruction wrote (rmx_device.h, RMX_DPP_SETTLE)
+#if RMX_NP == 64
+#define RMX_DPP_SETTLE 1
+#endif
 #include "rmx_kernels.h"
 
 // simLoop of driverRedMaxBDF1.m:57-91 (INTEG 1) / driverRedMaxBDF2.m:57-125 (INTEG 2: SDIRK2 start step, then BDF2) with the point

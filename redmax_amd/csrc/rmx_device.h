@@ -205,10 +205,19 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
 // LANE N (the pivot lane's multiplier is 0, so its rows are rewritten with the same values), so old and new agree.
 // Where a broadcast does read a value that the previous step changed (the look-ahead column and the right-hand side in
 // lu_diag_tail), a whole step's instructions lie in between, except in the last two steps, which take NOPS (s_nop 1 first).
+// RMX_DPP_SETTLE (a translation unit that defines it non-zero before this header: part_pf.hip at 64 lanes): every row-broadcast FMA
+// takes the two wait states itself.  The argument above covers the writes the SOURCE holds; it does not cover the register
+// allocator.  A kernel that spills reloads a spilled operand with v_accvgpr_read_b32 - a VALU write - directly in front of the
+// instruction that uses it, and in front of an inline-asm DPP instruction nothing adds the wait states: k_step_pf<64, BDF2> read the
+// stale HIGH word of one entry of every phase's first pivot row that way (k_step_pf<64, BDF1> the low word) and its guarded solve
+// returned a step that the Newton iteration could not converge with on a dense H.  Units that do not define it compile as before.
+#ifndef RMX_DPP_SETTLE
+#define RMX_DPP_SETTLE 0
+#endif
 template <int N, bool NOPS = false>
 __device__ __forceinline__ void fmsub_rowbcast(double& acc, const double src, const double m) {
     static_assert(N >= 0 && N < 16, "row_newbcast lane");
-    if constexpr (NOPS)
+    if constexpr (NOPS || RMX_DPP_SETTLE)
         asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(N));
     else
         asm volatile("v_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(N));
@@ -219,7 +228,10 @@ __device__ __forceinline__ void fmsub_rowbcast(double& acc, const double src, co
 template <int N>
 __device__ __forceinline__ void fmadd_rowbcast(double& acc, const double src, const double m) {
     static_assert(N >= 0 && N < 16, "row_newbcast lane");
-    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(N));
+    if constexpr (RMX_DPP_SETTLE)
+        asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(N));
+    else
+        asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(N));
 }
 
 // The DPP hazard above, for operands the compiler is free to compute late: every v[c] is materialised (an empty volatile asm takes it

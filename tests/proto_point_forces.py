@@ -191,15 +191,25 @@ def literal_fKD(m, forces, idxM, nm, q, qdot):
 
 
 class Literal:
-    """The literal residual of a scene with point forces: the oracle's force-free g0, H0, J, dJ/dq plus the blocks above."""
+    """The literal residual of a scene with point forces: the oracle's force-free g0, H0, J, dJ/dq plus the blocks above.
+
+    The oracle holds a multi-DOF joint (JointPlanar, JointTranslational, JointUniversal, JointFree2D) as a chain of 1-DOF nodes with
+    massless links (oracle.lower_composite), and so does the device; the restatement therefore lives on the LOWERED model: the body
+    of listing entry L is carried by node last_of_listing[L], node j owns the maximal rows 6 (n - 1 - j) .. + 5 (Scene.m:65-71 on
+    the lowered listing), nm and nr are the oracle's.  Without such a joint the lowered model is the listing itself."""
 
     def __init__(self, oracle_mod, scene):
         d = scene.desc()
+        low = oracle_mod.lower_composite(d)
         self.o = oracle_mod.Oracle(d)
-        self.m = pw.build_model(d)
-        self.forces = forces_of(d)
-        self.idxM = [b.idxM[0] for b in scene.bodies]
-        self.nm, self.nr = scene.nm, scene.nr
+        self.m = pw.build_model(low)
+        n = self.m["n"]
+        last = low.get("last_of_listing")
+        self.node_of_body = list(range(n)) if last is None else [int(j) for j in last]
+        self.forces = [(kind, [(-1 if b < 0 else self.node_of_body[b], x) for b, x in pts], ks, kd, L)
+                       for kind, pts, ks, kd, L in forces_of(d)]
+        self.idxM = [6 * (n - 1 - j) for j in range(n)]
+        self.nm, self.nr = self.o.nm, self.o.nr
 
     def eval(self, q, qA, qB, eta, want_H=True):
         q, qA, qB = (np.asarray(a, float) for a in (q, qA, qB))
@@ -338,12 +348,15 @@ def energy_world_pf(m, forces, q, qd):
 
 
 # ----------------------------------------------------------------------------- the reference's Newton and simLoops
-def newton(evalf, x, tol=1e-9, dxMax=1e3, iterLsMax=20):
-    """newton() of driverRedMaxBDF1.m:94-157; evalf(x, want_H) -> g or (g, H).  Returns x, iterations, status (0 = converged)."""
+def newton(evalf, x, tol=1e-9, dxMax=1e3, iterLsMax=20, on_H=None):
+    """newton() of driverRedMaxBDF1.m:94-157; evalf(x, want_H) -> g or (g, H).  Returns x, iterations, status (0 = converged).
+    on_H(H): called with the matrix of every linear solve (tests classify their inputs with it; it changes nothing)."""
     iterMax = 10 * len(x)
     it = 1
     while True:
         g, H = evalf(x, True)
+        if on_H is not None:
+            on_H(H)
         dx = -np.linalg.solve(H, g)
         if np.linalg.norm(dx) > dxMax:
             return x, it, 1
@@ -363,34 +376,35 @@ def newton(evalf, x, tol=1e-9, dxMax=1e3, iterLsMax=20):
         it += 1
 
 
-def sim_loop(evalf, energy, q, qd, h, nsteps, bdf=1, history=False):
+def sim_loop(evalf, energy, q, qd, h, nsteps, bdf=1, history=False, on_H=None):
     """simLoop of driverRedMaxBDF1.m:57-91 (bdf=1) / driverRedMaxBDF2.m:57-125 (SDIRK2 start step, then BDF2).
-    evalf(x, qA, qB, eta, want_H).  Returns q, qd, worst Newton status, [(q, qd, T, V) per step]."""
+    evalf(x, qA, qB, eta, want_H).  Returns q, qd, worst Newton status, [(q, qd, T, V) per step].  on_H(step, H): see newton."""
     q, qd = np.array(q, float), np.array(qd, float)
     qp = qdp = None
     worst = 0
     hist = []
     for k in range(nsteps):
         q0, qd0 = q, qd
+        hook = None if on_H is None else (lambda H, k=k: on_H(k, H))
         if bdf == 1:
             xB = q0 + h * qd0
-            q1, _, st = newton(lambda x, wH: evalf(x, q0, xB, h, wH), xB)
+            q1, _, st = newton(lambda x, wH: evalf(x, q0, xB, h, wH), xB, on_H=hook)
             q, qd = q1, (q1 - q0) / h
         elif k == 0:
             al = (2.0 - np.sqrt(2.0)) / 2.0
             xa0 = q0 + al * h * qd0
-            qa, _, st = newton(lambda x, wH: evalf(x, q0, xa0, al * h, wH), xa0)
+            qa, _, st = newton(lambda x, wH: evalf(x, q0, xa0, al * h, wH), xa0, on_H=hook)
             qda = (qa - q0) / (al * h)
             qA = q0 + (1.0 - al) * h * qda
             qB = q0 + (2.0 * al - 1.0) * h * qd0 + 2.0 * (1.0 - al) * h * qda
-            q1, _, st2 = newton(lambda x, wH: evalf(x, qA, qB, al * h, wH), qa + (1.0 - al) * h * qda)
+            q1, _, st2 = newton(lambda x, wH: evalf(x, qA, qB, al * h, wH), qa + (1.0 - al) * h * qda, on_H=hook)
             st = max(st, st2)
             q, qd = q1, (q1 - q0 - (1.0 - al) * h * qda) / (al * h)
             qp, qdp = q0, qd0
         else:
             qA = (4.0 / 3.0) * q - (1.0 / 3.0) * qp
             qB = qA + (8.0 / 9.0) * h * qd - (2.0 / 9.0) * h * qdp
-            q2, _, st = newton(lambda x, wH: evalf(x, qA, qB, (2.0 / 3.0) * h, wH), q + h * qd)
+            q2, _, st = newton(lambda x, wH: evalf(x, qA, qB, (2.0 / 3.0) * h, wH), q + h * qd, on_H=hook)
             qdn = (3.0 / (2.0 * h)) * (q2 - (4.0 / 3.0) * q + (1.0 / 3.0) * qp)
             qp, qdp = q, qd
             q, qd = q2, qdn
@@ -440,3 +454,436 @@ def treeWithForces(n=15):
         f5.addBodyPoint(body, x)
     sc.forces = [f1, f2, f3, f4, f5]
     return sc
+
+
+# ----------------------------------------------------------------------------- the guard of the device's diagonal solve
+LU_GROWTH_MAX2 = 64.0
+
+
+def lu_guard(m, H):
+    """The guard of lu_solve_neg_diag (redmax_amd/csrc/rmx_device.h) restated: H (reduced coordinates) is eliminated on the diagonal
+    in NODE order over the nodes that have a DOF; the solve trips when a pivot is not positive and finite or when a multiplier of
+    row i at pivot k has  l_ik^2 u_kk / H_ii = a_ik (a_ik / u_kk) / H_ii > 64  (a_ik: the entry when pivot k is reached, H_ii: the
+    diagonal before the elimination).  Returns the largest such ratio (inf for a bad pivot): the solve trips when it exceeds 64.
+    The device compares the high words of the doubles (2^-20 relative), so a caller classifies only inputs away from 64."""
+    perm = [k for k in m["idx"] if k >= 0]
+    A = np.array(H, float)[np.ix_(perm, perm)]
+    d0 = np.diag(A).copy()
+    worst = 0.0
+    for k in range(len(perm)):
+        u = A[k, k]
+        if not (u > 0 and np.isfinite(1.0 / u)):
+            return np.inf
+        a = A[k + 1:, k].copy()
+        l = a / u
+        for prod, d in zip(a * l, d0[k + 1:]):
+            if not d > 0:                          # (64 H_ii <= 0 < any product)
+                return np.inf
+            worst = max(worst, prod / d)
+        A[k + 1:, k + 1:] -= np.outer(l, A[k, k + 1:])
+    return worst
+
+
+def lu_guard_trips(m, H):
+    return lu_guard(m, H) > LU_GROWTH_MAX2
+
+
+# ----------------------------------------------------------------------------- scenes with multi-DOF joints and forces
+def _world_points(sc):
+    """E_wi of every body at the joints' initial q (Scene.bodyTransforms)."""
+    return sc.bodyTransforms()
+
+
+def _local(E, xw):
+    return E[:3, :3].T @ (np.asarray(xw, float) - E[:3, 3])
+
+
+def compositeSceneWithForces(sid):
+    """Scene 4 (JointPlanar), 5 (JointTranslational), 6 (JointFree2D) or 8 (JointUniversal) of the reference with a point-point
+    force, a spring-damper from the world and a three-point cable added.  The constants are sized so that the forces carry a
+    tenth or more of |H| and |g| (the callers assert it)."""
+    from redmax_amd.scenes import scenesRedMax
+    sc = scenesRedMax(sid)
+    c = 0.3 if sid == 8 else 1.0                 # (three universal joints in a row: the full constants make the reference's Newton diverge)
+    b = sc.bodies
+    first, lastb = b[0], b[-1]
+    other = b[len(b) // 2] if len(b) > 1 else None
+    E = _world_points(sc)
+    x_last = E[-1][:3, :3] @ np.array([0.3, 0.2, -4.0]) + E[-1][:3, 3]
+    f1 = ForcePointPoint(first if other is not None else None, _local(E[0], x_last + [0.4, -0.3, 0.5]) if other is not None
+                         else x_last + [0.4, -0.3, 0.5], lastb, [0.3, 0.2, -4.0])
+    f1.setStiffness(c * 4e5)
+    f1.setDamping(c * 3e2)
+    f2 = ForceSpringDamper(None, [3.0, -4.0, 6.0], lastb, [0.5, 0.0, 1.0])
+    f2.setStiffness(c * 6e6)
+    f2.setDamping(c * 2e3)
+    f3 = ForceCable()
+    f3.setStiffness(c * 5e6)
+    f3.setDamping(c * 1e3)
+    mid = other if other is not None else lastb
+    for body, x in ((None, [-6.0, 2.0, 5.0]), (mid, [0.2, 0.4, -2.0]), (first, [1.0, -1.0, 0.3])):
+        f3.addBodyPoint(body, x)
+    sc.forces = [f1, f2, f3]
+    sc.init()
+    f3.setRetLength(0.97 * f3.L)                 # taut at and around the initial state
+    sc.init()
+    return sc
+
+
+_KINDS = ("rev", "rev", "rev", "pri", "fix", "planar", "universal", "trans", "free2d")
+_COMPOSITE = ("planar", "universal", "trans", "free2d")
+_COST = {"planar": 2, "universal": 2, "trans": 3, "free2d": 3}
+
+
+def randomSceneWithForces(seed, big=False):
+    """A random tree (as tests/test_gpu_fuzz.py builds them: skew axes and planes, random joint and body frames, joint springs /
+    dampers / limits, fixed joints inside the tree, every joint class the force kernels admit; 3..11 joints and at most 30 nodes,
+    big: 33..62 nodes) with 5 or 6 forces of all three kinds: a point-point force between unrelated bodies, a spring-damper
+    between an ancestor and a descendant, a spring-damper from the world, a point-point force with both ends on ONE body, a cable of
+    4 or 5 points through the world, a body behind a multi-DOF joint and others, and sometimes one more cable.  The second
+    joint is always a multi-DOF one.  Stiffnesses and dampings are sized so that the forces carry a tenth or more of |H| and |g|
+    at states near the initial one (asserted by the tests, from the reference alone)."""
+    from redmax_amd.redmax import (BodyCuboid, JointFixed, JointFree2D, JointPlanar, JointPrismatic, JointRevolute,
+                                   JointTranslational, JointUniversal, Scene)
+    rng = np.random.default_rng(seed)
+    sc = Scene()
+    sc.h = 5e-3
+    kx = 4.0 if big else 1.0                        # |H| grows with the tree: the forces' constants with it
+    if big:
+        target = int(rng.integers(33, 63))
+        njoints = 10 ** 6
+    else:
+        target = 30
+        njoints = int(rng.integers(3, 12))
+    nodes = 0
+    i = 0
+    while i < njoints and nodes < target:
+        kind = _KINDS[int(rng.integers(len(_KINDS)))] if i else _KINDS[int(rng.integers(3))]
+        if i == 1:
+            kind = _COMPOSITE[int(rng.integers(len(_COMPOSITE)))]
+        cost = _COST.get(kind, 1)
+        if nodes + cost > target:
+            kind, cost = "rev", 1
+        nodes += cost
+        body = BodyCuboid(float(rng.uniform(0.5, 2.0)), rng.uniform(0.5, 4.0, 3))
+        parent = None
+        if i:                                        # a random earlier joint that keeps the listing depth-first
+            chain = [sc.joints[-1]]
+            while chain[-1].parent is not None:
+                chain.append(chain[-1].parent)
+            parent = chain[int(rng.integers(len(chain)))]
+        axis = rng.normal(size=3)
+        if kind == "rev":
+            j = JointRevolute(parent, body, axis)
+        elif kind == "pri":
+            j = JointPrismatic(parent, body, axis)
+        elif kind == "fix":
+            j = JointFixed(parent, body)
+        elif kind == "planar":
+            j = JointPlanar(parent, body, rng.normal(size=(3, 2)))
+        elif kind == "universal":
+            j = JointUniversal(parent, body)
+        elif kind == "trans":
+            j = JointTranslational(parent, body)
+        else:
+            j = JointFree2D(parent, body)
+        if kind in ("pri", "planar", "trans", "free2d"):
+            j.setStiffness(float(rng.uniform(1e3, 1e4)))
+        j.setJointTransform(se3.transform(R=se3.aaToMat(rng.normal(size=3), rng.uniform(-1, 1)), p=rng.uniform(-3, 3, 3)))
+        body.setBodyTransform(se3.transform(R=se3.aaToMat(rng.normal(size=3), rng.uniform(-1, 1)), p=rng.uniform(-2, 2, 3)))
+        if rng.random() < 0.4:
+            j.setDamping(float(rng.uniform(1e1, 1e3)))
+        if kind == "rev" and rng.random() < 0.3:
+            j.setLimitLower(-0.2)
+            j.setLimitUpper(0.3)
+            j.setLimitStiffness(1e5)
+            j.setLimitDamping(1e2)
+        if j.ndof:
+            j.q[:j.ndof] = rng.uniform(-0.3, 0.3, j.ndof)
+            j.qdot[:j.ndof] = rng.uniform(-1, 1, j.ndof)
+        sc.bodies.append(body)
+        sc.joints.append(j)
+        i += 1
+    # ---- the forces
+    b, J = sc.bodies, sc.joints
+    n = len(b)
+    E = _world_points(sc)
+
+    def anc_of(k):
+        out, j = [], J[k].parent
+        while j is not None:
+            out.append(J.index(j))
+            j = j.parent
+        return out
+    ancs = [anc_of(k) for k in range(n)]
+    unrelated = [(a, c) for a in range(n) for c in range(a + 1, n) if a not in ancs[c] and c not in ancs[a]]
+    related = [(a, c) for c in range(n) for a in ancs[c]]
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]      # noqa: E731
+    xl = lambda: rng.uniform(-2, 2, 3)                        # noqa: E731
+    behind = [k for k in range(n) if k == 1 or 1 in ancs[k]]  # bodies carried by or below the multi-DOF joint
+    forces = []
+    # point-point between unrelated bodies (a chain has none: its two ends then); zero rest length, so the second point starts near the first
+    a, c = pick(unrelated) if unrelated else (0, n - 1)
+    x1 = xl()
+    f = ForcePointPoint(b[a], x1, b[c], _local(E[c], E[a][:3, :3] @ x1 + E[a][:3, 3] + rng.uniform(-0.5, 0.5, 3)))
+    f.setStiffness(kx * float(10 ** rng.uniform(5, 6)))
+    f.setDamping(kx * float(10 ** rng.uniform(2, 3)))
+    forces.append(f)
+    # spring-damper between an ancestor and a descendant
+    a, c = pick(related)
+    f = ForceSpringDamper(b[a], xl(), b[c], xl())
+    f.setStiffness(kx * float(10 ** rng.uniform(6.5, 7.5)))
+    f.setDamping(kx * float(10 ** rng.uniform(3, 4)))
+    forces.append(f)
+    # spring-damper from the world
+    f = ForceSpringDamper(None, rng.uniform(-6, 6, 3), b[int(rng.integers(n))], xl())
+    f.setStiffness(kx * float(10 ** rng.uniform(6.5, 7.5)))
+    f.setDamping(kx * float(10 ** rng.uniform(3, 4)))
+    forces.append(f)
+    # both ends on one body (the damping part kd dv is not along the line: a net torque on the body)
+    k = pick(behind)
+    f = ForcePointPoint(b[k], xl(), b[k], xl())
+    f.setStiffness(kx * float(10 ** rng.uniform(5, 6)))
+    f.setDamping(kx * float(10 ** rng.uniform(2, 3)))
+    forces.append(f)
+    # a cable of 4 or 5 points: the world, a body behind the multi-DOF joint, others
+    cab = ForceCable()
+    cab.setStiffness(kx * float(10 ** rng.uniform(6.5, 7.5)))
+    cab.setDamping(kx * float(10 ** rng.uniform(3, 4)))
+    pts = [None, pick(behind)] + [int(rng.integers(n)) for _ in range(int(rng.integers(2, 4)))]
+    for k in pts:
+        cab.addBodyPoint(None if k is None else b[k], rng.uniform(-6, 6, 3) if k is None else xl())
+    forces.append(cab)
+    cables = [cab]
+    if rng.random() < 0.5:
+        c2 = ForceCable()
+        c2.setStiffness(kx * float(10 ** rng.uniform(6.5, 7.5)))
+        c2.setDamping(kx * float(10 ** rng.uniform(3, 4)))
+        for k in (int(rng.integers(n)), int(rng.integers(n)), int(rng.integers(n))):
+            c2.addBodyPoint(b[k], xl())
+        forces.append(c2)
+        cables.append(c2)
+    sc.forces = forces
+    sc.init()
+    for cb in cables:                                # rest length: a little under the initial length - taut near the initial state
+        cb.setRetLength(0.97 * cb.L)
+    sc.init()
+    return sc
+
+
+def _set(f, ks, kd):
+    f.setStiffness(float(ks))
+    f.setDamping(float(kd))
+    return f
+
+
+def sizedSceneWithForces(n):
+    """sceneTree(n) (n >= 2: revolute / prismatic, branching from 3 joints on; exactly n nodes, so n = 4, 8, 16, 32, 64 fill their
+    padded size and n = 5, 9, 17, 33 are one past it) with a point-point force root - last body, a spring-damper from the world, a
+    spring-damper between two bodies and a four-point cable.  The constants grow with n as |H| does."""
+    sc = sceneTree(n)
+    sc.h = 5e-3
+    b = sc.bodies
+    E = _world_points(sc)
+    c = 10.0 * n
+    x1 = np.array([4.0, 0.5, -0.5])
+    f1 = _set(ForcePointPoint(b[0], x1, b[n - 1], _local(E[n - 1], E[0][:3, :3] @ x1 + E[0][:3, 3] + [0.3, -0.2, 0.4])), 3e3 * c, 3.0 * c)
+    f2 = _set(ForceSpringDamper(None, E[n - 1][:3, 3] + [2.0, 3.0, 6.0], b[n - 1], [1.0, 0.2, 0.0]), 5e4 * c, 50.0 * c)
+    f3 = _set(ForceSpringDamper(b[(n - 1) // 2], [0.0, 0.5, 0.2], b[n - 1], [3.0, 0.0, 0.3]), 5e4 * c, 50.0 * c)
+    f4 = _set(ForceCable(), 5e4 * c, 50.0 * c)
+    for body, x in ((None, E[n // 3][:3, 3] + [0.0, -2.0, 4.0]), (b[n // 3], [1.0, 0.0, 0.5]), (b[(2 * n) // 3], [0.0, 0.3, 1.0]), (b[n - 1], [2.0, 0.0, 0.5])):
+        f4.addBodyPoint(body, x)
+    sc.forces = [f1, f2, f3, f4]
+    sc.init()
+    f4.setRetLength(0.97 * f4.L)
+    sc.init()
+    return sc
+
+
+def _mixedTree():
+    """Nine bodies, eleven DOFs, sixteen nodes: planar root, revolute / prismatic / fixed / universal joints below it, two branches."""
+    from redmax_amd.redmax import BodyCuboid, JointFixed, JointPlanar, JointPrismatic, JointRevolute, JointUniversal, Scene
+    sc = Scene()
+    sc.h = 5e-3
+    spec = [("planar", None), ("rev", 0), ("uni", 1), ("fix", 2), ("rev", 3), ("pri", 0), ("rev", 5), ("uni", 6), ("rev", 7)]
+    rng = np.random.default_rng(77)
+    for kind, par in spec:
+        body = BodyCuboid(1.0, rng.uniform(1.0, 4.0, 3))
+        parent = None if par is None else sc.joints[par]
+        if kind == "planar":
+            j = JointPlanar(parent, body, rng.normal(size=(3, 2)))
+            j.setStiffness(5e3)
+        elif kind == "rev":
+            j = JointRevolute(parent, body, rng.normal(size=3))
+        elif kind == "uni":
+            j = JointUniversal(parent, body)
+        elif kind == "fix":
+            j = JointFixed(parent, body)
+        else:
+            j = JointPrismatic(parent, body, rng.normal(size=3))
+            j.setStiffness(5e3)
+        j.setJointTransform(se3.transform(R=se3.aaToMat(rng.normal(size=3), rng.uniform(-1, 1)), p=rng.uniform(-3, 3, 3)))
+        body.setBodyTransform(se3.transform(R=se3.aaToMat(rng.normal(size=3), rng.uniform(-1, 1)), p=rng.uniform(-2, 2, 3)))
+        if j.ndof:
+            j.q[:j.ndof] = rng.uniform(-0.3, 0.3, j.ndof)
+            j.qdot[:j.ndof] = rng.uniform(-1, 1, j.ndof)
+        sc.bodies.append(body)
+        sc.joints.append(j)
+    return sc, rng
+
+
+def _finish(sc, forces, cables, slack=0.97):
+    sc.forces = forces
+    sc.init()
+    for cb in cables:
+        cb.setRetLength(slack * cb.L)
+    sc.init()
+    return sc
+
+
+def limitScene(which):
+    """The force table at its limits (include/redmax_hip.h: 32 forces, 8 points per cable, 128 points in all) on _mixedTree():
+      "forces32"   exactly 32 forces of all kinds; among them one cable of exactly 8 points, one with two consecutive points on ONE
+                   body, one with two consecutive world anchors and a spring-damper with both ends on one body;
+      "points128"  16 cables of 8 points: 128 points in all;
+      "samebody"   nothing but a spring-damper with both ends on one body, stretched (rest length 0.8 of the distance)."""
+    sc, rng = _mixedTree()
+    b = sc.bodies
+    n = len(b)
+    xl = lambda: rng.uniform(-2, 2, 3)                        # noqa: E731
+    xw = lambda: rng.uniform(-6, 6, 3)                        # noqa: E731
+    forces, cables = [], []
+    if which == "samebody":
+        f = _set(ForceSpringDamper(b[4], [1.0, 0.5, -0.5], b[4], [-1.0, 0.2, 1.5]), 3e6, 3e3)
+        f.setRetLength(0.8 * float(np.linalg.norm(f.xls[1] - f.xls[0])))         # stretched: a tension, and no net wrench
+        return _finish(sc, [f], [])
+    if which == "points128":
+        for i in range(16):
+            cb = _set(ForceCable(), 10 ** rng.uniform(6, 7), 10 ** rng.uniform(2.5, 3.5))
+            for k in range(8):
+                body = None if (k == 0 and i % 2 == 0) else b[int(rng.integers(n))]
+                cb.addBodyPoint(body, xw() if body is None else xl())
+            forces.append(cb)
+            cables.append(cb)
+        return _finish(sc, forces, cables)
+    assert which == "forces32"
+    c8 = _set(ForceCable(), 3e6, 1e3)                # exactly 8 points
+    for k in (None, 8, 4, 2, 6, 1, 7, 3):
+        c8.addBodyPoint(None if k is None else b[k], xw() if k is None else xl())
+    cs = _set(ForceCable(), 3e6, 1e3)                # two consecutive points on one body
+    for k in (2, 8, 8, 5):
+        cs.addBodyPoint(b[k], xl())
+    cw = _set(ForceCable(), 3e6, 1e3)                # two consecutive world anchors
+    for k in (4, None, None, 6):
+        cw.addBodyPoint(None if k is None else b[k], xw() if k is None else xl())
+    sb = _set(ForceSpringDamper(b[4], [1.0, 0.5, -0.5], b[4], [-1.0, 0.2, 1.5]), 3e6, 3e3)
+    forces += [c8, cs, cw, sb]
+    cables += [c8, cs, cw]
+    E = _world_points(sc)
+    while len(forces) < 32:
+        i = len(forces)
+        a, c = int(rng.integers(n)), int(rng.integers(n))
+        if i % 3 == 0:                               # zero rest length: the second point starts near the first
+            x1 = xl()
+            f = _set(ForcePointPoint(b[a], x1, b[c], _local(E[c], E[a][:3, :3] @ x1 + E[a][:3, 3] + rng.uniform(-0.3, 0.3, 3))), 10 ** rng.uniform(4, 5), 10 ** rng.uniform(1, 2))
+        elif i % 3 == 1:
+            f = _set(ForceSpringDamper(None if i % 2 else b[a], xw() if i % 2 else xl(), b[c], xl()), 10 ** rng.uniform(6, 7), 10 ** rng.uniform(2.5, 3.5))
+        else:
+            f = _set(ForceCable(), 10 ** rng.uniform(6, 7), 10 ** rng.uniform(2.5, 3.5))
+            for k in (a, c, int(rng.integers(n))):
+                f.addBodyPoint(b[k], xl())
+            cables.append(f)
+        forces.append(f)
+    sb.setRetLength(0.8 * float(np.linalg.norm(sb.xls[1] - sb.xls[0])))      # stretched: a tension, and no net wrench
+    return _finish(sc, forces, cables)
+
+
+def switchingScene(v=-0.8):
+    """A three-link chain hanging from two cables that go slack and taut again within twenty steps of h = 5e-3: the links start
+    level, the cables slightly stretched, with an upward velocity; gravity (980) brings them back and the stiff cables catch them."""
+    from redmax_amd.scenes import sceneChain
+    sc = sceneChain(3, axis=(0.1, 1.0, 0.05))
+    sc.h = 5e-3
+    b = sc.bodies
+    c1 = _set(ForceCable(), 4e6, 0.0)
+    c1.addBodyPoint(None, [12.0, 1.0, 9.0])
+    c1.addBodyPoint(b[1], [3.0, 0.0, 0.5])
+    c2 = _set(ForceCable(), 3e6, 0.0)
+    for body, x in ((None, [33.0, -1.0, 7.0]), (b[2], [4.0, 0.0, 0.5]), (b[0], [2.0, 0.0, 0.5])):
+        c2.addBodyPoint(body, x)
+    sc.joints[0].qdot[0] = v                        # thrown upwards: the cables slacken, gravity brings the links back into them
+    return _finish(sc, [c1, c2], [c1, c2], slack=0.995)
+
+
+def cable_states(lit, hist):
+    """Per cable of the literal's table: the list over the recorded steps of V > 0 (taut)."""
+    out = []
+    for f in lit.forces:
+        if f[0] == CABLE:
+            out.append([world_terms(lit.m, [f], q, qd, 1.0, False)[2] > 0 for q, qd, _, _ in hist])
+    return out
+
+
+def switches(taut):
+    """True when the sequence holds a state, then the other one, then the first again (taut - slack - taut or the reverse)."""
+    runs = [taut[0]]
+    for t in taut[1:]:
+        if t != runs[-1]:
+            runs.append(t)
+    return len(runs) >= 3
+
+
+def switchingStates(sc):
+    """The two initial states of the switching test: the scene's own and a perturbed one."""
+    q0, qd0 = sc.getQ()
+    rng = np.random.default_rng(2)
+    return np.stack([q0, q0 + rng.uniform(-0.02, 0.02, sc.nr)]), np.stack([qd0, qd0 + rng.uniform(-0.2, 0.2, sc.nr)])
+
+
+# Seeds of randomSceneWithForces chosen on the CPU (tests/test_point_forces_proto.py asserts what they were chosen for): the forces carry
+# a tenth or more of |H| and |g| at the states of nearInitialStates and the reference's Newton converges on every rollout from them.
+# Nodes: r300 4, r317 5, r313 11, r311 13, r304 15, r302 18, r309 18, r307 19; R401 45, R403 52.  On r307 (every rollout), r309 and
+# R403 (the BDF1 rollouts) H is indefinite at some solve and the device's guarded diagonal solve trips; on the others it never does.
+GPU_SMALL_SEEDS = ["r300", "r302", "r304", "r307", "r309", "r311", "r313", "r317"]
+GPU_BIG_SEEDS = ["R401", "R403"]
+
+
+def named_scene(name):
+    """"s4" / "s5" / "s6" / "s8": compositeSceneWithForces; "r<seed>": randomSceneWithForces(seed); "R<seed>": the big one."""
+    if name[0] == "s":
+        return compositeSceneWithForces(int(name[1:]))
+    return randomSceneWithForces(int(name[1:]), big=name[0] == "R")
+
+
+def seed_of(name):
+    return int(name[1:])
+
+
+def guard_trace(lit, q, qd, h, nsteps, bdf):
+    """The reference rollout with the restated guard's ratio of every linear solve: (q, qd, status, hist, [(step, ratio)])."""
+    tr = []
+    q, qd, st, hist = sim_loop(lit.eval, lit.energy, q, qd, h, nsteps, bdf, history=True, on_H=lambda k, H: tr.append((k, lu_guard(lit.m, H))))
+    return q, qd, st, hist, tr
+
+
+def sizedStates(sc, n):
+    """The states of the padded-size tests (chosen on the CPU: the reference's Newton converges from them at every size)."""
+    return nearInitialStates(sc, n + 100, 2)
+
+
+def nearInitialStates(sc, seed, B=2):
+    """The states the tests evaluate and start their rollouts at (the ones of tests/test_gpu_fuzz.py: near the scene's own initial
+    state): q0, qd0 [B][nr], the evaluation point q1 and the list of (eta, qA, qB) - a BDF1-style and a BDF2-style residual."""
+    rng = np.random.default_rng(seed + 1000)
+    nr, h = sc.nr, sc.h
+    q0 = np.tile(sc.getQ()[0], (B, 1)) + rng.uniform(-0.05, 0.05, (B, nr))
+    qd0 = np.tile(sc.getQ()[1], (B, 1)) + rng.uniform(-0.2, 0.2, (B, nr))
+    q1 = q0 + h * qd0 + rng.uniform(-1e-3, 1e-3, (B, nr))
+    return q0, qd0, q1, [(h, q0, q0 + h * qd0), (2 * h / 3, q0 + 1e-3 * rng.normal(size=(B, nr)), q0 + 0.8 * h * qd0)]
+
+
+def force_share(lit, q, qA, qB, eta):
+    """(|H - H0|_F / |H|_F, |g - g0| / |g|) of the literal residual: the part of it that the point forces carry."""
+    g, H = lit.eval(q, qA, qB, eta)
+    g0, H0 = lit.o.eval_residual(q, qA, qB, eta)
+    return np.linalg.norm(H - H0) / np.linalg.norm(H), np.linalg.norm(g - g0) / np.linalg.norm(g)

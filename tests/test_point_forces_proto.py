@@ -7,6 +7,12 @@
  3. the world-frame form the HIP kernels compute equals the literal one to 1e-12 relative in g and H (the bound of
     tests/test_proto_worldframe.py), with non-zero blocks between unrelated nodes for every kind, and a cable taut and slack.
 
+ 4. on multi-DOF joints (scenes 4, 5, 6, 8 with forces added, seeds of pf.randomSceneWithForces) the literal lives on the oracle's
+    lowered model; its H is pinned against central differences of its g (1e-6 relative, measured at most 9.3e-10), then the
+    world-frame form is held to it (1e-12, measured at most 4.8e-15); the forces carry a tenth or more of |H| and |g|;
+ 5. the numpy Newton converges on every state tests/test_gpu_point_forces_edges.py uses; the restated guard of the device's diagonal
+    solve (pf.lu_guard) on matrices whose elimination is known; the switching scene switches.
+
 Deviations of the restatement from the reference's goldens, H_end - Hexpected, as measured (printed by the test; run with -s):
     scene 12  BDF1  4.0e-11 (1.8e-15 relative)   BDF2 -6.5e-10 (7.2e-14)
     scene 13  BDF1  1.3e-10 (4.2e-15)            BDF2 -1.1e-09 (3.9e-14)
@@ -126,3 +132,127 @@ def test_worldframe_equals_literal(oracle_lib, name):
         assert cross[pf.CABLE] > 0 and taut >= 3 and slack >= 3
     if name == "tree15":
         assert cross[pf.PP] > 0 and cross[pf.SPRING] > 0 and cross[pf.CABLE] > 0 and taut >= 1
+
+
+# ----------------------------------------------------------------------------- multi-DOF joints: the literal on the lowered model
+# Scenes 4 (JointPlanar), 5 (JointTranslational), 6 (JointFree2D), 8 (JointUniversal) with forces added and seeds of the generator.
+# The literal is pinned by central differences first; then the world-frame form is held to it.  tests/test_gpu_point_forces_edges.py
+# uses the names of GPU_SMALL / GPU_BIG and the states of pf.nearInitialStates.
+COMPOSITE = ["s4", "s5", "s6", "s8"]
+CPU_SEEDS = ["r300", "r304", "r311", "r313"]
+GPU_SMALL = pf.GPU_SMALL_SEEDS
+GPU_BIG = pf.GPU_BIG_SEEDS
+
+
+@pytest.mark.parametrize("name", COMPOSITE + CPU_SEEDS)
+def test_composite_literal_is_pinned_and_worldframe_equals_it(oracle_lib, name):
+    """1. H of the literal = central differences of its g (1e-6 relative: Scene.printError's threshold; measured at most 9.3e-10),
+    2. eval_world_pf = the literal, 1e-12 in g and H, energies 1e-12 (measured at most 4.8e-15),
+    3. the forces carry a tenth or more of |H| and |g| (from the reference alone),
+    4. Scene.bodyTransforms (the rest lengths come from it) = the lowered model's kinematics at the initial state."""
+    sc = pf.named_scene(name)
+    lit = pf.Literal(oracle_lib, sc)
+    m, forces = lit.m, lit.forces
+    nr = sc.nr
+    q0, qd0, q1, etas = pf.nearInitialStates(sc, pf.seed_of(name), 2)
+    has_cable_behind_composite = False
+    typ = np.asarray(sc.desc()["type"])
+    for kind, pts, _, _, _ in pf.forces_of(sc.desc()):
+        if kind == pf.CABLE and len(pts) >= (4 if name.startswith("r") else 3):
+            for b, _ in pts:
+                k = b
+                while k >= 0:
+                    has_cable_behind_composite |= bool(typ[k] > 2)
+                    k = int(sc.desc()["parent"][k])
+    assert has_cable_behind_composite
+    for eta, qA, qB in etas:
+        for b in range(2):
+            g, H = lit.eval(q1[b], qA[b], qB[b], eta)
+            sH, sg = pf.force_share(lit, q1[b], qA[b], qB[b], eta)
+            assert sH >= 0.1 and sg >= 0.1, (name, b, sH, sg)
+            g2, H2 = pf.eval_world_pf(m, forces, q1[b], qA[b], qB[b], eta)
+            assert _rel(g2, g) <= 1e-12 and _rel(H2, H) <= 1e-12, (name, b, _rel(g2, g), _rel(H2, H))
+            assert _rel(pf.eval_world_pf(m, forces, q1[b], qA[b], qB[b], eta, want_H=False), g) <= 1e-12
+            assert _rel(lit.eval(q1[b], qA[b], qB[b], eta, want_H=False), g) <= 1e-14
+            if b == 0:
+                eps = 1e-6
+                Hfd = np.zeros_like(H)
+                for i in range(nr):
+                    e = np.zeros(nr)
+                    e[i] = eps
+                    Hfd[:, i] = (lit.eval(q1[b] + e, qA[b], qB[b], eta, False) - lit.eval(q1[b] - e, qA[b], qB[b], eta, False)) / (2 * eps)
+                print("%s eta=%.4g: |H - Hfd|/|H| = %.2e, force share of H %.2f, of g %.2f" % (name, eta, _rel(Hfd, H), sH, sg))
+                assert _rel(Hfd, H) <= 1e-6, (name, _rel(Hfd, H))
+    for b in range(2):
+        T, V = lit.energy(q1[b], qd0[b])
+        T2, V2 = pf.energy_world_pf(m, forces, q1[b], qd0[b])
+        assert abs(T - T2) <= 1e-12 * max(abs(T), 1) and abs(V - V2) <= 1e-12 * max(abs(V), 1)
+        assert V != pf.pw.energy_world(m, q1[b], qd0[b])[1]         # the forces' potential entered
+    Ew, _, _ = pf.fk(m, *sc.getQ())
+    for L, E in enumerate(sc.bodyTransforms()):
+        assert np.abs(E - Ew[lit.node_of_body[L]]).max() <= 1e-12 * max(1.0, np.abs(E).max()), (name, L)
+
+
+def test_literal_on_plain_joints_is_unmoved(oracle_lib):
+    """Without a multi-DOF joint the lowered model is the listing: nodes = bodies, rows as Scene.init numbers them."""
+    for name in ("10", "12", "13", "tree15"):
+        sc = _scene(name)
+        sc.init()
+        lit = pf.Literal(oracle_lib, sc)
+        assert lit.node_of_body == list(range(len(sc.bodies)))
+        assert lit.idxM == [b.idxM[0] for b in sc.bodies] and (lit.nm, lit.nr) == (sc.nm, sc.nr)
+        d = sc.desc()
+        assert [[b for b, _ in f[1]] for f in lit.forces] == [[b for b, _ in f[1]] for f in pf.forces_of(d)]
+
+
+@pytest.mark.parametrize("name", COMPOSITE + GPU_SMALL + GPU_BIG)
+def test_numpy_newton_converges_on_the_gpu_test_states(oracle_lib, name):
+    """The rollouts tests/test_gpu_point_forces_edges.py compares the device with: the reference's Newton on the literal converges
+    on every step (6 steps, big trees 3; BDF1 and SDIRK2 + BDF2)."""
+    sc = pf.named_scene(name)
+    lit = pf.Literal(oracle_lib, sc)
+    q0, qd0, _, _ = pf.nearInitialStates(sc, pf.seed_of(name), 2)
+    for bdf in (1, 2):
+        for b in range(2):
+            st = pf.sim_loop(lit.eval, lit.energy, q0[b], qd0[b], sc.h, 3 if name in GPU_BIG else 6, bdf)[2]
+            assert st == 0, (name, bdf, b, st)
+
+
+def test_lu_guard_restatement():
+    """pf.lu_guard on matrices whose elimination is known: SPD and well scaled passes; a negative pivot, a non-positive diagonal
+    and a multiplier above 8 in the equilibrated matrix trip."""
+    m = {"idx": [2, -1, 0, 1]}                                  # node order: reduced DOFs 2, 0, 1; one node without a DOF
+    A = np.array([[4.0, 1.0, 0.5], [1.0, 3.0, 0.2], [0.5, 0.2, 2.0]])
+    P = [2, 0, 1]
+    H = np.zeros((3, 3))
+    H[np.ix_(P, P)] = A
+    assert 0 < pf.lu_guard(m, H) < 1 and not pf.lu_guard_trips(m, H)
+    assert abs(pf.lu_guard(m, H) - max(1.0 / 4 / 3, 0.25 / 4 / 2, (0.2 - 0.125) ** 2 / (3 - 0.25) / 2)) <= 1e-15
+    B = A.copy()
+    B[0, 0] = -4.0
+    H[np.ix_(P, P)] = B
+    assert pf.lu_guard(m, H) == np.inf
+    B = A.copy()
+    B[1, 1] = 0.2                                               # second pivot 0.2 - 0.25 < 0
+    H[np.ix_(P, P)] = B
+    assert pf.lu_guard_trips(m, H)
+    B = np.array([[1e-4, 1.0, 0.0], [1.0, 3.0, 0.0], [0.0, 0.0, 1.0]])      # l^2 u / H_11 = 1e4 / 3
+    H[np.ix_(P, P)] = B
+    assert pf.lu_guard_trips(m, H)
+    B[1, 1] = 2e4                                               # the same multiplier against a large diagonal: 1e4 / 2e4
+    H[np.ix_(P, P)] = B
+    assert abs(pf.lu_guard(m, H) - 0.5) <= 1e-15
+
+
+def test_switching_scene_switches(oracle_lib):
+    """Both cables of pf.switchingScene are taut, slack and taut again (or the reverse) within 20 steps, under both integrators,
+    on the two states the GPU test uses."""
+    sc = pf.switchingScene()
+    lit = pf.Literal(oracle_lib, sc)
+    q, qd = pf.switchingStates(sc)
+    for bdf in (1, 2):
+        for b in range(2):
+            _, _, st, hist = pf.sim_loop(lit.eval, lit.energy, q[b], qd[b], sc.h, 20, bdf, history=True)
+            assert st == 0
+            states = pf.cable_states(lit, hist)
+            assert len(states) == 2 and all(pf.switches(s) for s in states), (bdf, b, states)
