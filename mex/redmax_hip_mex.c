@@ -997,18 +997,38 @@ static void cmd_adjoint_track(int nlhs, mxArray* plhs[], int nrhs, const mxArray
     give(nlhs, plhs, out, 3);
 }
 
+/* body (MATLAB listing index -> 0-based), xlocal and step of terms(i): the fields point and frame terms share */
+static void term_place(const mxArray* ta, size_t i, const char* who, int* body, double xlocal[3], int* step) {
+    *body = (int)mxGetScalar(term_field(ta, i, "body")) - 1;
+    const mxArray* xl = term_field(ta, i, "xlocal");
+    if (!mxIsDouble(xl) || mxGetNumberOfElements(xl) != 3) mexErrMsgIdAndTxt("redmax:hip", "%s: terms(%d).xlocal must have 3 elements", who, (int)i + 1);
+    memcpy(xlocal, mxGetPr(xl), 3 * sizeof(double));
+    *step = (int)mxGetScalar(term_field(ta, i, "step"));
+}
 /* the struct array `ta` (body 1-based, xlocal, step[, wpos]) as rmx_track_term's; the caller frees the result */
 static rmx_track_term* point_terms(const mxArray* ta, const char* who, int need_wpos, size_t* nterms) {
     if (!mxIsStruct(ta)) mexErrMsgIdAndTxt("redmax:hip", "%s: terms must be a struct array with the fields body, xlocal, step%s", who, need_wpos ? ", wpos" : "");
     *nterms = mxGetNumberOfElements(ta);
     rmx_track_term* terms = (rmx_track_term*)mxCalloc(*nterms ? *nterms : 1, sizeof *terms);
     for (size_t i = 0; i < *nterms; ++i) {
-        terms[i].body = (int)mxGetScalar(term_field(ta, i, "body")) - 1;   /* MATLAB listing index -> 0-based */
-        const mxArray* xl = term_field(ta, i, "xlocal");
-        if (!mxIsDouble(xl) || mxGetNumberOfElements(xl) != 3) mexErrMsgIdAndTxt("redmax:hip", "%s: terms(%d).xlocal must have 3 elements", who, (int)i + 1);
-        memcpy(terms[i].xlocal, mxGetPr(xl), 3 * sizeof(double));
-        terms[i].step = (int)mxGetScalar(term_field(ta, i, "step"));
+        term_place(ta, i, who, &terms[i].body, terms[i].xlocal, &terms[i].step);
         terms[i].wpos = need_wpos ? mxGetScalar(term_field(ta, i, "wpos")) : 0.0;
+    }
+    return terms;
+}
+/* ... (body 1-based, xlocal, step[, wpos, wvel, wrot]: a missing weight is 0) as rmx_frame_term's; the caller frees */
+static rmx_frame_term* frame_terms(const mxArray* ta, const char* who, size_t* nterms) {
+    if (!mxIsStruct(ta)) mexErrMsgIdAndTxt("redmax:hip", "%s: terms must be a struct array with the fields body, xlocal, step[, wpos, wvel, wrot]", who);
+    *nterms = mxGetNumberOfElements(ta);
+    rmx_frame_term* terms = (rmx_frame_term*)mxCalloc(*nterms ? *nterms : 1, sizeof *terms);
+    for (size_t i = 0; i < *nterms; ++i) {
+        term_place(ta, i, who, &terms[i].body, terms[i].xlocal, &terms[i].step);
+        const char* const names[3] = {"wpos", "wvel", "wrot"};
+        double* const w[3] = {&terms[i].wpos, &terms[i].wvel, &terms[i].wrot};
+        for (int k = 0; k < 3; ++k) {
+            const mxArray* f = mxGetField(ta, i, names[k]);
+            *w[k] = (f && !mxIsEmpty(f)) ? mxGetScalar(f) : 0.0;
+        }
     }
     return terms;
 }
@@ -1053,14 +1073,17 @@ static void cmd_rollout_points(int nlhs, mxArray* plhs[], int nrhs, const mxArra
     give(nlhs, plhs, out, 2);
 }
 
-static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+/* 'rollout_cost' and, with frames, 'rollout_cost_frames': the same arguments with vtarget and Rtarget behind xtarget */
+static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int frames) {
     handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 9) die("usage: [Jk,lx,Q] = redmax_hip_mex('rollout_cost', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget)");
+    if (nrhs < (frames ? 11 : 9))
+        die(frames ? "usage: [Jk,lx,Q] = redmax_hip_mex('rollout_cost_frames', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget)"
+                   : "usage: [Jk,lx,Q] = redmax_hip_mex('rollout_cost', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget)");
     const int nsteps = (int)mxGetScalar(prhs[2]);
-    if (nsteps < 1) die("rollout_cost: nsteps must be at least 1");
+    if (nsteps < 1) die(frames ? "rollout_cost_frames: nsteps must be at least 1" : "rollout_cost: nsteps must be at least 1");
     const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
     const size_t perq = 4 * nr * nr * N, perg = 2 * nr * N;
-    const char* who = "rollout_cost";
+    const char* who = frames ? "rollout_cost_frames" : "rollout_cost";
     const double* q = cost_arg(prhs[3], nr * N * B, 0, 0, who, "q", "nr x nsteps x batch");
     const double* qd = cost_arg(prhs[4], nr * N * B, 0, 0, who, "qdot", "nr x nsteps x batch");
     const double* Qin = cost_arg(prhs[5], perq, perq * B, 1, who, "Qin", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
@@ -1069,61 +1092,63 @@ static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
     const int Q_per = Qin && mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
     const int g_per = xg && mxGetNumberOfElements(prhs[6]) == perg * B && B > 1;
     size_t nterms = 0;
-    rmx_track_term* terms = mxIsEmpty(prhs[7]) ? NULL : point_terms(prhs[7], who, 1, &nterms);
-    const double* xt = terms ? cost_arg(prhs[8], 3 * nterms, 3 * nterms * B, 0, who, "xtarget", "3 x nterms or 3 x nterms x batch") : NULL;
-    const int t_per = terms && mxGetNumberOfElements(prhs[8]) == 3 * nterms * B && B > 1;
+    void* terms = mxIsEmpty(prhs[7]) ? NULL : frames ? (void*)frame_terms(prhs[7], who, &nterms) : (void*)point_terms(prhs[7], who, 1, &nterms);
+    /* the target tables - one for point terms, which must be given; three for frame terms, each [] where no term weighs it (the library
+       refuses otherwise) - share one per-rollout flag */
+    const size_t width[3] = {3 * nterms, 3 * nterms, 9 * nterms};
+    const char* const tname[3] = {"xtarget", "vtarget", "Rtarget"};
+    const char* const tshape[3] = {"3 x nterms or 3 x nterms x batch", "3 x nterms or 3 x nterms x batch", "3 x 3 x nterms or 3 x 3 x nterms x batch"};
+    const double* tab[3] = {NULL, NULL, NULL};
+    int t_per = -1;
+    for (int k = 0; k < (frames ? 3 : 1) && terms; ++k) {
+        tab[k] = cost_arg(prhs[8 + k], width[k], width[k] * B, frames, who, tname[k], tshape[k]);
+        if (!tab[k] || B == 1) continue;
+        const int per = mxGetNumberOfElements(prhs[8 + k]) == width[k] * B;
+        if (t_per >= 0 && per != t_per) {
+            mxFree(terms);
+            die("rollout_cost_frames: xtarget, vtarget and Rtarget must all be shared by the batch or all hold one table per rollout");
+        }
+        t_per = per;
+    }
+    if (t_per < 0) t_per = 0;
     const size_t dJ[2] = {N, B}, dl[3] = {2 * nr, N, B}, dQ[4] = {2 * nr, 2 * nr, N, B};
     mxArray* Jk = mxCreateNumericArray(2, dJ, mxDOUBLE_CLASS, mxREAL);
     mxArray* lx = nlhs > 1 ? mxCreateNumericArray(3, dl, mxDOUBLE_CLASS, mxREAL) : NULL;
     mxArray* Qo = nlhs > 2 ? mxCreateNumericArray(4, dQ, mxDOUBLE_CLASS, mxREAL) : NULL;
     rmx_state_cost sc;
     rmx_point_terms pts;
+    rmx_frame_terms ft;
     memset(&sc, 0, sizeof sc);
     memset(&pts, 0, sizeof pts);
+    memset(&ft, 0, sizeof ft);
     sc.Q_per_rollout = Q_per;
     sc.goal_per_rollout = g_per;
-    pts.nterms = (int)nterms;
-    pts.terms = terms;
-    pts.per_rollout = t_per;
+    pts.nterms = ft.nterms = (int)nterms;
+    pts.terms = frames ? NULL : (const rmx_track_term*)terms;
+    ft.terms = frames ? (const rmx_frame_term*)terms : NULL;
+    pts.per_rollout = ft.per_rollout = t_per;
     for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: the record, the per-rollout tables and the outputs advance */
         size_t f;
         rmx_batch* b = shard(h, s, &f);
         rmx_cost_model out;
         sc.Q = table_at(Qin, Q_per, f, perq);
         sc.xgoal = table_at(xg, g_per, f, perg);
-        pts.xtarget = table_at(xt, t_per, f, 3 * nterms);
+        pts.xtarget = ft.xtarget = table_at(tab[0], t_per, f, width[0]);
+        ft.vtarget = table_at(tab[1], t_per, f, width[1]);
+        ft.Rtarget = table_at(tab[2], t_per, f, width[2]);
         out.Jk = mxGetPr(Jk) + f * N;
         out.lx = lx ? mxGetPr(lx) + f * perg : NULL;
         out.Q = Qo ? mxGetPr(Qo) + f * perq : NULL;
-        if (rmx_rollout_cost(b, nsteps, q + f * nr * N, qd + f * nr * N, (Qin || xg) ? &sc : NULL, terms ? &pts : NULL, &out)) {
+        const rmx_state_cost* scp = (Qin || xg) ? &sc : NULL;
+        if (frames ? rmx_rollout_cost_frames(b, nsteps, q + f * nr * N, qd + f * nr * N, scp, terms ? &ft : NULL, &out)
+                   : rmx_rollout_cost(b, nsteps, q + f * nr * N, qd + f * nr * N, scp, terms ? &pts : NULL, &out)) {
             if (terms) mxFree(terms);
-            die_rmx("rmx_rollout_cost");
+            die_rmx(frames ? "rmx_rollout_cost_frames" : "rmx_rollout_cost");
         }
     }
     if (terms) mxFree(terms);
     mxArray* const res[3] = {Jk, lx, Qo};
     give(nlhs, plhs, res, 3);
-}
-
-/* the struct array `ta` (body 1-based, xlocal, step[, wpos, wvel, wrot]: a missing weight is 0) as rmx_frame_term's; the caller frees */
-static rmx_frame_term* frame_terms(const mxArray* ta, const char* who, size_t* nterms) {
-    if (!mxIsStruct(ta)) mexErrMsgIdAndTxt("redmax:hip", "%s: terms must be a struct array with the fields body, xlocal, step[, wpos, wvel, wrot]", who);
-    *nterms = mxGetNumberOfElements(ta);
-    rmx_frame_term* terms = (rmx_frame_term*)mxCalloc(*nterms ? *nterms : 1, sizeof *terms);
-    for (size_t i = 0; i < *nterms; ++i) {
-        terms[i].body = (int)mxGetScalar(term_field(ta, i, "body")) - 1;   /* MATLAB listing index -> 0-based */
-        const mxArray* xl = term_field(ta, i, "xlocal");
-        if (!mxIsDouble(xl) || mxGetNumberOfElements(xl) != 3) mexErrMsgIdAndTxt("redmax:hip", "%s: terms(%d).xlocal must have 3 elements", who, (int)i + 1);
-        memcpy(terms[i].xlocal, mxGetPr(xl), 3 * sizeof(double));
-        terms[i].step = (int)mxGetScalar(term_field(ta, i, "step"));
-        const char* const names[3] = {"wpos", "wvel", "wrot"};
-        double* const w[3] = {&terms[i].wpos, &terms[i].wvel, &terms[i].wrot};
-        for (int k = 0; k < 3; ++k) {
-            const mxArray* f = mxGetField(ta, i, names[k]);
-            *w[k] = (f && !mxIsEmpty(f)) ? mxGetScalar(f) : 0.0;
-        }
-    }
-    return terms;
 }
 
 static void cmd_rollout_frames(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -1165,75 +1190,6 @@ static void cmd_rollout_frames(int nlhs, mxArray* plhs[], int nrhs, const mxArra
     mxFree(terms);
     mxArray* const out[5] = {x, v, R, gq, gqd};
     give(nlhs, plhs, out, 5);
-}
-
-static void cmd_rollout_cost_frames(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    handle_t* h = get_handle(nrhs, prhs);
-    if (nrhs < 11) die("usage: [Jk,lx,Q] = redmax_hip_mex('rollout_cost_frames', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget)");
-    const int nsteps = (int)mxGetScalar(prhs[2]);
-    if (nsteps < 1) die("rollout_cost_frames: nsteps must be at least 1");
-    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B;
-    const size_t perq = 4 * nr * nr * N, perg = 2 * nr * N;
-    const char* who = "rollout_cost_frames";
-    const double* q = cost_arg(prhs[3], nr * N * B, 0, 0, who, "q", "nr x nsteps x batch");
-    const double* qd = cost_arg(prhs[4], nr * N * B, 0, 0, who, "qdot", "nr x nsteps x batch");
-    const double* Qin = cost_arg(prhs[5], perq, perq * B, 1, who, "Qin", "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
-    const double* xg = cost_arg(prhs[6], perg, perg * B, 1, who, "xgoal", "2nr x nsteps or 2nr x nsteps x batch");
-    /* (a batch of one: a table is one table either way) */
-    const int Q_per = Qin && mxGetNumberOfElements(prhs[5]) == perq * B && B > 1;
-    const int g_per = xg && mxGetNumberOfElements(prhs[6]) == perg * B && B > 1;
-    size_t nterms = 0;
-    rmx_frame_term* terms = mxIsEmpty(prhs[7]) ? NULL : frame_terms(prhs[7], who, &nterms);
-    /* the three target tables ([]: no term weighs it - the library refuses otherwise) share one per-rollout flag */
-    const size_t width[3] = {3 * nterms, 3 * nterms, 9 * nterms};
-    const char* const tname[3] = {"xtarget", "vtarget", "Rtarget"};
-    const char* const tshape[3] = {"3 x nterms or 3 x nterms x batch", "3 x nterms or 3 x nterms x batch", "3 x 3 x nterms or 3 x 3 x nterms x batch"};
-    const double* tab[3] = {NULL, NULL, NULL};
-    int t_per = -1;
-    for (int k = 0; k < 3 && terms; ++k) {
-        tab[k] = cost_arg(prhs[8 + k], width[k], width[k] * B, 1, who, tname[k], tshape[k]);
-        if (!tab[k] || B == 1) continue;
-        const int per = mxGetNumberOfElements(prhs[8 + k]) == width[k] * B;
-        if (t_per >= 0 && per != t_per) {
-            mxFree(terms);
-            die("rollout_cost_frames: xtarget, vtarget and Rtarget must all be shared by the batch or all hold one table per rollout");
-        }
-        t_per = per;
-    }
-    if (t_per < 0) t_per = 0;
-    const size_t dJ[2] = {N, B}, dl[3] = {2 * nr, N, B}, dQ[4] = {2 * nr, 2 * nr, N, B};
-    mxArray* Jk = mxCreateNumericArray(2, dJ, mxDOUBLE_CLASS, mxREAL);
-    mxArray* lx = nlhs > 1 ? mxCreateNumericArray(3, dl, mxDOUBLE_CLASS, mxREAL) : NULL;
-    mxArray* Qo = nlhs > 2 ? mxCreateNumericArray(4, dQ, mxDOUBLE_CLASS, mxREAL) : NULL;
-    rmx_state_cost sc;
-    rmx_frame_terms ft;
-    memset(&sc, 0, sizeof sc);
-    memset(&ft, 0, sizeof ft);
-    sc.Q_per_rollout = Q_per;
-    sc.goal_per_rollout = g_per;
-    ft.nterms = (int)nterms;
-    ft.terms = terms;
-    ft.per_rollout = t_per;
-    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: the record, the per-rollout tables and the outputs advance */
-        size_t f;
-        rmx_batch* b = shard(h, s, &f);
-        rmx_cost_model out;
-        sc.Q = table_at(Qin, Q_per, f, perq);
-        sc.xgoal = table_at(xg, g_per, f, perg);
-        ft.xtarget = table_at(tab[0], t_per, f, width[0]);
-        ft.vtarget = table_at(tab[1], t_per, f, width[1]);
-        ft.Rtarget = table_at(tab[2], t_per, f, width[2]);
-        out.Jk = mxGetPr(Jk) + f * N;
-        out.lx = lx ? mxGetPr(lx) + f * perg : NULL;
-        out.Q = Qo ? mxGetPr(Qo) + f * perq : NULL;
-        if (rmx_rollout_cost_frames(b, nsteps, q + f * nr * N, qd + f * nr * N, (Qin || xg) ? &sc : NULL, terms ? &ft : NULL, &out)) {
-            if (terms) mxFree(terms);
-            die_rmx("rmx_rollout_cost_frames");
-        }
-    }
-    if (terms) mxFree(terms);
-    mxArray* const res[3] = {Jk, lx, Qo};
-    give(nlhs, plhs, res, 3);
 }
 
 /* `clear mex` / MATLAB exit: free what is still alive on the device */
@@ -1388,11 +1344,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(cmd, "rollout_points")) {
         cmd_rollout_points(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_cost")) {
-        cmd_rollout_cost(nlhs, plhs, nrhs, prhs);
+        cmd_rollout_cost(nlhs, plhs, nrhs, prhs, 0);
     } else if (!strcmp(cmd, "rollout_frames")) {
         cmd_rollout_frames(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_cost_frames")) {
-        cmd_rollout_cost_frames(nlhs, plhs, nrhs, prhs);
+        cmd_rollout_cost(nlhs, plhs, nrhs, prhs, 1);
     } else {
         mexErrMsgIdAndTxt("redmax:hip", "unknown command '%s'", cmd);
     }

@@ -732,21 +732,28 @@ class BatchSim:
         _abi.check(self._L.rmx_rollout_lqr_device(self._batch, int(nsteps), C.byref(cost), C.byref(gains)), "rmx_rollout_lqr_device")
 
     @staticmethod
-    def _point_terms(terms, who, need_wpos, h=None):
-        """terms (a list of dict(body, xlocal, step[, wpos]), adjoint_track's) -> (array of TrackTerm, count).  With the step size h a
-        term may give its time `t` in the place of `step`."""
+    def _terms(ctype, terms, who, weights, need, h):
+        """The body of _point_terms / _frame_terms: terms (a list of dicts) -> (array of ctype, count).  weights: the names read; need:
+        a missing one is a KeyError and not 0."""
         terms = list(terms)
-        arr = (_abi.TrackTerm * max(len(terms), 1))()
+        arr = (ctype * max(len(terms), 1))()
         for a, t in zip(arr, terms):
             xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
             if xl.shape != (3,):
                 raise ValueError("%s: a term's xlocal must have shape (3,), got %r" % (who, xl.shape))
             a.body = int(t["body"])
             a.step = int(t["step"]) if "step" in t or h is None else int(round(float(t["t"]) / float(h)))
-            a.wpos = float(t["wpos"]) if need_wpos else float(t.get("wpos", 0.0))
+            for k in weights:
+                setattr(a, k, float(t[k]) if need else float(t.get(k, 0.0)))
             for i in range(3):
                 a.xlocal[i] = float(xl[i])
         return arr, len(terms)
+
+    @staticmethod
+    def _point_terms(terms, who, need_wpos, h=None):
+        """terms (a list of dict(body, xlocal, step[, wpos]), adjoint_track's) -> (array of TrackTerm, count).  With the step size h a
+        term may give its time `t` in the place of `step`."""
+        return BatchSim._terms(_abi.TrackTerm, terms, who, ("wpos",), need_wpos, h)
 
     def rollout_points(self, nsteps, q, terms, gx=None, points=True):
         """rmx_rollout_points: the world positions of body points along a state record q [B][nsteps][nr] (any record, typically a
@@ -775,6 +782,39 @@ class BatchSim:
         _abi.check(self._L.rmx_rollout_points_device(self._batch, int(nsteps), _vp(q_ptr), C.byref(pts), _vp(x_ptr), _vp(gx_ptr), _vp(gq_ptr)),
                    "rmx_rollout_points_device")
 
+    def _cost_inputs(self, who, nsteps, q, qdot, Q, xgoal, want):
+        """The checked inputs rollout_cost / rollout_cost_frames share -> (want, q, qdot, StateCost or None, the arrays it points into)."""
+        B, nr = self.B, self.nr
+        want = _names(who, "want", want, ("Jk", "lx", "Q"), False)
+        q, qdot = _f64_joint(who, ("q", "qdot"), (q, qdot), (B, nsteps, nr))
+        sc = None
+        if Q is not None or xgoal is not None:
+            sc = _abi.StateCost(None, None, 0, 0)
+            if Q is not None:      # (symmetric: row-major memory is the column-major table)
+                Q, sc.Q_per_rollout = _table(who, "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
+                sc.Q = Q.ctypes.data
+            if xgoal is not None:
+                xgoal, sc.goal_per_rollout = _table(who, "xgoal", xgoal, (nsteps, 2 * nr), B)
+                sc.xgoal = xgoal.ctypes.data
+        return want, q, qdot, sc, (Q, xgoal)
+
+    def _cost_call(self, entry, nsteps, q, qdot, sc, terms, want):
+        """The outputs named in want, packed as a CostModel, and the call of a cost-model entry -> the dict of outputs."""
+        B, nr = self.B, self.nr
+        shapes = {"Jk": (B, nsteps), "lx": (B, nsteps, 2 * nr), "Q": (B, nsteps, 2 * nr, 2 * nr)}
+        out = {w: np.empty(shapes[w]) for w in want}
+        cm = _abi.CostModel(*[_addr(out.get(n)) for n in ("Jk", "lx", "Q")])
+        _abi.check(getattr(self._L, entry)(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, None if sc is None else C.byref(sc),
+                                           None if terms is None else C.byref(terms), C.byref(cm)), entry)
+        return out
+
+    def _cost_call_device(self, entry, nsteps, q_ptr, qdot_ptr, Q_ptr, xgoal_ptr, Q_per_rollout, goal_per_rollout, terms, Jk_ptr, lx_ptr, Qout_ptr):
+        """The StateCost and CostModel of DEVICE pointers and the call of a cost-model entry's _device form."""
+        sc = _abi.StateCost(Q_ptr or None, xgoal_ptr or None, int(bool(Q_per_rollout)), int(bool(goal_per_rollout)))
+        cm = _abi.CostModel(Jk_ptr or None, lx_ptr or None, Qout_ptr or None)
+        _abi.check(getattr(self._L, entry)(self._batch, int(nsteps), _vp(q_ptr), _vp(qdot_ptr), C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
+                                           None if terms is None else C.byref(terms), C.byref(cm)), entry)
+
     def rollout_cost(self, nsteps, q, qdot, Q=None, xgoal=None, terms=None, xtarget=None, want=("Jk", "lx", "Q")):
         """rmx_rollout_cost: the cost of a state record q, qdot [B][nsteps][nr] and its second-order model for rollout_lqr -
         a joint-space quadratic (Q [nsteps][2nr][2nr] or [B][..], symmetric; xgoal [nsteps][2nr] or [B][..]; None: zero) plus point
@@ -784,28 +824,14 @@ class BatchSim:
         Q + sum_t w_t Jp_t'Jp_t in the q block (Gauss-Newton: the curvature of the points is dropped), symmetric bit for bit.  Needs
         no tape and changes neither the state nor the tape."""
         nsteps = int(nsteps)
-        B, nr = self.B, self.nr
-        want = _names("rollout_cost", "want", want, ("Jk", "lx", "Q"), False)
-        q, qdot = _f64_joint("rollout_cost", ("q", "qdot"), (q, qdot), (B, nsteps, nr))
-        sc = None
-        if Q is not None or xgoal is not None:
-            sc = _abi.StateCost(None, None, 0, 0)
-            if Q is not None:      # (symmetric: row-major memory is the column-major table)
-                Q, sc.Q_per_rollout = _table("rollout_cost", "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
-                sc.Q = Q.ctypes.data
-            if xgoal is not None:
-                xgoal, sc.goal_per_rollout = _table("rollout_cost", "xgoal", xgoal, (nsteps, 2 * nr), B)
-                sc.xgoal = xgoal.ctypes.data
+        want, q, qdot, sc, keep = self._cost_inputs("rollout_cost", nsteps, q, qdot, Q, xgoal, want)
         pts = None
         if terms is not None:
             arr, nterms = self._point_terms(terms, "rollout_cost", True)
             xtarget, per = self._targets("rollout_cost", xtarget, nterms)
             pts = _abi.PointTerms(nterms, arr, xtarget.ctypes.data, per)
-        shapes = {"Jk": (B, nsteps), "lx": (B, nsteps, 2 * nr), "Q": (B, nsteps, 2 * nr, 2 * nr)}
-        out = {w: np.empty(shapes[w]) for w in want}
-        cm = _abi.CostModel(*[_addr(out.get(n)) for n in ("Jk", "lx", "Q")])
-        _abi.check(self._L.rmx_rollout_cost(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, None if sc is None else C.byref(sc),
-                                            None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost")
+        out = self._cost_call("rmx_rollout_cost", nsteps, q, qdot, sc, pts, want)
+        del keep
         return out
 
     def rollout_cost_device(self, nsteps, q_ptr, qdot_ptr, Q_ptr=None, xgoal_ptr=None, Q_per_rollout=False, goal_per_rollout=False, terms=None,
@@ -814,31 +840,17 @@ class BatchSim:
         table per rollout with the flag set, 0 / None: zero; xtarget [nterms][3] or [B][nterms][3]; Jk [B][nsteps], lx
         [B][nsteps][2nr], Qout [B][nsteps][2nr*2nr], 0 / None: not formed (not all three).  terms stays the host list (None: no
         point targets)."""
-        sc = _abi.StateCost(Q_ptr or None, xgoal_ptr or None, int(bool(Q_per_rollout)), int(bool(goal_per_rollout)))
         pts = None
         if terms is not None:
             arr, nterms = self._point_terms(terms, "rollout_cost_device", True)
             pts = _abi.PointTerms(nterms, arr, xtarget_ptr or None, int(bool(target_per_rollout)))
-        cm = _abi.CostModel(Jk_ptr or None, lx_ptr or None, Qout_ptr or None)
-        _abi.check(self._L.rmx_rollout_cost_device(self._batch, int(nsteps), _vp(q_ptr), _vp(qdot_ptr),
-                                                   C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
-                                                   None if pts is None else C.byref(pts), C.byref(cm)), "rmx_rollout_cost_device")
+        self._cost_call_device("rmx_rollout_cost_device", nsteps, q_ptr, qdot_ptr, Q_ptr, xgoal_ptr, Q_per_rollout, goal_per_rollout, pts, Jk_ptr,
+                               lx_ptr, Qout_ptr)
 
     @staticmethod
     def _frame_terms(terms, who, h=None):
         """terms (a list of dict(body, xlocal, step | t, wpos, wvel, wrot); a missing weight is 0) -> (array of FrameTerm, count)."""
-        terms = list(terms)
-        arr = (_abi.FrameTerm * max(len(terms), 1))()
-        for a, t in zip(arr, terms):
-            xl = np.asarray(t["xlocal"], dtype=np.float64).reshape(-1)
-            if xl.shape != (3,):
-                raise ValueError("%s: a term's xlocal must have shape (3,), got %r" % (who, xl.shape))
-            a.body = int(t["body"])
-            a.step = int(t["step"]) if "step" in t or h is None else int(round(float(t["t"]) / float(h)))
-            a.wpos, a.wvel, a.wrot = (float(t.get(k, 0.0)) for k in ("wpos", "wvel", "wrot"))
-            for i in range(3):
-                a.xlocal[i] = float(xl[i])
-        return arr, len(terms)
+        return BatchSim._terms(_abi.FrameTerm, terms, who, ("wpos", "wvel", "wrot"), False, h)
 
     def _frame_targets(self, who, nterms, xtarget, vtarget, Rtarget):
         """The target tables of frame terms, each None or shared or one per rollout: ([xtarget, vtarget, Rtarget] as the library reads
@@ -901,28 +913,14 @@ class BatchSim:
         Rtarget|_F^2 (the last: wrot (1 - cos theta)); "lx" is its exact gradient in (q, qdot), "Q" the Gauss-Newton table with the
         velocity terms' q, qdot cross blocks, symmetric bit for bit.  Needs no tape and changes neither the state nor the tape."""
         nsteps = int(nsteps)
-        B, nr = self.B, self.nr
-        want = _names("rollout_cost_frames", "want", want, ("Jk", "lx", "Q"), False)
-        q, qdot = _f64_joint("rollout_cost_frames", ("q", "qdot"), (q, qdot), (B, nsteps, nr))
-        sc = None
-        if Q is not None or xgoal is not None:
-            sc = _abi.StateCost(None, None, 0, 0)
-            if Q is not None:      # (symmetric: row-major memory is the column-major table)
-                Q, sc.Q_per_rollout = _table("rollout_cost_frames", "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
-                sc.Q = Q.ctypes.data
-            if xgoal is not None:
-                xgoal, sc.goal_per_rollout = _table("rollout_cost_frames", "xgoal", xgoal, (nsteps, 2 * nr), B)
-                sc.xgoal = xgoal.ctypes.data
+        want, q, qdot, sc, keep = self._cost_inputs("rollout_cost_frames", nsteps, q, qdot, Q, xgoal, want)
         ft = None
         if terms is not None:
             arr, nterms = self._frame_terms(terms, "rollout_cost_frames", self.opts.h)
             tabs, per = self._frame_targets("rollout_cost_frames", nterms, xtarget, vtarget, Rtarget)
             ft = _abi.FrameTerms(nterms, arr, _addr(tabs[0]), _addr(tabs[1]), _addr(tabs[2]), per)
-        shapes = {"Jk": (B, nsteps), "lx": (B, nsteps, 2 * nr), "Q": (B, nsteps, 2 * nr, 2 * nr)}
-        out = {w: np.empty(shapes[w]) for w in want}
-        cm = _abi.CostModel(*[_addr(out.get(n)) for n in ("Jk", "lx", "Q")])
-        _abi.check(self._L.rmx_rollout_cost_frames(self._batch, nsteps, q.ctypes.data, qdot.ctypes.data, None if sc is None else C.byref(sc),
-                                                   None if ft is None else C.byref(ft), C.byref(cm)), "rmx_rollout_cost_frames")
+        out = self._cost_call("rmx_rollout_cost_frames", nsteps, q, qdot, sc, ft, want)
+        del keep
         return out
 
     def rollout_cost_frames_device(self, nsteps, q_ptr, qdot_ptr, Q_ptr=None, xgoal_ptr=None, Q_per_rollout=False, goal_per_rollout=False,
@@ -930,15 +928,12 @@ class BatchSim:
                                    lx_ptr=None, Qout_ptr=None):
         """rollout_cost_frames with DEVICE pointers (integers), as rollout_cost_device; vtarget [nterms][3] and Rtarget [nterms][9]
         (COLUMN-MAJOR) or one table per rollout with the flag set - the three target tables share the flag."""
-        sc = _abi.StateCost(Q_ptr or None, xgoal_ptr or None, int(bool(Q_per_rollout)), int(bool(goal_per_rollout)))
         ft = None
         if terms is not None:
             arr, nterms = self._frame_terms(terms, "rollout_cost_frames_device", self.opts.h)
             ft = _abi.FrameTerms(nterms, arr, xtarget_ptr or None, vtarget_ptr or None, Rtarget_ptr or None, int(bool(target_per_rollout)))
-        cm = _abi.CostModel(Jk_ptr or None, lx_ptr or None, Qout_ptr or None)
-        _abi.check(self._L.rmx_rollout_cost_frames_device(self._batch, int(nsteps), _vp(q_ptr), _vp(qdot_ptr),
-                                                          C.byref(sc) if (Q_ptr or xgoal_ptr) else None,
-                                                          None if ft is None else C.byref(ft), C.byref(cm)), "rmx_rollout_cost_frames_device")
+        self._cost_call_device("rmx_rollout_cost_frames_device", nsteps, q_ptr, qdot_ptr, Q_ptr, xgoal_ptr, Q_per_rollout, goal_per_rollout, ft,
+                               Jk_ptr, lx_ptr, Qout_ptr)
 
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent

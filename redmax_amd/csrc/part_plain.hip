@@ -5,7 +5,6 @@
 #include "rmx_jvp.h"
 #include "rmx_params.h"
 #include "rmx_cost.h"
-#include "rmx_frames.h"
 #if RMX_NP <= 32
 #include "rmx_lqr.h"
 #endif
@@ -120,16 +119,12 @@ void RMX_CAT(launch_jvp_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const 
     k_rollout_jvp<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
 
-// rmx_rollout_points / rmx_rollout_cost: one wavefront per (rollout, step) of the record (rmx_select.h select_rollout_cost)
-void RMX_CAT(launch_cost_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const CostArgs& a) {
+// rmx_rollout_points / rmx_rollout_cost, and with `frames` rmx_rollout_frames / rmx_rollout_cost_frames: one wavefront per (rollout,
+// step) of the record (rmx_select.h select_rollout_cost)
+void RMX_CAT(launch_cost_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const TaskArgs& a, bool frames) {
     const dim3 grid((unsigned)((size_t)b->B * a.nsteps)), block(64);
-    k_rollout_cost<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
-}
-
-// rmx_rollout_frames / rmx_rollout_cost_frames: the same shape (rmx_select.h select_rollout_cost)
-void RMX_CAT(launch_frames_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const FrameArgs& a) {
-    const dim3 grid((unsigned)((size_t)b->B * a.nsteps)), block(64);
-    k_rollout_frames<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+    if (frames) k_rollout_cost<RMX_NP, true><<<grid, block, 0, b->stream>>>(m->dm, a);
+    else k_rollout_cost<RMX_NP, false><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
 
 // rmx_rollout_vjp_params: the backward sweep of the tape's integrator in its ADJ_ZS instantiation (du, dq0, dqd0 as rmx_rollout_vjp's

@@ -2054,11 +2054,11 @@ extern "C" int rmx_rollout_lqr_box_device(rmx_batch* b, int nsteps, const rmx_lq
     return rollout_lqr_impl(b, nsteps, cost, out, true, true, box, d_ubar, max_iter, d_clamped);
 }
 
-// rmx_rollout_points / rmx_rollout_cost: point kinematics along a state record and the cost model the Riccati sweep takes, one
-// wavefront per (rollout, step) (rmx_cost.h; rmx_select.h select_rollout_cost).  They read the model and their arguments alone: no
-// tape is needed and none is touched.  The term table (rmx_track::plan_terms, a host array in both forms) goes to a small device
-// area of the batch's own that only grows; the host form stages every other array through an allocation of its own, as
-// rmx_rollout_lqr does.
+// rmx_rollout_points / rmx_rollout_cost / rmx_rollout_frames / rmx_rollout_cost_frames: kinematics of body points and frames along a
+// state record and the cost model the Riccati sweep takes, one wavefront per (rollout, step) (rmx_cost.h; rmx_select.h
+// select_rollout_cost).  They read the model and their arguments alone: no tape is needed and none is touched.  The term table
+// (rmx_track::plan_terms on the position part of every term, a host array in both forms) goes to a small device area of the batch's
+// own that only grows; the host form stages every other array through an allocation of its own, as rmx_rollout_lqr does.
 static hipError_t costws_reserve(rmx_batch* b, const size_t total) {
     if (total <= b->costws_bytes) return hipSuccess;
     void* fresh = nullptr;
@@ -2072,111 +2072,44 @@ static hipError_t costws_reserve(rmx_batch* b, const size_t total) {
     b->costws_bytes = total;
     return hipSuccess;
 }
-static int rollout_cost_impl(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_point_terms* pts,
-                             const rmx_cost_model* out, double* x, const double* gx, double* gq, const bool on_device, const bool points) {
-    const std::string who = points ? "rmx_rollout_points" : "rmx_rollout_cost";
-    if (!b || !q || (points ? !pts : (!qdot || !out || (!sc && !pts)))) return fail(RMX_E_INVALID, who + ": null argument");
-    if (!points && pts && !pts->xtarget) return fail(RMX_E_INVALID, who + ": null argument");
-    if (points ? (!x && !gq) : (!out->Jk && !out->lx && !out->Q)) return fail(RMX_E_INVALID, who + ": all outputs are null");
-    if (gq && !gx) return fail(RMX_E_INVALID, who + ": gq needs gx (the cotangents of the points)");
-    if (pts && pts->per_rollout != 0 && pts->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
-    if (sc && ((sc->Q_per_rollout != 0 && sc->Q_per_rollout != 1) || (sc->goal_per_rollout != 0 && sc->goal_per_rollout != 1)))
-        return fail(RMX_E_INVALID, who + ": Q_per_rollout and goal_per_rollout must be 0 or 1");
-    if (nsteps < 1) return fail(RMX_E_INVALID, who + ": nsteps < 1");
-    rmx_model* m = b->m;
-    const rmx_select::CostPlan plan = rmx_select::select_rollout_cost(step_traits(m), b->B, nsteps);
-    if (plan.kernel == rmx_select::CostKernel::RefusedSpherical)
-        return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
-    if (plan.kernel == rmx_select::CostKernel::RefusedNodes)
-        return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
-    if (plan.kernel != rmx_select::CostKernel::Wave) return fail(RMX_E_INVALID, who + ": batch * nsteps exceeds the grid");
-    rmx_track::Plan tplan;
-    if (pts) {
-        tplan = rmx_track::plan_terms(pts->terms, pts->nterms, nsteps, m->nlist, m->node_of_listing.data());
-        if (!tplan.error.empty()) return fail(RMX_E_INVALID, who + ": " + tplan.error);
-        for (int i = 0; i < pts->nterms && !points; ++i)
-            if (!(pts->terms[i].wpos >= 0.0) || !std::isfinite(pts->terms[i].wpos))
-                return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": wpos must be finite and >= 0 (the Gauss-Newton block must stay positive semi-definite)");
+struct CostTerms {      // an entry's terms as frame terms: rmx_frame_terms as it is, rmx_point_terms with wvel = wrot = 0 and no vtarget, Rtarget
+    bool given = false;
+    rmx_frame_terms ft{};
+    std::vector<rmx_frame_term> lifted;
+    explicit CostTerms(const rmx_frame_terms* f) : given(f != nullptr) {
+        if (f) ft = *f;
     }
-    HIPCHK(hipSetDevice(m->device));
-    if (int rc = pending_error_check(b, who.c_str())) return rc;
-    const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
-    const size_t nterms = pts ? (size_t)pts->nterms : 0;
-    const size_t bytes_traj = B * N * nr * dbl, bytes_pts = B * nterms * 3 * dbl, bytes_Q = N * 4 * nr * nr * dbl;
-    enum { S_Q, S_QD, S_XT, S_QIN, S_XG, S_JK, S_LX, S_QOUT, S_X, S_GX, S_GQ };
-    Staging st(on_device);
-    st.add(bytes_traj, q, nullptr);
-    st.add(bytes_traj, points ? nullptr : qdot, nullptr);
-    st.add((pts && pts->per_rollout ? B : 1) * nterms * 3 * dbl, (pts && !points) ? pts->xtarget : nullptr, nullptr);
-    st.add((sc && sc->Q_per_rollout ? B : 1) * bytes_Q, (sc && !points) ? sc->Q : nullptr, nullptr);
-    st.add((sc && sc->goal_per_rollout ? B : 1) * N * 2 * nr * dbl, (sc && !points) ? sc->xgoal : nullptr, nullptr);
-    st.add(B * N * dbl, nullptr, points ? nullptr : out->Jk);
-    st.add(B * N * 2 * nr * dbl, nullptr, points ? nullptr : out->lx);
-    st.add(B * bytes_Q, nullptr, points ? nullptr : out->Q);
-    st.add(bytes_pts, nullptr, x);
-    st.add(bytes_pts, gq ? gx : nullptr, nullptr);
-    st.add(bytes_traj, nullptr, gq);
-    if (int rc = st.allocate(who, "the staging")) return rc;
-    const size_t trk_bytes = rmx_tape::round256(nterms * sizeof(rmx_track::DevTerm)), begin_bytes = (N + 1) * sizeof(int);
-    hipError_t e = pts ? costws_reserve(b, trk_bytes + begin_bytes) : hipSuccess;
-    if (e == hipErrorOutOfMemory) {
-        st.release(b, hipSuccess);
-        return fail(RMX_E_NOMEM, who + ": no device memory for the term table");
+    explicit CostTerms(const rmx_point_terms* p) : given(p != nullptr) {
+        if (!p) return;
+        ft.nterms = p->nterms; ft.xtarget = p->xtarget; ft.per_rollout = p->per_rollout;
+        lifted.resize((size_t)std::max(p->nterms, 1));      // (never empty: a null `terms` is the caller's alone)
+        for (int i = 0; p->terms && i < p->nterms; ++i) {
+            const rmx_track_term& t = p->terms[i];
+            lifted[(size_t)i] = rmx_frame_term{t.body, {t.xlocal[0], t.xlocal[1], t.xlocal[2]}, t.step, t.wpos, 0.0, 0.0};
+        }
+        ft.terms = p->terms ? lifted.data() : nullptr;
     }
-    CostArgs a{};
-    a.nsteps = nsteps; a.nterms = (int)nterms;
-    a.q = st.dev(S_Q); a.qd = st.dev(S_QD);
-    if (pts && e == hipSuccess) {
-        a.trk = (const rmx_track::DevTerm*)b->costws;
-        a.trk_begin = (const int*)((const char*)b->costws + trk_bytes);
-        e = hipMemcpyAsync(b->costws, tplan.terms.data(), nterms * sizeof(rmx_track::DevTerm), hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)b->costws + trk_bytes, tplan.begin.data(), begin_bytes, hipMemcpyHostToDevice, b->stream);
-    }
-    a.xt = st.dev(S_XT); a.xt_stride = (pts && pts->per_rollout) ? nterms * 3 : 0;
-    a.Qin = st.dev(S_QIN); a.q_stride = (sc && sc->Q_per_rollout) ? N * 4 * nr * nr : 0;
-    a.xgoal = st.dev(S_XG); a.goal_stride = (sc && sc->goal_per_rollout) ? N * 2 * nr : 0;
-    a.Jk = st.dev(S_JK); a.lx = st.dev(S_LX); a.Qout = st.dev(S_QOUT);
-    a.x = st.dev(S_X); a.gx = st.dev(S_GX); a.gq = st.dev(S_GQ);
-    e = st.copy_in(b, e);
-    e = timed_launch(b, e, [&] {
-        DISPATCH_NP(plan.np, launch_cost, m, b, a)
-        b->last_kernel = rmx_select::label_rollout_cost();
-        return hipSuccess;
-    });
-    return tape_call_end(b, st.copy_out(b, e), st, who);      // (the wait keeps the plan's arrays alive for their copies)
-}
-extern "C" int rmx_rollout_points(rmx_batch* b, int nsteps, const double* q, const rmx_point_terms* pts, double* x, const double* gx, double* gq) {
-    return rollout_cost_impl(b, nsteps, q, nullptr, nullptr, pts, nullptr, x, gx, gq, false, true);
-}
-extern "C" int rmx_rollout_points_device(rmx_batch* b, int nsteps, const double* d_q, const rmx_point_terms* pts, double* d_x, const double* d_gx,
-                                         double* d_gq) {
-    return rollout_cost_impl(b, nsteps, d_q, nullptr, nullptr, pts, nullptr, d_x, d_gx, d_gq, true, true);
-}
-extern "C" int rmx_rollout_cost(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_point_terms* pts,
-                                const rmx_cost_model* out) {
-    return rollout_cost_impl(b, nsteps, q, qdot, sc, pts, out, nullptr, nullptr, nullptr, false, false);
-}
-extern "C" int rmx_rollout_cost_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
-                                       const rmx_point_terms* pts, const rmx_cost_model* out) {
-    return rollout_cost_impl(b, nsteps, d_q, d_qdot, sc, pts, out, nullptr, nullptr, nullptr, true, false);
-}
-
-// rmx_rollout_frames / rmx_rollout_cost_frames: rollout_cost_impl with frame terms (rmx_frames.h) - the same plan, the same term
-// planner (fed the position part of every term), the same device area for the term table and the same staging.
-struct FrameIO {      // rmx_rollout_frames' arrays
+};
+struct FrameIO {      // the arrays of the kinematics entries (rmx_rollout_points: x, gx, gq alone)
     double *x, *v, *R;
     const double *gx, *gv, *gR;
     double *gq, *gqd;
 };
-static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_frame_terms* ft,
-                               const rmx_cost_model* out, const FrameIO* io, const bool on_device) {
-    const bool frames = io != nullptr;
-    const std::string who = frames ? "rmx_rollout_frames" : "rmx_rollout_cost_frames";
-    if (!b || !q || !qdot || (frames ? !ft : (!out || (!sc && !ft)))) return fail(RMX_E_INVALID, who + ": null argument");
-    if (frames ? (!io->x && !io->v && !io->R && !io->gq && !io->gqd) : (!out->Jk && !out->lx && !out->Q))
+// The four modes: io (the kinematics entries) or sc + out (the cost-model entries), on point terms (frames false: the point
+// instantiation and its label) or frame terms.  `name` is the entry's, for the messages.
+static int rollout_cost_impl(const char* name, const bool frames, rmx_batch* b, int nsteps, const double* q, const double* qdot,
+                             const rmx_state_cost* sc, const CostTerms& ct, const rmx_cost_model* out, const FrameIO* io, const bool on_device) {
+    const bool kin = io != nullptr;
+    const std::string who = name;
+    const rmx_frame_terms* ft = ct.given ? &ct.ft : nullptr;
+    // (rmx_rollout_points has no qdot)
+    if (!b || !q || (!qdot && (frames || !kin)) || (kin ? !ft : (!out || (!sc && !ft)))) return fail(RMX_E_INVALID, who + ": null argument");
+    if (!frames && !kin && ft && !ft->xtarget) return fail(RMX_E_INVALID, who + ": null argument");
+    if (kin ? (!io->x && !io->v && !io->R && !io->gq && !io->gqd) : (!out->Jk && !out->lx && !out->Q))
         return fail(RMX_E_INVALID, who + ": all outputs are null");
-    if (frames && io->gq && !io->gx && !io->gv && !io->gR) return fail(RMX_E_INVALID, who + ": gq needs gx, gv or gR (the cotangents of the frames)");
-    if (frames && io->gqd && !io->gv) return fail(RMX_E_INVALID, who + ": gqd needs gv (the cotangents of the velocities)");
+    if (kin && io->gq && !io->gx && !io->gv && !io->gR)
+        return fail(RMX_E_INVALID, who + (frames ? ": gq needs gx, gv or gR (the cotangents of the frames)" : ": gq needs gx (the cotangents of the points)"));
+    if (kin && io->gqd && !io->gv) return fail(RMX_E_INVALID, who + ": gqd needs gv (the cotangents of the velocities)");
     if (ft && ft->per_rollout != 0 && ft->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
     if (sc && ((sc->Q_per_rollout != 0 && sc->Q_per_rollout != 1) || (sc->goal_per_rollout != 0 && sc->goal_per_rollout != 1)))
         return fail(RMX_E_INVALID, who + ": Q_per_rollout and goal_per_rollout must be 0 or 1");
@@ -2203,7 +2136,7 @@ static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const 
         }
         rmx_track::Plan tplan = rmx_track::plan_terms(pos.data(), ft->nterms, nsteps, m->nlist, m->node_of_listing.data());
         if (!tplan.error.empty()) return fail(RMX_E_INVALID, who + ": " + tplan.error);
-        for (int i = 0; i < ft->nterms && !frames; ++i) {
+        for (int i = 0; i < ft->nterms && !kin; ++i) {      // the weights: the cost-model entries alone read them
             const rmx_frame_term& t = ft->terms[i];
             const struct { const char* name; double w; const void* table; const char* tname; } ws[3] = {
                 {"wpos", t.wpos, ft->xtarget, "xtarget"}, {"wvel", t.wvel, ft->vtarget, "vtarget"}, {"wrot", t.wrot, ft->Rtarget, "Rtarget"}};
@@ -2228,13 +2161,13 @@ static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const 
     const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
     const size_t nterms = ft ? (size_t)ft->nterms : 0, tabs = (ft && ft->per_rollout ? B : 1) * nterms;
     const size_t bytes_traj = B * N * nr * dbl, bytes_Q = N * 4 * nr * nr * dbl;
-    // (each entry has eight arrays of its own after the record: the staging room holds rmx_tape::STAGE_MAX)
+    // (each mode has eight arrays of its own after the record: the staging room holds rmx_tape::STAGE_MAX)
     enum { S_Q, S_QD, S_XT, S_VT, S_RT, S_QIN, S_XG, S_JK, S_LX, S_QOUT };
     enum { S_X = S_QD + 1, S_V, S_R, S_GX, S_GV, S_GR, S_GQ, S_GQD };
     Staging st(on_device);
     st.add(bytes_traj, q, nullptr);
     st.add(bytes_traj, qdot, nullptr);
-    if (!frames) {
+    if (!kin) {
         st.add(tabs * 3 * dbl, ft ? ft->xtarget : nullptr, nullptr);
         st.add(tabs * 3 * dbl, ft ? ft->vtarget : nullptr, nullptr);
         st.add(tabs * 9 * dbl, ft ? ft->Rtarget : nullptr, nullptr);
@@ -2261,7 +2194,7 @@ static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const 
         st.release(b, hipSuccess);
         return fail(RMX_E_NOMEM, who + ": no device memory for the term table");
     }
-    FrameArgs a{};
+    TaskArgs a{};
     a.nsteps = nsteps; a.nterms = (int)nterms;
     a.q = st.dev(S_Q); a.qd = st.dev(S_QD);
     if (ft && e == hipSuccess) {
@@ -2273,7 +2206,7 @@ static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const 
     a.t_stride = (ft && ft->per_rollout) ? nterms : 0;
     a.q_stride = (sc && sc->Q_per_rollout) ? N * 4 * nr * nr : 0;
     a.goal_stride = (sc && sc->goal_per_rollout) ? N * 2 * nr : 0;
-    if (!frames) {
+    if (!kin) {
         a.xt = st.dev(S_XT); a.vt = st.dev(S_VT); a.Rt = st.dev(S_RT);
         a.Qin = st.dev(S_QIN); a.xgoal = st.dev(S_XG);
         a.Jk = st.dev(S_JK); a.lx = st.dev(S_LX); a.Qout = st.dev(S_QOUT);
@@ -2284,30 +2217,47 @@ static int rollout_frames_impl(rmx_batch* b, int nsteps, const double* q, const 
     }
     e = st.copy_in(b, e);
     e = timed_launch(b, e, [&] {
-        DISPATCH_NP(plan.np, launch_frames, m, b, a)
-        b->last_kernel = rmx_select::label_rollout_frames();
+        DISPATCH_NP(plan.np, launch_cost, m, b, a, frames)
+        b->last_kernel = frames ? rmx_select::label_rollout_frames() : rmx_select::label_rollout_cost();
         return hipSuccess;
     });
     return tape_call_end(b, st.copy_out(b, e), st, who);      // (the wait keeps the term arrays alive for their copies)
 }
+extern "C" int rmx_rollout_points(rmx_batch* b, int nsteps, const double* q, const rmx_point_terms* pts, double* x, const double* gx, double* gq) {
+    const FrameIO io{x, nullptr, nullptr, gx, nullptr, nullptr, gq, nullptr};
+    return rollout_cost_impl("rmx_rollout_points", false, b, nsteps, q, nullptr, nullptr, CostTerms(pts), nullptr, &io, false);
+}
+extern "C" int rmx_rollout_points_device(rmx_batch* b, int nsteps, const double* d_q, const rmx_point_terms* pts, double* d_x, const double* d_gx,
+                                         double* d_gq) {
+    const FrameIO io{d_x, nullptr, nullptr, d_gx, nullptr, nullptr, d_gq, nullptr};
+    return rollout_cost_impl("rmx_rollout_points", false, b, nsteps, d_q, nullptr, nullptr, CostTerms(pts), nullptr, &io, true);
+}
+extern "C" int rmx_rollout_cost(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc, const rmx_point_terms* pts,
+                                const rmx_cost_model* out) {
+    return rollout_cost_impl("rmx_rollout_cost", false, b, nsteps, q, qdot, sc, CostTerms(pts), out, nullptr, false);
+}
+extern "C" int rmx_rollout_cost_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
+                                       const rmx_point_terms* pts, const rmx_cost_model* out) {
+    return rollout_cost_impl("rmx_rollout_cost", false, b, nsteps, d_q, d_qdot, sc, CostTerms(pts), out, nullptr, true);
+}
 extern "C" int rmx_rollout_frames(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_frame_terms* ft, double* x, double* v,
                                   double* R, const double* gx, const double* gv, const double* gR, double* gq, double* gqd) {
     const FrameIO io{x, v, R, gx, gv, gR, gq, gqd};
-    return rollout_frames_impl(b, nsteps, q, qdot, nullptr, ft, nullptr, &io, false);
+    return rollout_cost_impl("rmx_rollout_frames", true, b, nsteps, q, qdot, nullptr, CostTerms(ft), nullptr, &io, false);
 }
 extern "C" int rmx_rollout_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_frame_terms* ft, double* d_x,
                                          double* d_v, double* d_R, const double* d_gx, const double* d_gv, const double* d_gR, double* d_gq,
                                          double* d_gqd) {
     const FrameIO io{d_x, d_v, d_R, d_gx, d_gv, d_gR, d_gq, d_gqd};
-    return rollout_frames_impl(b, nsteps, d_q, d_qdot, nullptr, ft, nullptr, &io, true);
+    return rollout_cost_impl("rmx_rollout_frames", true, b, nsteps, d_q, d_qdot, nullptr, CostTerms(ft), nullptr, &io, true);
 }
 extern "C" int rmx_rollout_cost_frames(rmx_batch* b, int nsteps, const double* q, const double* qdot, const rmx_state_cost* sc,
                                        const rmx_frame_terms* ft, const rmx_cost_model* out) {
-    return rollout_frames_impl(b, nsteps, q, qdot, sc, ft, out, nullptr, false);
+    return rollout_cost_impl("rmx_rollout_cost_frames", true, b, nsteps, q, qdot, sc, CostTerms(ft), out, nullptr, false);
 }
 extern "C" int rmx_rollout_cost_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
                                               const rmx_frame_terms* ft, const rmx_cost_model* out) {
-    return rollout_frames_impl(b, nsteps, d_q, d_qdot, sc, ft, out, nullptr, true);
+    return rollout_cost_impl("rmx_rollout_cost_frames", true, b, nsteps, d_q, d_qdot, sc, CostTerms(ft), out, nullptr, true);
 }
 
 extern "C" int rmx_rollout_tape(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,

@@ -151,45 +151,30 @@ struct LqrArgs {
     unsigned* clamped;        // [B][nsteps] or null: bit i of row k-1 is set where DOF i of step k ended on a bound
 };
 
-// rmx_rollout_points / rmx_rollout_cost (rmx_cost.h): one wavefront per (rollout, step) of a state record
-struct CostArgs {
+// rmx_rollout_points / rmx_rollout_cost / rmx_rollout_frames / rmx_rollout_cost_frames (rmx_cost.h): one wavefront per (rollout,
+// step) of a state record.  A point term is a frame term with wvel = wrot = 0; the point instantiation reads neither them nor the
+// arrays marked (frames).
+struct FrameDevTerm {
+    rmx_track::DevTerm t;     // the point, its node, wpos and the term's position in the caller's array
+    double wvel, wrot;
+};
+static_assert(sizeof(FrameDevTerm) == 56, "FrameDevTerm: a DevTerm and two doubles, no padding");
+struct TaskArgs {
     int nsteps, nterms;
-    const double *q, *qd;     // [B][nsteps][nr] the record (qd: rmx_rollout_cost alone)
-    const rmx_track::DevTerm* trk;   // [nterms] the terms sorted by step (rmx_track.h), or null: no terms
+    const double *q, *qd;     // [B][nsteps][nr] the record (qd may be null where no velocity is asked for)
+    const FrameDevTerm* trk;  // [nterms] the terms sorted by step (rmx_track.h), or null: no terms
     const int* trk_begin;     // [nsteps + 1] step k owns terms trk_begin[k-1] .. trk_begin[k]-1, or null
-    const double* xt;         // targets, [nterms][3] or [B][nterms][3], indexed by the term's position in the caller's array
-    size_t xt_stride;         // doubles from one rollout's target table to the next (0: one table for the batch)
+    const double *xt, *vt, *Rt;   // targets [nterms][3], [nterms][3], [nterms][9] (column-major) or [B][..], indexed by the term's position
+                              // in the caller's array; null: no term weighs it (vt, Rt: frames)
+    size_t t_stride;          // TERMS from one rollout's target tables to the next (0: one table for the batch)
     const double* Qin;        // [nsteps][2nr * 2nr] or [B][..], column-major, or null: zero
     size_t q_stride;          // doubles from one rollout's Q table to the next (0: one table for the batch)
     const double* xgoal;      // [nsteps][2nr] or [B][..], or null: zero
     size_t goal_stride;
     double *Jk, *lx, *Qout;   // [B][nsteps], [B][nsteps][2nr], [B][nsteps][2nr * 2nr]; null: not wanted
-    double* x;                // [B][nterms][3] the points (rmx_rollout_points), or null
-    const double* gx;         // [B][nterms][3] their cotangents (with gq)
-    double* gq;               // [B][nsteps][nr], or null
-};
-
-// rmx_rollout_frames / rmx_rollout_cost_frames (rmx_frames.h): k_rollout_cost's launch shape, frame terms in the place of point terms
-struct FrameDevTerm {
-    rmx_track::DevTerm t;     // the point, its node, wpos and the term's position in the caller's array (what cost_term reads)
-    double wvel, wrot;
-};
-static_assert(sizeof(FrameDevTerm) == 56, "FrameDevTerm: a DevTerm and two doubles, no padding");
-struct FrameArgs {
-    int nsteps, nterms;
-    const double *q, *qd;     // [B][nsteps][nr] the record (qd may be null where no velocity is asked for)
-    const FrameDevTerm* trk;  // [nterms] the terms sorted by step, or null: no terms
-    const int* trk_begin;     // [nsteps + 1], as CostArgs
-    const double *xt, *vt, *Rt;   // targets [nterms][3], [nterms][3], [nterms][9] (column-major) or [B][..]; null: no term weighs it
-    size_t t_stride;          // TERMS from one rollout's target tables to the next (0: one table for the batch)
-    const double* Qin;        // as CostArgs
-    size_t q_stride;
-    const double* xgoal;
-    size_t goal_stride;
-    double *Jk, *lx, *Qout;   // as CostArgs
-    double *x, *v, *R;        // [B][nterms][3], [B][nterms][3], [B][nterms][9] (rmx_rollout_frames), or null
-    const double *gx, *gv, *gR;   // their cotangents, or null: zero
-    double *gq, *gqd;         // [B][nsteps][nr], or null
+    double *x, *v, *R;        // [B][nterms][3], [B][nterms][3], [B][nterms][9] (rmx_rollout_points: x; rmx_rollout_frames), or null
+    const double *gx, *gv, *gR;   // their cotangents, or null: zero (gv, gR: frames)
+    double *gq, *gqd;         // [B][nsteps][nr], or null (gqd: frames)
 };
 
 struct rmx_model {
@@ -278,8 +263,7 @@ struct rmx_batch {
     void RMX_CAT(launch_vjp_feedback_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
-    void RMX_CAT(launch_cost_, NPV)(const rmx_model* m, const rmx_batch* b, const CostArgs& a); \
-    void RMX_CAT(launch_frames_, NPV)(const rmx_model* m, const rmx_batch* b, const FrameArgs& a); \
+    void RMX_CAT(launch_cost_, NPV)(const rmx_model* m, const rmx_batch* b, const TaskArgs& a, bool frames); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \
     void RMX_CAT(launch_param_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a); \
     void RMX_CAT(launch_phase_, NPV)(const rmx_model* m, const rmx_batch* b, int reps, double h, unsigned long long* d); \

@@ -234,7 +234,7 @@ inline const char* label_rollout_feedback_box(const int integ) {      // ... aft
 // holds nothing in LDS.  Kinematics alone decides: spherical joints (their Euler charts are not a function of q alone) and trees of
 // more than 64 nodes are refused; ground contact and point forces do not enter kinematics and are taken.
 enum class CostKernel {
-    Wave,                // part_plain: k_rollout_cost<NP>
+    Wave,                // part_plain: k_rollout_cost<NP, FRAMES>
     RefusedSpherical,
     RefusedNodes,        // more than 64 nodes
     RefusedGrid,         // batch * nsteps wavefronts exceed the grid
@@ -258,6 +258,7 @@ inline CostPlan select_rollout_cost(const StepTraits& t, const int B, const int 
     return p;
 }
 inline const char* label_rollout_cost() { return "k_rollout_cost"; }      // what rmx_last_step_kernel reports after the two entries
-inline const char* label_rollout_frames() { return "k_rollout_frames"; }  // ... after rmx_rollout_frames / rmx_rollout_cost_frames: the same plan
+inline const char* label_rollout_frames() { return "k_rollout_frames"; }  // ... after rmx_rollout_frames / rmx_rollout_cost_frames: the same plan,
+                                                                          // the FRAMES instantiation under the label it always had
 
 }      // namespace rmx_select

@@ -547,9 +547,9 @@ def _check_frame_targets(sim, terms, vtarget, Rtarget):
             raise ValueError("cost_model: %s must have shape %r or %r, got %r" % (name, (T,) + tail, (B, T) + tail, tuple(t.shape)))
 
 
-def _cost_model_frames(sim, dev, N, qc, qdc, Qc, xgc, Q_per, goal_per, terms, xtarget, vtarget, Rtarget, outs):
+def _cost_model_frames(sim, N, qc, qdc, xtarget, vtarget, Rtarget, common):
     """cost_model's call where a term weighs velocity or orientation: the three target tables share one per-rollout flag, so a shared
-    table beside a per-rollout one is repeated; Rtarget [..][3][3] goes column-major."""
+    table beside a per-rollout one is repeated; Rtarget [..][3][3] goes column-major.  common: the arguments both entries take."""
     B = sim.B
     per = any(t is not None and t.dim() == len(tail) + 2 for t, tail in ((xtarget, (3,)), (vtarget, (3,)), (Rtarget, (3, 3))))
 
@@ -563,9 +563,8 @@ def _cost_model_frames(sim, dev, N, qc, qdc, Qc, xgc, Q_per, goal_per, terms, xt
 
     xt, vt, Rt = table(xtarget, (3,)), table(vtarget, (3,)), table(Rtarget, (3, 3))
     ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
-    sim.rollout_cost_frames_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q_per, goal_per_rollout=goal_per,
-                                   terms=terms, xtarget_ptr=ptr(xt), vtarget_ptr=ptr(vt), Rtarget_ptr=ptr(Rt), target_per_rollout=per,
-                                   Jk_ptr=ptr(outs[0]), lx_ptr=ptr(outs[1]), Qout_ptr=ptr(outs[2]))
+    sim.rollout_cost_frames_device(N, qc.data_ptr(), qdc.data_ptr(), xtarget_ptr=ptr(xt), vtarget_ptr=ptr(vt), Rtarget_ptr=ptr(Rt),
+                                   target_per_rollout=per, **common)
 
 
 def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None, want=("J", "lx", "Q"), vtarget=None, Rtarget=None):
@@ -615,13 +614,12 @@ def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None,
     Qo = torch.empty((B, N, 2 * nr, 2 * nr), dtype=torch.float64, device=dev) if "Q" in want else None
     torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
     ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
+    common = dict(Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q is not None and Q.dim() == 4, goal_per_rollout=xgoal is not None and xgoal.dim() == 3,
+                  terms=terms, Jk_ptr=ptr(Jk), lx_ptr=ptr(lx), Qout_ptr=ptr(Qo))
     if _frame_weighted(terms):
-        _cost_model_frames(sim, dev, N, qc, qdc, Qc, xgc, Q is not None and Q.dim() == 4, xgoal is not None and xgoal.dim() == 3, terms,
-                           xtarget, vtarget, Rtarget, (Jk, lx, Qo))
+        _cost_model_frames(sim, N, qc, qdc, xtarget, vtarget, Rtarget, common)
     else:
-        sim.rollout_cost_device(N, qc.data_ptr(), qdc.data_ptr(), Q_ptr=ptr(Qc), xgoal_ptr=ptr(xgc), Q_per_rollout=Q is not None and Q.dim() == 4,
-                                goal_per_rollout=xgoal is not None and xgoal.dim() == 3, terms=terms, xtarget_ptr=ptr(xtc),
-                                target_per_rollout=xtc is not None and xtc.dim() == 3, Jk_ptr=ptr(Jk), lx_ptr=ptr(lx), Qout_ptr=ptr(Qo))
+        sim.rollout_cost_device(N, qc.data_ptr(), qdc.data_ptr(), xtarget_ptr=ptr(xtc), target_per_rollout=xtc is not None and xtc.dim() == 3, **common)
     out = {}
     if Jk is not None:
         out["J"] = Jk.sum(1)

@@ -1,5 +1,5 @@
 """rmx_rollout_points / rmx_rollout_cost: point kinematics along a state record and the cost model of the device iLQR
-(redmax_amd/csrc/rmx_cost.h), on the GPU.
+(redmax_amd/csrc/rmx_cost.h, the point instantiation), on the GPU.
 
 The checks, in the order of the sections below:
   1. against tests/proto_point_cost.py at every padded size: with ext the longdouble proto and ref the float64 proto on IDENTICAL

@@ -1,5 +1,5 @@
-"""Kernel time of the cost model with frame targets (k_rollout_frames) next to the point-target kernel (k_rollout_cost) on the same
-record: the figures of profiles/frame_cost.txt.
+"""Kernel time of the cost model with frame targets (label k_rollout_frames) next to the point-target instantiation (k_rollout_cost) on
+the same record: the figures of profiles/frame_cost.txt.
 
     python tools/measure_frame_cost.py [--links 32] [--batch 1024] [--steps 100] [--repeats 9] [--out FILE]
 
