@@ -867,6 +867,77 @@ int rmx_rollout_cost_frames(rmx_batch* b, int nsteps, const double* q, const dou
 int rmx_rollout_cost_frames_device(rmx_batch* b, int nsteps, const double* d_q, const double* d_qdot, const rmx_state_cost* sc,
                                    const rmx_frame_terms* ft, const rmx_cost_model* out);
 
+/* The backtracking line search of the device iLQR in ONE launch: every rollout tries its step lengths in turn, inside the wavefront
+ * that integrates it, and stops at the first that lowers its own cost; the record, uapp and the tape it leaves belong to the
+ * trajectory it kept.  An iLQR iteration is then three calls: rmx_rollout_cost[_frames] (the model), rmx_rollout_lqr[_box] (the
+ * gains), rmx_rollout_search.  Added WITHOUT a change of RMX_VERSION (it stays 111): probe for the symbols.  No existing struct grows
+ * and no existing entry changes.  BDF1 only: that is the tape rmx_rollout_lqr reads.
+ *
+ * fb->uff is the NOMINAL torque ubar; fb->K, fb->xref and fb->per_rollout keep the meaning they have in rmx_rollout_tape_feedback.
+ * Per rollout, from the state the batch holds at the call (q0, qdot0):
+ *     for a in alphas, in order:
+ *         uff_k = ubar_k + a * kff_k        the product rounded, then the sum - two roundings, NOT a fused multiply-add: the bits of
+ *                                           the float64 expression a caller forms
+ *         run the closed loop of rmx_rollout_tape_feedback_box (integrator 1) under uff, K, xref, box from (q0, qdot0)
+ *         J = the cost of that pass (below)
+ *         if no solve of the pass failed (status bits 1, 2, 4 clear) and J < Jbar (false for a NaN):   alpha = a; stop
+ *     if nothing was accepted, or nalpha == 0:
+ *         one pass with uff = ubar (kff is not read: a non-finite kff cannot reach it); alpha = 0; J = its cost
+ * The record (qtraj, qdtraj), uapp, the state the batch is left in, `out` and the tape all belong to the LAST pass the rollout ran.
+ * The tape is the open-loop BDF1 tape under uapp: rmx_rollout_vjp, _linearize, _jvp, _vjp_params, _lqr and _lqr_box read it
+ * unchanged.  Trial passes and the nominal pass run the same instructions - alpha is a value, not a code path -, hence, exactly:
+ * a call with nalpha = 0 and uff = ubar + a*kff formed by the caller in float64 returns the bits of a call that accepts a; and the
+ * nominal pass of a call reproduces the trajectory a previous call of this entry left, with its J, bit for bit, when xref is that
+ * trajectory (row 0: the initial state) and uff its uapp.  A rollout's results do not depend on its place in the batch, the batch
+ * size, shared against per-rollout tables, or which optional outputs are NULL.
+ *
+ * The cost, evaluated inside the launch on the states the pass has just produced - x_k = (q_k, qdot_k) the state after step k, u_k
+ * the APPLIED torque (behind the clamp), dx_k = x_k - xgoal_k:
+ *     J = sum_{k=1..N} [ 1/2 dx_k' Q_k dx_k  +  1/2 u_k' R u_k  +  sum_{t: step_t = k} wpos/2 |r|^2 + wvel/2 |rv|^2 + wrot/4 |R - Rtarget|_F^2 ]
+ * with the definitions of rmx_rollout_cost_frames (a point term is a frame term with wvel = wrot = 0).  One fixed order: steps
+ * ascending; within a step the state part, then the control part, then the terms in the caller's order.  Neither the gradient nor
+ * the Gauss-Newton table is formed here: rmx_rollout_cost* stays the call that makes them once per iteration.
+ * out->trials: passes run (trial passes + the nominal pass if it ran).  out->status and stats->status: the Newton status of the
+ * pass the rollout ended on; stats->newton_iters: its iterations.
+ *
+ * Refusals (RMX_E_INVALID), which leave an existing tape and the batch alone: everything rmx_rollout_tape_feedback_box refuses, in
+ * its words (box itself may be NULL here: no limits); everything rmx_rollout_cost_frames refuses about terms, weights, target tables
+ * and per-rollout flags, in its words; a null b, fb, fb->uff, s, cost, out or out->J ("null argument"); all of sc, ft, R null;
+ * nalpha outside 0 .. RMX_SEARCH_MAX_ALPHAS; an alpha that is not finite or not > 0 (the message names its index); a null kff or
+ * Jbar with nalpha > 0; nr > 32 or a tree of more than 32 nodes, in rmx_rollout_lqr's words - the search exists where the sweep that
+ * feeds it exists.  The host form stages through one allocation of its own, made first and freed before it returns.  The _device
+ * form: every array a DEVICE pointer (the structs, `alphas` and `terms` are host objects); it returns when the kernel has finished.
+ * Against rmx_rollout_tape_feedback_box on the same inputs a nalpha = 0 pass agrees to rounding, not bit for bit (the kernel is a
+ * text of its own).  Measured on an MI355X over 5 steps of 4 rollouts under LQR gains, the largest |difference| over q, qdot and
+ * uapp: 3.6e-15 (3-link chain), 0 - the same bits - (5), 4.2e-14 (11), 6.8e-14 (32); with limits that bind 2.6e-15, 2.7e-15,
+ * 6.8e-15, 2.9e-13 (tests/test_gpu_rollout_search.py).
+ * Out of scope: BDF2 tapes; nr > 32; gradients through the search; a regulariser schedule; per-step or per-rollout limits; several
+ * alphas of one rollout in parallel wavefronts. */
+#define RMX_SEARCH_MAX_ALPHAS 16
+typedef struct rmx_search_cost {       /* not all three NULL */
+    const rmx_state_cost*  sc;         /* joint-space quadratic on x_k = (q_k, qdot_k); may be NULL        */
+    const rmx_frame_terms* ft;         /* frame terms (a point term has wvel = wrot = 0); may be NULL      */
+    const double*          R;          /* [nr*nr] column-major, symmetric; NULL: no control cost           */
+} rmx_search_cost;
+typedef struct rmx_search {
+    const double* kff;      /* [batch][nsteps][nr]; may be NULL when nalpha == 0                            */
+    const double* alphas;   /* HOST [nalpha], each finite and > 0, tried in this order                      */
+    int           nalpha;   /* 0 .. RMX_SEARCH_MAX_ALPHAS; 0: the nominal pass alone                        */
+    const double* Jbar;     /* [batch] the cost a trial has to beat; may be NULL when nalpha == 0           */
+} rmx_search;
+typedef struct rmx_search_out {         /* J required, the others may be NULL */
+    double* J;        /* [batch] cost of the trajectory the rollout ended on                                */
+    double* alpha;    /* [batch] the accepted step length, 0: none                                          */
+    int*    trials;   /* [batch] passes run (trial passes + the nominal pass if it ran)                     */
+    int*    status;   /* [batch] Newton status of the pass the rollout ended on (rmx_stats' bits)           */
+} rmx_search_out;
+int rmx_rollout_search(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const rmx_feedback* fb,
+                       const rmx_box* box /* may be NULL */, const rmx_search* s, const rmx_search_cost* cost,
+                       double* qtraj, double* qdtraj, double* uapp, const rmx_search_out* out, rmx_stats* stats);
+int rmx_rollout_search_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const rmx_feedback* fb,
+                              const rmx_box* box, const rmx_search* s, const rmx_search_cost* cost, double* d_qtraj,
+                              double* d_qdtraj, double* d_uapp, const rmx_search_out* out, rmx_stats* stats);
+
 /* Model-parameter gradients from the taped rollout (system identification, calibration): dL/dtheta for joint stiffness, damping and
  * rest position, body inertia and mass, and gravity, for the same cotangents rmx_rollout_vjp takes.  Added WITHOUT a change of
  * RMX_VERSION (it stays 111): probe for the symbols.

@@ -361,5 +361,22 @@ classdef HipSim < handle
 			end
 			[Jk, lx, Q] = redmax_hip_mex('rollout_cost_frames', this.h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget);
 		end
+
+		function [qtraj, qdtraj, uapp, J, alpha, stats] = rolloutSearch(this, hstep, nsteps, pscale, ubar, kff, K, xref, alphas, Jbar, cost, ulo, uhi)
+			% The backtracking line search of iLQR in ONE launch (rmx_rollout_search, BDF1): from the current state every rollout
+			% runs the closed loop of rolloutFeedback (K, xref as there) under uff = ubar + a*kff for a in alphas, in order, and
+			% keeps the first pass without a failed solve whose cost is below its Jbar; a rollout no alpha helps - and every
+			% rollout with alphas = [], where kff and Jbar may be [] - runs the nominal pass uff = ubar.  cost is a struct with the
+			% fields Q, xgoal, terms, xtarget, vtarget, Rtarget (as rolloutCostFrames takes them) and R (nr x nr), each optional:
+			% J = sum_k 1/2 dx'Q dx + 1/2 u'R u + the terms, on the states each pass produces and its APPLIED torques.  ulo, uhi
+			% (nr, [] for no bound on that side): the torque limits of rolloutFeedbackBox.  J, alpha: 1 x batch (alpha 0: none
+			% accepted); qtraj, qdtraj, uapp, stats and the tape belong to the pass each rollout kept.  One iLQR iteration is
+			% rolloutCost[Frames], rolloutLqr[Box], rolloutSearch.
+			if nargin < 13
+				[qtraj, qdtraj, uapp, J, alpha, stats] = redmax_hip_mex('rollout_search', this.h, hstep, nsteps, pscale, ubar, kff, K, xref, alphas, Jbar, cost);
+			else
+				[qtraj, qdtraj, uapp, J, alpha, stats] = redmax_hip_mex('rollout_search', this.h, hstep, nsteps, pscale, ubar, kff, K, xref, alphas, Jbar, cost, ulo, uhi);
+			end
+		end
 	end
 end

@@ -109,6 +109,12 @@
  *                  q, qdot (nr x nsteps x B), and with cotangents gx, gv (3 x nterms x B), gR (3 x 3 x nterms x B), [] for zero, the
  *                  pull-back gq = sum_t Jp'*gx + G'*gv + Jw'*a(gR*R'), gqd = sum_t Jp'*gv (nr x nsteps x B).  terms: struct array
  *                  body (1-based), xlocal, step (weights are not read).  Needs no tape.
+ *   [qtraj,qdtraj,uapp,J,alpha,st] = redmax_hip_mex('rollout_search', h, hstep, nsteps, pscale, ubar, kff, K, xref, alphas, Jbar, cost [, ulo, uhi])
+ *                  rmx_rollout_search: the backtracking line search of iLQR in one launch (BDF1) - every rollout runs the closed loop
+ *                  of 'rollout_feedback' under ubar + a*kff for a in alphas, in order, keeps the first pass whose cost is below its
+ *                  Jbar, else its nominal (uff = ubar).  alphas [] (then kff, Jbar may be []): the nominal pass alone.  cost: a struct
+ *                  with the fields Q, xgoal, terms, xtarget, vtarget, Rtarget as 'rollout_cost_frames' takes them and R (nr x nr), each
+ *                  optional.  J, alpha: 1 x B (alpha 0: none accepted); the record, uapp, st and the tape belong to the pass kept.
  *   [Jk,lx,Q] = redmax_hip_mex('rollout_cost_frames', h, nsteps, q, qdot, Qin, xgoal, terms, xtarget, vtarget, Rtarget)
  *                  rmx_rollout_cost_frames: 'rollout_cost' with frame terms - struct array body, xlocal, step and the weights wpos,
  *                  wvel, wrot >= 0 (a missing one is 0) - and the targets xtarget, vtarget (3 x nterms [x B]) and Rtarget (3 x 3 x
@@ -1151,6 +1157,122 @@ static void cmd_rollout_cost(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
     give(nlhs, plhs, res, 3);
 }
 
+/* a member of the `cost` struct of 'rollout_search': absent or [] (NULL), or a real double array of `want` (or `alt`) elements */
+static const double* search_cost_field(const mxArray* c, const char* k, size_t want, size_t alt, int* per, const char* shape) {
+    const mxArray* f = mxGetField(c, 0, k);
+    if (!f || mxIsEmpty(f)) return NULL;
+    const double* p = cost_arg(f, want, alt, 0, "rollout_search", k, shape);
+    if (per) *per = alt && alt != want && mxGetNumberOfElements(f) == alt;
+    return p;
+}
+
+/* 'rollout_search': rmx_rollout_search - the line search of iLQR in one launch.  cost: a struct with the fields Q, xgoal, R, terms,
+ * xtarget, vtarget, Rtarget, each optional ([] or absent: that part is not there), shaped as 'rollout_cost_frames' takes them */
+static void cmd_rollout_search(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 12 || nrhs == 13)
+        die("usage: [qtraj,qdtraj,uapp,J,alpha,stats] = redmax_hip_mex('rollout_search', h, hstep, nsteps, pscale, ubar, kff, K, xref, alphas, "
+            "Jbar, cost [, ulo, uhi])");
+    rmx_opts o = tape_opts(mxGetScalar(prhs[2]));
+    const int nsteps = (int)mxGetScalar(prhs[3]);
+    if (nsteps < 1) die("rollout_search: nsteps must be at least 1");
+    const double pscale = mxGetScalar(prhs[4]);
+    const size_t nr = (size_t)h->nr, N = (size_t)nsteps, B = (size_t)h->B, per = nr * N;
+    const double* ubar = traj_arg(prhs[5], h, nsteps, "ubar");
+    const size_t nalpha = mxGetNumberOfElements(prhs[9]);
+    if (nalpha && (!mxIsDouble(prhs[9]) || mxIsComplex(prhs[9]))) die("rollout_search: alphas must be a real double vector");
+    if (nalpha > RMX_SEARCH_MAX_ALPHAS) die("rollout_search: at most 16 alphas");
+    const double* kff = nalpha ? traj_arg(prhs[6], h, nsteps, "kff") : NULL;
+    const double* Jbar = nalpha ? cost_arg(prhs[10], B, 0, 0, "rollout_search", "Jbar", "1 x batch") : NULL;
+    int per_rollout = -1;
+    const double* K = feedback_arg(prhs[7], h, 2 * nr * nr, nsteps, &per_rollout, "K");
+    const double* xref = feedback_arg(prhs[8], h, 2 * nr, nsteps, &per_rollout, "xref");
+    if (per_rollout < 0) per_rollout = 0;
+    const mxArray* c = prhs[11];
+    if (!mxIsStruct(c) || mxGetNumberOfElements(c) != 1) die("rollout_search: cost must be a struct with the fields Q, xgoal, R, terms, xtarget, vtarget, Rtarget");
+    const size_t perq = 4 * nr * nr * N, perg = 2 * nr * N;
+    int Q_per = 0, g_per = 0;
+    const double* Qin = search_cost_field(c, "Q", perq, perq * B, &Q_per, "2nr x 2nr x nsteps or 2nr x 2nr x nsteps x batch");
+    const double* xg = search_cost_field(c, "xgoal", perg, perg * B, &g_per, "2nr x nsteps or 2nr x nsteps x batch");
+    const double* R = search_cost_field(c, "R", nr * nr, 0, NULL, "nr x nr");
+    const mxArray* ta = mxGetField(c, 0, "terms");
+    size_t nterms = 0;
+    rmx_frame_term* terms = (ta && !mxIsEmpty(ta)) ? frame_terms(ta, "rollout_search", &nterms) : NULL;
+    const size_t width[3] = {3 * nterms, 3 * nterms, 9 * nterms};
+    const char* const tname[3] = {"xtarget", "vtarget", "Rtarget"};
+    const double* tab[3] = {NULL, NULL, NULL};
+    int t_per = -1;
+    for (int k = 0; k < 3 && terms; ++k) {
+        int p = 0;
+        tab[k] = search_cost_field(c, tname[k], width[k], width[k] * B, &p, "3 (x 3) x nterms or 3 (x 3) x nterms x batch");
+        if (!tab[k] || B == 1) continue;
+        if (t_per >= 0 && p != t_per) {
+            mxFree(terms);
+            die("rollout_search: xtarget, vtarget and Rtarget must all be shared by the batch or all hold one table per rollout");
+        }
+        t_per = p;
+    }
+    if (t_per < 0) t_per = 0;
+    rmx_box lim = {NULL, NULL};
+    const int box = nrhs >= 14;
+    if (box) {
+        lim.ulo = bound_arg(prhs[12], h, "rollout_search", "ulo");
+        lim.uhi = bound_arg(prhs[13], h, "rollout_search", "uhi");
+    }
+    const size_t dims[3] = {nr, N, B};
+    mxArray* out[6];
+    for (int i = 0; i < 3; ++i) out[i] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    out[3] = mxCreateDoubleMatrix(1, B, mxREAL);
+    out[4] = mxCreateDoubleMatrix(1, B, mxREAL);
+    out[5] = new_i32(B, 2);
+    rmx_state_cost sc;
+    rmx_frame_terms ft;
+    memset(&sc, 0, sizeof sc);
+    memset(&ft, 0, sizeof ft);
+    sc.Q_per_rollout = Q_per;
+    sc.goal_per_rollout = g_per;
+    ft.nterms = (int)nterms;
+    ft.terms = terms;
+    ft.per_rollout = t_per;
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard, as 'rollout_feedback' */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_stats st_s = shard_stats(out[5], h, f);
+        rmx_feedback fb;
+        fb.uff = ubar + f * per;
+        fb.K = table_at(K, per_rollout, f, per * 2 * nr);
+        fb.xref = table_at(xref, per_rollout, f, per * 2);
+        fb.per_rollout = per_rollout;
+        sc.Q = table_at(Qin, Q_per, f, perq);
+        sc.xgoal = table_at(xg, g_per, f, perg);
+        ft.xtarget = table_at(tab[0], t_per, f, width[0]);
+        ft.vtarget = table_at(tab[1], t_per, f, width[1]);
+        ft.Rtarget = table_at(tab[2], t_per, f, width[2]);
+        rmx_search_cost sco;
+        sco.sc = (Qin || xg) ? &sc : NULL;
+        sco.ft = terms ? &ft : NULL;
+        sco.R = R;
+        rmx_search sr;
+        sr.kff = kff ? kff + f * per : NULL;
+        sr.alphas = nalpha ? mxGetPr(prhs[9]) : NULL;
+        sr.nalpha = (int)nalpha;
+        sr.Jbar = Jbar ? Jbar + f : NULL;
+        rmx_search_out so;
+        so.J = mxGetPr(out[3]) + f;
+        so.alpha = mxGetPr(out[4]) + f;
+        so.trials = NULL;
+        so.status = NULL;
+        if (rmx_rollout_search(b, &o, nsteps, pscale, &fb, box ? &lim : NULL, &sr, &sco, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * per,
+                               mxGetPr(out[2]) + f * per, &so, &st_s)) {
+            if (terms) mxFree(terms);
+            die_rmx("rmx_rollout_search");
+        }
+    }
+    if (terms) mxFree(terms);
+    h->tape_integ = 1;
+    give(nlhs, plhs, out, 6);
+}
+
 static void cmd_rollout_frames(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
     const char* who = "rollout_frames";
@@ -1216,7 +1338,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
                                              "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
-                                             "rollout_points", "rollout_cost", "rollout_frames", "rollout_cost_frames", NULL};
+                                             "rollout_points", "rollout_cost", "rollout_frames", "rollout_cost_frames", "rollout_search", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
             mexErrMsgIdAndTxt("redmax:hip", "'%s' while a 'step_async' of this handle is in flight: 'sync' first", cmd);
@@ -1347,6 +1469,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_cost(nlhs, plhs, nrhs, prhs, 0);
     } else if (!strcmp(cmd, "rollout_frames")) {
         cmd_rollout_frames(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_search")) {
+        cmd_rollout_search(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_cost_frames")) {
         cmd_rollout_cost(nlhs, plhs, nrhs, prhs, 1);
     } else {

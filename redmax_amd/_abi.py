@@ -35,6 +35,7 @@ SYMBOLS = (
     "rmx_rollout_tape_feedback_box", "rmx_rollout_tape_feedback_box_device", "rmx_rollout_lqr_box", "rmx_rollout_lqr_box_device",
     "rmx_rollout_points", "rmx_rollout_points_device", "rmx_rollout_cost", "rmx_rollout_cost_device",
     "rmx_rollout_frames", "rmx_rollout_frames_device", "rmx_rollout_cost_frames", "rmx_rollout_cost_frames_device",
+    "rmx_rollout_search", "rmx_rollout_search_device",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -137,6 +138,21 @@ class FrameTerms(C.Structure):      # rmx_frame_terms: terms is a host array in 
                 ("per_rollout", C.c_int)]
 
 
+SEARCH_MAX_ALPHAS = 16      # RMX_SEARCH_MAX_ALPHAS
+
+
+class SearchCost(C.Structure):      # rmx_search_cost: sc and ft host structs; R a host pointer in the host form, a device pointer in the _device form
+    _fields_ = [("sc", C.POINTER(StateCost)), ("ft", C.POINTER(FrameTerms)), ("R", C.c_void_p)]
+
+
+class Search(C.Structure):      # rmx_search: alphas is a host array in both forms; kff and Jbar device pointers in the _device form
+    _fields_ = [("kff", C.c_void_p), ("alphas", _dp), ("nalpha", C.c_int), ("Jbar", C.c_void_p)]
+
+
+class SearchOut(C.Structure):      # rmx_search_out
+    _fields_ = [("J", C.c_void_p), ("alpha", C.c_void_p), ("trials", C.c_void_p), ("status", C.c_void_p)]
+
+
 FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
 PARAM_NAMES = ("stiffness", "damping", "qrest", "inertia", "grav")      # the members of rmx_param_grads, in their order
 
@@ -229,6 +245,9 @@ def lib():
     L.rmx_rollout_frames_device.argtypes = L.rmx_rollout_frames.argtypes
     L.rmx_rollout_cost_frames.argtypes = [vp, C.c_int, vp, vp, C.POINTER(StateCost), C.POINTER(FrameTerms), C.POINTER(CostModel)]
     L.rmx_rollout_cost_frames_device.argtypes = L.rmx_rollout_cost_frames.argtypes
+    L.rmx_rollout_search.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_double, C.POINTER(Feedback), C.POINTER(Box), C.POINTER(Search),
+                                     C.POINTER(SearchCost), vp, vp, vp, C.POINTER(SearchOut), C.POINTER(Stats)]
+    L.rmx_rollout_search_device.argtypes = L.rmx_rollout_search.argtypes
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]

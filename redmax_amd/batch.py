@@ -935,6 +935,103 @@ class BatchSim:
         self._cost_call_device("rmx_rollout_cost_frames_device", nsteps, q_ptr, qdot_ptr, Q_ptr, xgoal_ptr, Q_per_rollout, goal_per_rollout, ft,
                                Jk_ptr, lx_ptr, Qout_ptr)
 
+    @staticmethod
+    def _search_alphas(who, alphas):
+        """The trial step lengths of a search as a host array (kept by the caller until the call returns) and their count."""
+        al = np.ascontiguousarray(np.asarray(() if alphas is None else alphas, dtype=np.float64).reshape(-1))
+        if al.size > _abi.SEARCH_MAX_ALPHAS:
+            raise ValueError("%s: at most %d alphas, got %d" % (who, _abi.SEARCH_MAX_ALPHAS, al.size))
+        return al, int(al.size)
+
+    def rollout_search(self, nsteps, h, ubar, kff=None, K=None, xref=None, alphas=(), Jbar=None, Q=None, xgoal=None, R=None, terms=None,
+                       xtarget=None, vtarget=None, Rtarget=None, ulim=None, pscale=1.0, stats=False, want=("alpha", "trials", "status")):
+        """rmx_rollout_search: the backtracking line search of iLQR in one launch, BDF1.  Every rollout runs the closed loop of
+        rollout_feedback (K, xref, ulim as there) from the current state under uff = ubar + a*kff for a in `alphas`, in order, and
+        stops at the first pass without a failed solve whose cost is below Jbar[b]; with none (or no alphas) it runs the nominal
+        pass, uff = ubar.  The cost is that of rollout_cost_frames (Q, xgoal, terms and their targets; each may be None) plus
+        1/2 u'R u on the applied torques (R [nr][nr] symmetric, or None), summed over the steps inside the launch.  Returns
+        (qtraj, qdtraj, uapp, out): the record and applied torques of the pass each rollout ended on, and a dict with "J" [B] and the
+        names in `want` - "alpha" [B] (0: none accepted), "trials" [B] int32 (passes run), "status" [B] int32 (Newton status of the
+        last pass) - and, with stats=True, "info".  The tape it leaves is the open-loop tape under uapp.  Not differentiable."""
+        who = "rollout_search"
+        nsteps = int(nsteps)
+        B, nr = self.B, self.nr
+        want = _names(who, "want", want, ("alpha", "trials", "status"), True)
+        ubar = self._controls(who, "ubar", ubar, nsteps)
+        al, nalpha = self._search_alphas(who, alphas)
+        if nalpha:
+            if kff is None or Jbar is None:
+                raise ValueError("%s: alphas need kff and Jbar" % who)
+            kff = _f64(who, "kff", kff, (B, nsteps, nr))
+            Jbar = _f64(who, "Jbar", Jbar, (B,))
+        else:
+            kff = Jbar = None
+        K, xref, per = self._feedback_tables(nsteps, K, xref, who)
+        fb = _abi.Feedback(_addr(ubar), _addr(K), _addr(xref), per)
+        sc = None
+        if Q is not None or xgoal is not None:
+            sc = _abi.StateCost(None, None, 0, 0)
+            if Q is not None:      # (symmetric: row-major memory is the column-major table)
+                Q, sc.Q_per_rollout = _table(who, "Q", Q, (nsteps, 2 * nr, 2 * nr), B)
+                sc.Q = Q.ctypes.data
+            if xgoal is not None:
+                xgoal, sc.goal_per_rollout = _table(who, "xgoal", xgoal, (nsteps, 2 * nr), B)
+                sc.xgoal = xgoal.ctypes.data
+        ft, keep = None, None
+        if terms is not None:
+            arr, nterms = self._frame_terms(terms, who, self.opts.h if h is None else h)
+            tabs, tper = self._frame_targets(who, nterms, xtarget, vtarget, Rtarget)
+            ft = _abi.FrameTerms(nterms, arr, _addr(tabs[0]), _addr(tabs[1]), _addr(tabs[2]), tper)
+            keep = (arr, tabs)
+        if R is not None:
+            R = _f64(who, "R", R, (nr, nr))
+        cost = _abi.SearchCost(None if sc is None else C.pointer(sc), None if ft is None else C.pointer(ft), _addr(R))
+        srch = _abi.Search(_addr(kff), _abi.dptr(al) if nalpha else None, nalpha, _addr(Jbar))
+        qtraj, qdtraj, uapp = (np.empty((B, nsteps, nr)) for _ in range(3))
+        out = {"J": np.empty(B)}
+        for w in want:
+            out[w] = np.empty(B) if w == "alpha" else np.zeros(B, dtype=np.int32)
+        so = _abi.SearchOut(_addr(out["J"]), _addr(out.get("alpha")), _addr(out.get("trials")), _addr(out.get("status")))
+        box, lim = self._ulim(ulim, who) if ulim is not None else (None, None)
+        opts, info, st = self._begin_tape(h, stats, 1)
+        _abi.check(self._L.rmx_rollout_search(self._batch, C.byref(opts), nsteps, float(pscale), C.byref(fb), None if box is None else C.byref(box),
+                                              C.byref(srch), C.byref(cost), qtraj.ctypes.data, qdtraj.ctypes.data, uapp.ctypes.data, C.byref(so), st),
+                   "rmx_rollout_search")
+        del keep, lim
+        if stats:
+            info["ms"] = self._L.rmx_last_step_ms(self._batch)
+            out["info"] = info
+        return qtraj, qdtraj, uapp, out
+
+    def rollout_search_device(self, nsteps, h, ubar_ptr, kff_ptr, K_ptr, xref_ptr, alphas, Jbar_ptr, qtraj_ptr, qdtraj_ptr, uapp_ptr, J_ptr,
+                              alpha_ptr=None, trials_ptr=None, status_ptr=None, per_rollout=False, Q_ptr=None, xgoal_ptr=None,
+                              Q_per_rollout=False, goal_per_rollout=False, R_ptr=None, terms=None, xtarget_ptr=None, vtarget_ptr=None,
+                              Rtarget_ptr=None, target_per_rollout=False, ulim=None, pscale=1.0, stats=False):
+        """rollout_search with DEVICE pointers (integers): ubar, kff, qtraj, qdtraj, uapp [B][nsteps][nr]; K, xref as
+        rollout_feedback_device; Jbar, J, alpha [B] doubles; trials, status [B] int32; the cost's tables as rollout_cost_frames_device
+        (Rtarget COLUMN-MAJOR), R [nr*nr]; ulim=(ulo_ptr, uhi_ptr).  alphas and terms stay host objects.  0 / None: kff and Jbar with
+        no alphas, K (no feedback), xref (zero), qtraj and qdtraj together (no record), uapp, alpha, trials, status (not stored), any
+        part of the cost (not all of Q/xgoal, terms and R).  Returns info."""
+        who = "rollout_search_device"
+        al, nalpha = self._search_alphas(who, alphas)
+        fb = _abi.Feedback(ubar_ptr or None, K_ptr or None, xref_ptr or None, int(bool(per_rollout)))
+        sc = _abi.StateCost(Q_ptr or None, xgoal_ptr or None, int(bool(Q_per_rollout)), int(bool(goal_per_rollout)))
+        ft, arr = None, None
+        if terms is not None:
+            arr, nterms = self._frame_terms(terms, who, self.opts.h if h is None else h)
+            ft = _abi.FrameTerms(nterms, arr, xtarget_ptr or None, vtarget_ptr or None, Rtarget_ptr or None, int(bool(target_per_rollout)))
+        cost = _abi.SearchCost(C.pointer(sc) if (Q_ptr or xgoal_ptr) else None, None if ft is None else C.pointer(ft), R_ptr or None)
+        srch = _abi.Search(kff_ptr or None, _abi.dptr(al) if nalpha else None, nalpha, Jbar_ptr or None)
+        so = _abi.SearchOut(J_ptr or None, alpha_ptr or None, trials_ptr or None, status_ptr or None)
+        box = None if ulim is None else _abi.Box(ulim[0] or None, ulim[1] or None)
+        opts, info, st = self._begin_tape(h, stats, 1)
+        _abi.check(self._L.rmx_rollout_search_device(self._batch, C.byref(opts), int(nsteps), float(pscale), C.byref(fb),
+                                                     None if box is None else C.byref(box), C.byref(srch), C.byref(cost), _vp(qtraj_ptr),
+                                                     _vp(qdtraj_ptr), _vp(uapp_ptr), C.byref(so), st), "rmx_rollout_search_device")
+        del arr
+        info["ms"] = self._L.rmx_last_step_ms(self._batch)
+        return info
+
     def last_step_kernel(self):
         """Label of the step kernel the last step call launched (rmx_last_step_kernel): which size / batch / environment dependent
         variant the library chose."""

@@ -7,6 +7,7 @@
 #include "rmx_cost.h"
 #if RMX_NP <= 32
 #include "rmx_lqr.h"
+#include "rmx_search.h"
 #endif
 
 void RMX_CAT(launch_eval_, RMX_NP)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH) {
@@ -110,6 +111,11 @@ void RMX_CAT(launch_lqr_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const 
 void RMX_CAT(launch_lqr_box_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes) {
     const dim3 grid(b->B), block(LQR_THREADS);
     RMX_LAUNCH((k_rollout_lqr<RMX_NP, true>), grid, block, lds_bytes, b->stream, m->dm, a);
+}
+// rmx_rollout_search: one wavefront per rollout, every trial pass and the nominal pass in the one launch (select_rollout_search)
+void RMX_CAT(launch_search_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const SearchArgs& a, int threads) {
+    const dim3 grid(b->B), block(threads);      // (SearchPlan::block: one wavefront per rollout)
+    RMX_LAUNCH((k_rollout_search<RMX_NP>), grid, block, m->smem_bytes, b->stream, m->dm, o, a);
 }
 #endif
 

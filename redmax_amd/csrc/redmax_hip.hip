@@ -1652,12 +1652,28 @@ static int box_refusal(const rmx_batch* b, const rmx_box* box, const bool on_dev
     return RMX_OK;
 }
 
+// sr (rmx_rollout_search, with fb, BDF1): what rollout_search_impl has checked and planned.  The sweep is k_rollout_search (rmx_search.h)
+// in the place of the ADJ_FB kernel: the same closed loop, run once per trial step length and once more for the nominal where none
+// is accepted, with the cost formed inside the launch.  Direction, cost tables and outputs join the staging of the gain tables.
+struct SearchCall {
+    const rmx_search* s;
+    const rmx_search_cost* cost;
+    const rmx_search_out* out;
+    rmx_select::SearchPlan plan;
+    std::vector<FrameDevTerm> dterms;      // the cost's terms as the kernel reads them (plan_frame_terms), and their step offsets
+    std::vector<int> begin;
+};
+static hipError_t costws_reserve(rmx_batch* b, const size_t total);
+static hipError_t terms_to_device(rmx_batch* b, const std::vector<FrameDevTerm>& dterms, const std::vector<int>& begin, const size_t trk_bytes,
+                                  const FrameDevTerm*& trk, const int*& trk_begin);
+
 // fb (rmx_rollout_tape_feedback): u is fb->uff, the sweep is the ADJ_FB kernel and uapp (or null) takes the applied torques.  The host
 // form stages K, xref and uapp through a device allocation of its own, freed before the return; the tape's workspace is the same.
 // box (rmx_rollout_tape_feedback_box, with fb): the same kernel clamps the torque into the limits, staged with the gain tables.
 static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                              double* qdtraj, rmx_stats* stats, const bool on_device, const int integ = INTEG_BDF1,
-                             const rmx_feedback* fb = nullptr, double* uapp = nullptr, const rmx_box* box = nullptr) {
+                             const rmx_feedback* fb = nullptr, double* uapp = nullptr, const rmx_box* box = nullptr,
+                             const SearchCall* sr = nullptr) {
     if (!b || !u) return fail(RMX_E_INVALID, "rmx_rollout_tape: null argument");
     if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
     rmx_model* m = b->m;
@@ -1671,9 +1687,10 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
     if (rc) return rc;
     const rmx_tape::Layout t = tape_layout(b, nsteps, integ);
     if (3 * t.bytes_hist > ((size_t)200 << 30)) return fail(RMX_E_NOMEM, "adjoint history (H, M, D per step) would exceed 200 GiB");
-    if (box && (rc = box_refusal(b, box, on_device, "rmx_rollout_tape_feedback_box"))) return rc;
-    enum { F_K, F_X, F_UAPP, F_ULO, F_UHI };
+    if (box && (rc = box_refusal(b, box, on_device, sr ? "rmx_rollout_search" : "rmx_rollout_tape_feedback_box"))) return rc;
+    enum { F_K, F_X, F_UAPP, F_ULO, F_UHI, F_KFF, F_JBAR, F_XT, F_VT, F_RT, F_QIN, F_XG, F_R, F_J, F_AL, F_TR, F_ST };
     Staging fbst(on_device);
+    const size_t trk_bytes = sr ? rmx_tape::round256(sr->dterms.size() * sizeof(FrameDevTerm)) : 0;
     if (fb) {
         const size_t row = (fb->per_rollout ? (size_t)b->B : 1) * nsteps * 2 * m->nr * sizeof(double);
         fbst.add(row * m->nr, fb->K, nullptr);
@@ -1681,8 +1698,33 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         fbst.add(t.bytes_traj, nullptr, uapp);
         fbst.add(m->nr * sizeof(double), box ? box->ulo : nullptr, nullptr);
         fbst.add(m->nr * sizeof(double), box ? box->uhi : nullptr, nullptr);
+        if (sr) {
+            const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
+            const rmx_state_cost* sc = sr->cost->sc;
+            const rmx_frame_terms* ft = sr->cost->ft;
+            const size_t tabs = ft ? (ft->per_rollout ? B : 1) * (size_t)ft->nterms : 0;
+            const bool trial = sr->s->nalpha > 0;
+            fbst.add(t.bytes_traj, trial ? sr->s->kff : nullptr, nullptr);
+            fbst.add(B * dbl, trial ? sr->s->Jbar : nullptr, nullptr);
+            fbst.add(tabs * 3 * dbl, ft ? ft->xtarget : nullptr, nullptr);
+            fbst.add(tabs * 3 * dbl, ft ? ft->vtarget : nullptr, nullptr);
+            fbst.add(tabs * 9 * dbl, ft ? ft->Rtarget : nullptr, nullptr);
+            fbst.add((sc && sc->Q_per_rollout ? B : 1) * N * 4 * nr * nr * dbl, sc ? sc->Q : nullptr, nullptr);
+            fbst.add((sc && sc->goal_per_rollout ? B : 1) * N * 2 * nr * dbl, sc ? sc->xgoal : nullptr, nullptr);
+            fbst.add(nr * nr * dbl, sr->cost->R, nullptr);
+            fbst.add(B * dbl, nullptr, sr->out->J);
+            fbst.add(B * dbl, nullptr, sr->out->alpha);
+            fbst.add(B * sizeof(int), nullptr, sr->out->trials);
+            fbst.add(B * sizeof(int), nullptr, sr->out->status);
+        }
         if (fbst.plan.total > 0)      // (ahead of everything that ends the present tape)
-            if ((rc = fbst.allocate("rmx_rollout_tape_feedback", "the gain tables"))) return rc;
+            if ((rc = fbst.allocate(sr ? "rmx_rollout_search" : "rmx_rollout_tape_feedback",
+                                    sr ? "the staging of the gain tables, the direction, the cost tables and the outputs" : "the gain tables")))
+                return rc;
+        if (sr && !sr->dterms.empty() && costws_reserve(b, trk_bytes + sr->begin.size() * sizeof(int)) != hipSuccess) {
+            fbst.release(b, hipSuccess);
+            return fail(RMX_E_NOMEM, "rmx_rollout_search: no device memory for the term table");
+        }
     }
     b->tape_nsteps = 0;
     hipError_t e = adjws_reserve(b, t.total);
@@ -1716,7 +1758,37 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
         a.qdtraj = qtraj ? st.dev(S_QDT) : v.qdt;
         if (e == hipSuccess) e = hipMemcpyAsync(v.q0, b->q, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(v.qd0, b->qd, t.bytes_state, hipMemcpyDeviceToDevice, b->stream);
+        SearchArgs sa{};
+        if (sr) {      // (a is complete: the kernel reads the closed-loop sweep's arguments as they stand)
+            const rmx_state_cost* sc = sr->cost->sc;
+            const rmx_frame_terms* ft = sr->cost->ft;
+            const size_t N = (size_t)nsteps, nr = (size_t)m->nr;
+            sa.a = a;
+            sa.kff = fbst.dev(F_KFF); sa.Jbar = fbst.dev(F_JBAR);
+            sa.nalpha = sr->s->nalpha;
+            for (int i = 0; i < sa.nalpha; ++i) sa.alphas[i] = sr->s->alphas[i];
+            sa.c.nsteps = nsteps; sa.c.nterms = ft ? ft->nterms : 0;
+            sa.c.xt = fbst.dev(F_XT); sa.c.vt = fbst.dev(F_VT); sa.c.Rt = fbst.dev(F_RT);
+            sa.c.Qin = fbst.dev(F_QIN); sa.c.xgoal = fbst.dev(F_XG);
+            sa.c.t_stride = (ft && ft->per_rollout) ? (size_t)ft->nterms : 0;
+            sa.c.q_stride = (sc && sc->Q_per_rollout) ? N * 4 * nr * nr : 0;
+            sa.c.goal_stride = (sc && sc->goal_per_rollout) ? N * 2 * nr : 0;
+            sa.R = fbst.dev(F_R);
+            sa.J = fbst.dev(F_J); sa.alpha = fbst.dev(F_AL); sa.trials = (int*)fbst.at[F_TR]; sa.sstatus = (int*)fbst.at[F_ST];
+            if (!sr->dterms.empty() && e == hipSuccess) e = terms_to_device(b, sr->dterms, sr->begin, trk_bytes, sa.c.trk, sa.c.trk_begin);
+        }
         e = timed_launch(b, e, [&] {
+            if (sr) {
+                switch (sr->plan.np) {
+                    case 4: launch_search_4(m, b, o, sa, sr->plan.block); break;
+                    case 8: launch_search_8(m, b, o, sa, sr->plan.block); break;
+                    case 16: launch_search_16(m, b, o, sa, sr->plan.block); break;
+                    case 32: launch_search_32(m, b, o, sa, sr->plan.block); break;
+                    default: return hipErrorInvalidDeviceFunction;      // (the plan admits no other size: never a silent substitute)
+                }
+                b->last_kernel = rmx_select::label_rollout_search();
+                return hipSuccess;
+            }
             if (fb) {
                 const rmx_select::AdjPlan plan = rmx_select::select_rollout_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
                 if (generic_only(plan) == hipSuccess) DISPATCH_NP(m->NP, launch_rollout_feedback, m, b, integ, o, a)
@@ -2072,6 +2144,53 @@ static hipError_t costws_reserve(rmx_batch* b, const size_t total) {
     b->costws_bytes = total;
     return hipSuccess;
 }
+// The terms of a cost entry as the kernels read them - sorted by step on the nodes of the device (rmx_track::plan_terms on the position
+// part), the step offsets beside them - or the entry's refusal.  weights: the entry reads the weights (the cost-model entries and
+// rmx_rollout_search): each must be finite and >= 0, and one that is > 0 needs its target table.
+static int plan_frame_terms(const std::string& who, const rmx_frame_terms* ft, const int nsteps, const rmx_model* m, const bool weights,
+                            std::vector<FrameDevTerm>& dterms, std::vector<int>& begin) {
+    if (!ft->terms) return fail(RMX_E_INVALID, who + ": null terms");
+    if (ft->nterms < 1) return fail(RMX_E_INVALID, who + ": nterms < 1");
+    std::vector<rmx_track_term> pos((size_t)ft->nterms);
+    for (int i = 0; i < ft->nterms; ++i) {
+        const rmx_frame_term& t = ft->terms[i];
+        pos[(size_t)i].body = t.body;
+        for (int c = 0; c < 3; ++c) pos[(size_t)i].xlocal[c] = t.xlocal[c];
+        pos[(size_t)i].step = t.step;
+        pos[(size_t)i].wpos = t.wpos;
+    }
+    rmx_track::Plan tplan = rmx_track::plan_terms(pos.data(), ft->nterms, nsteps, m->nlist, m->node_of_listing.data());
+    if (!tplan.error.empty()) return fail(RMX_E_INVALID, who + ": " + tplan.error);
+    for (int i = 0; i < ft->nterms && weights; ++i) {      // the weights: the cost-model entries alone read them
+        const rmx_frame_term& t = ft->terms[i];
+        const struct { const char* name; double w; const void* table; const char* tname; } ws[3] = {
+            {"wpos", t.wpos, ft->xtarget, "xtarget"}, {"wvel", t.wvel, ft->vtarget, "vtarget"}, {"wrot", t.wrot, ft->Rtarget, "Rtarget"}};
+        for (const auto& e : ws) {
+            if (!(e.w >= 0.0) || !std::isfinite(e.w))
+                return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": " + e.name +
+                                               " must be finite and >= 0 (the Gauss-Newton block must stay positive semi-definite)");
+            if (e.w > 0.0 && !e.table)
+                return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": " + e.name + " > 0 needs " + e.tname + ", which is null");
+        }
+    }
+    dterms.resize((size_t)ft->nterms);
+    for (int i = 0; i < ft->nterms; ++i) {
+        dterms[(size_t)i].t = tplan.terms[(size_t)i];
+        dterms[(size_t)i].wvel = ft->terms[tplan.terms[(size_t)i].orig].wvel;
+        dterms[(size_t)i].wrot = ft->terms[tplan.terms[(size_t)i].orig].wrot;
+    }
+    begin = std::move(tplan.begin);
+    return RMX_OK;
+}
+// ... and their copy to the batch's term area (costws_reserve'd by the caller for both parts), where a finds them
+static hipError_t terms_to_device(rmx_batch* b, const std::vector<FrameDevTerm>& dterms, const std::vector<int>& begin, const size_t trk_bytes,
+                                  const FrameDevTerm*& trk, const int*& trk_begin) {
+    trk = (const FrameDevTerm*)b->costws;
+    trk_begin = (const int*)((const char*)b->costws + trk_bytes);
+    hipError_t e = hipMemcpyAsync(b->costws, dterms.data(), dterms.size() * sizeof(FrameDevTerm), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)b->costws + trk_bytes, begin.data(), begin.size() * sizeof(int), hipMemcpyHostToDevice, b->stream);
+    return e;
+}
 struct CostTerms {      // an entry's terms as frame terms: rmx_frame_terms as it is, rmx_point_terms with wvel = wrot = 0 and no vtarget, Rtarget
     bool given = false;
     rmx_frame_terms ft{};
@@ -2123,39 +2242,8 @@ static int rollout_cost_impl(const char* name, const bool frames, rmx_batch* b, 
     if (plan.kernel != rmx_select::CostKernel::Wave) return fail(RMX_E_INVALID, who + ": batch * nsteps exceeds the grid");
     std::vector<FrameDevTerm> dterms;
     std::vector<int> begin;
-    if (ft) {
-        if (!ft->terms) return fail(RMX_E_INVALID, who + ": null terms");
-        if (ft->nterms < 1) return fail(RMX_E_INVALID, who + ": nterms < 1");
-        std::vector<rmx_track_term> pos((size_t)ft->nterms);
-        for (int i = 0; i < ft->nterms; ++i) {
-            const rmx_frame_term& t = ft->terms[i];
-            pos[(size_t)i].body = t.body;
-            for (int c = 0; c < 3; ++c) pos[(size_t)i].xlocal[c] = t.xlocal[c];
-            pos[(size_t)i].step = t.step;
-            pos[(size_t)i].wpos = t.wpos;
-        }
-        rmx_track::Plan tplan = rmx_track::plan_terms(pos.data(), ft->nterms, nsteps, m->nlist, m->node_of_listing.data());
-        if (!tplan.error.empty()) return fail(RMX_E_INVALID, who + ": " + tplan.error);
-        for (int i = 0; i < ft->nterms && !kin; ++i) {      // the weights: the cost-model entries alone read them
-            const rmx_frame_term& t = ft->terms[i];
-            const struct { const char* name; double w; const void* table; const char* tname; } ws[3] = {
-                {"wpos", t.wpos, ft->xtarget, "xtarget"}, {"wvel", t.wvel, ft->vtarget, "vtarget"}, {"wrot", t.wrot, ft->Rtarget, "Rtarget"}};
-            for (const auto& e : ws) {
-                if (!(e.w >= 0.0) || !std::isfinite(e.w))
-                    return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": " + e.name +
-                                                   " must be finite and >= 0 (the Gauss-Newton block must stay positive semi-definite)");
-                if (e.w > 0.0 && !e.table)
-                    return fail(RMX_E_INVALID, who + ": term " + std::to_string(i) + ": " + e.name + " > 0 needs " + e.tname + ", which is null");
-            }
-        }
-        dterms.resize((size_t)ft->nterms);
-        for (int i = 0; i < ft->nterms; ++i) {
-            dterms[(size_t)i].t = tplan.terms[(size_t)i];
-            dterms[(size_t)i].wvel = ft->terms[tplan.terms[(size_t)i].orig].wvel;
-            dterms[(size_t)i].wrot = ft->terms[tplan.terms[(size_t)i].orig].wrot;
-        }
-        begin = std::move(tplan.begin);
-    }
+    if (ft)
+        if (int rc = plan_frame_terms(who, ft, nsteps, m, !kin, dterms, begin)) return rc;
     HIPCHK(hipSetDevice(m->device));
     if (int rc = pending_error_check(b, who.c_str())) return rc;
     const size_t B = (size_t)b->B, N = (size_t)nsteps, nr = (size_t)m->nr, dbl = sizeof(double);
@@ -2197,12 +2285,7 @@ static int rollout_cost_impl(const char* name, const bool frames, rmx_batch* b, 
     TaskArgs a{};
     a.nsteps = nsteps; a.nterms = (int)nterms;
     a.q = st.dev(S_Q); a.qd = st.dev(S_QD);
-    if (ft && e == hipSuccess) {
-        a.trk = (const FrameDevTerm*)b->costws;
-        a.trk_begin = (const int*)((const char*)b->costws + trk_bytes);
-        e = hipMemcpyAsync(b->costws, dterms.data(), nterms * sizeof(FrameDevTerm), hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)b->costws + trk_bytes, begin.data(), begin_bytes, hipMemcpyHostToDevice, b->stream);
-    }
+    if (ft && e == hipSuccess) e = terms_to_device(b, dterms, begin, trk_bytes, a.trk, a.trk_begin);
     a.t_stride = (ft && ft->per_rollout) ? nterms : 0;
     a.q_stride = (sc && sc->Q_per_rollout) ? N * 4 * nr * nr : 0;
     a.goal_stride = (sc && sc->goal_per_rollout) ? N * 2 * nr : 0;
@@ -2294,6 +2377,51 @@ extern "C" int rmx_rollout_tape_feedback(rmx_batch* b, const rmx_opts* opts, int
 extern "C" int rmx_rollout_tape_feedback_device(rmx_batch* b, const rmx_opts* opts, int nsteps, int integrator, double pscale,
                                                 const rmx_feedback* fb, double* d_qtraj, double* d_qdtraj, double* d_uapp, rmx_stats* stats) {
     return rollout_feedback_impl(b, opts, nsteps, integrator, pscale, fb, d_qtraj, d_qdtraj, d_uapp, stats, true);
+}
+// rmx_rollout_search: the entry's own refusals and the plan (rmx_select.h select_rollout_search), the cost's terms planned as
+// rmx_rollout_cost_frames plans them; the call itself is rollout_tape_impl's, which the entry follows without decisions of its own.
+static_assert(rmx_select::SEARCH_MAX_ALPHAS == RMX_SEARCH_MAX_ALPHAS, "the plan's cap on the alphas is the header's");
+static int rollout_search_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const rmx_feedback* fb, const rmx_box* box,
+                               const rmx_search* s, const rmx_search_cost* cost, double* qtraj, double* qdtraj, double* uapp,
+                               const rmx_search_out* out, rmx_stats* stats, const bool on_device) {
+    const std::string who = "rmx_rollout_search";
+    if (!b || !fb || !fb->uff || !s || !cost || !out || !out->J) return fail(RMX_E_INVALID, who + ": null argument");
+    if (fb->per_rollout != 0 && fb->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    if (!cost->sc && !cost->ft && !cost->R) return fail(RMX_E_INVALID, who + ": sc, ft and R are all null (there is no cost to search on)");
+    if (s->nalpha < 0 || s->nalpha > rmx_select::SEARCH_MAX_ALPHAS)
+        return fail(RMX_E_INVALID, who + ": nalpha must be 0 .. " + std::to_string(rmx_select::SEARCH_MAX_ALPHAS) + " (got " + std::to_string(s->nalpha) + ")");
+    if (s->nalpha > 0 && (!s->alphas || !s->kff || !s->Jbar)) return fail(RMX_E_INVALID, who + ": nalpha > 0 needs alphas, kff and Jbar");
+    for (int i = 0; i < s->nalpha; ++i)
+        if (!std::isfinite(s->alphas[i]) || !(s->alphas[i] > 0.0))
+            return fail(RMX_E_INVALID, who + ": alpha " + std::to_string(i) + " must be finite and > 0");
+    if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
+    if (nsteps < 1) return fail(RMX_E_INVALID, "nsteps < 1");
+    rmx_model* m = b->m;
+    if (int rc = adjoint_model_refusal(m)) return rc;
+    SearchCall sr{s, cost, out, rmx_select::select_rollout_search(step_traits(m), m->nr), {}, {}};
+    if (sr.plan.kernel == rmx_select::SearchKernel::RefusedNr)
+        return fail(RMX_E_INVALID, who + ": nr > " + std::to_string(rmx_select::LQR_MAX_NR) + " (the model has nr = " + std::to_string(m->nr) +
+                                       "; the LDS-resident sweep stops at " + std::to_string(rmx_select::LQR_MAX_NR) + " reduced DOFs)");
+    if (sr.plan.kernel != rmx_select::SearchKernel::Wave)
+        return fail(RMX_E_INVALID, who + ": more than " + std::to_string(rmx_select::LQR_MAX_NR) + " nodes (the model has " + std::to_string(m->n) +
+                                       " for nr = " + std::to_string(m->nr) + "; the LDS-resident sweep stops there)");
+    const rmx_state_cost* sc = cost->sc;
+    if (cost->ft && cost->ft->per_rollout != 0 && cost->ft->per_rollout != 1) return fail(RMX_E_INVALID, who + ": per_rollout must be 0 or 1");
+    if (sc && ((sc->Q_per_rollout != 0 && sc->Q_per_rollout != 1) || (sc->goal_per_rollout != 0 && sc->goal_per_rollout != 1)))
+        return fail(RMX_E_INVALID, who + ": Q_per_rollout and goal_per_rollout must be 0 or 1");
+    if (cost->ft)
+        if (int rc = plan_frame_terms(who, cost->ft, nsteps, m, true, sr.dterms, sr.begin)) return rc;
+    return rollout_tape_impl(b, opts, nsteps, pscale, fb->uff, qtraj, qdtraj, stats, on_device, INTEG_BDF1, fb, uapp, box, &sr);
+}
+extern "C" int rmx_rollout_search(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const rmx_feedback* fb, const rmx_box* box,
+                                  const rmx_search* s, const rmx_search_cost* cost, double* qtraj, double* qdtraj, double* uapp,
+                                  const rmx_search_out* out, rmx_stats* stats) {
+    return rollout_search_impl(b, opts, nsteps, pscale, fb, box, s, cost, qtraj, qdtraj, uapp, out, stats, false);
+}
+extern "C" int rmx_rollout_search_device(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const rmx_feedback* fb,
+                                         const rmx_box* box, const rmx_search* s, const rmx_search_cost* cost, double* d_qtraj,
+                                         double* d_qdtraj, double* d_uapp, const rmx_search_out* out, rmx_stats* stats) {
+    return rollout_search_impl(b, opts, nsteps, pscale, fb, box, s, cost, d_qtraj, d_qdtraj, d_uapp, out, stats, true);
 }
 extern "C" int rmx_rollout_tape_bdf2(rmx_batch* b, const rmx_opts* opts, int nsteps, double pscale, const double* u, double* qtraj,
                                      double* qdtraj, rmx_stats* stats) {

@@ -177,6 +177,20 @@ struct TaskArgs {
     double *gq, *gqd;         // [B][nsteps][nr], or null (gqd: frames)
 };
 
+// rmx_rollout_search (rmx_search.h): one wavefront per rollout runs the trial passes and the nominal pass of the line search
+struct SearchArgs {
+    AdjArgs a;                // the closed-loop sweep's, as rmx_rollout_tape_feedback_box fills it: u is the nominal torque ubar; qtraj and
+                              // qdtraj are never null here (without a caller's record: the tape's own rows)
+    const double* kff;        // [B][nsteps][nr] the search direction, or null with nalpha == 0
+    const double* Jbar;       // [B] the cost a trial has to beat, or null with nalpha == 0
+    int nalpha;               // 0 .. RMX_SEARCH_MAX_ALPHAS
+    double alphas[RMX_SEARCH_MAX_ALPHAS];
+    TaskArgs c;               // the cost: trk, trk_begin, xt, vt, Rt, t_stride, Qin, q_stride, xgoal, goal_stride (no record, no outputs)
+    const double* R;          // [nr * nr] or null: no control cost
+    double *J, *alpha;        // [B]; alpha may be null
+    int *trials, *sstatus;    // [B], or null
+};
+
 struct rmx_model {
     int device = 0;
     int n = 0, nr = 0, nm = 0, NP = 0;   // n: 1-DOF nodes on the device (after lowering multi-DOF joints)
@@ -311,6 +325,11 @@ void launch_lqr_box_4(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, 
 void launch_lqr_box_8(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
 void launch_lqr_box_16(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
 void launch_lqr_box_32(const rmx_model* m, const rmx_batch* b, const LqrArgs& a, size_t lds_bytes);
+// ... and the line search that follows it (k_rollout_search<NP>, rmx_search.h; select_rollout_search: the same sizes)
+void launch_search_4(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const SearchArgs& a, int block);
+void launch_search_8(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const SearchArgs& a, int block);
+void launch_search_16(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const SearchArgs& a, int block);
+void launch_search_32(const rmx_model* m, const rmx_batch* b, const DevOpts& o, const SearchArgs& a, int block);
 RMX_DECLARE_LAUNCHERS(4)
 RMX_DECLARE_LAUNCHERS(8)
 RMX_DECLARE_LAUNCHERS(16)

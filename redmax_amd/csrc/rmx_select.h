@@ -229,6 +229,30 @@ inline const char* label_rollout_feedback_box(const int integ) {      // ... aft
     return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback,box>" : "k_adjoint_fwd<bdf1,tape,feedback,box>";
 }
 
+// The line search of the device iLQR (rmx_rollout_search; rmx_search.h): one wavefront per rollout runs every trial pass and the
+// nominal pass of the closed loop, with the cost inside the launch - k_rollout_search<NP> in part_plain's object of the model's
+// padded size.  The search exists where the sweep that feeds it exists: the sizes, and so the refusals, are select_rollout_lqr's.
+constexpr int SEARCH_MAX_ALPHAS = 16;      // (RMX_SEARCH_MAX_ALPHAS of the header)
+enum class SearchKernel {
+    Wave,            // part_plain: k_rollout_search<NP>
+    RefusedNr,       // nr > LQR_MAX_NR
+    RefusedNodes,    // nr fits, the tree's padded size does not
+};
+struct SearchPlan {
+    SearchKernel kernel = SearchKernel::Wave;
+    int np = 0;                         // the padded size that runs
+    int block = 64;                     // threads per workgroup: one wavefront per rollout
+};
+inline SearchPlan select_rollout_search(const StepTraits& t, const int nr) {
+    SearchPlan p;
+    const LqrPlan l = select_rollout_lqr(t, nr);
+    if (l.kernel == LqrKernel::RefusedNr) p.kernel = SearchKernel::RefusedNr;
+    else if (l.kernel == LqrKernel::RefusedNodes) p.kernel = SearchKernel::RefusedNodes;
+    else p.np = t.NP;
+    return p;
+}
+inline const char* label_rollout_search() { return "k_rollout_search<bdf1,tape,feedback>"; }      // what rmx_last_step_kernel reports
+
 // Point kinematics and the cost model along a state record (rmx_rollout_points, rmx_rollout_cost; rmx_cost.h): one wavefront per
 // (rollout, step), lane = node, in part_plain's object of the model's padded size - every size has one, 64 included, and the kernel
 // holds nothing in LDS.  Kinematics alone decides: spherical joints (their Euler charts are not a function of q alone) and trees of

@@ -58,7 +58,7 @@ inline Layout layout(const int B, const int nsteps, const int integ /* 1: BDF1, 
 
 // The staging room of a host form: its arrays in the order they are added, each present one at a 256-byte boundary; an absent
 // (null) array takes no room.
-constexpr int STAGE_MAX = 16;
+constexpr int STAGE_MAX = 24;      // (rmx_rollout_search stages 17: gains, limits, direction, cost tables, outputs)
 struct StagePlan {
     int n = 0;
     size_t off[STAGE_MAX] = {}, bytes[STAGE_MAX] = {}, total = 0;

@@ -630,6 +630,96 @@ def cost_model(sim, qtraj, qdtraj, Q=None, xgoal=None, terms=None, xtarget=None,
     return out
 
 
+def rollout_search(sim, q0, qdot0, ubar, kff, K, xref, alphas, Jbar, cost=None, ulim=None, h=None, pscale=1.0):
+    """The backtracking line search of iLQR in ONE launch (rmx_rollout_search_device, include/redmax_hip.h), BDF1:
+    (qtraj, qdtraj, uapp, J, alpha, status).  From (q0, qdot0) every rollout runs the closed loop of ``rollout_feedback`` (K, xref and
+    ulim as there) under uff = ubar + a*kff for a in ``alphas``, in order, and keeps the first pass without a failed Newton solve whose
+    cost is below Jbar[b]; a rollout no alpha helps - and every rollout when ``alphas`` is empty, where kff and Jbar may be None -
+    runs the nominal pass uff = ubar.  cost: an ``ilqr.QuadraticCost`` or ``ilqr.TrackingCost`` (its Q, xgoal, R and terms with
+    their targets), evaluated inside the launch on the states each pass produces.  J [B]: the cost of the trajectory each rollout
+    ended on; alpha [B]: the accepted step length, 0: none; status [B] int32: the Newton status word of that pass.  The record,
+    uapp, the sim's state and its tape (the open-loop tape under uapp) belong to that pass.
+    NOT differentiable: no autograd graph is made and none can be - the accepted alpha is a discrete choice.  Differentiate the
+    trajectory it returns with ``rollout`` / ``rollout_closed_loop`` at uapp."""
+    import torch
+    _check_inputs(sim, q0, qdot0, ubar)
+    if cost is None:
+        raise ValueError("rollout_search: cost is None (an ilqr.QuadraticCost or ilqr.TrackingCost)")
+    B, N, nr = ubar.shape
+    dev = torch.device("cuda", sim.device)
+    alphas = tuple(float(a) for a in (() if alphas is None else alphas))
+    named = [(n, t) for n, t in (("kff", kff), ("K", K), ("xref", xref), ("Jbar", Jbar)) if t is not None]
+    Qc, Rc, xg = getattr(cost, "Q", None), getattr(cost, "R", None), getattr(cost, "xgoal", None)
+    terms = getattr(cost, "terms", None)
+    xt, vt, Rt = (getattr(cost, n, None) for n in ("xtarget", "vtarget", "Rtarget"))
+    named += [(n, t) for n, t in (("cost.Q", Qc), ("cost.R", Rc), ("cost.xgoal", xg), ("cost.xtarget", xt), ("cost.vtarget", vt),
+                                  ("cost.Rtarget", Rt)) if t is not None]
+    _check_tensors("rollout_search", sim, named)
+    if alphas and (kff is None or Jbar is None):
+        raise ValueError("rollout_search: alphas need kff and Jbar")
+    if kff is not None and tuple(kff.shape) != (B, N, nr):
+        raise ValueError("rollout_search: kff must have shape %r, got %r" % ((B, N, nr), tuple(kff.shape)))
+    if Jbar is not None and tuple(Jbar.shape) != (B,):
+        raise ValueError("rollout_search: Jbar must have shape %r, got %r" % ((B,), tuple(Jbar.shape)))
+    per = []
+    for name, t, tail in (("K", K, (N, 2 * nr, nr)), ("xref", xref, (N, 2 * nr))):
+        if t is None:
+            continue
+        if tuple(t.shape) not in (tail, (B,) + tail):
+            raise ValueError("rollout_search: %s must have shape %r or %r, got %r" % (name, tail, (B,) + tail, tuple(t.shape)))
+        per.append(t.dim() == len(tail) + 1)
+    if len(set(per)) > 1:
+        raise ValueError("rollout_search: K and xref must both be shared by the batch or both hold one table per rollout")
+    if xg is not None and xg.dim() == 3 and xg.shape[0] == 1:
+        xg = xg[0]
+    if Qc is not None and tuple(Qc.shape) not in ((N, 2 * nr, 2 * nr), (B, N, 2 * nr, 2 * nr)):
+        raise ValueError("rollout_search: cost.Q must have shape %r or %r, got %r" % ((N, 2 * nr, 2 * nr), (B, N, 2 * nr, 2 * nr), tuple(Qc.shape)))
+    if xg is not None and tuple(xg.shape) not in ((N, 2 * nr), (B, N, 2 * nr)):
+        raise ValueError("rollout_search: cost.xgoal must have shape %r or %r, got %r" % ((N, 2 * nr), (B, N, 2 * nr), tuple(xg.shape)))
+    if Rc is not None and tuple(Rc.shape) != (nr, nr):
+        raise ValueError("rollout_search: cost.R must have shape %r, got %r" % ((nr, nr), tuple(Rc.shape)))
+    tper = False
+    if terms is not None:
+        terms = [dict(t) for t in terms]
+        T = len(terms)
+        tabs = ((xt, (3,), "xtarget"), (vt, (3,), "vtarget"), (Rt, (3, 3), "Rtarget"))
+        for t, tail, name in tabs:
+            if t is not None and tuple(t.shape) not in ((T,) + tail, (B, T) + tail):
+                raise ValueError("rollout_search: cost.%s must have shape %r or %r, got %r" % (name, (T,) + tail, (B, T) + tail, tuple(t.shape)))
+        tper = any(t is not None and t.dim() == len(tail) + 2 for t, tail, _ in tabs)
+
+        def table(t, tail):      # (the three tables share one per-rollout flag; Rtarget [..][3][3] goes column-major)
+            if t is None:
+                return None
+            t = t.detach()
+            if tper and t.dim() == len(tail) + 1:
+                t = t.unsqueeze(0).expand((B,) + tuple(t.shape))
+            return (t.transpose(-1, -2) if len(tail) == 2 else t).contiguous()
+
+        xt, vt, Rt = table(xt, (3,)), table(vt, (3,)), table(Rt, (3, 3))
+    else:
+        xt = vt = Rt = None
+    h = float(sim.opts.h if h is None else h)
+    lim = None if ulim is None else _check_ulim("rollout_search", ulim, nr, dev)
+    c = lambda t: None if t is None else t.detach().contiguous()      # noqa: E731
+    q0c, qd0c, uc, kc, Kc, xc, Jc, Qd, xgd, Rd = (c(t) for t in (q0, qdot0, ubar, kff, K, xref, Jbar, Qc, xg, Rc))
+    qtraj = torch.empty((B, N, nr), dtype=torch.float64, device=dev)
+    qdtraj, uapp = torch.empty_like(qtraj), torch.empty_like(qtraj)
+    J = torch.empty(B, dtype=torch.float64, device=dev)
+    alpha = torch.empty_like(J)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    ptr = lambda t: 0 if t is None else t.data_ptr()      # noqa: E731
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: see _tape_forward)
+    sim.set_state_device(q0c.data_ptr(), qd0c.data_ptr())
+    sim.rollout_search_device(N, h, uc.data_ptr(), ptr(kc) if alphas else 0, ptr(Kc), ptr(xc), alphas, ptr(Jc) if alphas else 0, qtraj.data_ptr(),
+                              qdtraj.data_ptr(), uapp.data_ptr(), J.data_ptr(), alpha_ptr=alpha.data_ptr(), status_ptr=status.data_ptr(),
+                              per_rollout=bool(per and per[0]), Q_ptr=ptr(Qd), xgoal_ptr=ptr(xgd), Q_per_rollout=Qd is not None and Qd.dim() == 4,
+                              goal_per_rollout=xgd is not None and xgd.dim() == 3, R_ptr=ptr(Rd), terms=terms, xtarget_ptr=ptr(xt),
+                              vtarget_ptr=ptr(vt), Rtarget_ptr=ptr(Rt), target_per_rollout=tper, pscale=float(pscale),
+                              ulim=None if lim is None else tuple(0 if t is None else t.data_ptr() for t in lim))
+    return qtraj, qdtraj, uapp, J, alpha, status
+
+
 _ClosedLoop = None
 
 

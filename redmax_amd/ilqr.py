@@ -146,7 +146,8 @@ def backward_pass(A, Bm, lx, lu, Q, R, mu=0.0):
 Result = namedtuple("Result", "u qtraj qdtraj cost alpha")
 
 
-def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0, backward="torch", ulim=None):
+def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625), mu=1e-6, h=None, pscale=1.0, backward="torch", ulim=None,
+          search="host"):
     """Batched iLQR: one problem per rollout of ``sim`` (a BatchSim), BDF1.  Returns (result, history).
 
     q0, qdot0 [B][nr], u0 [B][N][nr]: float64 tensors on the sim's device; cost: a QuadraticCost on that device, or a cost with
@@ -173,11 +174,25 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
     (Tassa, Mansard, Todorov 2014).  Every launch is then the clamped feedback rollout (u0 is clamped by the first launch itself),
     and the backward pass is ``diff.lqr_backward_box`` at ubar = the applied torques of the accepted launch; it exists on the device
     alone, so backward must be "device".  A rollout whose backward pass reports a status != 0 keeps alpha = 0 in that iteration.
-    ``backward_pass`` knows no limits."""
+    ``backward_pass`` knows no limits.
+    search: "host" (the default) is steps 2 - 4 as written above.  "device" runs the whole line search of an iteration as ONE launch
+    (``diff.rollout_search``, rmx_rollout_search_device): every rollout tries its alphas in turn inside the wavefront that integrates
+    it, with the cost evaluated in the launch, and ends on the trajectory it keeps - no relaunch of accepted rollouts, no cost
+    launches, no host round trip per alpha.  An iteration is then ``quadratic_model``, ``lqr_backward[_box]`` and one
+    ``rollout_search``; it needs backward="device" and a QuadraticCost or TrackingCost (the costs the launch knows).  A rollout whose
+    sweep flags it has zero gains and is passed Jbar = -inf: it ends on its nominal pass.  The two searches apply one rule in
+    different summation orders of J: they may accept different alphas where a trial's J lies within rounding of Jbar."""
     import torch
     from . import diff
     if backward not in ("torch", "device"):
         raise ValueError("solve: backward must be 'torch' or 'device', got %r" % (backward,))
+    if search not in ("host", "device"):
+        raise ValueError("solve: search must be 'host' or 'device', got %r" % (search,))
+    if search == "device" and backward != "device":
+        raise ValueError("solve: search='device' needs backward='device': the search follows the Riccati sweep on the tape it leaves")
+    if search == "device" and not isinstance(cost, (QuadraticCost, TrackingCost)):
+        raise ValueError("solve: search='device' knows QuadraticCost and TrackingCost (the costs rmx_rollout_search evaluates), got %s"
+                         % type(cost).__name__)
     if ulim is not None and backward != "device":
         raise ValueError("solve: torque limits (ulim) need backward='device': the box-constrained backward pass exists on the device alone")
     diff._check_inputs(sim, q0, qdot0, u0)
@@ -199,7 +214,16 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
         J = cost.value(x, ua)
         return qt, qdt, ua, x, torch.where(torch.isfinite(J) & ~failed, J, torch.full_like(J, float("inf")))      # (a failed solve: never accepted)
 
-    qt, qdt, ubar, xbar, Jbar = launch(u0.detach(), None, None)
+    def searched(ub, kff, K, xref, als, Jb):                           # search="device": one launch, the cost inside it
+        qt, qdt, ua, J, al, st = diff.rollout_search(sim, q0, qdot0, ub, kff, K, xref, als, Jb, cost=cost, ulim=ulim, h=h, pscale=pscale)
+        tape[0] = sim.tape_count
+        J = torch.where(torch.isfinite(J) & ((st & diff._BAD_STATUS) == 0), J, torch.full_like(J, float("inf")))
+        return qt, qdt, ua, torch.cat([qt, qdt], dim=-1), J, al
+
+    if search == "device":
+        qt, qdt, ubar, xbar, Jbar, _ = searched(u0.detach().contiguous(), None, None, None, (), None)
+    else:
+        qt, qdt, ubar, xbar, Jbar = launch(u0.detach(), None, None)
     if not torch.isfinite(Jbar).all():
         raise RuntimeError("solve: the rollout under u0 failed")
     history = [Jbar]
@@ -228,6 +252,12 @@ def solve(sim, q0, qdot0, u0, cost, iters=10, alphas=(1.0, 0.5, 0.25, 0.125, 0.0
             Kabi = K.transpose(-1, -2).contiguous()
             notpd = None
         xref = torch.cat([x0, xbar[:, :-1]], dim=1).contiguous()      # the nominal state at the START of every step
+        if search == "device":
+            # a flagged rollout has zero gains: nothing can beat -inf, so it ends on its nominal pass (which reproduces xbar)
+            bar = Jbar if notpd is None else torch.where(notpd, torch.full_like(Jbar, float("-inf")), Jbar)
+            qt, qdt, ubar, xbar, Jbar, alpha = searched(ubar, kff, Kabi, xref, alphas, bar)
+            history.append(Jbar)
+            continue
         alpha = torch.zeros(B, dtype=torch.float64, device=u0.device)
         accepted = torch.zeros(B, dtype=torch.bool, device=u0.device)
         clean = False                                                  # does the last launch hold accepted trajectories only?

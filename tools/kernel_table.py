@@ -56,6 +56,10 @@ ROWS = (  # (name fragment, what it runs)
     ("k_rollout_lqr<8, true>", "rmx_rollout_lqr_box (the same sweep with the box QP of control-limited DDP in the place of the solve): 5..8 nodes"),
     ("k_rollout_lqr<16, true>", "rmx_rollout_lqr_box: 9..16 nodes"),
     ("k_rollout_lqr<32, true>", "rmx_rollout_lqr_box: 17..32 nodes (147 712 bytes of LDS)"),
+    ("k_rollout_search<4>", "rmx_rollout_search (the line search of iLQR: every trial pass and the nominal pass of the closed loop, the cost inside the launch; one wavefront per rollout): <= 4 nodes"),
+    ("k_rollout_search<8>", "rmx_rollout_search: 5..8 nodes"),
+    ("k_rollout_search<16>", "rmx_rollout_search: 9..16 nodes"),
+    ("k_rollout_search<32>", "rmx_rollout_search: 17..32 nodes, M and D on the matrix cores"),
     ("k_rollout_param_grad<4>", "rmx_rollout_vjp_params (the contraction over the slots of a tape; one wavefront per rollout): <= 4 nodes"),
     ("k_rollout_param_grad<8>", "rmx_rollout_vjp_params: 5..8 nodes"),
     ("k_rollout_param_grad<16>", "rmx_rollout_vjp_params: 9..16 nodes"),
