@@ -987,6 +987,44 @@ int rmx_rollout_vjp_params(rmx_batch* b, int nsteps, const double* gq, const dou
 int rmx_rollout_vjp_params_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
                                   double* d_dqd0, const rmx_param_grads* out);
 
+/* Taped rollouts of a model with point forces (ForcePointPoint, ForceSpringDamper, ForceCable: rmx_model_set_point_forces), so that
+ * spring-coupled and cable-driven mechanisms can be differentiated, linearised and controlled.  Added WITHOUT a change of RMX_VERSION
+ * (it stays 111): probe for the symbols.  No existing struct grows and no existing entry changes: the feature is a switch per model,
+ * off by default.
+ *
+ * enable = 1: rmx_rollout_tape, rmx_rollout_tape_bdf2, rmx_rollout_tape_feedback and rmx_rollout_tape_feedback_box (and their
+ * _device forms) take a model that has a force table; 0 (the default) restores the refusal, word for word.  A model without a force
+ * table is not affected either way: the same kernels, the same bits.  May be called before or after rmx_model_set_point_forces, any
+ * number of times; it takes effect at the next tape call and leaves an existing tape alone.
+ *
+ * The tape has the layout of every other tape.  Its H carries the forces' blocks (the H of rmx_eval on such a model), and its
+ * D = df/dqdot their damping.  With x_k the points of a force on their bodies, A_k(a) the column of the point Jacobian for joint a,
+ * and per segment j = (point j, point j+1) of the force's polyline dA_j = A_{j+1} - A_j, u_j the segment's unit vector:
+ *     point-point            D(a,i) -= kd  dA(a) . dA(i)
+ *     spring / taut cable    D(a,i) -= (kd/L) lam(a) lam(i),   lam(a) = sum_j u_j . dA_j(a)
+ *     slack cable            nothing
+ * which is the reference's J' Dm J (computeValues adds it to D).  The readers of a tape read the n x n blocks densely, so they run
+ * on such a tape unchanged: rmx_rollout_vjp, rmx_rollout_linearize, rmx_rollout_jvp, rmx_rollout_vjp_feedback, rmx_rollout_lqr,
+ * rmx_rollout_lqr_box.  rmx_last_step_kernel reports "k_adjoint_fwd<bdf1,tape,pf>", "<bdf2,tape,pf>", "<bdf1,tape,feedback,pf>" or
+ * "<bdf2,tape,feedback,pf>" after the tape call.
+ *
+ * A cable is not differentiable where a solve ends exactly at l = L.  The tape holds the blocks of the branch the last evaluated
+ * iterate of each solve was on (taut: l > L), and the gradients are those of that branch.
+ * The sweep is rmx_rollout_tape's: Newton WITHOUT a line search.  A solve whose iterates keep crossing l = L of a stiff cable can
+ * end at the iteration limit (stats->status bit 2) where rmx_step_bdf1's line search converges; the rows of such a rollout are
+ * unspecified, as for every tape call.  Measured on a 32-node tree with a stiff four-point cable from 512 random states: no
+ * rollout within 20 steps, 152 (BDF1) and 176 (BDF2) within 100 (profiles/tape_pf.txt; the numpy restatement of the sweep, without
+ * a line search either, fails from such states too).
+ *
+ * rmx_rollout_vjp_params refuses a tape that carries point forces (RMX_E_INVALID, "point forces"): its contraction covers the joint
+ * and body parameters of a model without them.  These refuse a model with a force table in the words they always had, whatever the
+ * switch says: rmx_rollout_search, rmx_adjoint_bdf1, rmx_adjoint_bdf2, rmx_adjoint_controls, rmx_adjoint_track, rmx_step_euler,
+ * rmx_eval_mfd, rmx_compute_values.
+ * Out of scope: parameter gradients of the force constants (stiffness, damping, rest length); the device line search; the
+ * in-library objectives; forces together with ground contact or spherical joints (rmx_model_set_point_forces refuses those). */
+int rmx_model_tape_point_forces(rmx_model* m, int enable);   /* enable: 0 or 1 */
+int rmx_model_get_tape_point_forces(const rmx_model* m);     /* 0 / 1; a null model: RMX_E_INVALID */
+
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.
  * hist_T/hist_V as in rmx_step_bdf1. */

@@ -123,6 +123,17 @@ classdef HipSim < handle
 			redmax_hip_mex('setcharts', this.h, int32(c));
 		end
 
+		function on = tapePointForces(this, enable)
+			% rmx_model_tape_point_forces: enable true (default) - rolloutTape, rolloutFeedback and rolloutFeedbackBox take a model with
+			% point forces (ForcePointPoint / ForceSpringDamper / ForceCable) and leave a tape whose H and D carry them, which
+			% rolloutVjp, rolloutLinearize, rolloutJvp, rolloutVjpFeedback and rolloutLqr[Box] read unchanged; false restores the
+			% refusal.  A model without such forces is not affected.  on: the switch as read back.
+			if nargin < 2
+				enable = true;
+			end
+			on = redmax_hip_mex('tape_point_forces', this.h, double(logical(enable))) ~= 0;
+		end
+
 		function [P, dPdp, stats] = adjoint(this, hstep, nsteps, task, p, itype)
 			% taskObjective of driverRedMaxAdjointBDF1.m (itype 1, default) / driverRedMaxAdjointBDF2.m (itype 2)
 			if nargin < 6

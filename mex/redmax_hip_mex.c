@@ -120,6 +120,9 @@
  *                  wvel, wrot >= 0 (a missing one is 0) - and the targets xtarget, vtarget (3 x nterms [x B]) and Rtarget (3 x 3 x
  *                  nterms [x B]); [] for a table no term weighs.  Per term wpos/2 |p - xtarget|^2 + wvel/2 |v - vtarget|^2 +
  *                  wrot/4 |R - Rtarget|_F^2; lx is the exact gradient, Q the Gauss-Newton table with the velocity terms' cross blocks.
+ *   on = redmax_hip_mex('tape_point_forces', h, enable)  rmx_model_tape_point_forces on the model of every shard: enable 1, 'rollout_tape'
+ *                  and 'rollout_feedback[_box]' take a model with point forces and leave a tape whose H and D carry them; 0 (the
+ *                  default) restores their refusal.  A model without a force table is not affected.  on: the switch as read back.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -1437,6 +1440,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (int i = 0; i < h->B; ++i) mxGetPr(out)[i] = (double)t[i];
         mxFree(t);
         plhs[0] = out;
+    } else if (!strcmp(cmd, "tape_point_forces")) {      /* on = redmax_hip_mex('tape_point_forces', h, enable) */
+        handle_t* h = get_handle(nrhs, prhs);
+        if (nrhs < 3 || mxGetNumberOfElements(prhs[2]) != 1) die("tape_point_forces: enable must be a scalar, 0 or 1");
+        const double en = mxGetScalar(prhs[2]);
+        if (en != 0.0 && en != 1.0) die("tape_point_forces: enable must be 0 or 1");
+        for (int s = 0; s < h->nshards; ++s)
+            if (rmx_model_tape_point_forces(rmx_group_shard_model(h->g, s), (int)en)) die_rmx("rmx_model_tape_point_forces");
+        if (nlhs > 0) plhs[0] = mxCreateDoubleScalar((double)rmx_model_get_tape_point_forces(rmx_group_shard_model(h->g, 0)));
     } else if (!strcmp(cmd, "adjoint")) {
         cmd_adjoint(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "adjoint_controls")) {

@@ -36,6 +36,7 @@ SYMBOLS = (
     "rmx_rollout_points", "rmx_rollout_points_device", "rmx_rollout_cost", "rmx_rollout_cost_device",
     "rmx_rollout_frames", "rmx_rollout_frames_device", "rmx_rollout_cost_frames", "rmx_rollout_cost_frames_device",
     "rmx_rollout_search", "rmx_rollout_search_device",
+    "rmx_model_tape_point_forces", "rmx_model_get_tape_point_forces",
     "rmx_last_step_ms", "rmx_last_step_kernel", "rmx_batch_stream", "rmx_step_bdf1_async", "rmx_step_bdf2_async", "rmx_step_history_async", "rmx_sync",
     "rmx_history_read", "rmx_stats_reset", "rmx_stats_read", "rmx_profile_phases", "rmx_step_ticks",
     "rmx_group_create", "rmx_group_destroy", "rmx_group_batch_size", "rmx_group_nshards", "rmx_group_shard", "rmx_group_shard_batch",
@@ -190,6 +191,8 @@ def lib():
     L.rmx_model_idxR.argtypes = [vp, _ip]
     L.rmx_model_set_ground_contact.argtypes = [vp, C.POINTER(GroundContact)]
     L.rmx_model_set_point_forces.argtypes = [vp, C.POINTER(PointForce), C.c_int]
+    L.rmx_model_tape_point_forces.argtypes = [vp, C.c_int]
+    L.rmx_model_get_tape_point_forces.argtypes = [vp]
     L.rmx_model_nsph.argtypes = [vp]
     L.rmx_get_charts.argtypes = [vp, _ip]
     L.rmx_set_charts.argtypes = [vp, _ip]

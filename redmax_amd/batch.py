@@ -84,10 +84,11 @@ def _history_arrays(B, nr, nsph, nsteps, record):
 
 
 class BatchSim:
-    def __init__(self, scene_or_desc, batch=1, device=0):
+    def __init__(self, scene_or_desc, batch=1, device=0, tape_forces=False):
+        """tape_forces: the taped rollouts take the scene's point forces (tape_point_forces); off, they refuse such a scene."""
         d = scene_or_desc.desc() if hasattr(scene_or_desc, "desc") else scene_or_desc
         self._L = _abi.lib()
-        self._async = None                                 # (nsteps, record) of a step_history_async whose record has not been replaced
+        self._async = None                               # (nsteps, record) of a step_history_async whose record has not been replaced
         self._desc, self._keep = _abi.make_desc(d)
         self._model = C.c_void_p()
         self._batch = C.c_void_p()
@@ -113,6 +114,19 @@ class BatchSim:
         self._L.rmx_opts_default(C.byref(self.opts))
         self._tape_integrator = 1                          # the integrator of the last rollout_tape* call: the slots rollout_linearize returns
         self.tape_count = 0                                # calls that rewrote the adjoint workspace (rollout_tape*, adjoint_*): see diff.rollout
+        if tape_forces:
+            self.tape_point_forces(True)
+
+    def tape_point_forces(self, enable=True):
+        """rmx_model_tape_point_forces: with the switch on, rollout_tape and rollout_feedback (both integrators, limits included)
+        take a scene with ForcePointPoint / ForceSpringDamper / ForceCable, and the tape they leave - H and D carry the forces -
+        is read by rollout_vjp, rollout_linearize, rollout_jvp, rollout_vjp_feedback, rollout_lqr unchanged.  Off (the default)
+        restores the refusal.  A scene without such forces is not affected.  Takes effect at the next tape call."""
+        _abi.check(self._L.rmx_model_tape_point_forces(self._model, 1 if enable else 0), "rmx_model_tape_point_forces")
+
+    @property
+    def tapes_point_forces(self):
+        return self._L.rmx_model_get_tape_point_forces(self._model) == 1
 
     def close(self):
         if getattr(self, "_batch", None):
@@ -1105,9 +1119,12 @@ class GroupSim:
     shards, every array the whole batch.  ``step`` launches all shards before it waits for the first - the multi-device simLoop a
     single host thread (MATLAB: matlab/+redmax/HipSim.m with a device vector) can drive; a device may be listed more than once."""
 
-    def __init__(self, scene_or_desc, batch, devices=(0,)):
+    def __init__(self, scene_or_desc, batch, devices=(0,), tape_forces=False):
         d = scene_or_desc.desc() if hasattr(scene_or_desc, "desc") else scene_or_desc
         self._L = _abi.lib()
+        if tape_forces:      # (a group takes no force table and records no tape: the keyword cannot be honoured)
+            raise _abi.RedMaxHipError("GroupSim: tape_forces is BatchSim's (rmx_model_tape_point_forces); a group has neither point "
+                                      "forces nor taped rollouts")
         if d.get("point_forces"):
             raise _abi.RedMaxHipError("GroupSim: rmx_group_create has no slot for point forces (ForcePointPoint / ForceSpringDamper / "
                                       "ForceCable); use BatchSim")

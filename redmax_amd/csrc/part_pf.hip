@@ -6,6 +6,7 @@
 #define RMX_DPP_SETTLE 1
 #endif
 #include "rmx_kernels.h"
+#include "rmx_tape_pf.h"      /* k_tape_pf and its launcher: the taped rollouts of these models */
 
 // simLoop of driverRedMaxBDF1.m:57-91 (INTEG 1) / driverRedMaxBDF2.m:57-125 (INTEG 2: SDIRK2 start step, then BDF2) with the point
 // forces: k_step_bdf1 / k_step_bdf2 of the plain kernels around newton_pf, all steps of a rollout in one launch.

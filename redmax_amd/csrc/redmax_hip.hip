@@ -702,6 +702,14 @@ extern "C" int rmx_model_set_point_forces(rmx_model* m, const rmx_point_force* f
     m->dpf = fresh;
     return RMX_OK;
 }
+// The switch of the taped rollouts with point forces: read by adjoint_model_refusal at every tape call, nothing else happens here.
+extern "C" int rmx_model_tape_point_forces(rmx_model* m, int enable) {
+    if (!m) return fail(RMX_E_INVALID, "rmx_model_tape_point_forces: null argument");
+    if (enable != 0 && enable != 1) return fail(RMX_E_INVALID, "rmx_model_tape_point_forces: enable must be 0 or 1");
+    m->tape_pf = enable == 1;
+    return RMX_OK;
+}
+extern "C" int rmx_model_get_tape_point_forces(const rmx_model* m) { return m ? (m->tape_pf ? 1 : 0) : RMX_E_INVALID; }
 extern "C" int rmx_model_nr(const rmx_model* m) { return m ? m->nr : RMX_E_INVALID; }
 extern "C" int rmx_model_nm(const rmx_model* m) { return m ? m->nm : RMX_E_INVALID; }
 extern "C" int rmx_model_idxR(const rmx_model* m, int* idx) {
@@ -1346,12 +1354,15 @@ extern "C" int rmx_step_euler(rmx_batch* b, double h, int nsteps, double* hT, do
 }
 
 
-// the models the adjoint path does not take (every rmx_adjoint_* entry and rmx_rollout_tape)
-static int adjoint_model_refusal(const rmx_model* m) {
+// the models the adjoint path does not take (every rmx_adjoint_* entry and rmx_rollout_tape).  tape_entry: one of the four tape
+// entries (rmx_rollout_tape, _tape_bdf2, _tape_feedback, _tape_feedback_box), which take a force table where the model's switch is
+// on (rmx_model_tape_point_forces; rmx_tape_pf.h) - every other caller refuses it whatever the switch says
+static int adjoint_model_refusal(const rmx_model* m, const bool tape_entry = false) {
     if (m->dm.con) return fail(RMX_E_INVALID, "rmx_adjoint: ground contact is outside the adjoint path (SURVEY.md 8(f))");
     if (m->dm.nsph) return fail(RMX_E_INVALID, "rmx_adjoint: spherical joints are outside the adjoint path (SURVEY.md 8(f))");
     if (m->big) return fail(RMX_E_INVALID, "rmx_adjoint: trees of more than 64 nodes are outside the adjoint path");
-    if (m->dpf) return fail(RMX_E_INVALID, "rmx_adjoint: point forces (rmx_model_set_point_forces) are outside the adjoint path");
+    if (m->dpf && !(tape_entry && m->tape_pf))
+        return fail(RMX_E_INVALID, "rmx_adjoint: point forces (rmx_model_set_point_forces) are outside the adjoint path");
     return RMX_OK;
 }
 
@@ -1678,7 +1689,8 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
     if ((qtraj == nullptr) != (qdtraj == nullptr)) return fail(RMX_E_INVALID, "rmx_rollout_tape: qtraj and qdtraj must be given together");
     rmx_model* m = b->m;
     if (nsteps < 1) return fail(RMX_E_INVALID, "nsteps < 1");
-    if (int rc = adjoint_model_refusal(m)) return rc;
+    if (int rc = adjoint_model_refusal(m, sr == nullptr)) return rc;
+    const bool with_pf = m->dpf != nullptr;      // (past the refusal: a tape entry of a model whose switch is on)
     HIPCHK(hipSetDevice(m->device));
     DevOpts o;
     int rc = make_opts(b, opts, o);
@@ -1789,6 +1801,13 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
                 b->last_kernel = rmx_select::label_rollout_search();
                 return hipSuccess;
             }
+            if (with_pf) {      // the sweep that carries the forces into H and D (rmx_tape_pf.h), open or closed loop
+                const rmx_select::TapePfPlan plan = rmx_select::select_rollout_tape_pf(step_traits(m), integ, fb != nullptr);
+                if (plan.kernel != rmx_select::TapePfKernel::Wave) return hipErrorInvalidDeviceFunction;      // (never a silent substitute)
+                DISPATCH_NP(plan.np, launch_tape_pf, m, b, integ, plan.feedback, o, a)
+                b->last_kernel = plan.label;
+                return hipSuccess;
+            }
             if (fb) {
                 const rmx_select::AdjPlan plan = rmx_select::select_rollout_feedback(step_traits(m), b->B, integ, rmx_select::knobs_from_env());
                 if (generic_only(plan) == hipSuccess) DISPATCH_NP(m->NP, launch_rollout_feedback, m, b, integ, o, a)
@@ -1818,6 +1837,7 @@ static int rollout_tape_impl(rmx_batch* b, const rmx_opts* opts, int nsteps, dou
             b->tape_integ = integ;
             b->tape_h = o.h;
             b->tape_pscale = pscale;
+            b->tape_pf = with_pf;
         }
     }
     fbst.release(b, e);
@@ -1928,6 +1948,8 @@ static int rollout_vjp_params_impl(rmx_batch* b, int nsteps, const double* gq, c
     if (!grads[0] && !grads[1] && !grads[2] && !grads[3] && !grads[4]) return fail(RMX_E_INVALID, who + ": all outputs are null");
     TapeView v;
     if (int rc = tape_view(b, nsteps, who, v)) return rc;
+    if (b->tape_pf)
+        return fail(RMX_E_INVALID, who + ": the tape carries point forces (rmx_model_tape_point_forces); the parameters' contraction does not cover them");
     rmx_model* m = b->m;
     DevOpts o;
     AdjArgs a = vjp_args(b, v, o);

@@ -211,6 +211,7 @@ struct rmx_model {
     int adj_help_max_batch = 0;     // trees of <= 16 nodes: adjoint batches of up to this many rollouts take a second wavefront each for M, D (part_adjhelp16.hip; 0: never)
     int w2_min_batch = 0;           // the full 32-link chain: ... and of at least this many (RMX_W2C_MIN; smaller batches keep the one-wave kernel every test pins)
     void* dpf = nullptr;            // body-to-body forces (rmx_model_set_point_forces): the PfTable of rmx_pf.h on the device, or null
+    bool tape_pf = false;           // rmx_model_tape_point_forces: the four tape entries take the model while it has a force table
     bool big = false;               // more than 64 nodes: the one-workgroup-per-tree kernels of rmx_big.hip
     std::vector<struct rmx_batch*> batches;   // live batches of this model (rmx_model_set_ground_contact drains their streams only)
 };
@@ -240,6 +241,7 @@ struct rmx_batch {
     int tape_nsteps = 0;           // rmx_rollout_tape: steps of the tape H, M, D in adjws hold (0: none - every rmx_adjoint_* call rewrites them)
     int tape_integ = 0;             // ... the integrator that recorded it (INTEG_BDF2: nsteps + 1 slots per rollout, rmx_rollout_tape_bdf2)
     double tape_h = 0.0, tape_pscale = 0.0;   // ... and the step size and torque scale it was recorded with
+    bool tape_pf = false;           // ... and whether its H and D carry point forces (rmx_tape_pf.h): rmx_rollout_vjp_params refuses it then
     double last_ms = 0.0;
     const char* last_kernel = "";   // label of the step kernel the last step call launched (rmx_last_step_kernel; StepPlan::label)
     bool async_pending = false;     // an rmx_step_*_async launch nobody has waited for yet (see pending_error_check)
@@ -264,7 +266,7 @@ struct rmx_batch {
     size_t costws_bytes = 0;
 };
 
-// launchers defined by the multi-size parts (part_plain / part_ct / part_fullchain / part_pf .hip) for one RMX_NP each
+// launchers defined by the multi-size parts (part_plain / part_ct / part_fullchain / part_pf / part_tape_pf .hip) for one RMX_NP each
 #define RMX_CAT_(a, b) a##b
 #define RMX_CAT(a, b) RMX_CAT_(a, b)
 #define RMX_DECLARE_LAUNCHERS(NPV) \
@@ -289,7 +291,8 @@ struct rmx_batch {
     void RMX_CAT(launch_step_fullchain_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_eval_pf_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
     void RMX_CAT(launch_step_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
-    void RMX_CAT(launch_energy_pf_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV);
+    void RMX_CAT(launch_energy_pf_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
+    void RMX_CAT(launch_tape_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, bool feedback, const DevOpts& o, const AdjArgs& a);
 // The one-size step launchers (StepKernel of rmx_select.h; the bools are StepPlan's instantiation flags)
 // part_gconst64.hip: 64-lane plain step kernels reading the per-node constants from global memory, and the staging kernel (part_plain.hip)
 void launch_step_gconst_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fulln);

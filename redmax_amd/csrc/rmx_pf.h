@@ -231,6 +231,57 @@ __device__ __forceinline__ void pf_apply(const PfTable& T, const FrontState& fs,
     if (lane == 0) out.eV += V;
 }
 
+// The point forces' share of D = df/dqdot at the state of `fs`, added to this lane's row (the taped rollouts: part_tape_pf.hip).
+// pf_apply never forms it on its own - it folds the damping into H through B = A/eta + ... -; it is the coefficient of 1/eta in C,
+// divided by eta, without the geometric terms:
+//   point-point          D(a,i) -= kd dA(a) . dA(i)
+//   spring / taut cable  D(a,i) -= (kd/L) lam(a) lam(i),   lam(a) = sum_j u_j . dA_j(a)   (the lam of pf_apply's first pass)
+//   slack cable          nothing
+// Same point stage, same broadcasts and same cable switch as pf_apply, force by force (tests/proto_rollout_pf.py holds the numpy
+// twin and checks it against the reference's literal J' Dm J).
+template <int NP>
+__device__ __forceinline__ void pf_damp(const PfTable& T, const FrontState& fs, const int lane, double (&Drow)[NP]) {
+    const double ieta = 1.0 / fs.eta;
+    const int nf = T.nf;
+    for (int f = 0; f < nf; ++f) {
+        const int k0 = T.first[f], k1 = T.first[f + 1], kind = T.kind[f];
+        const double kd = T.kd[f], L = T.L[f];
+        const bool pp = kind == RMX_PF_POINTPOINT;
+        double l = 0.0, lam = 0.0;
+        double xp[3], vp[3], Ap[3], Bp[3];
+        bool onp;
+        pf_point(T, k0, fs, lane, ieta, xp, vp, Ap, Bp, onp);
+        for (int k = k0 + 1; k < k1; ++k) {
+            double x[3], v[3], A[3], B[3];
+            bool on;
+            pf_point(T, k, fs, lane, ieta, x, v, A, B, on);
+            double dx[3], dA[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dx[c] = x[c] - xp[c];
+                dA[c] = A[c] - Ap[c];
+                xp[c] = x[c];
+                Ap[c] = A[c];
+            }
+            if (pp) {
+                const double C[3] = {-kd * dA[0], -kd * dA[1], -kd * dA[2]};
+                pf_seg_update<NP>(Drow, dA, C);
+            } else {
+                const double ln = sqrt(dot3(dx, dx)), il = 1.0 / ln;
+                const double u[3] = {dx[0] * il, dx[1] * il, dx[2] * il};
+                l += ln;
+                lam += dot3(u, dA);
+            }
+        }
+        if (pp) continue;
+        const double strain = (l - L) / L;
+        if (kind == RMX_PF_CABLE && !(strain > 0.0)) continue;      // a slack cable: no block
+        const double cl = (kd / L) * lam;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) Drow[i] -= cl * readlane_d(lam, i);
+    }
+}
+
 // H(lane, lane) of a row held in registers (the scale of the row for the solver's growth guard)
 template <int NP>
 __device__ __forceinline__ double pf_diag(const double (&Hrow)[NP], const int lane, double d) {

@@ -229,6 +229,39 @@ inline const char* label_rollout_feedback_box(const int integ) {      // ... aft
     return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback,box>" : "k_adjoint_fwd<bdf1,tape,feedback,box>";
 }
 
+// The taped rollouts of a model with point forces (rmx_model_tape_point_forces; rmx_tape_pf.h): always the one-wavefront kernel
+// k_tape_pf of part_pf's object of the model's padded size, for both integrators, open loop or under feedback (the box is the
+// feedback kernel's clamp) - never the helper-wave form, the full-chain instantiation or the matrix-core store of M, D, which all
+// belong to sparse H.  The backward sweeps that read its tape follow select_rollout_tape: the layout is every tape's.  The labels
+// name the sweep it stands in for; the ABI refuses what has no such kernel (more than 64 nodes, contact, spherical joints) before
+// a plan is asked for, and the plan says so again.
+enum class TapePfKernel {
+    Wave,            // part_pf: k_tape_pf<NP, INTEG, FB>
+    Refused,         // no force table, or a model rmx_model_set_point_forces refuses
+};
+struct TapePfPlan {
+    TapePfKernel kernel = TapePfKernel::Wave;
+    const char* label = "";             // what rmx_last_step_kernel reports
+    int np = 0;                         // the padded size that runs
+    bool feedback = false;              // the instantiation with the feedback stage
+    int block = 64;                     // threads per workgroup: one wavefront per rollout
+};
+inline const char* label_rollout_tape_pf(const int integ, const bool feedback) {
+    if (feedback) return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,feedback,pf>" : "k_adjoint_fwd<bdf1,tape,feedback,pf>";
+    return integ == BDF2 ? "k_adjoint_fwd<bdf2,tape,pf>" : "k_adjoint_fwd<bdf1,tape,pf>";
+}
+inline TapePfPlan select_rollout_tape_pf(const StepTraits& t, const int integ, const bool feedback) {
+    TapePfPlan p;
+    if (!t.point_forces || t.big || t.contact || t.spherical || (integ != BDF1 && integ != BDF2)) {
+        p.kernel = TapePfKernel::Refused;
+        return p;
+    }
+    p.label = label_rollout_tape_pf(integ, feedback);
+    p.np = t.NP;
+    p.feedback = feedback;
+    return p;
+}
+
 // The line search of the device iLQR (rmx_rollout_search; rmx_search.h): one wavefront per rollout runs every trial pass and the
 // nominal pass of the closed loop, with the cost inside the launch - k_rollout_search<NP> in part_plain's object of the model's
 // padded size.  The search exists where the sweep that feeds it exists: the sizes, and so the refusals, are select_rollout_lqr's.

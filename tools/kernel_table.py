@@ -77,6 +77,14 @@ ROWS = (  # (name fragment, what it runs)
     ("k_step_pf<32, 2>", "body-to-body forces, <= 32 nodes, BDF2"),
     ("k_step_pf<64, 1>", "body-to-body forces, 33..64 nodes, BDF1"),
     ("k_step_pf<64, 2>", "body-to-body forces, 33..64 nodes, BDF2"),
+    ("k_tape_pf<4, 1, false>", "taped rollout with body-to-body forces (rmx_tape_pf.h), <= 4 nodes, BDF1"),
+    ("k_tape_pf<8, 1, false>", "taped rollout with body-to-body forces, 5..8 nodes, BDF1"),
+    ("k_tape_pf<16, 1, false>", "taped rollout with body-to-body forces, 9..16 nodes, BDF1"),
+    ("k_tape_pf<32, 1, false>", "taped rollout with body-to-body forces, 17..32 nodes, BDF1"),
+    ("k_tape_pf<32, 2, true>", "taped rollout with body-to-body forces, 17..32 nodes, BDF2, feedback stage"),
+    ("k_tape_pf<64, 1, false>", "taped rollout with body-to-body forces, 33..64 nodes, BDF1"),
+    ("k_tape_pf<64, 2, false>", "taped rollout with body-to-body forces, 33..64 nodes, BDF2"),
+    ("k_tape_pf<64, 2, true>", "taped rollout with body-to-body forces, 33..64 nodes, BDF2, feedback stage"),
 )
 
 
