@@ -1017,13 +1017,48 @@ int rmx_rollout_vjp_params_device(rmx_batch* b, int nsteps, const double* d_gq, 
  * a line search either, fails from such states too).
  *
  * rmx_rollout_vjp_params refuses a tape that carries point forces (RMX_E_INVALID, "point forces"): its contraction covers the joint
- * and body parameters of a model without them.  These refuse a model with a force table in the words they always had, whatever the
+ * and body parameters of a model without them; rmx_rollout_vjp_forces (below) is the call for such a tape, and forms the gradients in
+ * the force constants too.  These refuse a model with a force table in the words they always had, whatever the
  * switch says: rmx_rollout_search, rmx_adjoint_bdf1, rmx_adjoint_bdf2, rmx_adjoint_controls, rmx_adjoint_track, rmx_step_euler,
  * rmx_eval_mfd, rmx_compute_values.
- * Out of scope: parameter gradients of the force constants (stiffness, damping, rest length); the device line search; the
+ * Out of scope: gradients in the attachment points of the forces; forward-mode parameter tangents; the device line search; the
  * in-library objectives; forces together with ground contact or spherical joints (rmx_model_set_point_forces refuses those). */
 int rmx_model_tape_point_forces(rmx_model* m, int enable);   /* enable: 0 or 1 */
 int rmx_model_get_tape_point_forces(const rmx_model* m);     /* 0 / 1; a null model: RMX_E_INVALID */
+
+/* Parameter gradients from a tape that carries point forces (calibration of a spring stiffness, a damper, a cable's rest length):
+ * rmx_rollout_vjp_params for such a tape, plus dL/dtheta for the constants of every row of the force table.  Added WITHOUT a change
+ * of RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * The rule is rmx_rollout_vjp_params': dL/dtheta = - sum over all slots s of the tape  z_s' dg_s/dtheta.  The forces' share of g is
+ * eta^2 sum_j dA_j(a) . F_j over the segments j of the force's polyline (dA_j = A_{j+1} - A_j: the columns of the point Jacobian,
+ * u_j the segment's unit vector, lam(a) = sum_j u_j . dA_j(a), l and ldot the total length and its rate).  Per slot:
+ *     point-point            with zA = sum_a z_a dA(a):   d(z'g)/dks = eta^2 zA . dx      d(z'g)/dkd = eta^2 zA . dv      (no L: +0.0)
+ *     spring / taut cable    with zl = sum_a z_a lam(a):  d(z'g)/dks = eta^2 zl (l - L)/L   d(z'g)/dkd = eta^2 zl ldot/L
+ *                                                         d(z'g)/dL  = -eta^2 zl (ks l + kd ldot)/L^2
+ *     cable with !(strain > 0) at the slot's solution: nothing in any of the three (the branch the tape holds)
+ * The joint, inertia and gravity parameters' dg/dtheta does not involve the forces: `model` fills rmx_rollout_vjp_params' five arrays
+ * by that entry's own contraction, from the z of this tape.
+ *
+ * rmx_rollout_vjp_forces reads the tape of the preceding rmx_rollout_tape / _tape_bdf2 / _tape_feedback / _tape_feedback_box call on a
+ * model whose tape carries point forces, and follows its integrator (a closed-loop tape is the open-loop tape under uapp).  gq, gqd,
+ * du, dq0, dqd0: as rmx_rollout_vjp, and the same bits.  model (may be NULL): as `out` of rmx_rollout_vjp_params.  forces (may be
+ * NULL): one row per rollout and force, in the order of the table given to rmx_model_set_point_forces.  Any pointer of either struct may be NULL -
+ * that output is neither computed nor stored - but not all eight; an output has the same bits whichever others are asked for, and
+ * repeated calls return the same bits.  The call changes neither the batch's state nor the tape.
+ * Refusals (RMX_E_INVALID): a null batch, gq, gqd or du ("null argument"); dq0 and dqd0 not given together; both structs NULL or all
+ * eight pointers NULL ("all outputs are null"); "no tape"; an nsteps that differs from the tape's; a tape without point forces (the
+ * message names rmx_rollout_vjp_params, the call for it).
+ * The _device form: every array a DEVICE pointer (the structs themselves are host objects), nothing staged. */
+typedef struct rmx_force_grads {   /* every pointer may be NULL (not formed) */
+    double* stiffness;   /* [batch][nforces]  the order of the force table               */
+    double* damping;     /* [batch][nforces]                                             */
+    double* L;           /* [batch][nforces]  a point-point force has no L: +0.0 there   */
+} rmx_force_grads;
+int rmx_rollout_vjp_forces(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                           const rmx_param_grads* model, const rmx_force_grads* forces);
+int rmx_rollout_vjp_forces_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
+                                  double* d_dqd0, const rmx_param_grads* model, const rmx_force_grads* forces);
 
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.

@@ -232,6 +232,20 @@ classdef HipSim < handle
 			grads = struct('stiffness', dk, 'damping', dd, 'qrest', dr, 'inertia', dI, 'grav', dg);
 		end
 
+		function [du, dq0, dqd0, fgrads, grads] = rolloutVjpForces(this, nsteps, gq, gqd, nforces)
+			% rolloutVjpParams for a tape that carries point forces (tapePointForces): rolloutVjp (the same du, dq0, dqd0), the
+			% gradient with respect to the constants of the nforces rows of the force table, one column per rollout -
+			% fgrads.stiffness, fgrads.damping, fgrads.L (nforces x B; a point-point force has no rest length, its L entry is 0) -
+			% and, where asked for, grads as rolloutVjpParams returns it.  The tape and the state stay as they are.
+			if nargout > 4
+				[du, dq0, dqd0, dks, dkd, dL, dk, dd, dr, dI, dg] = redmax_hip_mex('rollout_vjp_forces', this.h, nsteps, gq, gqd, nforces);
+				grads = struct('stiffness', dk, 'damping', dd, 'qrest', dr, 'inertia', dI, 'grav', dg);
+			else
+				[du, dq0, dqd0, dks, dkd, dL] = redmax_hip_mex('rollout_vjp_forces', this.h, nsteps, gq, gqd, nforces);
+			end
+			fgrads = struct('stiffness', dks, 'damping', dkd, 'L', dL);
+		end
+
 		function [XA, XB, XU] = rolloutLinearize(this, nsteps)
 			% the linearisation of the last rolloutTape: the sensitivities XA = dx/dqA, XB = dx/dqB, XU = dx/du of every taped
 			% solve x(qA, qB, u), each nr x nr x nslots x B with (i,j,s,b) = dx_i/d(.)_j of slot s; nslots = nsteps, or

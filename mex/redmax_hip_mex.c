@@ -78,6 +78,11 @@
  *                  the model's parameters, one column per rollout: joint stiffness dk, damping dd and rest position dqrest (nr x B,
  *                  reduced DOF order), body inertia dI (6 x njoints x B, the layout of desc.I_i) and gravity dgrav (3 x B).  The
  *                  gradient of a parameter the rollouts share is the sum over B.
+ *   [du,dq0,dqd0,dks,dkd,dL,dk,dd,dqrest,dI,dgrav] = redmax_hip_mex('rollout_vjp_forces', h, nsteps, gq, gqd, nforces)
+ *                  rmx_rollout_vjp_forces on a tape that carries point forces ('tape_point_forces'): 'rollout_vjp' (the same du, dq0,
+ *                  dqd0), the gradient with respect to the stiffness dks, damping dkd and rest length dL of every force (nforces x B,
+ *                  the order of the force table; nforces: its rows) and, where more than six outputs are asked for, the five arrays
+ *                  of 'rollout_vjp_params' on such a tape.  The library refuses a tape without point forces.
  *   [tq,tqd] = redmax_hip_mex('rollout_jvp', h, nsteps, tu, tq0, tqd0)  rmx_rollout_jvp on the tape of the last 'rollout_tape': the
  *                  tangents of the whole trajectory, tq, tqd (nr x nsteps x ntan x B), for tangents of the controls tu (nr x nsteps x
  *                  ntan x B) and of the initial state tq0, tqd0 (nr x ntan x B); ntan directions per rollout, taken from the arrays'
@@ -817,6 +822,49 @@ static void cmd_rollout_vjp_params(int nlhs, mxArray* plhs[], int nrhs, const mx
     give(nlhs, plhs, out, 8);
 }
 
+/* 'rollout_vjp_forces': rmx_rollout_vjp_forces shard by shard.  nforces: the rows of the force table the shards' models carry (the
+ * gateway cannot ask the library for it); the five model arrays are formed only where they are asked for (nlhs > 6). */
+static void cmd_rollout_vjp_forces(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 6)
+        die("usage: [du,dq0,dqd0,dks,dkd,dL,dk,dd,dqrest,dI,dgrav] = redmax_hip_mex('rollout_vjp_forces', h, nsteps, gq, gqd, nforces)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_vjp_forces: nsteps must be at least 1");
+    const double* gq = traj_arg(prhs[3], h, nsteps, "gq");
+    const double* gqd = traj_arg(prhs[4], h, nsteps, "gqd");
+    if (mxGetNumberOfElements(prhs[5]) != 1) die("rollout_vjp_forces: nforces must be a scalar");
+    const double nfd = mxGetScalar(prhs[5]);
+    if (!(nfd >= 0.0 && nfd <= (double)RMX_PF_MAX_FORCES) || nfd != (double)(int)nfd) die("rollout_vjp_forces: nforces must be an integer in 0 .. RMX_PF_MAX_FORCES");
+    const size_t nf = (size_t)nfd, nr = (size_t)h->nr, per = nr * (size_t)nsteps, perI = 6 * (size_t)h->njoints;
+    const size_t dims[3] = {nr, (size_t)nsteps, (size_t)h->B}, dimsI[3] = {6, (size_t)h->njoints, (size_t)h->B};
+    const int model = nlhs > 6;
+    mxArray* out[11];
+    out[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    for (int i = 1; i < 3; ++i) out[i] = mxCreateDoubleMatrix(nr, (size_t)h->B, mxREAL);       /* dq0, dqd0 */
+    for (int i = 3; i < 6; ++i) out[i] = mxCreateDoubleMatrix(nf, (size_t)h->B, mxREAL);       /* dks, dkd, dL */
+    for (int i = 6; i < 9; ++i) out[i] = mxCreateDoubleMatrix(model ? nr : 0, model ? (size_t)h->B : 0, mxREAL);      /* dk, dd, dqrest */
+    out[9] = model ? mxCreateNumericArray(3, dimsI, mxDOUBLE_CLASS, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    out[10] = mxCreateDoubleMatrix(model ? 3 : 0, model ? (size_t)h->B : 0, mxREAL);
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_force_grads fg;
+        fg.stiffness = nf ? mxGetPr(out[3]) + f * nf : NULL;
+        fg.damping = nf ? mxGetPr(out[4]) + f * nf : NULL;
+        fg.L = nf ? mxGetPr(out[5]) + f * nf : NULL;
+        rmx_param_grads pg;
+        pg.stiffness = model ? mxGetPr(out[6]) + f * nr : NULL;
+        pg.damping = model ? mxGetPr(out[7]) + f * nr : NULL;
+        pg.qrest = model ? mxGetPr(out[8]) + f * nr : NULL;
+        pg.inertia = model ? mxGetPr(out[9]) + f * perI : NULL;
+        pg.grav = model ? mxGetPr(out[10]) + f * 3 : NULL;
+        if (rmx_rollout_vjp_forces(b, nsteps, gq + f * per, gqd + f * per, mxGetPr(out[0]) + f * per, mxGetPr(out[1]) + f * nr,
+                                   mxGetPr(out[2]) + f * nr, &pg, &fg))
+            die_rmx("rmx_rollout_vjp_forces");
+    }
+    give(nlhs, plhs, out, 11);
+}
+
 static void cmd_rollout_linearize(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     handle_t* h = get_handle(nrhs, prhs);
     if (nrhs < 3) die("usage: [XA,XB,XU] = redmax_hip_mex('rollout_linearize', h, nsteps)");
@@ -1340,7 +1388,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
+                                             "rollout_vjp_params", "rollout_vjp_forces", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
                                              "rollout_points", "rollout_cost", "rollout_frames", "rollout_cost_frames", "rollout_search", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
@@ -1466,6 +1514,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_linearize(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_vjp_params")) {
         cmd_rollout_vjp_params(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_vjp_forces")) {
+        cmd_rollout_vjp_forces(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_jvp")) {
         cmd_rollout_jvp(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_lqr")) {

@@ -30,6 +30,7 @@ SYMBOLS = (
     "rmx_rollout_vjp_feedback", "rmx_rollout_vjp_feedback_device",
     "rmx_rollout_linearize", "rmx_rollout_linearize_device",
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
+    "rmx_rollout_vjp_forces", "rmx_rollout_vjp_forces_device",
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
     "rmx_rollout_lqr", "rmx_rollout_lqr_device",
     "rmx_rollout_tape_feedback_box", "rmx_rollout_tape_feedback_box_device", "rmx_rollout_lqr_box", "rmx_rollout_lqr_box_device",
@@ -97,6 +98,10 @@ class ParamGrads(C.Structure):
     _fields_ = [("stiffness", C.c_void_p), ("damping", C.c_void_p), ("qrest", C.c_void_p), ("inertia", C.c_void_p), ("grav", C.c_void_p)]
 
 
+class ForceGrads(C.Structure):      # rmx_force_grads: host pointers in the host form, device pointers in the _device form
+    _fields_ = [("stiffness", C.c_void_p), ("damping", C.c_void_p), ("L", C.c_void_p)]
+
+
 class Feedback(C.Structure):      # rmx_feedback: host pointers in the host form, device pointers in the _device form
     _fields_ = [("uff", C.c_void_p), ("K", C.c_void_p), ("xref", C.c_void_p), ("per_rollout", C.c_int)]
 
@@ -156,6 +161,7 @@ class SearchOut(C.Structure):      # rmx_search_out
 
 FEEDBACK_GRAD_NAMES = ("duff", "dK", "dxref", "dq0", "dqd0")      # the members of rmx_feedback_grads, in their order
 PARAM_NAMES = ("stiffness", "damping", "qrest", "inertia", "grav")      # the members of rmx_param_grads, in their order
+FORCE_PARAM_NAMES = ("force_stiffness", "force_damping", "force_L")      # the members of rmx_force_grads, in their order
 
 
 class History(C.Structure):
@@ -253,6 +259,8 @@ def lib():
     L.rmx_rollout_search_device.argtypes = L.rmx_rollout_search.argtypes
     L.rmx_rollout_vjp_params.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads)]
     L.rmx_rollout_vjp_params_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads)]
+    L.rmx_rollout_vjp_forces.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(ParamGrads), C.POINTER(ForceGrads)]
+    L.rmx_rollout_vjp_forces_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(ParamGrads), C.POINTER(ForceGrads)]
     L.rmx_step_ticks.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.rmx_energy.argtypes = [vp, _dp, _dp]
     L.rmx_last_step_ms.argtypes = [vp]

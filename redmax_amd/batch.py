@@ -106,6 +106,8 @@ class BatchSim:
                 self._L.rmx_model_destroy(self._model)
                 self._model = None
                 raise _abi.RedMaxHipError("rmx_model_set_point_forces failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+        self.nforces = int(npf)                          # rows of the force table (the rows of rollout_vjp_forces' force gradients)
+        self._force_values = np.array([[pf[i].stiffness, pf[i].damping, pf[i].L] for i in range(npf)], dtype=np.float64).reshape(npf, 3)
         self.nsph = self._L.rmx_model_nsph(self._model)
         self.B = int(batch)
         self.device = int(device)
@@ -620,6 +622,43 @@ class BatchSim:
         pg = _abi.ParamGrads(stiffness_ptr or None, damping_ptr or None, qrest_ptr or None, inertia_ptr or None, grav_ptr or None)
         _abi.check(self._L.rmx_rollout_vjp_params_device(self._batch, int(nsteps), _vp(gq_ptr), _vp(gqd_ptr), _vp(du_ptr), _vp(dq0_ptr),
                                                          _vp(dqd0_ptr), C.byref(pg)), "rmx_rollout_vjp_params_device")
+
+    def rollout_vjp_forces(self, nsteps, gq, gqd, want=_abi.FORCE_PARAM_NAMES, model=(), initial_state=True):
+        """rmx_rollout_vjp_forces on the tape of the last rollout_tape / rollout_feedback of a sim whose tape carries point forces
+        (tape_forces): rollout_vjp's sweep for the cotangents gq, gqd [B][nsteps][nr], the gradient with respect to the constants of
+        the force table and, with `model`, rollout_vjp_params' gradients on such a tape.  Returns (du, dq0, dqd0, grads): the first
+        three are rollout_vjp's (the same bits); grads maps every name in `want` ("force_stiffness", "force_damping", "force_L":
+        [B][nforces] each, one row per rollout in the order of the scene's point forces; a point-point force has no rest length, its
+        "force_L" entry is 0) and every name in `model` (rollout_vjp_params' names and shapes) to its rows.  `want` and `model` may
+        each be empty, not both.  The gradient of a constant the rollouts share is the sum over the batch.  Neither the state nor the
+        tape changes."""
+        nsteps = int(nsteps)
+        want = _names("rollout_vjp_forces", "want", want, _abi.FORCE_PARAM_NAMES, True)
+        model = _names("rollout_vjp_forces", "model", model, _abi.PARAM_NAMES, True)
+        if not want and not model:
+            raise ValueError("rollout_vjp_forces: want and model name no output")
+        gq, gqd = _f64_joint("rollout_vjp_forces", ("gq", "gqd"), (gq, gqd), (self.B, nsteps, self.nr))
+        du, dq0, dqd0 = self._vjp_outputs(nsteps, initial_state)
+        shapes = self._param_shapes()
+        grads = {w: np.zeros((self.B, self.nforces)) for w in want}
+        grads.update({w: np.zeros((self.B,) + shapes[w]) for w in model})
+        pg = _abi.ParamGrads(*[_addr(grads.get(n)) for n in _abi.PARAM_NAMES])
+        fg = _abi.ForceGrads(*[_addr(grads.get(n)) for n in _abi.FORCE_PARAM_NAMES])
+        _abi.check(self._L.rmx_rollout_vjp_forces(self._batch, nsteps, _abi.dptr(gq), _abi.dptr(gqd), _abi.dptr(du), _abi.dptr(dq0),
+                                                  _abi.dptr(dqd0), C.byref(pg) if model else None, C.byref(fg) if want else None),
+                   "rmx_rollout_vjp_forces")
+        return du, dq0, dqd0, grads
+
+    def rollout_vjp_forces_device(self, nsteps, gq_ptr, gqd_ptr, du_ptr, dq0_ptr=None, dqd0_ptr=None, force_stiffness_ptr=None,
+                                  force_damping_ptr=None, force_L_ptr=None, stiffness_ptr=None, damping_ptr=None, qrest_ptr=None,
+                                  inertia_ptr=None, grav_ptr=None):
+        """rollout_vjp_forces with DEVICE pointers (integers): gq, gqd, du [B][nsteps][nr]; dq0, dqd0 [B][nr], 0 / None together: not
+        formed; force_stiffness, force_damping, force_L [B][nforces]; stiffness .. grav as rollout_vjp_params_device.  0 / None: that
+        output is neither computed nor stored (not all eight)."""
+        pg = _abi.ParamGrads(stiffness_ptr or None, damping_ptr or None, qrest_ptr or None, inertia_ptr or None, grav_ptr or None)
+        fg = _abi.ForceGrads(force_stiffness_ptr or None, force_damping_ptr or None, force_L_ptr or None)
+        _abi.check(self._L.rmx_rollout_vjp_forces_device(self._batch, int(nsteps), _vp(gq_ptr), _vp(gqd_ptr), _vp(du_ptr), _vp(dq0_ptr),
+                                                         _vp(dqd0_ptr), C.byref(pg), C.byref(fg)), "rmx_rollout_vjp_forces_device")
 
     def rollout_linearize(self, nsteps, which=("XA", "XB", "XU")):
         """rmx_rollout_linearize on the tape of the last rollout_tape: the forward sensitivities of every taped solve x(qA, qB, u),

@@ -7,6 +7,7 @@
 #endif
 #include "rmx_kernels.h"
 #include "rmx_tape_pf.h"      /* k_tape_pf and its launcher: the taped rollouts of these models */
+#include "rmx_force_params.h" /* k_rollout_force_grad and its launcher: the gradients in the force constants from such a tape */
 
 // simLoop of driverRedMaxBDF1.m:57-91 (INTEG 1) / driverRedMaxBDF2.m:57-125 (INTEG 2: SDIRK2 start step, then BDF2) with the point
 // forces: k_step_bdf1 / k_step_bdf2 of the plain kernels around newton_pf, all steps of a rollout in one launch.

@@ -700,6 +700,7 @@ extern "C" int rmx_model_set_point_forces(rmx_model* m, const rmx_point_force* f
     }
     if (m->dpf) (void)hipFree(m->dpf);
     m->dpf = fresh;
+    m->npf = nforces;
     return RMX_OK;
 }
 // The switch of the taped rollouts with point forces: read by adjoint_model_refusal at every tape call, nothing else happens here.
@@ -1937,6 +1938,23 @@ static int rollout_vjp_feedback_impl(rmx_batch* b, int nsteps, const rmx_feedbac
     return rc;
 }
 
+// what k_rollout_param_grad reads (rmx_rollout_vjp_params, rmx_rollout_vjp_forces): the tape's states and z, the five outputs where
+// the kernel finds them, the listing index of the body each node carries
+static ParamArgs param_args(const rmx_model* m, const TapeView& v, const int nsteps, double* const* dev) {
+    ParamArgs pa{};
+    pa.nsteps = nsteps; pa.nslots = v.nslots; pa.bdf2 = v.bdf2;
+    pa.njoints = m->nlist; pa.h = v.h;
+    pa.q0 = v.q0; pa.qd0 = v.qd0; pa.qt = v.qt; pa.qdt = v.qdt;
+    pa.zs = v.zs;
+    pa.stiffness = dev[0]; pa.damping = dev[1]; pa.qrest = dev[2]; pa.inertia = dev[3]; pa.grav = dev[4];
+    for (int i = 0; i < MAXN; ++i) pa.lst[i] = -1;
+    for (int L = 0; L < m->nlist; ++L) {
+        const int k = m->node_of_listing[L];
+        if (k >= 0 && k < MAXN) pa.lst[k] = (short)L;
+    }
+    return pa;
+}
+
 // rmx_rollout_vjp_params: rmx_rollout_vjp's sweep in the instantiation that also stores z of every slot, then the contraction of
 // rmx_params.h over the slots with the states the tape kept.  Everything it stages lies in parts the tape call reserved.
 static int rollout_vjp_params_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
@@ -1958,17 +1976,7 @@ static int rollout_vjp_params_impl(rmx_batch* b, int nsteps, const double* gq, c
     double* dev[5];
     for (int i = 0; i < 5; ++i) dev[i] = st.dev(st.add(v.t.pg_bytes[i], nullptr, grads[i], v.pg[i]));
     a.zs = v.zs;
-    ParamArgs pa{};
-    pa.nsteps = nsteps; pa.nslots = v.nslots; pa.bdf2 = v.bdf2;
-    pa.njoints = m->nlist; pa.h = v.h;
-    pa.q0 = v.q0; pa.qd0 = v.qd0; pa.qt = v.qt; pa.qdt = v.qdt;
-    pa.zs = a.zs;
-    pa.stiffness = dev[0]; pa.damping = dev[1]; pa.qrest = dev[2]; pa.inertia = dev[3]; pa.grav = dev[4];
-    for (int i = 0; i < MAXN; ++i) pa.lst[i] = -1;
-    for (int L = 0; L < m->nlist; ++L) {
-        const int k = m->node_of_listing[L];
-        if (k >= 0 && k < MAXN) pa.lst[k] = (short)L;
-    }
+    const ParamArgs pa = param_args(m, v, nsteps, dev);
     hipError_t e = st.copy_in(b, hipSuccess);
     e = timed_launch(b, e, [&] {
         DISPATCH_NP(m->NP, launch_vjp_zs, m, b, v.integ, o, a, tape_plan(b, v.integ).fullchain);
@@ -1977,6 +1985,61 @@ static int rollout_vjp_params_impl(rmx_batch* b, int nsteps, const double* gq, c
         return el;
     });
     return tape_call_end(b, st.copy_out(b, e), st, who);
+}
+
+// rmx_rollout_vjp_forces: rmx_rollout_vjp_params on a tape that carries point forces.  The sweep that stores z and the contraction of
+// rmx_params.h run unchanged (dg/dtheta of the joint, inertia and gravity parameters does not involve the forces); the contraction of
+// rmx_force_params.h forms the rows of the force constants from the same z.  The five model arrays stage where rmx_rollout_vjp_params
+// stages them; the three force arrays through an allocation of the call's own, as rmx_rollout_linearize's outputs do.
+static int rollout_vjp_forces_impl(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                                   const rmx_param_grads* model, const rmx_force_grads* forces, const bool on_device) {
+    const std::string who = "rmx_rollout_vjp_forces";
+    if (!b || !gq || !gqd || !du) return fail(RMX_E_INVALID, who + ": null argument");
+    if ((dq0 == nullptr) != (dqd0 == nullptr)) return fail(RMX_E_INVALID, who + ": dq0 and dqd0 must be given together");
+    double* const grads[5] = {model ? model->stiffness : nullptr, model ? model->damping : nullptr, model ? model->qrest : nullptr,
+                              model ? model->inertia : nullptr, model ? model->grav : nullptr};
+    double* const fgrads[3] = {forces ? forces->stiffness : nullptr, forces ? forces->damping : nullptr, forces ? forces->L : nullptr};
+    const bool want_model = grads[0] || grads[1] || grads[2] || grads[3] || grads[4];
+    const bool want_forces = fgrads[0] || fgrads[1] || fgrads[2];
+    if (!want_model && !want_forces) return fail(RMX_E_INVALID, who + ": all outputs are null");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
+    rmx_model* m = b->m;
+    if (!b->tape_pf)
+        return fail(RMX_E_INVALID, who + ": the tape carries no point forces (rmx_model_tape_point_forces); rmx_rollout_vjp_params is the call for it");
+    if (!m->dpf) return fail(RMX_E_INVALID, who + ": the model's force table has been removed since the tape was recorded");
+    DevOpts o;
+    AdjArgs a = vjp_args(b, v, o);
+    Staging st(on_device), fst(on_device);
+    vjp_stage(st, v, a, gq, gqd, du, dq0, dqd0);
+    double *dev[5], *fdev[3];
+    for (int i = 0; i < 5; ++i) dev[i] = st.dev(st.add(v.t.pg_bytes[i], nullptr, grads[i], v.pg[i]));
+    const size_t fbytes = (size_t)b->B * m->npf * sizeof(double);
+    for (int i = 0; i < 3; ++i) fst.add(fbytes, nullptr, fgrads[i]);
+    if (int rc = fst.allocate(who, "the staging of the force gradients")) return rc;
+    for (int i = 0; i < 3; ++i) fdev[i] = fst.dev(i);
+    a.zs = v.zs;
+    const ParamArgs pa = param_args(m, v, nsteps, dev);
+    ForceArgs fa{};
+    fa.nsteps = nsteps; fa.nslots = v.nslots; fa.bdf2 = v.bdf2; fa.h = v.h;
+    fa.q0 = v.q0; fa.qd0 = v.qd0; fa.qt = v.qt; fa.qdt = v.qdt;
+    fa.zs = a.zs;
+    fa.stiffness = fdev[0]; fa.damping = fdev[1]; fa.L = fdev[2];
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] {
+        DISPATCH_NP(m->NP, launch_vjp_zs, m, b, v.integ, o, a, tape_plan(b, v.integ).fullchain);
+        hipError_t el = hipGetLastError();
+        if (el == hipSuccess && want_model) {
+            DISPATCH_NP(m->NP, launch_param_grad, m, b, pa);
+            el = hipGetLastError();
+        }
+        if (el == hipSuccess && want_forces) DISPATCH_NP(m->NP, launch_force_grad, m, b, fa);
+        return el;
+    });
+    e = wait_or_drain(b, fst.copy_out(b, st.copy_out(b, e)));
+    st.release(b, e);
+    fst.release(b, e);
+    return call_result(b, e, who);
 }
 
 // rmx_rollout_linearize: XA, XB, XU of every slot of the tape, one kernel over B * nslots wavefronts (rmx_linearize.h).  The host form
@@ -2475,6 +2538,14 @@ extern "C" int rmx_rollout_vjp_params(rmx_batch* b, int nsteps, const double* gq
 extern "C" int rmx_rollout_vjp_params_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
                                              double* d_dqd0, const rmx_param_grads* out) {
     return rollout_vjp_params_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, out, true);
+}
+extern "C" int rmx_rollout_vjp_forces(rmx_batch* b, int nsteps, const double* gq, const double* gqd, double* du, double* dq0, double* dqd0,
+                                      const rmx_param_grads* model, const rmx_force_grads* forces) {
+    return rollout_vjp_forces_impl(b, nsteps, gq, gqd, du, dq0, dqd0, model, forces, false);
+}
+extern "C" int rmx_rollout_vjp_forces_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
+                                             double* d_dqd0, const rmx_param_grads* model, const rmx_force_grads* forces) {
+    return rollout_vjp_forces_impl(b, nsteps, d_gq, d_gqd, d_du, d_dq0, d_dqd0, model, forces, true);
 }
 extern "C" int rmx_rollout_linearize(rmx_batch* b, int nsteps, double* XA, double* XB, double* XU) {
     return rollout_linearize_impl(b, nsteps, XA, XB, XU, false);

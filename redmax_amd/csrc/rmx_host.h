@@ -108,6 +108,17 @@ struct ParamArgs {
     short lst[MAXN];          // listing index of the body each node carries, -1: none (the inner nodes of a lowered multi-DOF joint)
 };
 
+// rmx_rollout_vjp_forces (rmx_force_params.h): one wavefront per rollout walks the slots of its tape, as above
+struct ForceArgs {
+    int nsteps, nslots;       // nslots per rollout: nsteps (BDF1) or nsteps + 1 (BDF2: slot nsteps holds the SDIRK2a solve)
+    int bdf2;                 // the tape's integrator
+    double h;                 // the tape's
+    const double *q0, *qd0;   // [B][nr] the state the tape started from
+    const double *qt, *qdt;   // [B][nsteps][nr] q, qdot after every step
+    const double* zs;         // [B][nslots][n] z of every slot (AdjArgs::zs)
+    double *stiffness, *damping, *L;   // [B][nforces] in the order of the force table; null: not wanted
+};
+
 // rmx_rollout_linearize (rmx_linearize.h): one wavefront per (rollout, slot) of the tape
 struct LinArgs {
     int nslots;               // per rollout: nsteps (BDF1) or nsteps + 1 (BDF2: slot nsteps holds the SDIRK2a solve)
@@ -211,6 +222,7 @@ struct rmx_model {
     int adj_help_max_batch = 0;     // trees of <= 16 nodes: adjoint batches of up to this many rollouts take a second wavefront each for M, D (part_adjhelp16.hip; 0: never)
     int w2_min_batch = 0;           // the full 32-link chain: ... and of at least this many (RMX_W2C_MIN; smaller batches keep the one-wave kernel every test pins)
     void* dpf = nullptr;            // body-to-body forces (rmx_model_set_point_forces): the PfTable of rmx_pf.h on the device, or null
+    int npf = 0;                    // ... and the number of its rows (the rows of rmx_force_grads)
     bool tape_pf = false;           // rmx_model_tape_point_forces: the four tape entries take the model while it has a force table
     bool big = false;               // more than 64 nodes: the one-workgroup-per-tree kernels of rmx_big.hip
     std::vector<struct rmx_batch*> batches;   // live batches of this model (rmx_model_set_ground_contact drains their streams only)
@@ -292,7 +304,8 @@ struct rmx_batch {
     void RMX_CAT(launch_eval_pf_, NPV)(const rmx_model* m, const rmx_batch* b, bool wantH, double eta, double* dg, double* dH); \
     void RMX_CAT(launch_step_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a); \
     void RMX_CAT(launch_energy_pf_, NPV)(const rmx_model* m, const rmx_batch* b, double* dT, double* dV); \
-    void RMX_CAT(launch_tape_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, bool feedback, const DevOpts& o, const AdjArgs& a);
+    void RMX_CAT(launch_tape_pf_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, bool feedback, const DevOpts& o, const AdjArgs& a); \
+    void RMX_CAT(launch_force_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ForceArgs& a);
 // The one-size step launchers (StepKernel of rmx_select.h; the bools are StepPlan's instantiation flags)
 // part_gconst64.hip: 64-lane plain step kernels reading the per-node constants from global memory, and the staging kernel (part_plain.hip)
 void launch_step_gconst_64(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const StepArgs& a, bool fulln);

@@ -1,6 +1,8 @@
 """A differentiable controlled BDF1 or BDF2 rollout for PyTorch: ``rollout(sim, q0, qdot0, u)`` returns the trajectory, and
 ``backward()`` of any loss on it yields dL/du, dL/dq0 and dL/dqdot0 - and, with ``params=model_params(sim)``, the gradient with respect to
 the model's own parameters (joint stiffness, damping and rest position, body inertia and mass, gravity; rmx_rollout_vjp_params_device).
+On a sim whose tape carries point forces (BatchSim(..., tape_forces=True)) ``force_params=force_params(sim)`` adds the stiffness, damping
+and rest length of every spring, damper and cable, and both keywords go through rmx_rollout_vjp_forces_device.
 
 Forward is rmx_rollout_tape_device (rmx_rollout_tape_bdf2_device under integrator=2), backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
 objective lives wholly on the PyTorch side.  Forward mode (torch.autograd.forward_ad, torch.func.jvp, torch.func.jacfwd) runs
@@ -26,7 +28,8 @@ def _function():
     class _Rollout(torch.autograd.Function):
         @staticmethod
         def forward(q0, qdot0, u, sim, h, pscale, check, integrator, names=(), *ptensors):
-            # (names, ptensors: the model parameters of rollout(params=...); the forward does not read their values)
+            # (names, ptensors: the model parameters of rollout(params=...) and the force constants of rollout(force_params=...), in
+            # that order; the forward does not read their values)
             return _tape_forward(sim, q0.contiguous(), qdot0.contiguous(), u.contiguous(), h, pscale, check, integrator)
 
         @staticmethod
@@ -35,6 +38,8 @@ def _function():
             u, sim = inputs[2], inputs[3]
             ctx.names = tuple(inputs[8]) if len(inputs) > 8 else ()
             ctx.sim, ctx.nsteps, ctx.tape = sim, u.shape[1], sim.tape_count
+            # a tape that carries point forces: rmx_rollout_vjp_forces is the entry for every parameter gradient on it
+            ctx.pf_tape = bool(getattr(sim, "nforces", 0)) and bool(sim.tapes_point_forces)
 
         @staticmethod
         def backward(ctx, gq, gqd):
@@ -52,10 +57,13 @@ def _function():
             if not ctx.names:
                 sim.rollout_vjp_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr())
                 return dq0, dqd0, du, None, None, None, None, None, None      # (apply binds forward's default names=())
-            shapes = sim._param_shapes()
+            from . import _abi
+            shapes = {n: (sim.nforces,) for n in _abi.FORCE_PARAM_NAMES} if ctx.pf_tape else {}
+            shapes.update(sim._param_shapes())
             rows = {n: torch.zeros((sim.B,) + shapes[n], dtype=torch.float64, device=dev) for n in ctx.names}
-            sim.rollout_vjp_params_device(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr(),
-                                          **{n + "_ptr": rows[n].data_ptr() for n in ctx.names})
+            entry = sim.rollout_vjp_forces_device if ctx.pf_tape else sim.rollout_vjp_params_device
+            entry(nsteps, gq.data_ptr(), gqd.data_ptr(), du.data_ptr(), dq0.data_ptr(), dqd0.data_ptr(),
+                  **{n + "_ptr": rows[n].data_ptr() for n in ctx.names})
             # one row per rollout from the library; the rollouts share the model, so the parameter's gradient is their sum
             return (dq0, dqd0, du, None, None, None, None, None, None) + tuple(rows[n].sum(dim=0) for n in ctx.names)
 
@@ -232,7 +240,39 @@ def _check_params(sim, params):
     return names, tuple(params[n] for n in names)
 
 
-def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, params=None):
+def force_params(sim):
+    """The constants of the point forces of ``sim`` (a BatchSim built with tape_forces=True) the taped rollout can be differentiated
+    by, as float64 leaf tensors [nforces] on the sim's device that hold the force table's values and require grad, in the order of the
+    scene's point forces: "force_stiffness", "force_damping" and "force_L" (the rest length; a point-point force has none, its entry
+    takes no gradient).  Pass the dict, or part of it, as ``force_params`` of rollout."""
+    import torch
+    from . import _abi
+    dev = torch.device("cuda", sim.device)
+    return {n: torch.tensor(sim._force_values[:, i].copy(), dtype=torch.float64, device=dev, requires_grad=True)
+            for i, n in enumerate(_abi.FORCE_PARAM_NAMES)}
+
+
+def _check_force_params(sim, force_params):
+    """force_params of rollout -> (names, tensors) in the order of rmx_force_grads; ValueError for anything the library cannot fill."""
+    from . import _abi
+    if not isinstance(force_params, dict):
+        raise ValueError("rollout: force_params must be a dict of tensors (force_params(sim) or part of it), got %s" % type(force_params).__name__)
+    unknown = [k for k in force_params if k not in _abi.FORCE_PARAM_NAMES]
+    if unknown:
+        raise ValueError("rollout: unknown force parameter %r (known: %s)" % (unknown[0], ", ".join(_abi.FORCE_PARAM_NAMES)))
+    if not force_params:
+        raise ValueError("rollout: force_params names no parameter (pass None for a rollout without force gradients)")
+    if not getattr(sim, "nforces", 0) or not sim.tapes_point_forces:
+        raise ValueError("rollout: force_params needs a sim whose tape carries point forces (a scene with point forces, BatchSim(..., tape_forces=True))")
+    names = tuple(n for n in _abi.FORCE_PARAM_NAMES if n in force_params)
+    for n in names:
+        _check_tensors("rollout", sim, [("force_params[%r]" % n, force_params[n])])
+        if tuple(force_params[n].shape) != (sim.nforces,):
+            raise ValueError("rollout: force_params[%r] must have shape %r, got %r" % (n, (sim.nforces,), tuple(force_params[n].shape)))
+    return names, tuple(force_params[n] for n in names)
+
+
+def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, params=None, force_params=None):
     """A controlled BDF1 (integrator=1) or BDF2 (integrator=2) rollout of every trajectory of ``sim`` (a BatchSim) that autograd can differentiate.
 
     q0, qdot0: [B][nr]; u: [B][nsteps][nr], one torque per joint and step (tau + pscale*u at step k) - float64 tensors on the sim's
@@ -250,14 +290,19 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, par
     "inertia", "grav").  backward() then also accumulates into each given tensor's .grad the gradient of the loss with respect to
     that parameter, summed over the batch (one rmx_rollout_vjp_params call).  The forward does NOT read the tensors' values: the sim
     simulates the model it was built from, so the tensors must describe that model, and a parameter update means building a new
-    BatchSim from the updated scene.  Unknown names and tensors of another shape, dtype or device raise ValueError."""
+    BatchSim from the updated scene.  Unknown names and tensors of another shape, dtype or device raise ValueError.
+    force_params: None, or a dict of force-constant tensors - force_params(sim) or any part of it ("force_stiffness", "force_damping",
+    "force_L"), on a sim whose tape carries point forces (tape_forces=True).  backward() then accumulates the gradient with respect to
+    the constants of the scene's point forces in the same way (one rmx_rollout_vjp_forces call, which on such a sim also serves
+    ``params``); the rules of ``params`` hold: the forward does not read the values, errors are ValueError."""
     _check_integrator(integrator)
     _check_inputs(sim, q0, qdot0, u)
     args = (q0, qdot0, u, sim, float(sim.opts.h if h is None else h), float(pscale), bool(check), integrator)
-    if params is None:
+    if params is None and force_params is None:
         return _function().apply(*args)
-    names, tensors = _check_params(sim, params)
-    return _function().apply(*args, names, *tensors)
+    names, tensors = _check_params(sim, params) if params is not None else ((), ())
+    fnames, ftensors = _check_force_params(sim, force_params) if force_params is not None else ((), ())
+    return _function().apply(*args, names + fnames, *tensors, *ftensors)
 
 
 def linearize(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1):

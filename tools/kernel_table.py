@@ -85,6 +85,11 @@ ROWS = (  # (name fragment, what it runs)
     ("k_tape_pf<64, 1, false>", "taped rollout with body-to-body forces, 33..64 nodes, BDF1"),
     ("k_tape_pf<64, 2, false>", "taped rollout with body-to-body forces, 33..64 nodes, BDF2"),
     ("k_tape_pf<64, 2, true>", "taped rollout with body-to-body forces, 33..64 nodes, BDF2, feedback stage"),
+    ("k_rollout_force_grad<4>", "rmx_rollout_vjp_forces (the contraction for the force constants over the slots of a tape, rmx_force_params.h; one wavefront per rollout): <= 4 nodes"),
+    ("k_rollout_force_grad<8>", "rmx_rollout_vjp_forces: 5..8 nodes"),
+    ("k_rollout_force_grad<16>", "rmx_rollout_vjp_forces: 9..16 nodes"),
+    ("k_rollout_force_grad<32>", "rmx_rollout_vjp_forces: 17..32 nodes"),
+    ("k_rollout_force_grad<64>", "rmx_rollout_vjp_forces: 33..64 nodes"),
 )
 
 
