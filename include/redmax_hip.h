@@ -1021,7 +1021,7 @@ int rmx_rollout_vjp_params_device(rmx_batch* b, int nsteps, const double* d_gq, 
  * the force constants too.  These refuse a model with a force table in the words they always had, whatever the
  * switch says: rmx_rollout_search, rmx_adjoint_bdf1, rmx_adjoint_bdf2, rmx_adjoint_controls, rmx_adjoint_track, rmx_step_euler,
  * rmx_eval_mfd, rmx_compute_values.
- * Out of scope: gradients in the attachment points of the forces; forward-mode parameter tangents; the device line search; the
+ * Out of scope: gradients in the attachment points of the forces; forward-mode tangents in the force constants; the device line search; the
  * in-library objectives; forces together with ground contact or spherical joints (rmx_model_set_point_forces refuses those). */
 int rmx_model_tape_point_forces(rmx_model* m, int enable);   /* enable: 0 or 1 */
 int rmx_model_get_tape_point_forces(const rmx_model* m);     /* 0 / 1; a null model: RMX_E_INVALID */
@@ -1059,6 +1059,55 @@ int rmx_rollout_vjp_forces(rmx_batch* b, int nsteps, const double* gq, const dou
                            const rmx_param_grads* model, const rmx_force_grads* forces);
 int rmx_rollout_vjp_forces_device(rmx_batch* b, int nsteps, const double* d_gq, const double* d_gqd, double* d_du, double* d_dq0,
                                   double* d_dqd0, const rmx_param_grads* model, const rmx_force_grads* forces);
+
+/* Forward-mode tangents of the taped rollout with respect to the model's parameters: J t for directions in joint stiffness, damping
+ * and rest position, body inertia and mass, and gravity - whole columns of the Jacobian of the trajectory, what Gauss-Newton and
+ * Levenberg-Marquardt system identification (few parameters, many residuals) ask for.  With it the taped rollout is differentiable in
+ * both modes with respect to everything rmx_rollout_vjp and rmx_rollout_vjp_params differentiate.  Added WITHOUT a change of
+ * RMX_VERSION (it stays 111): probe for the symbols.
+ *
+ * Every taped solve is g(x; qA, qB, u, theta) = 0, so the recursion is rmx_rollout_jvp's with one more term on the right,
+ *     H dx = M dqB - eta D dqA + eta^2 pscale du - (dg/dtheta) ttheta ,     dv = (dx - dqA)/eta
+ * with dg/dtheta taken at the slot's recorded x, qA, qB and eta (under BDF2 the SDIRK2a solve, slot nsteps, has its own term; its
+ * state is rebuilt as rmx_rollout_vjp_params rebuilds it).  With v = (x - qA)/eta, and per body i in the BODY frame phi = (J v)_i,
+ * beta = (J (x - qB) + eta^2 Jdot v)_i, the entry of (dg/dtheta) ttheta at DOF j is
+ *     eta^2 (tstiffness_j (x_j - qRest_j) + tdamping_j v_j - k_j tqrest_j)  +  s_j . (sum over the bodies i of j's subtree of W_i)
+ *     W_i = the wrench  tI_i o beta - eta^2 ad(phi)'(tI_i o phi) - eta^2 (0 ; tI_i[3] R_i' grav)  carried to the world frame
+ *           - eta^2 m_i (p_i x tgrav ; tgrav)
+ * (o: entry by entry; s_j the world-frame screw of joint j).  It is the transpose of rmx_rollout_vjp_params on the same tape: with
+ * that call's per-rollout rows for cotangents (gq, gqd),
+ *     <gq, tq> + <gqd, tqd> = <du, tu> + <dq0, tq0> + <dqd0, tqd0> + sum over the five groups of <grad_group[b], ttheta_group[b, t]>.
+ * The inertia entries 3 .. 5 are each "the mass", and gravity belongs to entry 3, exactly as for the gradient: a physical mass
+ * tangent is the same number in all three.  Only the `inertia` rows whose listing index maps to a node are read.
+ *
+ * rmx_rollout_jvp_params reads the tape of the preceding rmx_rollout_tape / _tape_bdf2 / _tape_feedback / _tape_feedback_box call on
+ * the batch and follows its integrator; h and pscale are the tape's (a closed-loop tape is the open-loop tape under uapp).  A tape
+ * that carries point forces is accepted: the five groups' dg/dtheta does not involve the forces, and H and D on the tape already
+ * carry them.  ntan >= 1 directions per rollout; direction t of rollout b moves the parameters by tp's rows (b, t) and u, q0, qdot0
+ * by tu, tq0, tqd0 (rmx_rollout_jvp's layouts; NULL: zero).  tq, tqd: [batch][ntan][nsteps][nr], both required.
+ *
+ * The call changes neither the batch's state nor the tape: it may be repeated with the same bits, and the other readers of the tape
+ * return the same bits before and after it.  One direction has the same bits whatever ntan is and wherever it stands in the call; a
+ * rollout's rows do not depend on its place in the batch.  With all five parameter tangents given as arrays of zeros, tq and tqd
+ * equal rmx_rollout_jvp's for the same tu, tq0, tqd0 as numbers.  Refusals (RMX_E_INVALID), in rmx_rollout_jvp's words where they
+ * coincide: "no tape", an nsteps that differs from the tape's, a null batch, tp, tq or tqd ("null argument"), "ntan < 1", all five
+ * pointers of tp NULL (the message names rmx_rollout_jvp, the call for it).  The rows of a rollout whose tape call reported a failed
+ * Newton solve are unspecified.  Both forms allocate [batch][ntan][nslots][n] doubles for the parameter term, and the host form its
+ * staging, in an allocation of the call's own, freed before it returns; the tape's workspace does not grow.
+ * The _device form: every array a DEVICE pointer (the struct itself is a host object); it returns when the kernels have finished.
+ * Out of scope: tangents in the force constants and attachment points; joint-limit constants, axes and frames, as for the
+ * gradients; models the tape calls refuse. */
+typedef struct rmx_param_tangents {   /* every pointer may be NULL (zero), but not all five */
+    const double* stiffness;   /* [batch][ntan][nr]          reduced DOF order                 */
+    const double* damping;     /* [batch][ntan][nr]                                            */
+    const double* qrest;       /* [batch][ntan][nr]                                            */
+    const double* inertia;     /* [batch][ntan][njoints][6]  listing order, layout of desc.I_i */
+    const double* grav;        /* [batch][ntan][3]                                             */
+} rmx_param_tangents;
+int rmx_rollout_jvp_params(rmx_batch* b, int nsteps, int ntan, const rmx_param_tangents* tp, const double* tu, const double* tq0,
+                           const double* tqd0, double* tq, double* tqd);
+int rmx_rollout_jvp_params_device(rmx_batch* b, int nsteps, int ntan, const rmx_param_tangents* tp, const double* d_tu,
+                                  const double* d_tq0, const double* d_tqd0, double* d_tq, double* d_tqd);
 
 /* euler() of matlab-simple/testRedMax.m:67-109 (BASELINE.json configs[0]): nsteps linearly-implicit Euler steps,
  *   Mr = J'MmJ ; (Mr + h Dr - h^2 Kr) qdot1 = Mr qdot0 + h (J'(fm - Mm Jdot qdot0) + fr) ; q1 = q0 + h qdot1.

@@ -277,6 +277,36 @@ classdef HipSim < handle
 			[tq, tqd] = redmax_hip_mex('rollout_jvp', this.h, nsteps, tu, tq0, tqd0);
 		end
 
+		function [tq, tqd] = rolloutJvpParams(this, nsteps, tp, tu, tq0, tqd0)
+			% forward-mode tangents of the last rolloutTape with respect to the model's parameters: rolloutJvp with the parameter
+			% term on the right of every taped solve.  tp: a struct with any of the fields stiffness, damping, qrest (nr x T x B,
+			% per reduced DOF), inertia (6 x njoints x T x B, the layout of I_i: a mass tangent is the same number in entries
+			% 4..6) and grav (3 x T x B), at least one; a missing or empty field means zero.  tu, tq0, tqd0 as rolloutJvp
+			% (optional).  tq, tqd (nr x nsteps x T x B).  It is the transpose of rolloutVjpParams: with its outputs for cotangents
+			% gq, gqd, gq(:)'*tq(:) + gqd(:)'*tqd(:) equals rolloutJvp's right-hand side plus dk(:)'*tp.stiffness(:) + ... over
+			% the five groups.  Columns of the Jacobian for Gauss-Newton / Levenberg-Marquardt identification: one unit direction
+			% per parameter entry, all in one call.  The tape and the state stay as they are.
+			if nargin < 4
+				tu = [];
+			end
+			if nargin < 5
+				tq0 = [];
+			end
+			if nargin < 6
+				tqd0 = [];
+			end
+			names = {'stiffness', 'damping', 'qrest', 'inertia', 'grav'};
+			args = cell(1, 5);
+			for i = 1:5
+				if isfield(tp, names{i})
+					args{i} = tp.(names{i});
+				else
+					args{i} = [];
+				end
+			end
+			[tq, tqd] = redmax_hip_mex('rollout_jvp_params', this.h, nsteps, args{:}, tu, tq0, tqd0);
+		end
+
 		function [kff, K, expected, notpd] = rolloutLqr(this, nsteps, lx, lu, Q, R, mu)
 			% the Riccati sweep of iLQR on the BDF1 tape of the last rolloutTape / rolloutFeedback, in one launch: for the cost's
 			% gradients at the nominal lx (2nr x nsteps x B), lu (nr x nsteps x B) and its Hessians Q (2nr x 2nr x nsteps, shared,

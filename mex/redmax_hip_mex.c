@@ -87,6 +87,10 @@
  *                  tangents of the whole trajectory, tq, tqd (nr x nsteps x ntan x B), for tangents of the controls tu (nr x nsteps x
  *                  ntan x B) and of the initial state tq0, tqd0 (nr x ntan x B); ntan directions per rollout, taken from the arrays'
  *                  sizes.  [] for any of the three: zero (not all three).
+ *   [tq,tqd] = redmax_hip_mex('rollout_jvp_params', h, nsteps, tk, td, tqrest, tI, tgrav, tu, tq0, tqd0)  rmx_rollout_jvp_params on
+ *                  the same tape: 'rollout_jvp' with tangents of the model's parameters - tk, td, tqrest (nr x ntan x B: stiffness,
+ *                  damping, rest position per reduced DOF), tI (6 x njoints x ntan x B, the layout of desc.I_i) and tgrav (3 x ntan
+ *                  x B).  [] for any of the eight: zero (not all five parameter arrays); ntan from the first non-empty array.
  *   [kff,K,expected,notpd] = redmax_hip_mex('rollout_lqr', h, nsteps, lx, lu, Q, R [, mu])  rmx_rollout_lqr on the BDF1 tape of the
  *                  last 'rollout_tape' / 'rollout_feedback': the Riccati sweep of iLQR.  lx (2nr x nsteps x B), lu (nr x nsteps x B):
  *                  the cost's gradients at the nominal; Q: 2nr x 2nr x nsteps (shared) or 2nr x 2nr x nsteps x B, R: nr x nr, both
@@ -953,14 +957,17 @@ static void cmd_rollout_lqr(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
 
 /* one tangent argument of 'rollout_jvp': [] (NULL: zero) or a double array of `per` * ntan * B elements; *ntan is set by the first
  * array given and the others must agree */
-static const double* tangent_arg(const mxArray* a, const handle_t* h, size_t per, size_t* ntan, const char* what) {
+static const double* tangent_arg_of(const char* cmd, const mxArray* a, const handle_t* h, size_t per, size_t* ntan, const char* what) {
     if (mxIsEmpty(a)) return NULL;
     const size_t n = mxGetNumberOfElements(a), unit = per * (size_t)h->B;
-    if (!mxIsDouble(a) || mxIsComplex(a) || n % unit != 0 || (*ntan && n != unit * *ntan))
-        mexErrMsgIdAndTxt("redmax:hip", "rollout_jvp: %s must be a real double array of %d x ntan x %d elements, the same ntan in every array",
-                          what, (int)per, h->B);
+    if (!mxIsDouble(a) || mxIsComplex(a) || !unit || n % unit != 0 || (*ntan && n != unit * *ntan))
+        mexErrMsgIdAndTxt("redmax:hip", "%s: %s must be a real double array of %d x ntan x %d elements, the same ntan in every array",
+                          cmd, what, (int)per, h->B);
     *ntan = n / unit;
     return mxGetPr(a);
+}
+static const double* tangent_arg(const mxArray* a, const handle_t* h, size_t per, size_t* ntan, const char* what) {
+    return tangent_arg_of("rollout_jvp", a, h, per, ntan, what);
 }
 
 static void cmd_rollout_jvp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -982,6 +989,44 @@ static void cmd_rollout_jvp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
         if (rmx_rollout_jvp(b, nsteps, (int)ntan, table_at(tu, 1, f, ntan * per), table_at(tq0, 1, f, ntan * nr), table_at(tqd0, 1, f, ntan * nr),
                             mxGetPr(out[0]) + f * ntan * per, mxGetPr(out[1]) + f * ntan * per))
             die_rmx("rmx_rollout_jvp");
+    }
+    give(nlhs, plhs, out, 2);
+}
+
+/* 'rollout_jvp_params': rmx_rollout_jvp_params shard by shard.  Eight tangent arguments, [] is NULL; ntan comes from the first
+ * non-empty one, as 'rollout_jvp' reads it. */
+static void cmd_rollout_jvp_params(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    handle_t* h = get_handle(nrhs, prhs);
+    if (nrhs < 11)
+        die("usage: [tq,tqd] = redmax_hip_mex('rollout_jvp_params', h, nsteps, tk, td, tqrest, tI, tgrav, tu, tq0, tqd0)");
+    const int nsteps = (int)mxGetScalar(prhs[2]);
+    if (nsteps < 1) die("rollout_jvp_params: nsteps must be at least 1");
+    const char* const cmd = "rollout_jvp_params";
+    const size_t nr = (size_t)h->nr, per = nr * (size_t)nsteps, perI = 6 * (size_t)h->njoints;
+    size_t ntan = 0;
+    const double* tk = tangent_arg_of(cmd, prhs[3], h, nr, &ntan, "tk");             /* nr x ntan x B */
+    const double* td = tangent_arg_of(cmd, prhs[4], h, nr, &ntan, "td");
+    const double* tr = tangent_arg_of(cmd, prhs[5], h, nr, &ntan, "tqrest");
+    const double* tI = tangent_arg_of(cmd, prhs[6], h, perI, &ntan, "tI");           /* 6 x njoints x ntan x B */
+    const double* tg = tangent_arg_of(cmd, prhs[7], h, 3, &ntan, "tgrav");           /* 3 x ntan x B */
+    const double* tu = tangent_arg_of(cmd, prhs[8], h, per, &ntan, "tu");            /* nr x nsteps x ntan x B */
+    const double* tq0 = tangent_arg_of(cmd, prhs[9], h, nr, &ntan, "tq0");
+    const double* tqd0 = tangent_arg_of(cmd, prhs[10], h, nr, &ntan, "tqd0");
+    if (!ntan) ntan = 1;      /* (every tangent empty: the library refuses it in its own words) */
+    const size_t dims[4] = {nr, (size_t)nsteps, ntan, (size_t)h->B};
+    mxArray* const out[2] = {mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL), mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL)};
+    for (int s = 0; s < h->nshards; ++s) {     /* shard by shard: every shard's batch holds its own tape */
+        size_t f;
+        rmx_batch* b = shard(h, s, &f);
+        rmx_param_tangents tp;
+        tp.stiffness = table_at(tk, 1, f, ntan * nr);
+        tp.damping = table_at(td, 1, f, ntan * nr);
+        tp.qrest = table_at(tr, 1, f, ntan * nr);
+        tp.inertia = table_at(tI, 1, f, ntan * perI);
+        tp.grav = table_at(tg, 1, f, ntan * 3);
+        if (rmx_rollout_jvp_params(b, nsteps, (int)ntan, &tp, table_at(tu, 1, f, ntan * per), table_at(tq0, 1, f, ntan * nr),
+                                   table_at(tqd0, 1, f, ntan * nr), mxGetPr(out[0]) + f * ntan * per, mxGetPr(out[1]) + f * ntan * per))
+            die_rmx("rmx_rollout_jvp_params");
     }
     give(nlhs, plhs, out, 2);
 }
@@ -1388,7 +1433,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * scratch buffers or the counters of a launch in flight, and would clear its pending mark without taking the event time. */
     static const char* const needs_idle[] = {"set", "get", "gather", "euler", "eval", "values", "energy", "getcharts", "setcharts", "ticks",
                                              "adjoint", "adjoint_controls", "adjoint_track", "rollout_tape", "rollout_vjp", "rollout_linearize",
-                                             "rollout_vjp_params", "rollout_vjp_forces", "rollout_jvp", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
+                                             "rollout_vjp_params", "rollout_vjp_forces", "rollout_jvp", "rollout_jvp_params", "rollout_feedback", "rollout_vjp_feedback", "rollout_lqr", "rollout_feedback_box", "rollout_lqr_box",
                                              "rollout_points", "rollout_cost", "rollout_frames", "rollout_cost_frames", "rollout_search", NULL};
     for (int i = 0; needs_idle[i]; ++i)
         if (!strcmp(cmd, needs_idle[i]) && get_handle(nrhs, prhs)->pending)
@@ -1518,6 +1563,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         cmd_rollout_vjp_forces(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_jvp")) {
         cmd_rollout_jvp(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(cmd, "rollout_jvp_params")) {
+        cmd_rollout_jvp_params(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(cmd, "rollout_lqr")) {
         cmd_rollout_lqr(nlhs, plhs, nrhs, prhs, 0);
     } else if (!strcmp(cmd, "rollout_feedback_box")) {

@@ -32,6 +32,7 @@ SYMBOLS = (
     "rmx_rollout_vjp_params", "rmx_rollout_vjp_params_device",
     "rmx_rollout_vjp_forces", "rmx_rollout_vjp_forces_device",
     "rmx_rollout_jvp", "rmx_rollout_jvp_device",
+    "rmx_rollout_jvp_params", "rmx_rollout_jvp_params_device",
     "rmx_rollout_lqr", "rmx_rollout_lqr_device",
     "rmx_rollout_tape_feedback_box", "rmx_rollout_tape_feedback_box_device", "rmx_rollout_lqr_box", "rmx_rollout_lqr_box_device",
     "rmx_rollout_points", "rmx_rollout_points_device", "rmx_rollout_cost", "rmx_rollout_cost_device",
@@ -95,6 +96,10 @@ class PointForce(C.Structure):
 
 
 class ParamGrads(C.Structure):
+    _fields_ = [("stiffness", C.c_void_p), ("damping", C.c_void_p), ("qrest", C.c_void_p), ("inertia", C.c_void_p), ("grav", C.c_void_p)]
+
+
+class ParamTangents(C.Structure):      # rmx_param_tangents: host pointers in the host form, device pointers in the _device form
     _fields_ = [("stiffness", C.c_void_p), ("damping", C.c_void_p), ("qrest", C.c_void_p), ("inertia", C.c_void_p), ("grav", C.c_void_p)]
 
 
@@ -238,6 +243,8 @@ def lib():
     L.rmx_rollout_linearize_device.argtypes = [vp, C.c_int, vp, vp, vp]
     L.rmx_rollout_jvp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.rmx_rollout_jvp_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.rmx_rollout_jvp_params.argtypes = [vp, C.c_int, C.c_int, C.POINTER(ParamTangents), _dp, _dp, _dp, _dp, _dp]
+    L.rmx_rollout_jvp_params_device.argtypes = [vp, C.c_int, C.c_int, C.POINTER(ParamTangents), vp, vp, vp, vp, vp]
     L.rmx_rollout_lqr.argtypes = [vp, C.c_int, C.POINTER(LqrCost), C.POINTER(LqrGains)]
     L.rmx_rollout_lqr_device.argtypes = L.rmx_rollout_lqr.argtypes
     L.rmx_rollout_tape_feedback_box.argtypes = [vp, C.POINTER(Opts), C.c_int, C.c_int, C.c_double, C.POINTER(Feedback), C.POINTER(Box), _dp, _dp, _dp,

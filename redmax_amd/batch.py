@@ -711,6 +711,54 @@ class BatchSim:
         _abi.check(self._L.rmx_rollout_jvp_device(self._batch, int(nsteps), int(ntan), _vp(tu_ptr), _vp(tq0_ptr), _vp(tqd0_ptr), _vp(tq_ptr),
                                                   _vp(tqd_ptr)), "rmx_rollout_jvp_device")
 
+    def rollout_jvp_params(self, nsteps, tparams, tu=None, tq0=None, tqd0=None):
+        """rmx_rollout_jvp_params on the tape of the last rollout_tape: the tangents of the whole trajectory for tangents of the model's
+        parameters - rollout_jvp with the parameter term on the right of every taped solve.  tparams: a dict over "stiffness",
+        "damping", "qrest" ([B][T][nr], reduced DOF order), "inertia" ([B][T][njoints][6], listing order, the layout of desc.I_i: a
+        mass tangent is the same number in entries 3 .. 5) and "grav" ([B][T][3]); at least one name.  Direction t of rollout b moves
+        the parameters by the rows (b, t) and, where given, u, q0 and qdot0 by tu, tq0, tqd0 (rollout_jvp's shapes).  Returns
+        (tq, tqd), both [B][T][nsteps][nr].  Every input without its T axis ([B] + shape) is one direction, and the T axis is dropped
+        again in the result.  It is the transpose of rollout_vjp_params.  Neither the state nor the tape changes."""
+        who = "rollout_jvp_params"
+        nsteps = int(nsteps)
+        if not isinstance(tparams, dict):
+            raise ValueError("%s: tparams must be a dict of arrays over %s, got %s" % (who, ", ".join(_abi.PARAM_NAMES), type(tparams).__name__))
+        unknown = [k for k in tparams if k not in _abi.PARAM_NAMES]
+        if unknown:
+            raise ValueError("%s: unknown model parameter %r (known: %s)" % (who, unknown[0], ", ".join(_abi.PARAM_NAMES)))
+        if not tparams:
+            raise ValueError("%s: tparams names no parameter (rollout_jvp is the call for tangents of u, q0 and qdot0 alone)" % who)
+        tail = {"tparams[%r]" % n: s for n, s in self._param_shapes().items()}
+        tail.update({"tu": (nsteps, self.nr), "tq0": (self.nr,), "tqd0": (self.nr,)})
+        given = [("tparams[%r]" % n, tparams[n]) for n in _abi.PARAM_NAMES if n in tparams] + [("tu", tu), ("tq0", tq0), ("tqd0", tqd0)]
+        arrs = {n: np.ascontiguousarray(a, dtype=np.float64) for n, a in given if a is not None}
+        single = all(a.ndim == 1 + len(tail[n]) for n, a in arrs.items())
+        if single:
+            arrs = {n: np.ascontiguousarray(a[:, None]) for n, a in arrs.items()}
+        Ts = sorted({a.shape[1] for n, a in arrs.items() if a.ndim == 2 + len(tail[n])})
+        if len(Ts) > 1:
+            raise ValueError("%s: every tangent must carry the same number of directions, got %s" % (who, _and("%d" % t for t in Ts)))
+        T = Ts[0] if Ts else 1
+        for n, a in arrs.items():
+            if a.shape != (self.B, T) + tail[n]:
+                raise ValueError("%s: %s must have shape %r - or, every input alike, that shape without the direction axis -, got %r"
+                                 % (who, n, (self.B, T) + tail[n], a.shape[:1] + a.shape[2:] if single else a.shape))
+        tp = _abi.ParamTangents(*[_addr(arrs.get("tparams[%r]" % n)) for n in _abi.PARAM_NAMES])
+        tq = np.empty((self.B, T, nsteps, self.nr))
+        tqd = np.empty_like(tq)
+        _abi.check(self._L.rmx_rollout_jvp_params(self._batch, nsteps, T, C.byref(tp), _abi.dptr(arrs.get("tu")), _abi.dptr(arrs.get("tq0")),
+                                                  _abi.dptr(arrs.get("tqd0")), _abi.dptr(tq), _abi.dptr(tqd)), "rmx_rollout_jvp_params")
+        return (tq[:, 0], tqd[:, 0]) if single else (tq, tqd)
+
+    def rollout_jvp_params_device(self, nsteps, ntan, tq_ptr, tqd_ptr, stiffness_ptr=None, damping_ptr=None, qrest_ptr=None,
+                                  inertia_ptr=None, grav_ptr=None, tu_ptr=None, tq0_ptr=None, tqd0_ptr=None):
+        """rollout_jvp_params with DEVICE pointers (integers): stiffness, damping, qrest [B][ntan][nr], inertia [B][ntan][njoints][6],
+        grav [B][ntan][3], 0 / None: zero (not all five); tu [B][ntan][nsteps][nr], tq0, tqd0 [B][ntan][nr], 0 / None: zero; tq, tqd
+        [B][ntan][nsteps][nr]."""
+        tp = _abi.ParamTangents(stiffness_ptr or None, damping_ptr or None, qrest_ptr or None, inertia_ptr or None, grav_ptr or None)
+        _abi.check(self._L.rmx_rollout_jvp_params_device(self._batch, int(nsteps), int(ntan), C.byref(tp), _vp(tu_ptr), _vp(tq0_ptr),
+                                                         _vp(tqd0_ptr), _vp(tq_ptr), _vp(tqd_ptr)), "rmx_rollout_jvp_params_device")
+
     def rollout_lqr(self, nsteps, lx, lu, Q, R, mu=0.0, mu_b=None):
         """rmx_rollout_lqr on the BDF1 tape of the last rollout_tape / rollout_feedback: the Riccati sweep of iLQR (the recursion of
         ilqr.backward_pass, include/redmax_hip.h) for the cost's gradients lx [B][nsteps][2nr], lu [B][nsteps][nr] at the nominal and

@@ -4,6 +4,7 @@
 #include "rmx_linearize.h"
 #include "rmx_jvp.h"
 #include "rmx_params.h"
+#include "rmx_jvp_params.h"
 #include "rmx_cost.h"
 #if RMX_NP <= 32
 #include "rmx_lqr.h"
@@ -123,6 +124,13 @@ void RMX_CAT(launch_search_, RMX_NP)(const rmx_model* m, const rmx_batch* b, con
 void RMX_CAT(launch_jvp_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a) {
     const dim3 grid((unsigned)((size_t)b->B * a.nchunks)), block(64);
     k_rollout_jvp<RMX_NP><<<grid, block, 0, b->stream>>>(m->dm, a);
+}
+
+// rmx_rollout_jvp_params: r = (dg/dtheta) ttheta of every (rollout, slot, direction), then the sweep that subtracts it
+void RMX_CAT(launch_jvp_params_, RMX_NP)(const rmx_model* m, const rmx_batch* b, const ParamRhsArgs& p, const JvpArgs& a) {
+    const dim3 rgrid((unsigned)((size_t)b->B * p.nslots)), grid((unsigned)((size_t)b->B * a.nchunks)), block(64);
+    RMX_LAUNCH((k_rollout_param_rhs<RMX_NP>), rgrid, block, m->smem_bytes, b->stream, m->dm, p);
+    k_rollout_jvp<RMX_NP, true><<<grid, block, 0, b->stream>>>(m->dm, a);
 }
 
 // rmx_rollout_points / rmx_rollout_cost, and with `frames` rmx_rollout_frames / rmx_rollout_cost_frames: one wavefront per (rollout,

@@ -1938,6 +1938,15 @@ static int rollout_vjp_feedback_impl(rmx_batch* b, int nsteps, const rmx_feedbac
     return rc;
 }
 
+// the listing index of the body each node carries, -1: none (ParamArgs::lst, ParamRhsArgs::lst)
+static void listing_of_nodes(const rmx_model* m, short (&lst)[MAXN]) {
+    for (int i = 0; i < MAXN; ++i) lst[i] = -1;
+    for (int L = 0; L < m->nlist; ++L) {
+        const int k = m->node_of_listing[L];
+        if (k >= 0 && k < MAXN) lst[k] = (short)L;
+    }
+}
+
 // what k_rollout_param_grad reads (rmx_rollout_vjp_params, rmx_rollout_vjp_forces): the tape's states and z, the five outputs where
 // the kernel finds them, the listing index of the body each node carries
 static ParamArgs param_args(const rmx_model* m, const TapeView& v, const int nsteps, double* const* dev) {
@@ -1947,11 +1956,7 @@ static ParamArgs param_args(const rmx_model* m, const TapeView& v, const int nst
     pa.q0 = v.q0; pa.qd0 = v.qd0; pa.qt = v.qt; pa.qdt = v.qdt;
     pa.zs = v.zs;
     pa.stiffness = dev[0]; pa.damping = dev[1]; pa.qrest = dev[2]; pa.inertia = dev[3]; pa.grav = dev[4];
-    for (int i = 0; i < MAXN; ++i) pa.lst[i] = -1;
-    for (int L = 0; L < m->nlist; ++L) {
-        const int k = m->node_of_listing[L];
-        if (k >= 0 && k < MAXN) pa.lst[k] = (short)L;
-    }
+    listing_of_nodes(m, pa.lst);
     return pa;
 }
 
@@ -2109,6 +2114,64 @@ static int rollout_jvp_impl(rmx_batch* b, int nsteps, int ntan, const double* tu
     hipError_t e = st.copy_in(b, hipSuccess);
     e = timed_launch(b, e, [&] { DISPATCH_NP(m->NP, launch_jvp, m, b, a); return hipSuccess; });
     return tape_call_end(b, st.copy_out(b, e), st, who);
+}
+
+// rmx_rollout_jvp_params: rmx_rollout_jvp's sweep with the parameter term on the right of every slot (rmx_jvp_params.h): one kernel over
+// B * nslots wavefronts forms r = (dg/dtheta) ttheta, the sweep's RHS instantiation subtracts it.  r and, in the host form, the tangent
+// arrays live in an allocation of the call's own, freed before it returns; the tape's workspace does not grow.
+static int rollout_jvp_params_impl(rmx_batch* b, int nsteps, int ntan, const rmx_param_tangents* tp, const double* tu, const double* tq0,
+                                   const double* tqd0, double* tq, double* tqd, const bool on_device) {
+    const std::string who = "rmx_rollout_jvp_params";
+    if (!b || !tp || !tq || !tqd) return fail(RMX_E_INVALID, who + ": null argument");
+    if (ntan < 1) return fail(RMX_E_INVALID, who + ": ntan < 1");
+    const double* const tans[5] = {tp->stiffness, tp->damping, tp->qrest, tp->inertia, tp->grav};
+    if (!tans[0] && !tans[1] && !tans[2] && !tans[3] && !tans[4])
+        return fail(RMX_E_INVALID, who + ": all parameter tangents are null; rmx_rollout_jvp is the call for it");
+    TapeView v;
+    if (int rc = tape_view(b, nsteps, who, v)) return rc;
+    rmx_model* m = b->m;
+    JvpArgs a{};
+    a.nsteps = nsteps; a.nslots = v.nslots; a.bdf2 = v.bdf2;
+    a.ntan = ntan;
+    a.nchunks = (ntan + JVP_CHUNK - 1) / JVP_CHUNK;
+    a.h = v.h; a.pscale = v.pscale;
+    a.Hs = v.Hs; a.Ms = v.Ms; a.Ds = v.Ds;
+    if ((size_t)b->B * a.nchunks > (size_t)0x7fffffff) return fail(RMX_E_INVALID, who + ": batch * chunks of directions exceeds the grid");
+    if ((size_t)b->B * a.nslots > (size_t)0x7fffffff) return fail(RMX_E_INVALID, who + ": batch * slots exceeds the grid");
+    const size_t bytes_traj = ntan * v.t.bytes_traj, bytes_state = ntan * v.t.bytes_state;
+    const size_t bytes_r = (size_t)b->B * ntan * a.nslots * m->n * sizeof(double);
+    enum { S_TQ, S_TQD, S_TU, S_TQ0, S_TQD0, S_TP };      // the outputs first, the five parameter tangents last
+    Staging st(on_device);
+    st.add(bytes_traj, nullptr, tq);
+    st.add(bytes_traj, nullptr, tqd);
+    st.add(bytes_traj, tu, nullptr);
+    st.add(bytes_state, tq0, nullptr);
+    st.add(bytes_state, tqd0, nullptr);
+    for (int i = 0; i < 5; ++i) st.add(ntan * v.t.pg_bytes[i], tans[i], nullptr);
+    if (!bytes_traj) return RMX_OK;      // (no reduced DOF: nothing to compute, and no kernel time to take)
+    if (int rc = st.allocate(who, "the staging of the tangents")) return rc;
+    double* d_r = nullptr;      // r is the call's own in both forms: the scratch between the two launches, never copied
+    if (hipMalloc((void**)&d_r, bytes_r) != hipSuccess) {
+        (void)hipGetLastError();
+        st.release(b, hipSuccess);
+        return fail(RMX_E_NOMEM, who + ": no device memory for the parameter term of every slot");
+    }
+    a.tu = st.dev(S_TU); a.tq0 = st.dev(S_TQ0); a.tqd0 = st.dev(S_TQD0);
+    a.tq = st.dev(S_TQ); a.tqd = st.dev(S_TQD);
+    a.r = d_r;
+    ParamRhsArgs p{};
+    p.nsteps = nsteps; p.nslots = v.nslots; p.bdf2 = v.bdf2;
+    p.njoints = m->nlist; p.ntan = ntan; p.h = v.h;
+    p.q0 = v.q0; p.qd0 = v.qd0; p.qt = v.qt; p.qdt = v.qdt;
+    p.stiffness = st.dev(S_TP); p.damping = st.dev(S_TP + 1); p.qrest = st.dev(S_TP + 2); p.inertia = st.dev(S_TP + 3); p.grav = st.dev(S_TP + 4);
+    p.r = d_r;
+    listing_of_nodes(m, p.lst);
+    hipError_t e = st.copy_in(b, hipSuccess);
+    e = timed_launch(b, e, [&] { DISPATCH_NP(m->NP, launch_jvp_params, m, b, p, a); return hipSuccess; });
+    e = wait_or_drain(b, st.copy_out(b, e));
+    st.release(b, e);
+    (void)hipFree(d_r);
+    return call_result(b, e, who);
 }
 
 // rmx_rollout_lqr: the Riccati sweep of iLQR over the BDF1 tape, one workgroup per rollout (rmx_lqr.h); the per-slot sensitivities
@@ -2560,6 +2623,14 @@ extern "C" int rmx_rollout_jvp(rmx_batch* b, int nsteps, int ntan, const double*
 extern "C" int rmx_rollout_jvp_device(rmx_batch* b, int nsteps, int ntan, const double* d_tu, const double* d_tq0, const double* d_tqd0,
                                       double* d_tq, double* d_tqd) {
     return rollout_jvp_impl(b, nsteps, ntan, d_tu, d_tq0, d_tqd0, d_tq, d_tqd, true);
+}
+extern "C" int rmx_rollout_jvp_params(rmx_batch* b, int nsteps, int ntan, const rmx_param_tangents* tp, const double* tu, const double* tq0,
+                                      const double* tqd0, double* tq, double* tqd) {
+    return rollout_jvp_params_impl(b, nsteps, ntan, tp, tu, tq0, tqd0, tq, tqd, false);
+}
+extern "C" int rmx_rollout_jvp_params_device(rmx_batch* b, int nsteps, int ntan, const rmx_param_tangents* tp, const double* d_tu,
+                                             const double* d_tq0, const double* d_tqd0, double* d_tq, double* d_tqd) {
+    return rollout_jvp_params_impl(b, nsteps, ntan, tp, d_tu, d_tq0, d_tqd0, d_tq, d_tqd, true);
 }
 
 static int track_refusal(const rmx_task_track* task, const double* xtarget, int integrator) {

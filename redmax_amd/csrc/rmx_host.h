@@ -139,6 +139,23 @@ struct JvpArgs {
     const double* tu;         // [B][ntan][nsteps][nr], or null: zero
     const double *tq0, *tqd0; // [B][ntan][nr], or null: zero
     double *tq, *tqd;         // [B][ntan][nsteps][nr] (out)
+    const double* r;          // rmx_rollout_jvp_params (the RHS instantiation alone reads it): [B][ntan][nslots][n], node order
+};
+
+// rmx_rollout_jvp_params (rmx_jvp_params.h): one wavefront per (rollout, slot) of the tape forms r = (dg/dtheta) ttheta of every direction
+struct ParamRhsArgs {
+    int nsteps, nslots;       // nslots per rollout: nsteps (BDF1) or nsteps + 1 (BDF2: slot nsteps holds the SDIRK2a solve)
+    int bdf2;                 // the tape's integrator
+    int njoints;              // joints / bodies in the caller's listing (the rows of `inertia`)
+    int ntan;                 // tangent directions per rollout
+    double h;                 // the tape's
+    const double *q0, *qd0;   // [B][nr] the state the tape started from
+    const double *qt, *qdt;   // [B][nsteps][nr] q, qdot after every step
+    const double *stiffness, *damping, *qrest;   // [B][ntan][nr] reduced DOF order; null: zero
+    const double* inertia;    // [B][ntan][njoints][6] listing order; null: zero
+    const double* grav;       // [B][ntan][3]; null: zero
+    double* r;                // [B][ntan][nslots][n] (out), node order
+    short lst[MAXN];          // as ParamArgs::lst
 };
 
 // rmx_rollout_lqr (rmx_lqr.h): one workgroup per rollout walks the slots of its BDF1 tape backwards
@@ -291,6 +308,7 @@ struct rmx_batch {
     void RMX_CAT(launch_vjp_feedback_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a); \
     void RMX_CAT(launch_linearize_, NPV)(const rmx_model* m, const rmx_batch* b, const LinArgs& a); \
     void RMX_CAT(launch_jvp_, NPV)(const rmx_model* m, const rmx_batch* b, const JvpArgs& a); \
+    void RMX_CAT(launch_jvp_params_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamRhsArgs& p, const JvpArgs& a); \
     void RMX_CAT(launch_cost_, NPV)(const rmx_model* m, const rmx_batch* b, const TaskArgs& a, bool frames); \
     void RMX_CAT(launch_vjp_zs_, NPV)(const rmx_model* m, const rmx_batch* b, int integ, const DevOpts& o, const AdjArgs& a, bool fullchain); \
     void RMX_CAT(launch_param_grad_, NPV)(const rmx_model* m, const rmx_batch* b, const ParamArgs& a); \

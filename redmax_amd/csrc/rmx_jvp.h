@@ -49,7 +49,10 @@ __device__ __forceinline__ void jvp_rhs(double (&R)[TW], const double (&dqA)[TW]
     }
 }
 
-template <int NP>
+// RHS (rmx_rollout_jvp_params, rmx_jvp_params.h): the right-hand side of every slot loses this lane's entry of a.r, the parameter
+// term (dg/dtheta) ttheta that k_rollout_param_rhs formed, [B][ntan][nslots][n] in node order.  The instantiation without it is the
+// kernel of rmx_rollout_jvp, text for text.
+template <int NP, bool RHS = false>
 __global__ void __launch_bounds__(64) k_rollout_jvp(const DevModel M, const JvpArgs a) {
     constexpr int TW = JVP_TW;
     __shared__ double xs[TW][64];
@@ -107,6 +110,10 @@ __global__ void __launch_bounds__(64) k_rollout_jvp(const DevModel M, const JvpA
                 dqB[t] = dqA[t] + (8.0 / 9.0) * h * v[t] - (2.0 / 9.0) * h * pv[t];
             }
             R[t] = (dof && t < cnt) ? e2p * tu : 0.0;
+            if constexpr (RHS) {      // (an unconditional load: lanes beyond the tree read node 0's entry and drop it)
+                const double rr = a.r[(dir[t] * a.nslots + slot) * n + (lane < n ? lane : 0)];
+                R[t] = (dof && t < cnt) ? e2p * tu - rr : 0.0;
+            }
         }
         jvp_rhs<NP, TW>(R, dqA, dqB, Mb + (size_t)slot * nn, Db + (size_t)slot * nn, n, lane, dof, eta);
         double Hrow[NP], rinv = 0.0;

@@ -7,11 +7,14 @@ and rest length of every spring, damper and cable, and both keywords go through 
 Forward is rmx_rollout_tape_device (rmx_rollout_tape_bdf2_device under integrator=2), backward rmx_rollout_vjp_device (include/redmax_hip.h): device pointers end to end, the
 objective lives wholly on the PyTorch side.  Forward mode (torch.autograd.forward_ad, torch.func.jvp, torch.func.jacfwd) runs
 rmx_rollout_jvp_device on the same tape; ``jvp(sim, q0, qdot0, u, ...)`` pushes several tangent directions through one tape in one
-call.  ``rollout_closed_loop`` is the same for a rollout under state feedback (rmx_rollout_tape_feedback_device forward,
+call, ``jvp_params`` does the same for tangents of the model's parameters (rmx_rollout_jvp_params_device) and ``param_jacobian`` returns
+whole columns of the trajectory's Jacobian in them.  ``rollout_closed_loop`` is the same for a rollout under state feedback (rmx_rollout_tape_feedback_device forward,
 rmx_rollout_vjp_feedback_device backward): autograd reaches the gains K, the reference xref and the feed-forward uff through the
 closed loop.  torch is imported inside the functions: ``import redmax_amd`` does not need it.
 """
 from __future__ import annotations
+
+from ._abi import PARAM_NAMES      # (the members of rmx_param_grads / rmx_param_tangents, in their order)
 
 _BAD_STATUS = 1 | 2 | 4      # RMX_ST_DIVERGED, RMX_ST_MAXITER, RMX_ST_NAN
 
@@ -285,7 +288,8 @@ def rollout(sim, q0, qdot0, u, h=None, pscale=1.0, check=True, integrator=1, par
     exact through the start step too.  Any other integrator raises ValueError.
     Forward mode works too: under torch.autograd.forward_ad or torch.func.jvp the tangents of q0, qdot0 and u (any subset) go through
     one rmx_rollout_jvp_device call on the tape just recorded, and torch.func.jacfwd runs all its directions in ONE such call; a
-    tangent on a params tensor raises RuntimeError (parameter tangents are not built), torch.func.vmap over q0, qdot0 or u too.
+    tangent on a params tensor raises RuntimeError (the forward never reads the params tensors; ``jvp_params`` is the call for
+    forward-mode parameter tangents, ``param_jacobian`` for whole columns), torch.func.vmap over q0, qdot0 or u too.
     params: None, or a dict of model-parameter tensors - model_params(sim) or any part of it ("stiffness", "damping", "qrest",
     "inertia", "grav").  backward() then also accumulates into each given tensor's .grad the gradient of the loss with respect to
     that parameter, summed over the batch (one rmx_rollout_vjp_params call).  The forward does NOT read the tensors' values: the sim
@@ -885,3 +889,107 @@ def jvp(sim, q0, qdot0, u, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, c
     sim.rollout_jvp_device(nsteps, T, *(tans[n].data_ptr() if n in tans else 0 for n in ("tu", "tq0", "tqdot0")), tq.data_ptr(),
                            tqd.data_ptr())
     return (qtraj, qdtraj, tq[:, 0], tqd[:, 0]) if single else (qtraj, qdtraj, tq, tqd)
+
+
+def _check_tparams(who, tparams):
+    """tparams of jvp_params -> {name: tensor}, in the order of rmx_param_tangents; ValueError for anything the library cannot read."""
+    from . import _abi
+    if not isinstance(tparams, dict):
+        raise ValueError("%s: tparams must be a dict of tensors over %s, got %s" % (who, ", ".join(_abi.PARAM_NAMES), type(tparams).__name__))
+    unknown = [k for k in tparams if k not in _abi.PARAM_NAMES]
+    if unknown:
+        raise ValueError("%s: unknown model parameter %r (known: %s)" % (who, unknown[0], ", ".join(_abi.PARAM_NAMES)))
+    if not tparams:
+        raise ValueError("%s: tparams names no parameter (jvp is the call for tangents of u, q0 and qdot0 alone)" % who)
+    return {n: tparams[n] for n in _abi.PARAM_NAMES if n in tparams}
+
+
+def jvp_params(sim, q0, qdot0, u, tparams, tq0=None, tqdot0=None, tu=None, h=None, pscale=1.0, check=True, integrator=1):
+    """The controlled rollout of ``rollout`` and the forward-mode tangents of its whole trajectory with respect to the model's
+    parameters: (qtraj, qdtraj, tq, tqd), what ``jvp`` returns.
+
+    tparams: a dict of float64 tensors on the sim's device over "stiffness", "damping", "qrest" ([B][T][nr]), "inertia"
+    ([B][T][njoints][6]; a mass tangent is the same number in entries 3 .. 5) and "grav" ([B][T][3]), at least one: direction t of
+    rollout b moves the model's parameters by the rows (b, t), and u, q0, qdot0 by tu, tq0, tqdot0 where given (jvp's shapes).
+    Every given tensor without its T axis is one direction, and tq, tqd come back without it.  One tape and one
+    rmx_rollout_jvp_params_device call for all directions; no autograd graph is made.  The forward does not read parameter values:
+    the sim simulates the model it was built from.  Arguments, checks and words are rollout's; the call replaces the sim's tape and
+    leaves the sim at the end of the rollout.  It is the transpose of rollout(..., params=...).backward()."""
+    import torch
+    from . import _abi
+    who = "jvp_params"
+    _check_integrator(integrator)
+    _check_inputs(sim, q0, qdot0, u)
+    B, nsteps, nr = u.shape
+    tp = _check_tparams(who, tparams)
+    tans = {"tparams[%r]" % n: t for n, t in tp.items()}
+    tans.update({n: t for n, t in (("tu", tu), ("tq0", tq0), ("tqdot0", tqdot0)) if t is not None})
+    tail = {"tparams[%r]" % n: s for n, s in sim._param_shapes().items()}
+    tail.update({"tu": (nsteps, nr), "tq0": (nr,), "tqdot0": (nr,)})
+    dev = _check_tensors(who, sim, tans.items())
+    single = all(t.dim() == 1 + len(tail[n]) for n, t in tans.items())
+    if single:
+        tans = {n: t.unsqueeze(1) for n, t in tans.items()}
+    Ts = sorted({int(t.shape[1]) for n, t in tans.items() if t.dim() == 2 + len(tail[n])})
+    if len(Ts) > 1:
+        raise ValueError("%s: every tangent must carry the same number of directions, got %s" % (who, " and ".join("%d" % t for t in Ts)))
+    T = Ts[0] if Ts else 1
+    for n, t in tans.items():
+        if tuple(t.shape) != (B, T) + tail[n]:
+            raise ValueError("%s: %s must have shape %r - or, every tangent alike, that shape without the direction axis -, got %r"
+                             % (who, n, (B, T) + tail[n], tuple(t.shape[:1] + t.shape[2:]) if single else tuple(t.shape)))
+    tans = {n: t.detach().contiguous() for n, t in tans.items()}
+    h = float(sim.opts.h if h is None else h)
+    tq = torch.empty((B, T, nsteps, nr), dtype=torch.float64, device=dev)
+    tqd = torch.empty_like(tq)
+    qtraj, qdtraj = _tape_forward(sim, q0.detach().contiguous(), qdot0.detach().contiguous(), u.detach().contiguous(), h, float(pscale),
+                                  bool(check), integrator)
+
+    def ptr(n):
+        return tans[n].data_ptr() if n in tans else 0
+    sim.rollout_jvp_params_device(nsteps, T, tq.data_ptr(), tqd.data_ptr(), *(ptr("tparams[%r]" % n) for n in _abi.PARAM_NAMES),
+                                  tu_ptr=ptr("tu"), tq0_ptr=ptr("tq0"), tqd0_ptr=ptr("tqdot0"))
+    return (qtraj, qdtraj, tq[:, 0], tqd[:, 0]) if single else (qtraj, qdtraj, tq, tqd)
+
+
+def param_jacobian(sim, nsteps, names=PARAM_NAMES):
+    """The Jacobian of the taped trajectory with respect to the model's parameters, on the sim's CURRENT tape (the last rollout,
+    jvp or rollout_tape call): name -> (Jq, Jqd), float64 tensors on the sim's device of shape [B][nsteps][nr] + the parameter's
+    shape ("stiffness", "damping", "qrest": [nr]; "inertia": [njoints][6]; "grav": [3]), Jq[b, k-1, i, ...] = d q_k[i] / d theta[...]
+    for rollout b.  One unit direction per parameter entry, and all entries of all names go in ONE rmx_rollout_jvp_params_device
+    call - one elimination per taped solve however many parameters there are.  names: distinct names among the five (default: all).
+    An "inertia" column of entry 3, 4 or 5 alone is the derivative in that entry; the derivative in the physical mass is their sum.
+    Memory: the call holds tq and tqd of [B][T][nsteps][nr] doubles and the library a parameter term of [B][T][nslots][n], with T the
+    number of parameter entries asked for (all five names: 3 nr + 6 njoints + 3) - at 512 rollouts of a 32-link chain and 100 steps
+    about 3.8 GB per array.  ``names`` restricts T to the groups wanted; for a large batch take the groups, or the rollouts, in turn.
+    Neither the state nor the tape changes."""
+    import torch
+    from . import _abi
+    who = "param_jacobian"
+    given = (names,) if isinstance(names, str) else tuple(names)
+    if not given or any(n not in _abi.PARAM_NAMES for n in given) or len(set(given)) != len(given):
+        raise ValueError("%s: names must name distinct parameters among %s, got %r" % (who, ", ".join(repr(n) for n in _abi.PARAM_NAMES), given))
+    nsteps = int(nsteps)
+    if nsteps < 1:
+        raise ValueError("%s: nsteps must be the number of steps of the sim's tape, got %d" % (who, nsteps))
+    shapes = sim._param_shapes()
+    B, nr = sim.B, sim.nr
+    dev = torch.device("cuda", sim.device)
+    order = [n for n in _abi.PARAM_NAMES if n in given]
+    count = {n: int(torch.Size(shapes[n]).numel()) for n in order}
+    T = sum(count.values())
+    tans, off = {}, {}
+    at = 0
+    for n in order:
+        t = torch.zeros((B, T, count[n]), dtype=torch.float64, device=dev)
+        t[:, at:at + count[n]] = torch.eye(count[n], dtype=torch.float64, device=dev)
+        tans[n], off[n] = t.reshape((B, T) + shapes[n]).contiguous(), at
+        at += count[n]
+    tq = torch.empty((B, T, nsteps, nr), dtype=torch.float64, device=dev)
+    tqd = torch.empty_like(tq)
+    torch.cuda.current_stream(dev).synchronize()      # (the library works on a stream of its own: _tape_forward)
+    sim.rollout_jvp_params_device(nsteps, T, tq.data_ptr(), tqd.data_ptr(), *(tans[n].data_ptr() if n in tans else 0 for n in _abi.PARAM_NAMES))
+
+    def cols(t, n):
+        return t[:, off[n]:off[n] + count[n]].permute(0, 2, 3, 1).reshape((B, nsteps, nr) + shapes[n]).contiguous()
+    return {n: (cols(tq, n), cols(tqd, n)) for n in given}
